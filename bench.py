@@ -15,10 +15,12 @@ A "step" is one pass of the hot path over one record already resident in HBM:
 
 Run as `python bench.py --gpus N` it starts the N ranks itself (fresh child processes, before
 anything touches a GPU); under torch.distributed.run it takes RANK / LOCAL_RANK / WORLD_SIZE from the
-environment.  Rank 0 prints ONE JSON line.  After the timed region the last step's results are
-verified on the device ("verified"), and outside it the line also reports the host-buffer
-(PCIe-inclusive) rates ("end_to_end"), the FASTA-ingest-inclusive rate ("fasta_record") and the
-reference's own CPU path on a bounded sample ("cpu_baseline").
+environment.  Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times exactly --steps
+steps, writes the last step's outputs if --dump-outputs is given, and prints the headline fields
+(metric, value, unit, ms_per_step, ...).  With --full the timed steps carry the roofline's events,
+the last step's results are verified on the device ("verified"), and outside the timed region the
+line also reports the host-buffer (PCIe-inclusive) rates ("end_to_end"), the FASTA-ingest-inclusive
+rate ("fasta_record") and the reference's own CPU path on a bounded sample ("cpu_baseline").
 
 Layout (round 5): this file holds the argument parser, the rank launcher, the CPU-baseline leg (the one place that runs the
 reference / the oracle) and run_rank with the timed region; the other legs live in stralg_amd/benchlegs/ -- ceiling.py (the
@@ -87,6 +89,13 @@ def parse_args(argv=None):
                     help="skip the row at the reference's published size (n = 49 000 / 65 536 through the host C API)")
     ap.add_argument("--no-egress", action="store_true",
                     help="FASTA records: skip the egress leg (the record's index leaving the GPU on every rank at once)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: memory ceiling, per-kernel table and roofline, device-side "
+                         "verification and reference pins, FASTA ingest / RO / egress legs, host-buffer rates, the other "
+                         "configurations and the CPU baselines (the --no-* options above switch parts of it off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0; float32 / "
+                         "float64; arrays too large for the budget as a fixed, seeded sample of their entries)")
     return ap.parse_args(argv)
 
 
@@ -269,6 +278,68 @@ def cpu_cfg5_row(records, log2n, sigma=5, seed=42):
             "note": "suffix arrays only (the reference's O table overflows its uint32_t size beyond 204.8 Mi positions, bwt.c:50-51)"}
 
 
+# ---- --dump-outputs ----------------------------------------------------------------------------------------
+
+DUMP_SAMPLE = 1 << 21  # entries kept of an array longer than this: 2 Mi x 8 B x 2 + 2 Mi x 4 B = 40 MB for SA, O and BWT
+
+
+def dump_outputs(path, arrays):
+    """arrays: name -> torch tensor the timed path handed its caller.  Each goes to path/<name>.npy as float64 (float32 for
+    byte arrays: exact either way; int32 storage is read as the uint32 the C API returns), whole when it has at most
+    DUMP_SAMPLE entries, else its entries at DUMP_SAMPLE positions drawn by a generator seeded with the array's length --
+    the same positions in every run with the same arguments, so that two builds can be compared entry by entry."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            pos = np.unique(np.random.default_rng(t.numel()).integers(0, t.numel(), DUMP_SAMPLE, dtype=np.int64))
+            t = t[torch.from_numpy(pos).to(t.device)]
+        a = t.cpu().numpy()
+        a = a.astype(np.float32) if a.dtype == np.uint8 else a.view(np.uint32).astype(np.float64)
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def headline(args, world, coll, workload, n, sigma, gen, tables, stats, numa_node, value, elapsed):
+    """the line's headline fields: what ran, on what, and the rate and time of one timed step"""
+    size_label = (f"{n >> 30} GiB" if n >= (1 << 30) and n % (1 << 30) == 0 else
+                  (f"{n >> 20} MiB" if n >= (1 << 20) and n % (1 << 20) == 0 else f"{n} B"))
+    alpha_label = {"dna": "DNA", "fasta": "DNA, FASTA records", "bytes": "sigma=256"}.get(workload, workload if workload != "uniform" else f"sigma={sigma}")
+    # name the algorithm that ran: lms_path 3 is the direct prefix sort of all suffixes (sx_build.hip), not SA-IS
+    algo = "direct prefix sort" if stats.get("lms_path") == 3 else "SA-IS"
+    what = f"{algo} + BWT C/O tables" if tables else algo
+    if workload == "fasta":
+        wl = (f"one FASTA record of 2^{args.log2n} bases per GPU (bwt_readmapper.c:54-62): image in HBM -> pack -> remap -> "
+              f"sa_is_construction + init_bwt_table (C, O)" if args.n == 0 else f"one FASTA record of {n} bases per GPU")
+    elif tables:
+        wl = (f"sa_is_construction + init_bwt_table (C, O) on {n} symbols ({workload}), alphabet_size={sigma}, "
+              f"one independent record per GPU")
+    else:
+        wl = f"sa_is_construction on {n} symbols ({workload}), alphabet_size={sigma}"
+    return {
+        "metric": f"Msuffixes/s ({what}, {size_label} {alpha_label})",
+        "value": round(value, 3),
+        "unit": "Msuffixes/s",
+        "n_gpus": world,
+        **({"collective_backend": coll["collective_backend"], "n_ranks_seen": coll["n_ranks_seen"]} if coll else {}),
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8 text / u32 indices",
+        "data": "synthetic",
+        "config": {
+            "workload": wl,
+            "n": n, "alphabet_size": sigma, "records_per_gpu": 1, "parallelism": f"batch x{world}, no collectives",
+            "seed": 42, "generator": gen, "numa_node_rank0": numa_node,
+        },
+        "build_stats": stats,
+    }
+
+
 # ---- one rank ----------------------------------------------------------------------------------------------
 
 def run_rank(args):
@@ -362,7 +433,7 @@ def run_rank(args):
     N = n + 1
     tables = (not args.no_tables) and sigma <= 128
     cpu_n = min(n, 1 << args.cpu_log2n)
-    cpu_sample = text[:cpu_n].cpu().numpy() if rank == 0 and world == 1 and not args.no_cpu else None
+    cpu_sample = text[:cpu_n].cpu().numpy() if args.full and rank == 0 and world == 1 and not args.no_cpu else None
     job = None
     if workload == "fasta":
         image = workloads.fasta_image(text, f"record{rank}")
@@ -390,6 +461,14 @@ def run_rank(args):
         else:
             ctx.sa_build_dev(text, n, sigma, sa)
 
+    def step_outputs():
+        """what a step hands its caller: the suffix array, and with the tables the BWT, C and O"""
+        if job is not None:
+            outs = {"sa": job.sa, "bwt": job.bwt, "c_table": job.c, "o_table": job.o}
+        else:
+            outs = {"sa": sa, "bwt": bwt, "c_table": c_tab, "o_table": o_tab}
+        return {k: v for k, v in outs.items() if v is not None and (k == "sa" or tables)}
+
     def profiled_step():
         """one untimed step with HIP events around every launch: the per-class table, and which class dominates"""
         ctx.profile_reset()
@@ -401,10 +480,26 @@ def run_rank(args):
         return ctx.profile_read()
 
     # the box's measured memory ceiling, a few milliseconds before the timed region (rank 0 reports it)
-    ceiling = measured_ceiling(ctx, dev, nbytes=(1 << 20) if emu else (2 << 30)) if (rank == 0 and not args.no_ceiling) else None
+    ceiling = (measured_ceiling(ctx, dev, nbytes=(1 << 20) if emu else (2 << 30))
+               if (args.full and rank == 0 and not args.no_ceiling) else None)
     for _ in range(args.warmup):
         step()
-    # one more untimed step, with events around every launch: the per-class table and the dominant class
+    if not args.full:
+        # the headline alone: exactly `steps` steps between barrier + torch.cuda.synchronize(), no events on any launch
+        elapsed_own = farm.timed(step, args.steps, 0, cuda=cuda)
+        stats = ctx.last_stats()
+        elapsed, total_units = farm.reduce_scalars(elapsed_own, args.steps * N)
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, step_outputs())
+        if rank == 0:
+            print(json.dumps(headline(args, world, coll, workload, n, sigma, gen, tables, stats, numa_node,
+                                      total_units / elapsed / 1e6, elapsed)), flush=True)
+        if world > 1:
+            farm.fence(cuda)
+            dist.destroy_process_group()
+        ctx.close()
+        return 0
+    # --full: one more untimed step, with events around every launch: the per-class table and the dominant class
     table = profiled_step()
     dom = max(table, key=lambda k: table[k]["ms"])  # the class with the largest summed time, whichever it is
     # Timed region: events only on the dominant kernel's launches (the roofline figure is measured live, on the library's
@@ -434,6 +529,8 @@ def run_rank(args):
     # max time over ranks, total suffixes over ranks (the only collectives; none on the data path)
     red_dev = None  # (farm.reduce_scalars uses the group and device farm.init_collectives chose)
     elapsed, total_units = farm.reduce_scalars(elapsed_own, args.steps * N, device=red_dev)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, step_outputs())
 
     # ---- after the timed region: check the last step's results on the device ------------------------------
     verified, checks = None, []
@@ -530,44 +627,12 @@ def run_rank(args):
             fasta.update(eg)
 
     if rank == 0:
-        value = total_units / elapsed / 1e6
         # dominant kernel class (by summed HIP-event time of the profiled step), measured in the timed steps
         d = prof[dom]
         achieved = d["alg_bytes"] / (d["ms"] * 1e-3) / 1e9 if d["ms"] > 0 else 0.0
-        size_label = (f"{n >> 30} GiB" if n >= (1 << 30) and n % (1 << 30) == 0 else
-                      (f"{n >> 20} MiB" if n >= (1 << 20) and n % (1 << 20) == 0 else f"{n} B"))
-        alpha_label = {"dna": "DNA", "fasta": "DNA, FASTA records", "bytes": "sigma=256"}.get(workload, workload if workload != "uniform" else f"sigma={sigma}")
-        # name the algorithm that ran: lms_path 3 is the direct prefix sort of all suffixes (sx_build.hip), not SA-IS
-        algo = "direct prefix sort" if stats.get("lms_path") == 3 else "SA-IS"
-        what = f"{algo} + BWT C/O tables" if tables else algo
-        if workload == "fasta":
-            wl = (f"one FASTA record of 2^{args.log2n} bases per GPU (bwt_readmapper.c:54-62): image in HBM -> pack -> remap -> "
-                  f"sa_is_construction + init_bwt_table (C, O)" if args.n == 0 else f"one FASTA record of {n} bases per GPU")
-        elif tables:
-            wl = (f"sa_is_construction + init_bwt_table (C, O) on {n} symbols ({workload}), alphabet_size={sigma}, "
-                  f"one independent record per GPU")
-        else:
-            wl = f"sa_is_construction on {n} symbols ({workload}), alphabet_size={sigma}"
         traffic, traffic_stale = pmc_traffic(workload, args.log2n, sigma, tables, dom) if args.n == 0 else (None, None)
         out = {
-            "metric": f"Msuffixes/s ({what}, {size_label} {alpha_label})",
-            "value": round(value, 3),
-            "unit": "Msuffixes/s",
-            "n_gpus": world,
-            **({"collective_backend": coll["collective_backend"], "n_ranks_seen": coll["n_ranks_seen"]} if coll else {}),
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8 text / u32 indices",
-            "data": "synthetic",
-            "config": {
-                "workload": wl,
-                "n": n, "alphabet_size": sigma, "records_per_gpu": 1, "parallelism": f"batch x{world}, no collectives",
-                "seed": 42, "generator": gen, "numa_node_rank0": numa_node,
-            },
+            **headline(args, world, coll, workload, n, sigma, gen, tables, stats, numa_node, total_units / elapsed / 1e6, elapsed),
             "roofline": {
                 "bound": "hbm",
                 "kernel": dom,
@@ -598,7 +663,6 @@ def run_rank(args):
             "kernels": {k: {"ms_per_step": round(v["ms"], 3), "launches_per_step": v["launches"],
                             "GBps": round(v["alg_bytes"] / (v["ms"] * 1e-3) / 1e9, 1) if v["ms"] > 0 else 0.0}
                         for k, v in table.items() if v["launches"]},
-            "build_stats": stats,
         }
         # whole-step algorithmic traffic over the step time: sum of the classes' bytes
         alg_total = sum(v["alg_bytes"] for v in table.values())

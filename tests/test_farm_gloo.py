@@ -125,7 +125,7 @@ def test_bench_launches_its_own_ranks_on_fasta_records(emu_ctx):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["STRALG_BENCH_EMU"] = "1"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--n", "5003", "--steps", "1",
-                          "--warmup", "0"], env=env, capture_output=True, text=True, timeout=900)
+                          "--warmup", "0", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -160,7 +160,7 @@ def test_bench_falls_back_to_gloo_when_rccl_does_not_come_up(emu_ctx):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(STRALG_BENCH_EMU="1", STRALG_BENCH_BACKEND="nccl", STRALG_BENCH_FORCE_NCCL_ATTEMPT="1")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--n", "1500", "--steps", "1",
-                          "--warmup", "0", "--no-egress"], env=env, capture_output=True, text=True, timeout=900)
+                          "--warmup", "0", "--no-egress", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     doc = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
     assert doc["n_gpus"] == 2 and doc["verified"] is True
@@ -183,7 +183,8 @@ def test_bench_under_torch_distributed_run(emu_ctx):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     env.update(STRALG_BENCH_EMU="1", STRALG_BENCH_LOG2N="12")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                          "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"],
+                          "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+                          "--full"],
                          env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -203,7 +204,7 @@ def test_bench_default_run_carries_the_other_configs(emu_ctx):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["STRALG_BENCH_EMU"] = "1"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--log2n", "12", "--steps", "1", "--warmup", "0",
-                          "--no-e2e", "--no-cpu", "--other-steps", "1"], env=env, capture_output=True, text=True, timeout=900)
+                          "--no-e2e", "--no-cpu", "--other-steps", "1", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     doc = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
     # (a record this short is sorted directly -- SX_FLAG_SMALL_DIRECT_MAX -- and the line says so; at BASELINE's sizes it reads "SA-IS + ...")
@@ -226,7 +227,7 @@ def test_bench_line_carries_round5_legs(emu_ctx):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["STRALG_BENCH_EMU"] = "1"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--log2n", "12", "--steps", "6", "--warmup", "0",
-                          "--e2e-log2n", "12", "--cpu-log2n", "12", "--no-other-configs"], env=env, capture_output=True, text=True, timeout=900)
+                          "--e2e-log2n", "12", "--cpu-log2n", "12", "--no-other-configs", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     doc = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
     assert "peak_measured" in doc["roofline"] and doc["roofline"]["peak"] == 8000.0
@@ -240,11 +241,63 @@ def test_bench_line_carries_round5_legs(emu_ctx):
     e2e = doc["end_to_end"]["2^12"]
     assert e2e["build_complete_table_ms"] > 0 and e2e["with_ro_ms"] > 0 and "readmapper_loop" in e2e
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "fasta", "--n", "5003", "--steps", "1", "--warmup", "0",
-                          "--cpu-log2n", "12", "--no-e2e", "--no-egress"], env=env, capture_output=True, text=True, timeout=900)
+                          "--cpu-log2n", "12", "--no-e2e", "--no-egress", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     doc = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
     row = doc["fasta_record"]["cpu_cfg5"]
     assert row["records"] == 8 and row["aggregate_Msuffixes_per_s"] > 0 and len(row["seconds_per_process"]) == 8, row
+
+
+def test_bench_plain_run_dumps_the_last_steps_outputs(emu_ctx, tmp_path):
+    """without --full the line is the headline alone (exactly --steps timed steps, none of --full's legs), and
+    --dump-outputs writes what the last step computed -- suffix array, BWT, C and O -- as float arrays that two runs with
+    the same arguments reproduce and that hold the oracle's results (over the CPU execution harness at 2^12 symbols)"""
+    import json
+    import subprocess
+    import oracle
+    from stralg_amd.synth import synth
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    env["STRALG_BENCH_EMU"] = "1"
+    dumps = []
+    for run in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--log2n", "12", "--steps", "3",
+                              "--warmup", "1", "--dump-outputs", str(tmp_path / run)], env=env, capture_output=True, text=True,
+                             timeout=900)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout[-2000:]
+        doc = json.loads(lines[0])
+        assert doc["unit"] == "Msuffixes/s" and doc["higher_is_better"] is True and doc["value"] > 0
+        assert doc["metric"].startswith("Msuffixes/s (") and doc["dtype"] == "u8 text / u32 indices"
+        assert doc["steps"] == 3 and doc["warmup"] == 1 and doc["ms_per_step"] > 0
+        assert not {"roofline", "kernels", "verified", "end_to_end", "other_configs", "cpu_baseline"} & set(doc), sorted(doc)
+        dumps.append({k: np.load(tmp_path / run / f"{k}.npy") for k in ("sa", "bwt", "c_table", "o_table")})
+    for k, a in dumps[0].items():
+        assert a.dtype in (np.float32, np.float64) and (a == dumps[1][k]).all(), k
+    x = synth(1 << 12, 5, 42)
+    sa = oracle.sa_is(x, 5)
+    assert (dumps[0]["sa"] == sa).all()
+    assert (dumps[0]["bwt"] == oracle.bwt(x, sa)).all()
+    assert (dumps[0]["c_table"] == oracle.c_table(x, 5)).all()
+    assert (dumps[0]["o_table"] == oracle.o_table(x, sa, 5).reshape(-1)).all()
+
+
+def test_bench_dump_samples_a_large_output(tmp_path):
+    """an output too large to write whole is written as its entries at a fixed, seeded sample of positions, within the
+    64 MB budget for the largest step's outputs (1 GiB of DNA: SA, BWT and O of 2^30 + 1 rows)"""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    n = 3 << 20
+    o = (torch.arange(n, dtype=torch.int64) - n // 2).to(torch.int32)  # the first half negative: uint32 counts in int32 storage
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"o_table": o, "c_table": torch.arange(5, dtype=torch.int32)})
+    a, b = (np.load(tmp_path / run / "o_table.npy") for run in ("a", "b"))
+    assert a.dtype == np.float64 and 0 < a.size <= bench.DUMP_SAMPLE and (a == b).all()
+    pos = (a.astype(np.int64) + n // 2) % (1 << 32)
+    assert (np.diff(pos) > 0).all() and pos[-1] < n and a.max() >= 2 ** 31  # distinct positions in order, read as uint32
+    assert np.load(tmp_path / "a" / "c_table.npy").tolist() == [0, 1, 2, 3, 4]
+    assert bench.DUMP_SAMPLE * (8 + 4 + 8) <= 64 * 10 ** 6  # SA and O as float64, BWT as float32
 
 
 def test_bench_reports_a_failed_verification(emu_ctx, tmp_path):

@@ -8,7 +8,7 @@ for v in "$@"; do
   for f in ${file//,/ }; do touch stralg_amd/csrc/$f; done
   make -s -C stralg_amd/csrc -j16 HIPFLAGS="$base $v" 2>&1 | grep -E "error" | head -3
   echo "== [$v]"
-  timeout 300 python bench.py --no-e2e --no-cpu --no-other-configs --no-egress $args 2>/dev/null | python3 -c "
+  timeout 300 python bench.py --full --no-e2e --no-cpu --no-other-configs --no-egress $args 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], d.get('verified'), {k:v['ms_per_step'] for k,v in d['kernels'].items() if k in '$cls'.split(',')})"
 done

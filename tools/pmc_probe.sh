@@ -7,7 +7,7 @@ OUT="$ROOT/gpurun_out/pmc_probe"
 rm -rf "$OUT"; mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
-ARGS="${BENCH_ARGS:---steps 1 --warmup 0 --no-cpu}"
+ARGS="${BENCH_ARGS:---full --steps 1 --warmup 0 --no-cpu}"
 # (TCC_* / TCP_* groups made rocprofv3 abort and then hang until the gpurun limit on this pool: SQ counters only,
 #  and every pass under its own timeout)
 CSETS=(

@@ -8,7 +8,7 @@ OUT="$ROOT/gpurun_out/prof"
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
-ARGS="${BENCH_ARGS:---steps 2 --warmup 1 --no-cpu}"
+ARGS="${BENCH_ARGS:---full --steps 2 --warmup 1 --no-cpu}"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 "$ROOT/bench.py" $ARGS > "$OUT/trace.log" 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -- python3 "$ROOT/bench.py" $ARGS > "$OUT/pmc_fetch.log" 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write" -- python3 "$ROOT/bench.py" $ARGS > "$OUT/pmc_write.log" 2>&1

@@ -5,10 +5,10 @@ set -o pipefail
 part=$1
 out=gpurun_out/r04_final
 mkdir -p $out
-common="--no-cpu --no-e2e --no-other-configs"
+common="--full --no-cpu --no-e2e --no-other-configs"
 case $part in
   a) # the driver-like line (with the CPU baselines and the host-buffer legs), its kernel trace and PMC passes
-    bash tools/gpu_step.sh r04_final/a "bench:--steps 20 --warmup 5" "prof:bench.py --steps 2 --warmup 1 $common" \
+    bash tools/gpu_step.sh r04_final/a "bench:--full --steps 20 --warmup 5" "prof:bench.py --steps 2 --warmup 1 $common" \
       "py:tools/e2e_probe.py 30";;
   b) # PMC passes of the other configurations bench.py reports (other_configs and the FASTA step)
     bash tools/gpu_step.sh r04_final/b "prof:bench.py --log2n 28 --steps 2 --warmup 1 $common" \
@@ -27,8 +27,8 @@ case $part in
       "bench:--workload text_like --steps 3 --warmup 1 $common" \
       "bench:--workload pangenome --steps 3 --warmup 1 $common" \
       "bench:--workload periodic --steps 3 --warmup 1 $common" \
-      "bench:--workload fasta --steps 5 --warmup 2 --no-cpu --no-e2e" \
+      "bench:--workload fasta --steps 5 --warmup 2 --full --no-cpu --no-e2e" \
       "bench:--log2n 22 --steps 50 --warmup 5 $common" \
-      "bench2n:--log2n 26 --steps 3 --warmup 1" "bench2:--log2n 26 --steps 3 --warmup 1" \
+      "bench2n:--log2n 26 --steps 3 --warmup 1 --full" "bench2:--log2n 26 --steps 3 --warmup 1 --full" \
       "py:tools/bench_next.py" "prof:tools/bench_next.py";;
 esac
