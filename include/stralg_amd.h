@@ -31,7 +31,8 @@ enum {
     SX_E_ARG = -1,     /* malformed argument (symbol >= alphabet_size, interior 0, n too large) */
     SX_E_NOMEM = -2,   /* host allocation failed */
     SX_E_INTERNAL = -3, /* a device-side invariant did not hold */
-    SX_E_MALFORMED = -4 /* a FASTA image that ends inside a header line (bioinf/fasta.c:121-124 MALFORMED_FILE) */
+    SX_E_MALFORMED = -4, /* a FASTA image that ends inside a header line (bioinf/fasta.c:121-124 MALFORMED_FILE) */
+    SX_E_CAPACITY = -5   /* more results than the caller's buffer holds (the count is reported all the same) */
 };
 
 /* Kernel classes for the in-library HIP-event profiler (bench.py roofline). */
@@ -55,7 +56,7 @@ enum {
     SX_KC_FASTA,          /* FASTA image -> packed records                bioinf/fasta.c:92-135 */
     SX_KC_REMAP,          /* presence bits + table lookup                 remap.c:8-31,102-114  */
     SX_KC_LCP,            /* inverse + LCP                                suffix_array.c:53-85  */
-    SX_KC_SEARCH,         /* batched exact BWT search                     bwt.c:164-199         */
+    SX_KC_SEARCH,         /* batched exact and k-edit BWT search          bwt.c:164-199, 226-422 */
     SX_KC_LOCAL_SORT,     /* hybrid LMS sort: sub-buckets ordered in LDS, ties listed          */
     SX_KC_COUNT
 };
@@ -201,6 +202,42 @@ int sx_sa_inverse_lcp(sx_ctx *ctx, const uint8_t *text, const uint32_t *sa, uint
 int sx_bwt_exact_search_dev(sx_ctx *ctx, const uint32_t *d_c_table, const uint32_t *d_o_table, uint64_t N,
                             uint32_t sigma, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count,
                             uint32_t *d_l_out, uint32_t *d_r_out);
+
+/* stralg/bwt.c:226-422 init_bwt_approx_iter / next_bwt_approx_match for `count` patterns at once, at most max_edits
+ * edits (mismatch, insertion I, deletion D).  One hit is one interval of the reference iterator's list: the matches
+ * sa[L], sa[L+1], ..., sa[R-1], each with match_length and the CIGAR of the hit.  Matches and mismatches are both 'M'
+ * in the reference's CIGARs, so a hit's CIGAR is fixed by its I/D operations: gap[j] (j < n_gaps, ascending) is the
+ * index of the j-th I/D in the edit string in pattern order (low 15 bits; the edit string has pattern length + the
+ * number of D symbols) and SX_APPROX_GAP_D set for a D.  Render it as runs of equal operations, "%d%c" each
+ * (cigar.c edits_to_cigar). */
+#define SX_APPROX_MAX_EDITS 8
+#define SX_APPROX_GAP_D 0x8000u
+typedef struct sx_approx_hit {
+    uint32_t query;        /* pattern number */
+    uint32_t L, R;         /* interval of the suffix array, L < R */
+    uint16_t match_length; /* symbols of the text the pattern is aligned to */
+    uint16_t n_gaps;       /* I/D operations (<= max_edits) */
+    uint16_t gap[SX_APPROX_MAX_EDITS];
+} sx_approx_hit; /* 32 bytes */
+/* Patterns as in sx_bwt_exact_search_dev; tables as sx_bwt_tables_dev writes them; d_ro_table (the reversed text's
+ * O table, build_complete_table(.., true)) feeds the reference's D table, NULL: a D table of zeros (bwt.c:319-338).
+ * The hits of pattern q are d_hits[d_hit_offsets[q] .. d_hit_offsets[q+1]) in the reference's order (a depth-first
+ * search from the pattern's last symbol; children M over a = 1 .. sigma-1, I, D over a = 1 .. sigma-1; no D at the
+ * root); identical from run to run.  d_hit_offsets (count + 1 entries) and *total_hits_out are always written; more
+ * than hit_capacity hits: no hit is written and the call returns SX_E_CAPACITY; d_hits == NULL: count only.
+ * d_hits 16-byte aligned.  Limits: max_edits <= SX_APPROX_MAX_EDITS, every pattern length + max_edits < 2^15, fewer
+ * than 2^32 hits in one call (else SX_E_ARG); max_edits < 0: no hits.  A pattern that is empty or holds a symbol 0 or
+ * >= sigma has no hits (the reference asserts or reads out of bounds there). */
+int sx_bwt_approx_search_dev(sx_ctx *ctx, const uint32_t *d_c_table, const uint32_t *d_o_table,
+                             const uint32_t *d_ro_table, uint64_t N, uint32_t sigma, const uint8_t *d_patterns,
+                             const uint32_t *d_offsets, uint32_t count, int max_edits, uint64_t *d_hit_offsets,
+                             sx_approx_hit *d_hits, uint64_t hit_capacity, uint64_t *total_hits_out);
+/* The same over host buffers: the tables and patterns are uploaded (the whole O / RO tables, (N+1) x sigma words each,
+ * once per call), hit_offsets (host, count + 1) is filled, *hits_out receives a malloc'd array of *total_hits_out hits
+ * (NULL when there are none) that the caller releases with free(). */
+int sx_bwt_approx_search(sx_ctx *ctx, const uint32_t *c_table, const uint32_t *o_table, const uint32_t *ro_table,
+                         uint64_t N, uint32_t sigma, const uint8_t *patterns, const uint32_t *offsets, uint32_t count,
+                         int max_edits, uint64_t *hit_offsets, sx_approx_hit **hits_out, uint64_t *total_hits_out);
 
 /* ---- streaming download (serialisation without a host copy of the tables) ---- */
 /* sink(user, section, data, bytes): consecutive chunks of one section after the other; data is only valid

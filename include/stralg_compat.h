@@ -109,6 +109,9 @@ void init_bwt_exact_match_iter(struct bwt_exact_match_iter *iter, struct bwt_tab
 bool next_bwt_exact_match_iter(struct bwt_exact_match_iter *iter, struct bwt_exact_match *match);
 void dealloc_bwt_exact_match_iter(struct bwt_exact_match_iter *iter);
 
+/* stralg/bwt.h:236-330 (bwt.c:226-422): the reference's approximate iterator (init_bwt_approx_iter /
+ * next_bwt_approx_match) stays in libstralg; its batched device form is stralg_amd_bwt_approx_batch below. */
+
 /* ---- index serialisation: the reference's file format (stralg/serialise.h:8-23, string_utils.h,
  * suffix_array.h, remap.h, bwt.h write_ / read_ pairs) ------------------------------------------- */
 /* (every FILE form has its _fname sibling: string_utils.h:48-71, suffix_array.h:109-126, remap.h:89-104, bwt.h:337-354) */
@@ -218,6 +221,29 @@ int stralg_amd_fasta_tables_batch_ex(struct fasta_records *records, bool include
                                      int n_devices, struct bwt_table **out, size_t *n_failed);
 int stralg_amd_fasta_tables_batch(struct fasta_records *records, bool include_reverse, const int *devices,
                                   int n_devices, struct bwt_table **out);
+
+/* k-edit search for a batch of patterns at once on the GPU (sx_bwt_approx_search): what init_bwt_approx_iter +
+ * next_bwt_approx_match (bwt.c:226-422) yield for each remapped, NUL-terminated pattern over table t, at most `edits`
+ * edits, in the iterator's order and with byte-identical CIGARs: the matches of pattern q are
+ * matches[first[q] .. first[q+1]).  The RO table, when t has one, feeds the search's D table.  Each call uploads t's C,
+ * O and RO tables ((n+1) x alphabet_size words each, 20 bytes a symbol for DNA), so batch many patterns into one call.
+ * Limits: edits <= 8, strlen(pattern) + edits < 2^15; an empty pattern or one with a symbol >= alphabet_size has no
+ * matches, edits < 0 gives none.  Returns NULL (and a line on stderr) on failure; release the result with
+ * stralg_amd_free_approx_result. */
+struct stralg_amd_approx_match {
+    uint32_t position;     /* bwt_approx_match.position */
+    uint32_t match_length; /* bwt_approx_match.match_length */
+    const char *cigar;     /* bwt_approx_match.cigar (owned by the result; shared by the matches of one interval) */
+};
+struct stralg_amd_approx_result {
+    size_t count;                            /* patterns */
+    size_t *first;                           /* count + 1 entries */
+    struct stralg_amd_approx_match *matches; /* first[count] entries */
+    char *cigars;                            /* the CIGAR strings */
+};
+struct stralg_amd_approx_result *stralg_amd_bwt_approx_batch(struct bwt_table *t, const uint8_t *const *remapped_patterns,
+                                                             size_t count, int edits);
+void stralg_amd_free_approx_result(struct stralg_amd_approx_result *result);
 
 #ifdef __cplusplus
 }

@@ -31,6 +31,14 @@ class BuildStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+# include/stralg_amd.h sx_approx_hit (32 bytes)
+APPROX_MAX_EDITS = 8
+APPROX_GAP_D = 0x8000
+APPROX_HIT_DTYPE = [("query", "<u4"), ("L", "<u4"), ("R", "<u4"), ("match_length", "<u2"), ("n_gaps", "<u2"),
+                    ("gap", "<u2", (APPROX_MAX_EDITS,))]
+SX_E_ARG, SX_E_CAPACITY = -1, -5
+
+
 def load(path=None):
     """Load the shared library and declare every entry point of include/stralg_amd.h."""
     path = path or PRODUCT_LIB
@@ -67,6 +75,10 @@ def load(path=None):
         "sx_sa_lcp_dev": (C.c_int, [vp, u8p, u32p, C.c_uint64, u32p, u32p]),
         "sx_sa_inverse_lcp": (C.c_int, [vp, u8p, u32p, C.c_uint64, u32p, u32p]),
         "sx_bwt_exact_search_dev": (C.c_int, [vp, u32p, u32p, C.c_uint64, C.c_uint32, u8p, u32p, C.c_uint32, u32p, u32p]),
+        "sx_bwt_approx_search_dev": (C.c_int, [vp, u32p, u32p, u32p, C.c_uint64, C.c_uint32, u8p, u32p, C.c_uint32, C.c_int,
+                                               u64p, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+        "sx_bwt_approx_search": (C.c_int, [vp, u32p, u32p, u32p, C.c_uint64, C.c_uint32, u8p, u32p, C.c_uint32, C.c_int,
+                                           u64p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
         "sx_build_tables_stream": (C.c_int, [vp, u8p, C.c_uint64, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]),
         "sx_fasta_pack_dev": (C.c_int, [vp, u8p, C.c_uint64, u8p, C.POINTER(C.c_uint64), u32p, C.c_uint64,
                                         C.POINTER(C.c_uint32)]),
@@ -104,7 +116,7 @@ def load(path=None):
 EXPORTS = ["sx_device_count", "sx_device_numa_node", "sx_ctx_create", "sx_ctx_destroy", "sx_ctx_live_count", "sx_last_error", "sx_ctx_trim", "sx_ctx_set_flag",
            "sx_sa_build", "sx_sa_build_dev", "sx_sa_bwt_build_dev", "sx_bwt_tables", "sx_bwt_tables_dev",
            "sx_bwt_tables_from_bwt_dev", "sx_build_tables", "sx_sa_inverse_dev", "sx_sa_lcp_dev", "sx_sa_inverse_lcp",
-           "sx_bwt_exact_search_dev", "sx_build_tables_stream", "sx_fasta_pack_dev", "sx_fasta_pack", "sx_remap_dev", "sx_reverse_dev", "sx_profile_enable", "sx_profile_only",
+           "sx_bwt_exact_search_dev", "sx_bwt_approx_search_dev", "sx_bwt_approx_search", "sx_build_tables_stream", "sx_fasta_pack_dev", "sx_fasta_pack", "sx_remap_dev", "sx_reverse_dev", "sx_profile_enable", "sx_profile_only",
            "sx_profile_reset", "sx_profile_read", "sx_kernel_class_name", "sx_last_stats",
            "sx_synth_dev", "sx_membw_probe", "sx_prim_sort_pairs_dev", "sx_prim_exclusive_sum_dev", "sx_prim_classify_dev"]
 

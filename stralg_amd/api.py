@@ -138,6 +138,38 @@ class Context:
                                                      _ptr(d_offsets), count, _ptr(d_l), _ptr(d_r)),
                     "sx_bwt_exact_search_dev")
 
+    def bwt_approx_search_dev(self, d_c, d_o, d_ro, N, sigma, d_patterns, d_offsets, count, max_edits, d_hit_offsets,
+                              d_hits=None, hit_capacity=0):
+        """sx_bwt_approx_search_dev: fills d_hit_offsets (count + 1 uint64) and, when d_hits is given and large enough,
+        d_hits (hit_capacity records of _lib.APPROX_HIT_DTYPE); returns the number of hits.  More hits than
+        hit_capacity raise StralgAmdError with code SX_E_CAPACITY (-5); the offsets are written all the same."""
+        total = C.c_uint64(0)
+        self._check(self.lib.sx_bwt_approx_search_dev(self.h, _ptr(d_c), _ptr(d_o), _ptr(d_ro), N, sigma, _ptr(d_patterns),
+                                                      _ptr(d_offsets), count, max_edits, _ptr(d_hit_offsets), _ptr(d_hits),
+                                                      hit_capacity, C.byref(total)), "sx_bwt_approx_search_dev")
+        return int(total.value)
+
+    def bwt_approx_search(self, c, o, ro, sigma, patterns, offsets, max_edits):
+        """sx_bwt_approx_search over host arrays (o, ro: (N+1, sigma); ro may be None): (hit offsets[count + 1], hits as a
+        structured array of _lib.APPROX_HIT_DTYPE)."""
+        c = np.ascontiguousarray(c, dtype=np.uint32)
+        o = np.ascontiguousarray(o, dtype=np.uint32)
+        ro = None if ro is None else np.ascontiguousarray(ro, dtype=np.uint32)
+        patterns = np.ascontiguousarray(patterns, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint32)
+        count = offsets.size - 1
+        hit_off = np.zeros(count + 1, dtype=np.uint64)
+        hp, total = C.c_void_p(), C.c_uint64(0)
+        self._check(self.lib.sx_bwt_approx_search(self.h, _ptr(c), _ptr(o), _ptr(ro), o.shape[0] - 1, sigma,
+                                                  _ptr(patterns) if patterns.size else None, _ptr(offsets), count, max_edits,
+                                                  _ptr(hit_off), C.byref(hp), C.byref(total)), "sx_bwt_approx_search")
+        n = int(total.value)
+        hits = np.zeros(n, dtype=_lib.APPROX_HIT_DTYPE)
+        if hp.value:
+            C.memmove(hits.ctypes.data, hp.value, n * hits.dtype.itemsize)
+            _libc_free(hp.value)
+        return hit_off, hits
+
     # ---- FASTA ingest and remap (SURVEY.md section 8f row 2) ------------------------------
     def fasta_pack_dev(self, d_file, file_len, d_packed, d_term=None, term_cap=0):
         """bioinf/fasta.c load_fasta_records' packing on the device: returns (packed_len, n_records); raises
@@ -302,6 +334,13 @@ class Context:
 _tls = threading.local()
 
 
+def _libc_free(address):
+    libc = C.CDLL(None)
+    libc.free.argtypes = [C.c_void_p]
+    libc.free.restype = None
+    libc.free(address)
+
+
 def default_context(device=None):
     """The calling thread's context (created on first use, like the C host layer's)."""
     ctx = getattr(_tls, "ctx", None)
@@ -433,3 +472,48 @@ def build_complete_table(string, include_reverse=True, ctx=None):
         _, _, ro = ctx.build_tables(remapped[::-1].copy(), sigma, want_sa=False)
     sa = SuffixArray(_with_terminator(remapped), sa_arr)
     return BwtTable(table, sa, c, o, ro)
+
+
+def approx_cigar(m, gaps):
+    """The reference's CIGAR (cigar.c edits_to_cigar of the reversed edit string) of a hit of a pattern of m symbols
+    whose I/D operations are `gaps` (sx_approx_hit.gap[:n_gaps]: index in the edit string | APPROX_GAP_D for a D)."""
+    ops = ["M"] * (m + sum(1 for g in gaps if g & _lib.APPROX_GAP_D))
+    for g in gaps:
+        ops[g & 0x7FFF] = "D" if g & _lib.APPROX_GAP_D else "I"
+    out, k = [], 0
+    while k < len(ops):
+        r = k
+        while r < len(ops) and ops[r] == ops[k]:
+            r += 1
+        out.append(f"{r - k}{ops[k]}")
+        k = r
+    return "".join(out)
+
+
+def approx_matches(hits, hit_offsets, pattern_lengths, sa):
+    """sx_approx_hit records -> per pattern the list next_bwt_approx_match yields: (position, match_length, cigar)"""
+    out = []
+    for q in range(len(hit_offsets) - 1):
+        res = []
+        for h in hits[int(hit_offsets[q]):int(hit_offsets[q + 1])]:
+            cigar = approx_cigar(int(pattern_lengths[q]), [int(g) for g in h["gap"][:int(h["n_gaps"])]])
+            ml = int(h["match_length"])
+            res.extend((int(pos), ml, cigar) for pos in sa[int(h["L"]):int(h["R"])])
+        out.append(res)
+    return out
+
+
+def bwt_approx_search(bwt_table, patterns, edits, ctx=None):
+    """stralg/bwt.c:226-422 (init_bwt_approx_iter / next_bwt_approx_match) for a batch of remapped patterns at once:
+    per pattern the list of (position, match_length, cigar) the reference iterator yields, in its order.  The RO table
+    (when the table has one) feeds the search's D table.  A pattern that is empty or holds a symbol 0 or >=
+    alphabet_size has no matches."""
+    ctx = ctx or default_context()
+    pats = [np.asarray(p, dtype=np.uint8) if not isinstance(p, (bytes, bytearray)) else np.frombuffer(bytes(p), np.uint8)
+            for p in patterns]
+    offsets = np.zeros(len(pats) + 1, dtype=np.uint32)
+    offsets[1:] = np.cumsum([p.size for p in pats])
+    flat = np.concatenate(pats).astype(np.uint8) if offsets[-1] else np.zeros(0, np.uint8)
+    hit_off, hits = ctx.bwt_approx_search(bwt_table.c_table, bwt_table.o_table, bwt_table.ro_table,
+                                          bwt_table.remap_table.alphabet_size, flat, offsets, edits)
+    return approx_matches(hits, hit_off, [p.size for p in pats], bwt_table.sa.array)

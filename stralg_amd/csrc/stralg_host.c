@@ -1543,3 +1543,112 @@ int stralg_amd_fasta_tables_batch(struct fasta_records *records, bool include_re
 {
     return stralg_amd_fasta_tables_batch_ex(records, include_reverse, devices, n_devices, out, NULL);
 }
+
+/* ---- k-edit search for a batch of patterns (stralg/bwt.c:226-422 on the device) ---------------------------- */
+
+/* cigar.c edits_to_cigar of the hit's edit string in pattern order: runs of equal operations, "%d%c" each */
+static size_t approx_cigar(char *out, uint32_t m, const sx_approx_hit *h)
+{
+    uint32_t n_d = 0;
+    for (uint32_t g = 0; g < h->n_gaps; ++g) n_d += (h->gap[g] & SX_APPROX_GAP_D) ? 1u : 0u;
+    const uint32_t len = m + n_d;
+    size_t w = 0;
+    uint32_t pos = 0, g = 0;
+    while (pos < len) {
+        const char op = (g < h->n_gaps && (h->gap[g] & 0x7FFFu) == pos) ? ((h->gap[g] & SX_APPROX_GAP_D) ? 'D' : 'I') : 'M';
+        uint32_t run = 0;
+        for (;;) {
+            const char here = (g < h->n_gaps && (h->gap[g] & 0x7FFFu) == pos) ? ((h->gap[g] & SX_APPROX_GAP_D) ? 'D' : 'I') : 'M';
+            if (pos >= len || here != op) break;
+            if (here != 'M') ++g;
+            ++pos;
+            ++run;
+        }
+        w += (size_t)sprintf(out + w, "%u%c", run, op);
+    }
+    out[w] = '\0';
+    return w + 1;
+}
+
+void stralg_amd_free_approx_result(struct stralg_amd_approx_result *result)
+{
+    if (!result) return;
+    free(result->first);
+    free(result->matches);
+    free(result->cigars);
+    free(result);
+}
+
+struct stralg_amd_approx_result *stralg_amd_bwt_approx_batch(struct bwt_table *t, const uint8_t *const *remapped_patterns,
+                                                             size_t count, int edits)
+{
+    if (!t || !t->sa || !t->remap_table || !t->c_table || !t->o_table || (count && !remapped_patterns) || count > 0xFFFFFFFEu) {
+        fprintf(stderr, "stralg_amd_bwt_approx_batch: malformed arguments\n");
+        return NULL;
+    }
+    sx_ctx *ctx = thread_ctx();
+    const uint32_t sigma = t->remap_table->alphabet_size;
+    const uint64_t N = t->sa->length;
+    struct stralg_amd_approx_result *res = calloc(1, sizeof *res);
+    uint32_t *offsets = malloc((count + 1) * sizeof *offsets);
+    uint64_t *hit_off = malloc((count + 1) * sizeof *hit_off);
+    size_t total_len = 0;
+    for (size_t q = 0; q < count; ++q) total_len += strlen((const char *)remapped_patterns[q]);
+    uint8_t *flat = malloc(total_len + 1);
+    if (!res || !offsets || !hit_off || !flat || total_len > 0xFFFFFFFFu) goto fail;
+    offsets[0] = 0;
+    for (size_t q = 0, at = 0; q < count; ++q) {
+        const size_t m = strlen((const char *)remapped_patterns[q]);
+        memcpy(flat + at, remapped_patterns[q], m);
+        at += m;
+        offsets[q + 1] = (uint32_t)at;
+    }
+    sx_approx_hit *hits = NULL;
+    uint64_t total = 0;
+    const int rc = sx_bwt_approx_search(ctx, t->c_table, t->o_table, t->ro_table, N, sigma, flat, offsets, (uint32_t)count, edits,
+                                        hit_off, &hits, &total);
+    if (rc != 0) {
+        fprintf(stderr, "stralg_amd_bwt_approx_batch: sx_bwt_approx_search failed (code %d): %s\n", rc, sx_last_error(ctx));
+        goto fail;
+    }
+    /* matches: every interval expanded through the suffix array; one CIGAR string an interval */
+    size_t n_matches = 0, cig_bytes = 0;
+    for (uint64_t h = 0; h < total; ++h) {
+        n_matches += hits[h].R - hits[h].L;
+        cig_bytes += 8u * ((offsets[hits[h].query + 1] - offsets[hits[h].query]) + SX_APPROX_MAX_EDITS) + 1;
+    }
+    res->count = count;
+    res->first = malloc((count + 1) * sizeof *res->first);
+    res->matches = malloc((n_matches ? n_matches : 1) * sizeof *res->matches);
+    res->cigars = malloc(cig_bytes ? cig_bytes : 1);
+    if (!res->first || !res->matches || !res->cigars) {
+        free(hits);
+        goto fail;
+    }
+    size_t at = 0, cat = 0;
+    for (size_t q = 0; q < count; ++q) {
+        res->first[q] = at;
+        for (uint64_t h = hit_off[q]; h < hit_off[q + 1]; ++h) {
+            char *cigar = res->cigars + cat;
+            cat += approx_cigar(cigar, offsets[q + 1] - offsets[q], &hits[h]);
+            for (uint32_t i = hits[h].L; i < hits[h].R; ++i) {
+                res->matches[at].position = t->sa->array[i];
+                res->matches[at].match_length = hits[h].match_length;
+                res->matches[at].cigar = cigar;
+                ++at;
+            }
+        }
+    }
+    res->first[count] = at;
+    free(hits);
+    free(flat);
+    free(offsets);
+    free(hit_off);
+    return res;
+fail:
+    free(flat);
+    free(offsets);
+    free(hit_off);
+    stralg_amd_free_approx_result(res);
+    return NULL;
+}

@@ -1,0 +1,444 @@
+// sx_approx.hip -- batched k-edit BWT search (stralg/bwt.c:226-422 init_bwt_approx_iter / next_bwt_approx_match).
+//
+// One lane searches one pattern at a time, depth first, in the reference's order: at a node the children are M over
+// a = 1 .. sigma-1 (cost 0 where a is the pattern symbol), then I, then D over a = 1 .. sigma-1 (the root has no D);
+// a node whose pattern is used up (i < 0) is a hit.  Two passes over the same search: the first counts every
+// pattern's hits, a scan turns the counts into offsets, the second writes the hits at their pattern's offset -- the
+// output depends on nothing but the pattern numbers, so it is the same from run to run however lanes pick up work.
+//
+// Design ("k-edit search"):
+//  * Frames only where edits are left.  A node with no edit left has one child that can lead anywhere, the exact M,
+//    so its whole subtree is the exact backward search of the rest of the pattern: the lane walks it in a loop of
+//    its own (the "chain") and pushes nothing.  A node with edits left is pushed as one 16-byte frame {L, R, next
+//    child | edits_left, i | match_length}; nodes with edits left form a prefix of the path, so frame d is the node
+//    at search depth d, and a path holds at most m + k - 1 of them.  Frames live in a workspace in device memory,
+//    frame d of lane t at stack[d * lanes + t] (a per-lane array indexed at run time would go to scratch anyway).
+//  * The edit string is never stored: matches and mismatches are both 'M' in the reference's CIGARs, so a path's
+//    CIGAR is fixed by its I/D operations, which a 128-bit shift register of 16-bit entries holds (push on the way
+//    down, pop on the way back).
+//  * D table in registers: it is non-decreasing and a node is cut when edits_left < D[i], i.e. when i >= brk[e]
+//    with brk[e] the first i where D[i] > e; only brk[0 .. k] matter.
+//  * Load balance: hit counts (and search trees) differ by orders of magnitude between patterns.  The lane's loop is
+//    flat -- one step of the search, of the chain or of starting a pattern per iteration -- and a lane that finishes
+//    its pattern takes the next one from a counter, so it does not wait for the rest of its wave.
+#include "sx_common.hpp"
+#include "sx_device.hpp"
+#include "sx_scan.hpp"
+
+#include <stdlib.h>
+
+namespace sx {
+
+#ifndef SX_APPROX_LANES
+#define SX_APPROX_LANES (1u << 18) // persistent lanes (1024 a CU); each holds a stack of (longest pattern + k) frames
+#endif
+
+constexpr int kApproxBlock = 256;
+constexpr int kMaxEdits = SX_APPROX_MAX_EDITS;
+
+struct ApproxArgs {
+    const uint32_t *c, *o, *ro;
+    uint64_t N;
+    uint32_t sigma;
+    const uint8_t *pat;
+    const uint32_t *off;
+    uint32_t count;
+    int k;
+    uint32_t lanes, frames; // frames per lane
+    uint4 *stack;
+    uint32_t *next;         // [0] work counter, [1] error word (a stack that would overflow)
+    uint32_t *counts;       // count pass: hits per pattern
+    unsigned long long *total;
+    const uint64_t *hit_off; // emit pass
+    uint4 *hits;
+    uint64_t cap;
+};
+
+enum : uint32_t { kFetch = 0, kScan = 1, kChain = 2 };
+
+__device__ __forceinline__ uint4 u4(uint32_t x, uint32_t y, uint32_t z, uint32_t w)
+{
+    uint4 v;
+    v.x = x;
+    v.y = y;
+    v.z = z;
+    v.w = w;
+    return v;
+}
+
+template <bool kEmit>
+__global__ __launch_bounds__(kApproxBlock) void bwt_approx_kernel(ApproxArgs A)
+{
+    const uint32_t t = blockIdx.x * kApproxBlock + threadIdx.x;
+    if (t >= A.lanes) return;
+    const uint32_t sigma = A.sigma;
+    const uint32_t nI = sigma - 1; // child index of I; M(a) is a - 1, D(a) is sigma - 1 + a
+    const uint32_t *__restrict__ C = A.c;
+    const uint32_t *__restrict__ O = A.o;
+    uint4 *stack = A.stack + t;
+
+    uint32_t mode = kFetch, q = 0, m = 0, cnt = 0;
+    const uint8_t *p = nullptr;
+    uint64_t out_base = 0;
+    uint32_t brk[kMaxEdits + 1];
+    // current node
+    uint32_t L = 0, R = 0, c = 0, depth = 0;
+    int32_t i = 0, e = 0;
+    uint32_t ml = 0;
+    // I/D operations on the path: 16-bit entries (search depth | D bit), the latest in the low bits
+    uint64_t g_lo = 0, g_hi = 0;
+    uint32_t ng = 0;
+    // chain (the exact search below a child with no edit left, or a hit right away)
+    uint32_t L2 = 0, R2 = 0, hml = 0, hlen = 0;
+    int32_t j = 0;
+
+    for (;;) {
+        if (mode == kChain) {
+            if (j >= 0 && L2 < R2) {
+                const uint32_t a = p[j];
+                L2 = C[a] + O[(uint64_t)L2 * sigma + a];
+                R2 = C[a] + O[(uint64_t)R2 * sigma + a];
+                --j;
+                continue;
+            }
+            if (L2 < R2) { // a hit: the interval, its match length, its I/D operations in pattern order
+                if (kEmit) {
+                    const uint64_t idx = out_base + cnt;
+                    if (idx < A.cap) {
+                        uint32_t gw[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+                        for (int s = 0; s < kMaxEdits; ++s) {
+                            if ((uint32_t)s < ng) {
+                                const uint32_t g = (uint32_t)((s < 4 ? g_lo >> (16 * s) : g_hi >> (16 * (s - 4))) & 0xFFFFu);
+                                const uint32_t v = ((hlen - 1u - (g & 0x7FFFu)) & 0x7FFFu) | (g & SX_APPROX_GAP_D);
+                                gw[s >> 1] |= v << (16 * (s & 1));
+                            }
+                        }
+                        A.hits[2 * idx] = u4(q, L2, R2, (hml & 0xFFFFu) | (ng << 16));
+                        A.hits[2 * idx + 1] = u4(gw[0], gw[1], gw[2], gw[3]);
+                    }
+                }
+                ++cnt;
+            }
+            if (c >= nI) { // back from an I or D child: its operation leaves the path
+                g_lo = (g_lo >> 16) | (g_hi << 48);
+                g_hi >>= 16;
+                --ng;
+            }
+            ++c;
+            mode = kScan;
+            continue;
+        }
+        if (mode == kScan) {
+            const uint32_t nchild = depth == 0 ? sigma : 2 * sigma - 1;
+            if (c < nchild) {
+                uint32_t nL = L, nR = R;
+                int32_t ci = i - 1, ce = e - 1;
+                bool take = false;
+                if (c != nI) { // M(a) or D(a): the same child interval
+                    const uint32_t a = c < nI ? c + 1 : c - nI;
+                    if (c < nI) ce = e - (a == (uint32_t)p[i] ? 0 : 1);
+                    else ci = i;
+                    if (ce >= 0) {
+                        nL = C[a] + O[(uint64_t)L * sigma + a];
+                        nR = C[a] + O[(uint64_t)R * sigma + a];
+                        take = nL < nR;
+                    }
+                } else {
+                    take = ce >= 0;
+                }
+                if (take && ci >= 0) { // the reference's cut at the child: edits_left < D[i]
+                    uint32_t b = brk[0];
+#pragma unroll
+                    for (int s = 1; s <= kMaxEdits; ++s)
+                        if (s == ce) b = brk[s];
+                    take = (uint32_t)ci < b;
+                }
+                if (!take) {
+                    ++c;
+                    continue;
+                }
+                const uint32_t cml = ml + (c == nI ? 0u : 1u);
+                if (c >= nI) { // I or D: onto the path's list of operations
+                    g_hi = (g_hi << 16) | (g_lo >> 48);
+                    g_lo = (g_lo << 16) | (uint64_t)(depth | (c > nI ? SX_APPROX_GAP_D : 0u));
+                    ++ng;
+                }
+                if (ci < 0 || ce == 0) { // a hit, or the exact search of the rest: no frame
+                    L2 = nL;
+                    R2 = nR;
+                    j = ci;
+                    hml = cml + (uint32_t)(ci + 1);
+                    hlen = depth + 1u + (uint32_t)(ci + 1);
+                    mode = kChain;
+                    continue;
+                }
+                if (depth >= A.frames) { // (cannot happen: frames = longest pattern + k)
+                    atomicOr(A.next + 1, 1u);
+                    mode = kFetch;
+                    if (!kEmit) A.counts[q] = cnt;
+                    continue;
+                }
+                stack[(uint64_t)depth * A.lanes] = u4(L, R, c | ((uint32_t)e << 16), (uint32_t)i | (ml << 16));
+                L = nL;
+                R = nR;
+                i = ci;
+                e = ce;
+                ml = cml;
+                c = 0;
+                ++depth;
+                continue;
+            }
+            if (depth > 0) { // the node is done: back to its parent, on to the parent's next child
+                --depth;
+                const uint4 f = stack[(uint64_t)depth * A.lanes];
+                L = f.x;
+                R = f.y;
+                c = f.z & 0xFFFFu;
+                e = (int32_t)(f.z >> 16);
+                i = (int32_t)(f.w & 0xFFFFu);
+                ml = f.w >> 16;
+                if (c >= nI) {
+                    g_lo = (g_lo >> 16) | (g_hi << 48);
+                    g_hi >>= 16;
+                    --ng;
+                }
+                ++c;
+                continue;
+            }
+            // the root is done
+            if (!kEmit) {
+                A.counts[q] = cnt;
+                if (cnt) atomicAdd(A.total, (unsigned long long)cnt);
+            }
+            mode = kFetch;
+            continue;
+        }
+        // kFetch: the next pattern
+        q = atomicAdd(A.next, 1u);
+        if (q >= A.count) break;
+        const uint32_t begin = A.off[q];
+        m = A.off[q + 1] - begin;
+        p = A.pat + begin;
+        cnt = 0;
+        if (kEmit) out_base = A.hit_off[q];
+        // symbols in [1, sigma) (the reference asserts it) and the D table's break points (bwt.c:319-338)
+        bool ok = m > 0;
+#pragma unroll
+        for (int s = 0; s <= kMaxEdits; ++s) brk[s] = m;
+        uint32_t rL = 0, rR = (uint32_t)A.N;
+        int32_t me = 0;
+        for (uint32_t s = 0; s < m; ++s) {
+            const uint32_t a = p[s];
+            if (a == 0 || a >= sigma) {
+                ok = false;
+                break;
+            }
+            if (A.ro && me <= A.k) {
+                rL = C[a] + A.ro[(uint64_t)rL * sigma + a];
+                rR = C[a] + A.ro[(uint64_t)rR * sigma + a];
+                if (rL >= rR) {
+                    ++me;
+#pragma unroll
+                    for (int b = 0; b <= kMaxEdits; ++b)
+                        if (b == me - 1) brk[b] = s;
+                    rL = 0;
+                    rR = (uint32_t)A.N;
+                }
+            }
+        }
+        if (!ok) {
+            if (!kEmit) A.counts[q] = 0;
+            continue;
+        }
+        L = 0;
+        R = (uint32_t)A.N;
+        i = (int32_t)m - 1;
+        e = A.k;
+        ml = 0;
+        c = 0;
+        depth = 0;
+        g_lo = g_hi = 0;
+        ng = 0;
+        mode = kScan;
+    }
+}
+
+struct InLen {
+    const uint32_t *off;
+    __device__ __forceinline__ uint32_t operator()(uint64_t q) const { return off[q + 1] - off[q]; }
+};
+struct OutNone {
+    __device__ __forceinline__ void operator()(uint64_t, uint32_t, uint32_t) const {}
+};
+struct OutOffsets64 {
+    uint64_t *p;
+    __device__ __forceinline__ void operator()(uint64_t q, uint32_t excl, uint32_t) const { p[q] = excl; }
+};
+
+__global__ void approx_finish_offsets_kernel(const unsigned long long *total, uint64_t *hit_off, uint32_t count)
+{
+    if (threadIdx.x == 0) hit_off[count] = *total;
+}
+
+static uint32_t approx_lanes(uint32_t count)
+{
+    const uint32_t want = ((count + kApproxBlock - 1) / kApproxBlock) * kApproxBlock;
+    return want < SX_APPROX_LANES ? want : SX_APPROX_LANES;
+}
+
+// count pass + offsets; the workspace (stack, counts, counters) stays in the N slab for the emit pass
+static int approx_count(sx_ctx *ctx, ApproxArgs &A, uint64_t *d_hit_off, uint64_t *total_out)
+{
+    // the longest pattern (the stack's depth, the 2^15 limit)
+    SX_TRY(sx_slab_ensure(ctx, SX_SLAB_BWT, 4096));
+    uint32_t *scal = (uint32_t *)ctx->slab[SX_SLAB_BWT].p; // [0] longest, [2..3] u64 total, [4] counter, [5] error
+    SX_CHECK(hipMemsetAsync(scal, 0, 64, ctx->stream));
+    SX_TRY((device_scan<OpMax>(ctx, A.count, InLen{A.off}, OutNone{}, scal, SX_KC_SEARCH, (uint64_t)A.count * 8)));
+    uint32_t longest = 0;
+    SX_TRY(sx_readback(ctx, scal, 1, &longest));
+    if ((uint64_t)longest + (uint64_t)A.k >= (1u << 15))
+        return sx_fail_msg(ctx, SX_E_ARG, "approximate search: pattern length + max_edits must stay below 2^15");
+    A.lanes = approx_lanes(A.count);
+    A.frames = longest + (uint32_t)A.k + 1u;
+    const size_t cnt_b = ((size_t)A.count * 4 + 255) & ~(size_t)255;
+    SX_TRY(sx_slab_ensure(ctx, SX_SLAB_N, cnt_b + (size_t)A.lanes * A.frames * sizeof(uint4)));
+    A.counts = (uint32_t *)ctx->slab[SX_SLAB_N].p;
+    A.stack = (uint4 *)((char *)ctx->slab[SX_SLAB_N].p + cnt_b);
+    A.total = (unsigned long long *)(scal + 2);
+    A.next = scal + 4;
+    sx_launch(ctx, SX_KC_SEARCH, 0, bwt_approx_kernel<false>, dim3(A.lanes / kApproxBlock), dim3(kApproxBlock), A);
+    SX_TRY((device_scan<OpAdd>(ctx, A.count, InU32{A.counts}, OutOffsets64{d_hit_off}, nullptr, SX_KC_SEARCH, (uint64_t)A.count * 12)));
+    sx_launch(ctx, SX_KC_SEARCH, 0, approx_finish_offsets_kernel, dim3(1), dim3(64), (const unsigned long long *)A.total, d_hit_off, A.count);
+    uint32_t h[4] = {0, 0, 0, 0};
+    SX_TRY(sx_readback(ctx, scal + 2, 4, h));
+    if (h[3]) return sx_fail_msg(ctx, SX_E_INTERNAL, "approximate search: a search stack overflowed");
+    const uint64_t total = (uint64_t)h[0] | ((uint64_t)h[1] << 32);
+    if (total >= (1ull << 32)) return sx_fail_msg(ctx, SX_E_ARG, "approximate search: 2^32 hits or more in one call");
+    *total_out = total;
+    return 0;
+}
+
+static int approx_emit(sx_ctx *ctx, ApproxArgs &A, const uint64_t *d_hit_off, sx_approx_hit *d_hits, uint64_t total)
+{
+    A.hit_off = d_hit_off;
+    A.hits = (uint4 *)d_hits;
+    A.cap = total;
+    SX_CHECK(hipMemsetAsync(A.next, 0, 8, ctx->stream));
+    sx_launch(ctx, SX_KC_SEARCH, total * sizeof(sx_approx_hit), bwt_approx_kernel<true>, dim3(A.lanes / kApproxBlock),
+              dim3(kApproxBlock), A);
+    uint32_t h[2] = {0, 0};
+    SX_TRY(sx_readback(ctx, A.next, 2, h));
+    if (h[1]) return sx_fail_msg(ctx, SX_E_INTERNAL, "approximate search: a search stack overflowed");
+    return 0;
+}
+
+static int approx_args(sx_ctx *ctx, ApproxArgs &A, const uint32_t *c, const uint32_t *o, const uint32_t *ro, uint64_t N,
+                       uint32_t sigma, const uint8_t *pat, const uint32_t *off, uint32_t count, int k)
+{
+    (void)ctx;
+    if (!c || !o || !off || N == 0 || N > 0xFFFFFFFFull || sigma < 2 || sigma > 256 || k > kMaxEdits) return SX_E_ARG;
+    A = ApproxArgs{};
+    A.c = c;
+    A.o = o;
+    A.ro = ro;
+    A.N = N;
+    A.sigma = sigma;
+    A.pat = pat;
+    A.off = off;
+    A.count = count;
+    A.k = k;
+    return 0;
+}
+
+} // namespace sx
+
+using namespace sx;
+
+extern "C" {
+
+int sx_bwt_approx_search_dev(sx_ctx *ctx, const uint32_t *d_c_table, const uint32_t *d_o_table,
+                             const uint32_t *d_ro_table, uint64_t N, uint32_t sigma, const uint8_t *d_patterns,
+                             const uint32_t *d_offsets, uint32_t count, int max_edits, uint64_t *d_hit_offsets,
+                             sx_approx_hit *d_hits, uint64_t hit_capacity, uint64_t *total_hits_out)
+{
+    if (!ctx || !d_hit_offsets || !total_hits_out || ((uintptr_t)d_hits & 15)) return SX_E_ARG;
+    ApproxArgs A;
+    SX_TRY(approx_args(ctx, A, d_c_table, d_o_table, d_ro_table, N, sigma, d_patterns, d_offsets, count, max_edits));
+    SX_CHECK(hipSetDevice(ctx->device));
+    *total_hits_out = 0;
+    if (max_edits < 0 || count == 0) { // no search: every offset 0
+        SX_CHECK(hipMemsetAsync(d_hit_offsets, 0, ((size_t)count + 1) * sizeof(uint64_t), ctx->stream));
+        return sx_sync(ctx);
+    }
+    uint64_t total = 0;
+    SX_TRY(approx_count(ctx, A, d_hit_offsets, &total));
+    *total_hits_out = total;
+    if (!d_hits) return sx_sync(ctx);
+    if (total > hit_capacity) {
+        SX_TRY(sx_sync(ctx));
+        sx_fail_msg(ctx, SX_E_CAPACITY, "approximate search: more hits than hit_capacity");
+        return SX_E_CAPACITY;
+    }
+    if (total) SX_TRY(approx_emit(ctx, A, d_hit_offsets, d_hits, total));
+    return sx_sync(ctx);
+}
+
+int sx_bwt_approx_search(sx_ctx *ctx, const uint32_t *c_table, const uint32_t *o_table, const uint32_t *ro_table,
+                         uint64_t N, uint32_t sigma, const uint8_t *patterns, const uint32_t *offsets, uint32_t count,
+                         int max_edits, uint64_t *hit_offsets, sx_approx_hit **hits_out, uint64_t *total_hits_out)
+{
+    if (!ctx || !hit_offsets || !hits_out || !total_hits_out) return SX_E_ARG;
+    *hits_out = nullptr;
+    *total_hits_out = 0;
+    ApproxArgs A;
+    SX_TRY(approx_args(ctx, A, c_table, o_table, ro_table, N, sigma, patterns, offsets, count, max_edits));
+    if (max_edits < 0 || count == 0) {
+        memset(hit_offsets, 0, ((size_t)count + 1) * sizeof(uint64_t));
+        return 0;
+    }
+    SX_CHECK(hipSetDevice(ctx->device));
+    // staging: C, O, RO, patterns, offsets, hit offsets (the hits themselves go to the M slab once their number is known)
+    const uint64_t plen = offsets[count];
+    const size_t c_b = ((size_t)sigma * 4 + 255) & ~(size_t)255, o_b = (((N + 1) * sigma * 4) + 255) & ~(size_t)255,
+                 p_b = (plen + 16 + 255) & ~(size_t)255, off_b = (((size_t)count + 1) * 4 + 255) & ~(size_t)255,
+                 ho_b = (((size_t)count + 1) * 8 + 255) & ~(size_t)255;
+    SX_TRY(sx_slab_ensure(ctx, SX_SLAB_IO, c_b + o_b * (ro_table ? 2 : 1) + p_b + off_b + ho_b));
+    char *base = (char *)ctx->slab[SX_SLAB_IO].p;
+    uint32_t *d_c = (uint32_t *)base, *d_o = (uint32_t *)(base + c_b);
+    uint32_t *d_ro = ro_table ? (uint32_t *)(base + c_b + o_b) : nullptr;
+    char *rest = base + c_b + o_b * (ro_table ? 2 : 1);
+    uint8_t *d_p = (uint8_t *)rest;
+    uint32_t *d_off = (uint32_t *)(rest + p_b);
+    uint64_t *d_ho = (uint64_t *)(rest + p_b + off_b);
+    SX_CHECK(hipMemcpyAsync(d_c, c_table, (size_t)sigma * 4, hipMemcpyHostToDevice, ctx->stream));
+    SX_CHECK(hipMemcpyAsync(d_o, o_table, (size_t)(N + 1) * sigma * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (ro_table) SX_CHECK(hipMemcpyAsync(d_ro, ro_table, (size_t)(N + 1) * sigma * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (plen) SX_CHECK(hipMemcpyAsync(d_p, patterns, plen, hipMemcpyHostToDevice, ctx->stream));
+    SX_CHECK(hipMemcpyAsync(d_off, offsets, ((size_t)count + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+    A.c = d_c;
+    A.o = d_o;
+    A.ro = d_ro;
+    A.pat = d_p;
+    A.off = d_off;
+    uint64_t total = 0;
+    SX_TRY(approx_count(ctx, A, d_ho, &total));
+    SX_CHECK(hipMemcpyAsync(hit_offsets, d_ho, ((size_t)count + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (total) {
+        SX_TRY(sx_slab_ensure(ctx, SX_SLAB_M, total * sizeof(sx_approx_hit)));
+        sx_approx_hit *d_hits = (sx_approx_hit *)ctx->slab[SX_SLAB_M].p;
+        SX_TRY(approx_emit(ctx, A, d_ho, d_hits, total));
+        sx_approx_hit *h = (sx_approx_hit *)malloc(total * sizeof(sx_approx_hit));
+        if (!h) return sx_fail_msg(ctx, SX_E_NOMEM, "approximate search: host hit array");
+        const hipError_t e = hipMemcpyAsync(h, d_hits, total * sizeof(sx_approx_hit), hipMemcpyDeviceToHost, ctx->stream);
+        if (e != hipSuccess || sx_sync(ctx) != 0) {
+            free(h);
+            return sx_fail_msg(ctx, SX_E_INTERNAL, "approximate search: hit download");
+        }
+        *hits_out = h;
+    }
+    *total_hits_out = total;
+    return sx_sync(ctx);
+}
+
+} // extern "C"
