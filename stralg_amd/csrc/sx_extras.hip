@@ -213,6 +213,9 @@ __global__ __launch_bounds__(kInvThreads) void inverse_refine_kernel(const uint2
 
 // workgroup = fine window: its pairs into LDS by target, the window out as one block
 constexpr int kInvWinThreads = 1024;
+#ifndef SX_INV_WINDOW_GRID
+#define SX_INV_WINDOW_GRID 65536ull // workgroups at most; more fine windows are strided over (the CPU test harness builds with 5)
+#endif
 __global__ __launch_bounds__(kInvWinThreads) void inverse_window_kernel(const uint2 *__restrict__ pairs2, uint64_t N,
                                                                         uint32_t *__restrict__ inv, const uint32_t *__restrict__ bad)
 {
@@ -539,7 +542,7 @@ static int permute_dev(sx_ctx *ctx, const uint32_t *d_sa, const uint32_t *values
                       nparts, wbits, cursor, pairs, bad);
             sx_launch(ctx, SX_KC_LCP, N * 16, inverse_refine_kernel, dim3(grid), dim3(kInvThreads), (const uint2 *)pairs, N, wbits, fine_cursor,
                       pairs2, bad);
-            uint32_t wgrid = (uint32_t)(nfine < 65536 ? nfine : 65536);
+            uint32_t wgrid = (uint32_t)(nfine < SX_INV_WINDOW_GRID ? nfine : SX_INV_WINDOW_GRID);
             sx_launch(ctx, SX_KC_LCP, N * 12, inverse_window_kernel, dim3(wgrid), dim3(kInvWinThreads), (const uint2 *)pairs2, N, d_inv,
                       (const uint32_t *)bad);
         } else {
@@ -558,14 +561,18 @@ static int permute_dev(sx_ctx *ctx, const uint32_t *d_sa, const uint32_t *values
 
 static int inverse_dev(sx_ctx *ctx, const uint32_t *d_sa, uint64_t N, uint32_t *d_inv) { return permute_dev(ctx, d_sa, nullptr, 0u, N, d_inv); }
 
+#ifndef SX_LCP_PHI_MAX
+#define SX_LCP_PHI_MAX (1ull << 31) // (the CPU test harness builds with a few thousand: both LCP forms on small arrays)
+#endif
 static int lcp_dev(sx_ctx *ctx, const uint8_t *d_text, const uint32_t *d_sa, uint64_t N, uint32_t *d_inv_opt,
                    uint32_t *d_lcp)
 {
     const uint64_t n = N - 1;
     const size_t text_b = (n + 128 + 255) & ~(size_t)255, arr_b = ((size_t)N * 4 + 255) & ~(size_t)255;
     uint32_t wbits_unused = 0;
-    // Phi form (round 5): arrays that take the three-pass scatter, up to 2^31 entries (its scratch: two more arrays of N words)
-    const bool by_phi = permute_three_passes(N, wbits_unused) && N <= (1ull << 31);
+    // Phi form (round 5): arrays that take the three-pass scatter, up to SX_LCP_PHI_MAX entries (its scratch: two more arrays
+    // of N words); longer ones take Kasai's chunks on top of the three-pass inverse
+    const bool by_phi = permute_three_passes(N, wbits_unused) && N <= (uint64_t)SX_LCP_PHI_MAX;
     SX_TRY(sx_slab_ensure(ctx, SX_SLAB_N, text_b + (d_inv_opt ? 0 : arr_b) + (by_phi ? 2 * arr_b : 0) + 256));
     uint8_t *T = (uint8_t *)ctx->slab[SX_SLAB_N].p; // padded copy: text[n] = 0 and zeros behind it
     uint32_t *inv = d_inv_opt ? d_inv_opt : (uint32_t *)((char *)ctx->slab[SX_SLAB_N].p + text_b);

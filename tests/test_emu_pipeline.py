@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import oracle
+from next_rows_cases import exact_patterns, fibonacci
 from stralg_amd.synth import synth, repeat_families
 
 
@@ -530,6 +531,152 @@ def test_next_rows(emu_ctx, golden):
         want = oracle.bwt_exact_search(ct, ot, 5, pats[k])
         got = (int(l[k]), int(r[k]))
         assert got == want or (got[0] >= got[1] and want[0] >= want[1]), (k, got, want)
+
+
+def test_inverse_lcp_every_form_and_entry(emu_ctx):
+    """inverse and LCP through all three entry points against the oracle, at N on both sides of the harness's three-pass
+    threshold (SX_INVERSE_TWO_PASS_FROM = 3000) and of its Phi limit (SX_LCP_PHI_MAX = 6000: longer arrays take Kasai's
+    chunks on top of the three-pass inverse); fine windows of 64 strided over by 5 workgroups (SX_INV_WINDOW_GRID), the
+    last one partly filled, and outputs one word off the 16-byte alignment (the window kernel's uint4 store falls back to
+    its scalar tail).  sx_sa_lcp_dev without an inverse output keeps the inverse in its own slab."""
+    rng = np.random.default_rng(23)
+    for N in (2999, 3000, 3001, 6000, 6001, 6337):
+        n = N - 1
+        dup = synth(n, 5, N)
+        dup[n // 2:n // 2 + n // 3] = dup[10:10 + n // 3]
+        for name, x, sigma in (("random", rng.integers(1, 5, n).astype(np.uint8), 5), ("one-symbol", np.ones(n, np.uint8), 2),
+                               ("fibonacci", fibonacci(n), 3), ("duplication", dup, 5)):
+            sa = oracle.sa_is(x, sigma)
+            want_inv, want_lcp = oracle.inverse(sa), oracle.lcp(x, sa)
+            inv, lcp = emu_ctx.inverse_lcp(x, sa)
+            assert (inv == want_inv).all() and (lcp == want_lcp).all(), (N, name, "sx_sa_inverse_lcp")
+            inv, _ = emu_ctx.inverse_lcp(x, sa, want_lcp=False)
+            assert (inv == want_inv).all(), (N, name, "sx_sa_inverse_lcp, inverse only")
+            for off in (0, 1):
+                buf_inv, buf_lcp = np.zeros(N + 1, np.uint32), np.zeros(N + 1, np.uint32)
+                d_inv, d_lcp = buf_inv[off:off + N], buf_lcp[off:off + N]
+                emu_ctx.sa_inverse_dev(sa, N, d_inv)
+                assert (d_inv == want_inv).all(), (N, name, off, "sx_sa_inverse_dev")
+                d_inv[:] = 0
+                emu_ctx.sa_lcp_dev(x, sa, N, d_inv, d_lcp)
+                assert (d_inv == want_inv).all() and (d_lcp == want_lcp).all(), (N, name, off, "sx_sa_lcp_dev")
+                d_lcp[:] = 0
+                emu_ctx.sa_lcp_dev(x, sa, N, None, d_lcp)
+                assert (d_lcp == want_lcp).all(), (N, name, off, "sx_sa_lcp_dev, no inverse output")
+                assert not buf_lcp[N if off == 0 else 0] and not buf_inv[N if off == 0 else 0]  # nothing beyond the arrays
+
+
+def test_exact_search_every_pattern(emu_ctx):
+    """sx_bwt_exact_search_dev: every pattern's (L, R) equal to the reference's arithmetic (bwt.c:164-199) exactly, empty
+    intervals included, for sigma from 2 to 256"""
+    rng = np.random.default_rng(31)
+    for sigma, n in ((2, 300), (5, 900), (21, 700), (128, 500), (256, 500)):
+        x = np.ones(n, np.uint8) if sigma == 2 else rng.integers(1, sigma, n).astype(np.uint8)
+        if sigma == 5:
+            x[600:800] = x[100:300]  # long repeats: wide intervals deep into the pattern
+        sa = oracle.sa_is(x, sigma)
+        ct, ot = oracle.c_table(x, sigma), oracle.o_table(x, sa, sigma)
+        pats, want = exact_patterns(x, sigma, rng)
+        offs = np.concatenate([[0], np.cumsum([p.size for p in pats])]).astype(np.uint32)
+        flat = np.concatenate(pats).astype(np.uint8)
+        assert flat.size == offs[-1]
+        count = len(pats)
+        l, r = np.full(count, 7, np.uint32), np.full(count, 7, np.uint32)
+        emu_ctx.bwt_exact_search_dev(np.ascontiguousarray(ct), np.ascontiguousarray(ot), sa.size, sigma, flat, offs, count, l, r)
+        for k in range(count):
+            w = want[k] if want[k] is not None else oracle.bwt_exact_search(ct, ot, sigma, pats[k])
+            assert (int(l[k]), int(r[k])) == w, (sigma, k, pats[k].size)
+
+
+def test_approx_several_patterns_a_lane(emu_ctx):
+    """sx_bwt_approx_search_dev with more patterns than lanes (the harness has SX_APPROX_LANES = 256): 200 distinct
+    patterns x 10 shuffled copies, k = 0 .. 3, with RO and without; each copy's stream equals the model's for its original,
+    hits follow the offsets; then too small a hit buffer on the same batch"""
+    import approx_model
+    from stralg_amd import _lib, api
+    rng = np.random.default_rng(41)
+    sigma, n = 5, 2500
+    x = rng.integers(1, sigma, n).astype(np.uint8)
+    x[1800:2100] = x[200:500]
+    sa, c, o, ro = approx_model.tables(x, sigma)
+    distinct = []
+    for _ in range(200):
+        m = int(rng.integers(7, 16))
+        a = int(rng.integers(0, n - m))
+        p = x[a:a + m].copy()
+        for _ in range(int(rng.integers(0, 3))):
+            p[int(rng.integers(0, m))] = int(rng.integers(1, sigma))
+        distinct.append(p)
+    order = rng.permutation(np.repeat(np.arange(200), 10))
+    pats = [distinct[q] for q in order]
+    off = np.concatenate([[0], np.cumsum([p.size for p in pats])]).astype(np.uint32)
+    flat = np.concatenate(pats).astype(np.uint8)
+    count = len(pats)
+
+    def run(k, r, capacity=None):
+        hit_off = np.zeros(count + 1, np.uint64)
+        total = emu_ctx.bwt_approx_search_dev(c, o, r, o.shape[0] - 1, sigma, flat, off, count, k, hit_off)
+        hits = np.zeros(max(total, 1), dtype=_lib.APPROX_HIT_DTYPE)
+        emu_ctx.bwt_approx_search_dev(c, o, r, o.shape[0] - 1, sigma, flat, off, count, k, hit_off, hits,
+                                      total if capacity is None else capacity)
+        return hit_off, hits[:total], total
+
+    first = np.full(200, -1)
+    for i, q in enumerate(order):
+        if first[q] < 0:
+            first[q] = i
+    for k in (0, 1, 2, 3):
+        for r in (ro, None):
+            hit_off, hits, total = run(k, r)
+            assert total > 0 and int(hit_off[-1]) == total
+            assert (hits["query"] == np.repeat(np.arange(count), np.diff(hit_off).astype(np.int64))).all(), (k, r is None)
+            # every copy's records (all but the pattern number) are its original's first copy's, byte for byte
+            rec = hits.view(np.uint32).reshape(-1, 8)[:, 1:]
+            for i, q in enumerate(order):
+                j = first[q]
+                assert (rec[hit_off[i]:hit_off[i + 1]].shape == rec[hit_off[j]:hit_off[j + 1]].shape and
+                        (rec[hit_off[i]:hit_off[i + 1]] == rec[hit_off[j]:hit_off[j + 1]]).all()), (k, r is None, i)
+            # and the first copies' streams are the model's
+            sel = np.concatenate([np.arange(hit_off[j], hit_off[j + 1]) for j in first]).astype(np.int64)
+            sel_off = np.concatenate([[0], np.cumsum([hit_off[j + 1] - hit_off[j] for j in first])]).astype(np.uint64)
+            got = api.approx_matches(hits[sel], sel_off, [distinct[q].size for q in range(200)], sa)
+            assert got == [approx_model.matches(c, o, r, sa, p, k) for p in distinct], (k, r is None)
+    hit_off = np.zeros(count + 1, np.uint64)
+    total = emu_ctx.bwt_approx_search_dev(c, o, ro, o.shape[0] - 1, sigma, flat, off, count, 2, hit_off)
+    hits = np.zeros(total, dtype=_lib.APPROX_HIT_DTYPE)
+    hit_off[:] = 0
+    with pytest.raises(api.StralgAmdError, match=str(_lib.SX_E_CAPACITY)):
+        emu_ctx.bwt_approx_search_dev(c, o, ro, o.shape[0] - 1, sigma, flat, off, count, 2, hit_off, hits[:total - 1], total - 1)
+    assert int(hit_off[-1]) == total and not hits.view(np.uint8).any()
+
+
+def test_approx_wide_alphabets_and_many_edits(emu_ctx):
+    """sigma = 256 (511 children a node) at k <= 2, sigma = 21 at k up to 5, and k = 8 on short patterns, with RO and without,
+    against the model"""
+    import approx_model
+    from stralg_amd import _lib, api
+    rng = np.random.default_rng(43)
+    for sigma, n, ks, lengths, npat in ((256, 400, (0, 1, 2), (1, 6), 12), (21, 600, (0, 2, 5), (1, 5), 10),
+                                        (4, 300, (8,), (1, 4), 6)):
+        x = rng.integers(1, sigma, n).astype(np.uint8)
+        sa, c, o, ro = approx_model.tables(x, sigma)
+        pats = []
+        for _ in range(npat):
+            m = int(rng.integers(*lengths))
+            a = int(rng.integers(0, n - m))
+            p = x[a:a + m].copy()
+            p[int(rng.integers(0, m))] = int(rng.integers(1, sigma))
+            pats.append(p)
+        off = np.concatenate([[0], np.cumsum([p.size for p in pats])]).astype(np.uint32)
+        flat = np.concatenate(pats).astype(np.uint8)
+        for k in ks:
+            for r in (ro, None):
+                hit_off = np.zeros(len(pats) + 1, np.uint64)
+                total = emu_ctx.bwt_approx_search_dev(c, o, r, o.shape[0] - 1, sigma, flat, off, len(pats), k, hit_off)
+                hits = np.zeros(max(total, 1), dtype=_lib.APPROX_HIT_DTYPE)
+                emu_ctx.bwt_approx_search_dev(c, o, r, o.shape[0] - 1, sigma, flat, off, len(pats), k, hit_off, hits, total)
+                got = api.approx_matches(hits[:total], hit_off, np.diff(off), sa)
+                assert got == [approx_model.matches(c, o, r, sa, p, k) for p in pats], (sigma, k, r is None)
 
 
 def test_fasta_ingest_and_remap(emu_routed, golden_fasta):

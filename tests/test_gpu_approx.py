@@ -31,13 +31,16 @@ def device_tables(ctx, sym, sigma):
     d_sa = torch.zeros(N, dtype=torch.int32, device="cuda")
     d_c = torch.zeros(sigma, dtype=torch.int32, device="cuda")
     d_o = torch.zeros((N + 1) * sigma, dtype=torch.int32, device="cuda")
-    ctx.sa_build_dev(d_text, n, sigma, d_sa)
-    ctx.bwt_tables_dev(d_text, d_sa, N, sigma, d_c, d_o)
     d_rev = torch.zeros(N + 16, dtype=torch.uint8, device="cuda")
-    ctx.reverse_dev(d_text, n, d_rev)
     d_rsa = torch.zeros(N, dtype=torch.int32, device="cuda")
     d_c2 = torch.zeros_like(d_c)
     d_ro = torch.zeros_like(d_o)
+    # (torch fills these on its own stream; the library's stream does not wait for it: a fill that ran late overwrote the
+    #  reversed text the library had written)
+    torch.cuda.synchronize()
+    ctx.sa_build_dev(d_text, n, sigma, d_sa)
+    ctx.bwt_tables_dev(d_text, d_sa, N, sigma, d_c, d_o)
+    ctx.reverse_dev(d_text, n, d_rev)
     ctx.sa_build_dev(d_rev, n, sigma, d_rsa)
     ctx.bwt_tables_dev(d_rev, d_rsa, N, sigma, d_c2, d_ro)
     del d_rsa, d_c2, d_rev, d_text
@@ -51,8 +54,10 @@ def device_search(ctx, d_c, d_o, d_ro, N, sigma, pat, off, k):
     d_pat = dev(np.concatenate([pat, np.zeros(16, np.uint8)]))
     d_off = dev(off, np.int32)
     d_hoff = torch.zeros(count + 1, dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()  # (the fill above is on torch's stream)
     total = ctx.bwt_approx_search_dev(d_c, d_o, d_ro, N, sigma, d_pat, d_off, count, k, d_hoff)
     d_hits = torch.zeros(max(total, 1) * 32, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
     assert ctx.bwt_approx_search_dev(d_c, d_o, d_ro, N, sigma, d_pat, d_off, count, k, d_hoff, d_hits, total) == total
     hits = d_hits.cpu().numpy()[:total * 32].view(_lib.APPROX_HIT_DTYPE)
     return d_hoff.cpu().numpy().view(np.uint64), hits
@@ -140,6 +145,7 @@ def test_dna_2p26_reads(gpu_ctx):
     # the exact search on the same patterns
     d_l = torch.zeros(len(reads), dtype=torch.int32, device="cuda")
     d_r = torch.zeros_like(d_l)
+    torch.cuda.synchronize()  # (the fills are on torch's stream)
     gpu_ctx.bwt_exact_search_dev(d_c, d_o, N, sigma, dev(np.concatenate([flat, np.zeros(16, np.uint8)])), dev(off, np.int32),
                                  len(reads), d_l, d_r)
     ex_l, ex_r = d_l.cpu().numpy().view(np.uint32), d_r.cpu().numpy().view(np.uint32)

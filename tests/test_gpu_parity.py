@@ -844,13 +844,24 @@ def test_beyond_31_bits(gpu_ctx):
     free, _ = torch.cuda.mem_get_info()
     if free < 150 * (1 << 30):
         pytest.skip("needs ~150 GiB of device memory")
-    n = (1 << 31) + 12345
-    text = torch.empty(n, dtype=torch.uint8, device="cuda")
-    gpu_ctx.synth_dev(text, n, 5, 99)
-    sa = torch.empty(n + 1, dtype=torch.int32, device="cuda")
-    gpu_ctx.sa_build_dev(text, n, 5, sa)
-    gpu_ctx.trim()  # the verification below needs the memory
-    _verify_sa_on_device(text, sa, n)
+    from stralg_amd import verify
+    # n = 2^31 - 1: N = 2^31, the largest LCP through Phi; n = 2^31 + 12345: Kasai's chunks on the three-pass inverse,
+    # whose window kernel strides over more than 65 536 fine windows
+    for n in ((1 << 31) + 12345, (1 << 31) - 1):
+        text = torch.empty(n, dtype=torch.uint8, device="cuda")
+        gpu_ctx.synth_dev(text, n, 5, 99)
+        sa = torch.empty(n + 1, dtype=torch.int32, device="cuda")
+        gpu_ctx.sa_build_dev(text, n, 5, sa)
+        gpu_ctx.trim()  # the verification below needs the memory
+        _verify_sa_on_device(text, sa, n)
+        inv = torch.empty(n + 1, dtype=torch.int32, device="cuda")
+        lcp = torch.empty(n + 1, dtype=torch.int32, device="cuda")
+        gpu_ctx.sa_inverse_dev(sa, n + 1, inv)
+        gpu_ctx.sa_lcp_dev(text, sa, n + 1, None, lcp)
+        gpu_ctx.trim()
+        verify.verify_inverse_lcp_on_device(text, sa, inv, lcp, n)
+        del text, sa, inv, lcp
+        torch.cuda.empty_cache()
 
 
 # BASELINE.json configs[1..3] at their sizes: 256 MiB DNA, 1 GiB DNA (SA + BWT + C/O), 1 GiB sigma = 256.
