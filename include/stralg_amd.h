@@ -58,6 +58,7 @@ enum {
     SX_KC_LCP,            /* inverse + LCP                                suffix_array.c:53-85  */
     SX_KC_SEARCH,         /* batched exact and k-edit BWT search          bwt.c:164-199, 226-422 */
     SX_KC_LOCAL_SORT,     /* hybrid LMS sort: sub-buckets ordered in LDS, ties listed          */
+    SX_KC_SAM,            /* SAM text of search hits: size pass, 64-bit scan, emit  bioinf/sam.c:4-10 */
     SX_KC_COUNT
 };
 
@@ -149,6 +150,10 @@ enum {
                                        takes the kernel of rounds 3 and 4 (pairs through LDS, stable passes where equal keys
                                        crowd a bin); 0 (default) = the lean kernel of round 5, which leaves only the workgroups it
                                        cannot finish to that one */
+    ,SX_FLAG_SAM_BATCH_READS = 18  /* sx_map_reads_stream: at most this many reads in one search batch (0: the default, 2^20;
+                                       tests set small values so that one run takes several batches) */
+    ,SX_FLAG_SAM_WINDOW_BYTES = 19 /* sx_map_reads_stream: bytes of SAM text per window, rounded up to 16 (0: the default and the
+                                       most, 32 MiB, one pinned staging buffer) */
 };
 int sx_ctx_set_flag(sx_ctx *ctx, int flag, int value);
 
@@ -243,12 +248,86 @@ int sx_bwt_approx_search(sx_ctx *ctx, const uint32_t *c_table, const uint32_t *o
 /* sink(user, section, data, bytes): consecutive chunks of one section after the other; data is only valid
  * during the call; a non-zero return aborts the build. */
 typedef int (*sx_sink_fn)(void *user, int section, const void *data, size_t bytes);
-enum { SX_SECTION_SA = 0, SX_SECTION_C = 1, SX_SECTION_O = 2 };
+enum { SX_SECTION_SA = 0, SX_SECTION_C = 1, SX_SECTION_O = 2, SX_SECTION_SAM = 3 /* sx_map_reads_stream */ };
 /* sx_build_tables, but the suffix array (when want_sa), the C table and the O table leave the device through
  * `sink` in 32 MiB chunks from pinned staging memory, in this order (the order of stralg/serialise.c:7-18 around
  * the remap table); the copy of a chunk overlaps the sink's work on the previous one. */
 int sx_build_tables_stream(sx_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t sigma, int want_sa, sx_sink_fn sink,
                            void *user);
+
+/* ---- the read mapper's output on the device (tools/readmappers/bwt_readmapper/bwt_readmapper.c) ---------------- */
+/* One batch of hits and what their SAM lines are made of; every pointer is device memory.  Hit h prints, for
+ * i = L .. R-1 ascending, the line of bioinf/sam.c print_sam_line
+ *     <qname>\t0\t<rname>\t<sa[i]+1>\t0\t<cigar>\t*\t0\t0\t<seq>\t<qual>\n
+ * with read = query / n_records and record rank = query % n_records (n_records == 1: query is the read, as
+ * sx_bwt_approx_search_dev leaves it).  Read q has its name at d_names[d_name_off[q] .. d_name_off[q+1]), sequence and
+ * quality alike (raw bytes, n_reads + 1 offsets each; the pattern length of the CIGAR is the sequence's length); record
+ * rank r has its name at d_rnames[d_rname_off[r] .. d_rname_off[r+1]).  The suffix array is d_sa (sa_len entries) for
+ * every record, or, when d_sa_list is given, d_sa_list[r] with d_sa_len_list[r] entries for rank r.  The CIGAR is
+ * rendered from gap[] as approx_cigar / cigar.c edits_to_cigar do (at most 80 bytes; 8 gaps need 70). */
+typedef struct sx_sam_batch {
+    const sx_approx_hit *d_hits; /* 16-byte aligned */
+    uint64_t n_hits;
+    const uint32_t *d_sa;
+    uint64_t sa_len;
+    const uint32_t *const *d_sa_list;
+    const uint64_t *d_sa_len_list;
+    const uint8_t *d_names, *d_seqs, *d_quals;
+    const uint32_t *d_name_off, *d_seq_off, *d_qual_off;
+    uint32_t n_reads;
+    const uint8_t *d_rnames;
+    const uint32_t *d_rname_off;
+    uint32_t n_records;
+} sx_sam_batch;
+/* Size pass and 64-bit scan: d_byte_offsets[h] (n_hits + 1 entries) <- the first output byte of hit h's lines,
+ * d_byte_offsets[n_hits] and *total_bytes_out <- the length of the text.  SX_E_ARG when a hit's query or interval lies
+ * outside the batch. */
+int sx_sam_layout_dev(sx_ctx *ctx, const sx_sam_batch *batch, uint64_t *d_byte_offsets, uint64_t *total_bytes_out);
+/* Bytes [byte_lo, byte_hi) of the text (byte_hi <= total_bytes) to d_out[0 .. byte_hi - byte_lo), d_out 16-byte
+ * aligned.  Windows may cut lines anywhere; the concatenation of consecutive windows is the text, and it is the same
+ * from run to run. */
+int sx_sam_emit_dev(sx_ctx *ctx, const sx_sam_batch *batch, const uint64_t *d_byte_offsets, uint64_t total_bytes, uint64_t byte_lo,
+                    uint64_t byte_hi, uint8_t *d_out);
+
+/* A FASTQ image indexed on the host (one pass of memchr over the file): read q's name is names[name_off[q] ..
+ * name_off[q+1]), its sequence seqs[seq_off[q] ..), its quality quals[qual_off[q] ..): the raw bytes of the record's
+ * first line behind '@' (blanks stay), of its second and of its fourth line; the third line is dropped
+ * (bioinf/fastq.c:17-35).  A file without a final newline is fine.  Out of contract, where the reference reads a line in
+ * pieces or crashes, and answered with SX_E_MALFORMED: a line of 2047 bytes or more, an empty name, sequence or quality
+ * line (so also blank lines between or behind the records; the first byte of a record's first line is dropped whatever
+ * it is, as the reference does), a record cut off before
+ * its fourth line, a NUL byte inside a record; SX_E_ARG: an image of 2^32 - 1 bytes or more.  Release with sx_fastq_free. */
+typedef struct sx_fastq {
+    uint32_t count;
+    uint8_t *names, *seqs, *quals;
+    uint32_t *name_off, *seq_off, *qual_off; /* count + 1 entries each */
+} sx_fastq;
+int sx_fastq_index(const uint8_t *file, size_t len, sx_fastq *out);
+void sx_fastq_free(sx_fastq *fq);
+
+/* One genome record of the mapper's list (host pointers): tables as build_complete_table leaves them. */
+typedef struct sx_map_record {
+    const char *name;          /* NUL-terminated */
+    const uint32_t *sa;        /* N entries */
+    const uint32_t *c_table;   /* sigma */
+    const uint32_t *o_table;   /* (N + 1) x sigma, position-major */
+    const uint32_t *ro_table;  /* the same of the reversed text, or NULL (then the D table is zeros) */
+    uint64_t N;
+    uint32_t sigma;
+    const signed char *remap;  /* 256 entries: the code of every byte, < 0 where the record lacks it (remap_table.table) */
+} sx_map_record;
+/* The mapper's loop (bwt_readmapper.c:130-160, 257-266) over a FASTQ image: for every read in file order, for every record in
+ * the order given, for every interval of the k-edit search in the iterator's order, for i = L .. R-1: one SAM line;
+ * byte-identical to the reference mapper's stdout.  A read with a byte that a record's remap table lacks has no lines
+ * for that record.  The text leaves through sink(user, SX_SECTION_SAM, data, bytes) in windows (SX_FLAG_SAM_WINDOW_BYTES)
+ * from two pinned staging buffers; the copy of a window overlaps the sink's work on the one before.  Reads are searched
+ * in batches (SX_FLAG_SAM_BATCH_READS) that are halved when their hits do not fit.  Memory: the reads, and every
+ * record's suffix array and tables (N x (4 + 8 sigma) bytes with RO) stay on the device for the whole call; 32 bytes a
+ * hit twice and 8 bytes a hit of offsets for one batch.  Limits: 0 <= edits <= 8, reads x records < 2^32, the FASTQ
+ * contract of sx_fastq_index (SX_E_MALFORMED); its lines of at most 2046 bytes keep every read below the search's limit
+ * (pattern length + edits < 2^15), so that limit cannot be met here. */
+int sx_map_reads_stream(sx_ctx *ctx, const sx_map_record *records, uint32_t n_records, const uint8_t *fastq, size_t fastq_len,
+                        int edits, sx_sink_fn sink, void *user);
 
 /* ---- FASTA ingest and remap on the device ---------------- */
 /* bioinf/fasta.c:92-135 load_fasta_records' packing of a file image in device memory into

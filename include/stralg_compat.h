@@ -245,6 +245,14 @@ struct stralg_amd_approx_result *stralg_amd_bwt_approx_batch(struct bwt_table *t
                                                              size_t count, int edits);
 void stralg_amd_free_approx_result(struct stralg_amd_approx_result *result);
 
+/* The body of bwt_readmapper.c's main behind read_string_tables (the loop over next_fastq_record with map_read,
+ * bwt_readmapper.c:130-160, 257-266) on the GPU: the rest of `fastq` is read, every read is searched in every table with at
+ * most `edits` edits, and the SAM lines of print_sam_line go to `sam`, byte-identical to the reference's and in its order:
+ * reads in file order, tables[0 .. n) in the order given (pass the mapper's list order: the reverse of the order in the
+ * .bwttables file), matches in the iterator's order.  names[r] is the record name of tables[r].  Returns 0, or the code of
+ * sx_map_reads_stream (SX_E_MALFORMED for a FASTQ stream outside the contract of sx_fastq_index) with a line on stderr. */
+int stralg_amd_map_reads(struct bwt_table *const *tables, const char *const *names, size_t n, FILE *fastq, int edits, FILE *sam);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,7 @@ include/stralg_amd.h.  There is no CPU fallback.
 from .api import (  # noqa: F401
     Context, SuffixArray, BwtTable, RemapTable, StralgAmdError,
     sa_is_construction, sa_is_mem_construction, skew_sa_construction,
-    remap_string, alloc_remap_table, remap, init_bwt_table, build_complete_table, bwt_approx_search,
+    remap_string, alloc_remap_table, remap, init_bwt_table, build_complete_table, bwt_approx_search, map_reads,
     default_context,
 )
 from .synth import synth  # noqa: F401

@@ -12,7 +12,7 @@ PRODUCT_LIB = os.path.join(_HERE, "libstralg_amd.so")
 
 KC_NAMES = ["classify", "samples", "keys", "radix_hist", "radix_scatter", "scan", "names", "doubling",
             "induce_gather", "induce_scan", "induce_scatter", "induce_chain", "bwt_gather", "otable", "misc",
-            "fasta", "remap", "lcp", "search", "local_sort"]
+            "fasta", "remap", "lcp", "search", "local_sort", "sam"]
 
 
 class KernelStat(C.Structure):
@@ -36,7 +36,33 @@ APPROX_MAX_EDITS = 8
 APPROX_GAP_D = 0x8000
 APPROX_HIT_DTYPE = [("query", "<u4"), ("L", "<u4"), ("R", "<u4"), ("match_length", "<u2"), ("n_gaps", "<u2"),
                     ("gap", "<u2", (APPROX_MAX_EDITS,))]
-SX_E_ARG, SX_E_CAPACITY = -1, -5
+SX_E_ARG, SX_E_MALFORMED, SX_E_CAPACITY = -1, -4, -5
+SX_SECTION_SAM = 3
+SX_FLAG_SAM_BATCH_READS, SX_FLAG_SAM_WINDOW_BYTES = 18, 19
+
+
+class SamBatch(C.Structure):
+    """include/stralg_amd.h sx_sam_batch (device pointers)"""
+    _fields_ = [("d_hits", C.c_void_p), ("n_hits", C.c_uint64), ("d_sa", C.c_void_p), ("sa_len", C.c_uint64),
+                ("d_sa_list", C.c_void_p), ("d_sa_len_list", C.c_void_p),
+                ("d_names", C.c_void_p), ("d_seqs", C.c_void_p), ("d_quals", C.c_void_p),
+                ("d_name_off", C.c_void_p), ("d_seq_off", C.c_void_p), ("d_qual_off", C.c_void_p), ("n_reads", C.c_uint32),
+                ("d_rnames", C.c_void_p), ("d_rname_off", C.c_void_p), ("n_records", C.c_uint32)]
+
+
+class Fastq(C.Structure):
+    """include/stralg_amd.h sx_fastq"""
+    _fields_ = [("count", C.c_uint32), ("names", C.c_void_p), ("seqs", C.c_void_p), ("quals", C.c_void_p),
+                ("name_off", C.c_void_p), ("seq_off", C.c_void_p), ("qual_off", C.c_void_p)]
+
+
+class MapRecord(C.Structure):
+    """include/stralg_amd.h sx_map_record (host pointers)"""
+    _fields_ = [("name", C.c_char_p), ("sa", C.c_void_p), ("c_table", C.c_void_p), ("o_table", C.c_void_p),
+                ("ro_table", C.c_void_p), ("N", C.c_uint64), ("sigma", C.c_uint32), ("remap", C.c_void_p)]
+
+
+SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t)
 
 
 def load(path=None):
@@ -80,6 +106,11 @@ def load(path=None):
         "sx_bwt_approx_search": (C.c_int, [vp, u32p, u32p, u32p, C.c_uint64, C.c_uint32, u8p, u32p, C.c_uint32, C.c_int,
                                            u64p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
         "sx_build_tables_stream": (C.c_int, [vp, u8p, C.c_uint64, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]),
+        "sx_sam_layout_dev": (C.c_int, [vp, C.POINTER(SamBatch), u64p, C.POINTER(C.c_uint64)]),
+        "sx_sam_emit_dev": (C.c_int, [vp, C.POINTER(SamBatch), u64p, C.c_uint64, C.c_uint64, C.c_uint64, u8p]),
+        "sx_fastq_index": (C.c_int, [u8p, C.c_size_t, C.POINTER(Fastq)]),
+        "sx_fastq_free": (None, [C.POINTER(Fastq)]),
+        "sx_map_reads_stream": (C.c_int, [vp, C.POINTER(MapRecord), C.c_uint32, u8p, C.c_size_t, C.c_int, SINK_FN, C.c_void_p]),
         "sx_fasta_pack_dev": (C.c_int, [vp, u8p, C.c_uint64, u8p, C.POINTER(C.c_uint64), u32p, C.c_uint64,
                                         C.POINTER(C.c_uint32)]),
         "sx_fasta_pack": (C.c_int, [vp, u8p, C.c_uint64, u8p, C.POINTER(C.c_uint64), u32p, C.c_uint64,
@@ -116,7 +147,7 @@ def load(path=None):
 EXPORTS = ["sx_device_count", "sx_device_numa_node", "sx_ctx_create", "sx_ctx_destroy", "sx_ctx_live_count", "sx_last_error", "sx_ctx_trim", "sx_ctx_set_flag",
            "sx_sa_build", "sx_sa_build_dev", "sx_sa_bwt_build_dev", "sx_bwt_tables", "sx_bwt_tables_dev",
            "sx_bwt_tables_from_bwt_dev", "sx_build_tables", "sx_sa_inverse_dev", "sx_sa_lcp_dev", "sx_sa_inverse_lcp",
-           "sx_bwt_exact_search_dev", "sx_bwt_approx_search_dev", "sx_bwt_approx_search", "sx_build_tables_stream", "sx_fasta_pack_dev", "sx_fasta_pack", "sx_remap_dev", "sx_reverse_dev", "sx_profile_enable", "sx_profile_only",
+           "sx_bwt_exact_search_dev", "sx_bwt_approx_search_dev", "sx_bwt_approx_search", "sx_build_tables_stream", "sx_sam_layout_dev", "sx_sam_emit_dev", "sx_fastq_index", "sx_fastq_free", "sx_map_reads_stream", "sx_fasta_pack_dev", "sx_fasta_pack", "sx_remap_dev", "sx_reverse_dev", "sx_profile_enable", "sx_profile_only",
            "sx_profile_reset", "sx_profile_read", "sx_kernel_class_name", "sx_last_stats",
            "sx_synth_dev", "sx_membw_probe", "sx_prim_sort_pairs_dev", "sx_prim_exclusive_sum_dev", "sx_prim_classify_dev"]
 

@@ -7,6 +7,7 @@ or GPU raises -- there is no CPU fallback.
 """
 import ctypes as C
 import threading
+import time
 
 import numpy as np
 
@@ -169,6 +170,95 @@ class Context:
             C.memmove(hits.ctypes.data, hp.value, n * hits.dtype.itemsize)
             _libc_free(hp.value)
         return hit_off, hits
+
+    # ---- SAM text of search hits (the read mapper's output) ---------------------------------
+    def sam_batch(self, d_hits, n_hits, d_sa, sa_len, d_names, d_name_off, d_seqs, d_seq_off, d_quals, d_qual_off, n_reads,
+                  d_rnames, d_rname_off, n_records=1, d_sa_list=None, d_sa_len_list=None):
+        """sx_sam_batch over device tensors (the caller keeps them alive): hits as sx_bwt_approx_search_dev leaves them,
+        the suffix array, the reads' flat name / sequence / quality bytes with n_reads + 1 offsets each (uint32), the
+        record names likewise."""
+        return _lib.SamBatch(_ptr(d_hits), n_hits, _ptr(d_sa), sa_len, _ptr(d_sa_list), _ptr(d_sa_len_list), _ptr(d_names),
+                             _ptr(d_seqs), _ptr(d_quals), _ptr(d_name_off), _ptr(d_seq_off), _ptr(d_qual_off), n_reads,
+                             _ptr(d_rnames), _ptr(d_rname_off), n_records)
+
+    def sam_layout_dev(self, batch, d_byte_offsets):
+        """sx_sam_layout_dev: d_byte_offsets (n_hits + 1 uint64) <- every hit's first output byte; returns the text's length"""
+        total = C.c_uint64(0)
+        self._check(self.lib.sx_sam_layout_dev(self.h, C.byref(batch), _ptr(d_byte_offsets), C.byref(total)), "sx_sam_layout_dev")
+        return int(total.value)
+
+    def sam_emit_dev(self, batch, d_byte_offsets, total_bytes, byte_lo, byte_hi, d_out):
+        """sx_sam_emit_dev: bytes [byte_lo, byte_hi) of the text into d_out (uint8, 16-byte aligned)"""
+        self._check(self.lib.sx_sam_emit_dev(self.h, C.byref(batch), _ptr(d_byte_offsets), total_bytes, byte_lo, byte_hi,
+                                             _ptr(d_out)), "sx_sam_emit_dev")
+
+    def fastq_index(self, data):
+        """sx_fastq_index of the bytes of a FASTQ file: (names, name_off, seqs, seq_off, quals, qual_off) as numpy arrays
+        (uint8 bytes, uint32 offsets of count + 1 entries); raises StralgAmdError (code SX_E_MALFORMED = -4) outside the
+        contract (include/stralg_amd.h)."""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        fq = _lib.Fastq()
+        rc = self.lib.sx_fastq_index(_ptr(buf) if buf.size else None, buf.size, C.byref(fq))
+        if rc != 0:
+            raise StralgAmdError(f"sx_fastq_index failed with code {rc}")
+        try:
+            n = int(fq.count)
+            out = []
+            for data_p, off_p in ((fq.names, fq.name_off), (fq.seqs, fq.seq_off), (fq.quals, fq.qual_off)):
+                off = np.ctypeslib.as_array(C.cast(off_p, C.POINTER(C.c_uint32)), (n + 1,)).copy()
+                nbytes = int(off[n])
+                out.append(np.ctypeslib.as_array(C.cast(data_p, C.POINTER(C.c_uint8)), (nbytes,)).copy() if nbytes
+                           else np.zeros(0, np.uint8))
+                out.append(off)
+            return tuple(out)
+        finally:
+            self.lib.sx_fastq_free(C.byref(fq))
+
+    def set_sam_batch_reads(self, reads):
+        """sx_map_reads_stream: at most this many reads in one search batch (0: the default)"""
+        self._check(self.lib.sx_ctx_set_flag(self.h, _lib.SX_FLAG_SAM_BATCH_READS, int(reads)), "sx_ctx_set_flag")
+
+    def set_sam_window_bytes(self, nbytes):
+        """sx_map_reads_stream: bytes of SAM text per window (0: the default, 32 MiB)"""
+        self._check(self.lib.sx_ctx_set_flag(self.h, _lib.SX_FLAG_SAM_WINDOW_BYTES, int(nbytes)), "sx_ctx_set_flag")
+
+    def map_reads_stream(self, records, fastq, edits, sink):
+        """sx_map_reads_stream: records = [(name bytes, BwtTable), ...] in the mapper's list order; sink(bytes) receives the
+        SAM text window after window.  sink=None discards the text without touching it and returns [(time.perf_counter(),
+        bytes)] per window (measurement)."""
+        recs = (_lib.MapRecord * max(1, len(records)))()
+        keep = []
+        for r, (name, t) in enumerate(records):
+            sa = np.ascontiguousarray(t.sa.array, dtype=np.uint32)
+            c = np.ascontiguousarray(t.c_table, dtype=np.uint32)
+            o = np.ascontiguousarray(t.o_table, dtype=np.uint32)
+            ro = None if t.ro_table is None else np.ascontiguousarray(t.ro_table, dtype=np.uint32)
+            tab = np.ascontiguousarray(np.clip(t.remap_table.table, -1, 127), dtype=np.int8)
+            keep.append((sa, c, o, ro, tab))
+            recs[r] = _lib.MapRecord(bytes(name), _ptr(sa), _ptr(c), _ptr(o), _ptr(ro), sa.size, t.remap_table.alphabet_size,
+                                     _ptr(tab))
+        buf = np.frombuffer(bytes(fastq), dtype=np.uint8)
+        failure = []
+
+        seen = []
+
+        def _sink(user, section, data, nbytes):
+            try:
+                if sink is None:
+                    seen.append((time.perf_counter(), nbytes))
+                else:
+                    sink(C.string_at(data, nbytes))
+                return 0
+            except Exception as e:  # (an exception must not cross the C frames)
+                failure.append(e)
+                return 1
+
+        cb = _lib.SINK_FN(_sink)
+        rc = self.lib.sx_map_reads_stream(self.h, recs, len(records), _ptr(buf) if buf.size else None, buf.size, edits, cb, None)
+        if failure:
+            raise failure[0]
+        self._check(rc, "sx_map_reads_stream")
+        return seen if sink is None else None
 
     # ---- FASTA ingest and remap (SURVEY.md section 8f row 2) ------------------------------
     def fasta_pack_dev(self, d_file, file_len, d_packed, d_term=None, term_cap=0):
@@ -517,3 +607,15 @@ def bwt_approx_search(bwt_table, patterns, edits, ctx=None):
     hit_off, hits = ctx.bwt_approx_search(bwt_table.c_table, bwt_table.o_table, bwt_table.ro_table,
                                           bwt_table.remap_table.alphabet_size, flat, offsets, edits)
     return approx_matches(hits, hit_off, [p.size for p in pats], bwt_table.sa.array)
+
+
+def map_reads(fasta, fastq, edits, ctx=None):
+    """The reference read mapper (tools/readmappers/bwt_readmapper: -p genome.fa, then -d edits genome.fa reads.fq) on the
+    bytes of a FASTA and a FASTQ file: its stdout, the SAM lines of every match of every read in every record within
+    `edits` edits, byte for byte.  Per read the records come in the mapper's list order, which is the FASTA file's order
+    (the iterator yields the records last first, -p writes them so, and -d prepends each to its list)."""
+    ctx = ctx or default_context()
+    records = [(name, build_complete_table(seq, True, ctx)) for name, seq in ctx.fasta_records(fasta)]
+    chunks = []
+    ctx.map_reads_stream(records, fastq, edits, chunks.append)
+    return b"".join(chunks)

@@ -1652,3 +1652,136 @@ fail:
     stralg_amd_free_approx_result(res);
     return NULL;
 }
+
+/* ---- FASTQ index (bioinf/fastq.c:17-35 next_fastq_record, as one pass over a file image) ------------------- */
+
+void sx_fastq_free(sx_fastq *fq)
+{
+    if (!fq) return;
+    free(fq->names);
+    free(fq->seqs);
+    free(fq->quals);
+    free(fq->name_off);
+    free(fq->seq_off);
+    free(fq->qual_off);
+    memset(fq, 0, sizeof *fq);
+}
+
+/* the line at `at`: its end (the newline or the image's end); false at the image's end or when it is too long */
+static bool fastq_line(const uint8_t *file, size_t len, size_t at, size_t *end)
+{
+    if (at >= len) return false;
+    const uint8_t *nl = memchr(file + at, '\n', len - at);
+    *end = nl ? (size_t)(nl - file) : len;
+    return *end - at < 2047; /* fgets(buffer, 2048) takes 2047 bytes, the newline among them */
+}
+
+int sx_fastq_index(const uint8_t *file, size_t len, sx_fastq *out)
+{
+    if (!out || (len && !file)) return SX_E_ARG;
+    memset(out, 0, sizeof *out);
+    if (len > 0xFFFFFFFEu) return SX_E_ARG;
+    /* pass 1 over the lines: count the records and the bytes of each kind; pass 2 copies */
+    for (int pass = 0; pass < 2; ++pass) {
+        size_t at = 0, nb = 0, sb = 0, qb = 0;
+        uint32_t count = 0;
+        while (at < len) {
+            size_t e[4], from = at;
+            for (int l = 0; l < 4; ++l) {
+                if (!fastq_line(file, len, from, &e[l])) goto malformed;
+                /* strtok(.., "\n") of an empty line is NULL in the reference; the third line may hold anything */
+                if (l != 2 && e[l] == from + (l == 0 ? 1u : 0u)) goto malformed;
+                if (l == 0 && file[from] == '\n') goto malformed;
+                if (l < 3) from = e[l] + 1;
+            }
+            const size_t n0 = at + 1, s0 = e[0] + 1, q0 = e[2] + 1;
+            if (memchr(file + at, '\0', e[3] - at)) goto malformed; /* (the reference's strings end at a NUL) */
+            if (pass) {
+                out->name_off[count] = (uint32_t)nb;
+                out->seq_off[count] = (uint32_t)sb;
+                out->qual_off[count] = (uint32_t)qb;
+                memcpy(out->names + nb, file + n0, e[0] - n0);
+                memcpy(out->seqs + sb, file + s0, e[1] - s0);
+                memcpy(out->quals + qb, file + q0, e[3] - q0);
+            }
+            nb += e[0] - n0;
+            sb += e[1] - s0;
+            qb += e[3] - q0;
+            ++count;
+            at = e[3] + 1;
+        }
+        if (pass) {
+            out->name_off[count] = (uint32_t)nb;
+            out->seq_off[count] = (uint32_t)sb;
+            out->qual_off[count] = (uint32_t)qb;
+            break;
+        }
+        out->count = count;
+        out->names = malloc(nb + 1);
+        out->seqs = malloc(sb + 1);
+        out->quals = malloc(qb + 1);
+        out->name_off = malloc(((size_t)count + 1) * sizeof(uint32_t));
+        out->seq_off = malloc(((size_t)count + 1) * sizeof(uint32_t));
+        out->qual_off = malloc(((size_t)count + 1) * sizeof(uint32_t));
+        if (!out->names || !out->seqs || !out->quals || !out->name_off || !out->seq_off || !out->qual_off) {
+            sx_fastq_free(out);
+            return SX_E_NOMEM;
+        }
+    }
+    return 0;
+malformed:
+    sx_fastq_free(out);
+    return SX_E_MALFORMED;
+}
+
+/* ---- the read mapper's loop (bwt_readmapper.c:257-266 with map_read, :130-160) --------------------------------- */
+
+static int sam_to_file(void *user, int section, const void *data, size_t bytes)
+{
+    (void)section;
+    return fwrite(data, 1, bytes, (FILE *)user) == bytes ? 0 : 1;
+}
+
+int stralg_amd_map_reads(struct bwt_table *const *tables, const char *const *names, size_t n, FILE *fastq, int edits, FILE *sam)
+{
+    if ((n && (!tables || !names)) || !fastq || !sam || n > 0xFFFFFFFFu) {
+        fprintf(stderr, "stralg_amd_map_reads: malformed arguments\n");
+        return SX_E_ARG;
+    }
+    sx_map_record *recs = calloc(n ? n : 1, sizeof *recs);
+    size_t cap = 1 << 20, len = 0;
+    uint8_t *image = malloc(cap);
+    int rc = SX_E_NOMEM;
+    if (!recs || !image) goto done;
+    for (;;) { /* the rest of the stream */
+        const size_t got = fread(image + len, 1, cap - len, fastq);
+        len += got;
+        if (len < cap) break;
+        uint8_t *grown = realloc(image, cap *= 2);
+        if (!grown) goto done;
+        image = grown;
+    }
+    for (size_t r = 0; r < n; ++r) {
+        const struct bwt_table *t = tables[r];
+        if (!t || !t->sa || !t->remap_table || !t->c_table || !t->o_table || !names[r]) {
+            fprintf(stderr, "stralg_amd_map_reads: table %zu is incomplete\n", r);
+            rc = SX_E_ARG;
+            goto done;
+        }
+        recs[r].name = names[r];
+        recs[r].sa = t->sa->array;
+        recs[r].c_table = t->c_table;
+        recs[r].o_table = t->o_table;
+        recs[r].ro_table = t->ro_table;
+        recs[r].N = t->sa->length;
+        recs[r].sigma = t->remap_table->alphabet_size;
+        recs[r].remap = t->remap_table->table;
+    }
+    sx_ctx *ctx = thread_ctx();
+    rc = sx_map_reads_stream(ctx, recs, (uint32_t)n, image, len, edits, sam_to_file, sam);
+    if (rc != 0) fprintf(stderr, "stralg_amd_map_reads: failed (code %d): %s\n", rc, sx_last_error(ctx));
+done:
+    free(recs);
+    free(image);
+    return rc;
+}

@@ -87,6 +87,8 @@ struct sx_ctx {
     int local_sort_lean_off = 0; // SX_FLAG_LOCAL_SORT_LEAN_OFF
     int64_t small_direct_max = -1; // SX_FLAG_SMALL_DIRECT_MAX; -1 = the default
     int copy_text_first = 0;  // SX_FLAG_COPY_TEXT_FIRST
+    int64_t sam_batch_reads = 0;  // SX_FLAG_SAM_BATCH_READS; 0 = the default
+    int64_t sam_window_bytes = 0; // SX_FLAG_SAM_WINDOW_BYTES; 0 = the default
     int64_t sample_min = -1;  // SX_FLAG_SAMPLE_MIN; -1 = texts of 2^20 suffixes and more get the look at a sample
     int64_t recurse_min = -1; // SX_FLAG_RECURSE_MIN; -1 = the default length from which a reduced string of <= 255 names recurses
     sx_ctx *child = nullptr;  // the context a reduced string over a byte alphabet is sorted in (sx_build.hip), created on first use

@@ -9,7 +9,7 @@
 static const char *kClassNames[SX_KC_COUNT] = {
     "classify", "samples", "keys", "radix_hist", "radix_scatter", "scan", "names",
     "doubling", "induce_gather", "induce_scan", "induce_scatter", "induce_chain", "bwt_gather", "otable", "misc",
-    "fasta", "remap", "lcp", "search", "local_sort",
+    "fasta", "remap", "lcp", "search", "local_sort", "sam",
 };
 
 int sx_fail(sx_ctx *ctx, int code, const char *what, const char *file, int line)
@@ -395,6 +395,14 @@ int sx_ctx_set_flag(sx_ctx *ctx, int flag, int value)
     }
     if (flag == SX_FLAG_LOCAL_SORT_LEAN_OFF) {
         ctx->local_sort_lean_off = value ? 1 : 0;
+        return 0;
+    }
+    if (flag == SX_FLAG_SAM_BATCH_READS) {
+        ctx->sam_batch_reads = value > 0 ? value : 0;
+        return 0;
+    }
+    if (flag == SX_FLAG_SAM_WINDOW_BYTES) {
+        ctx->sam_window_bytes = value > 0 ? value : 0;
         return 0;
     }
     if (flag == SX_FLAG_INDUCE_NO_HOIST) {

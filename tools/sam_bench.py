@@ -1,0 +1,193 @@
+"""SAM text of k-edit search hits on the device (sx_sam_layout_dev / sx_sam_emit_dev): the reads and the 2^28-symbol DNA
+record of tools/approx_bench.py, k = 1 and 2.  Prints one JSON line (kept in profiles/sam_bench_2p28.json): per k the hits,
+lines and bytes of text, ms and GB/s of the layout pass and of the emit pass into device memory (HIP events of the
+SX_KC_SAM class; the emit pass fills one window buffer again and again) next to the bytes each moves, the search's kernel
+ms on the same batch, the box's fill rate (sx_membw_probe), the rate of a plain pinned device-to-host copy, and the
+streamed form (sx_map_reads_stream from host tables through a sink that discards) as wall time and as the rate of its
+windows, a fraction of that copy rate; the host's FASTQ index pass.
+
+    python tools/sam_bench.py [--log2n 28] [--reads 1000000] [--window-mib 1024]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--log2n", type=int, default=28)
+    ap.add_argument("--reads", type=int, default=1_000_000)
+    ap.add_argument("--length", type=int, default=100)
+    ap.add_argument("--window-mib", type=int, default=1024)
+    ap.add_argument("--ks", default="1,2")
+    ap.add_argument("--reference-lines-per-s", type=float, default=0.0,
+                    help="the reference mapper's rate measured elsewhere, recorded in the line as given")
+    args = ap.parse_args()
+    import torch
+
+    from stralg_amd import Context, synth
+
+    ctx = Context(0)
+    n, sigma, L = 1 << args.log2n, 5, args.length
+    text = synth(n, sigma, 28)
+    N = n + 1
+    d_text = torch.from_numpy(np.concatenate([text, np.zeros(16, np.uint8)])).cuda()
+    d_sa = torch.zeros(N, dtype=torch.int32, device="cuda")
+    d_c = torch.zeros(sigma, dtype=torch.int32, device="cuda")
+    d_o = torch.zeros((N + 1) * sigma, dtype=torch.int32, device="cuda")
+    ctx.sa_build_dev(d_text, n, sigma, d_sa)
+    ctx.bwt_tables_dev(d_text, d_sa, N, sigma, d_c, d_o)
+    d_rev = torch.zeros(N + 16, dtype=torch.uint8, device="cuda")
+    ctx.reverse_dev(d_text, n, d_rev)
+    d_rsa = torch.zeros(N, dtype=torch.int32, device="cuda")
+    d_c2 = torch.zeros_like(d_c)
+    d_ro = torch.zeros_like(d_o)
+    ctx.sa_build_dev(d_rev, n, sigma, d_rsa)
+    ctx.bwt_tables_dev(d_rev, d_rsa, N, sigma, d_c2, d_ro)
+    del d_rsa, d_c2, d_rev, d_text
+    torch.cuda.empty_cache()
+
+    # the reads of tools/approx_bench.py; as a FASTQ file they are named read<q>, letters ACGT, quality '~'
+    rng = np.random.default_rng(100)
+    R = args.reads
+    starts = rng.integers(0, n - L, R)
+    reads = text[starts[:, None] + np.arange(L)[None, :]]
+    for e in range(2):
+        hit = rng.random(R) < (0.5 if e == 0 else 0.25)
+        at = rng.integers(0, L, R)
+        rows = np.flatnonzero(hit)
+        reads[rows, at[rows]] = 1 + (reads[rows, at[rows]] % 4)
+    flat = np.ascontiguousarray(reads.reshape(-1))
+    off = (np.arange(R + 1, dtype=np.uint64) * L).astype(np.uint32)
+    names = [b"read%d" % q for q in range(R)]
+    name_off = np.zeros(R + 1, np.uint32)
+    name_off[1:] = np.cumsum([len(x) for x in names])
+    pad = np.zeros(16, np.uint8)
+    d_pat = torch.from_numpy(np.concatenate([flat, pad])).cuda()
+    d_off = torch.from_numpy(off.view(np.int32)).cuda()
+    d_names = torch.from_numpy(np.concatenate([np.frombuffer(b"".join(names), np.uint8), pad])).cuda()
+    d_name_off = torch.from_numpy(name_off.view(np.int32)).cuda()
+    d_seqs = torch.from_numpy(np.concatenate([np.frombuffer(b"\0ACGT", np.uint8)[flat], pad])).cuda()
+    d_quals = torch.full((R * L + 16,), ord("~"), dtype=torch.uint8, device="cuda")
+    d_rname = torch.from_numpy(np.concatenate([np.frombuffer(b"chr1", np.uint8), pad])).cuda()
+    d_rname_off = torch.tensor([0, 4], dtype=torch.int32, device="cuda")
+    d_hoff = torch.zeros(R + 1, dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()  # (torch fills on its own stream)
+
+    def profiled(kclass, fn):
+        ctx.profile_only(kclass)
+        ctx.profile_enable(True)
+        ctx.profile_reset()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = fn()
+        torch.cuda.synchronize()
+        wall = time.perf_counter() - t0
+        ms = ctx.profile_read()[kclass]["ms"]
+        ctx.profile_enable(False)
+        return res, wall, ms
+
+    window = args.window_mib << 20
+    d_win = torch.zeros(window + 16, dtype=torch.uint8, device="cuda")
+    d_other = torch.zeros(window + 16, dtype=torch.uint8, device="cuda")
+    probe = ctx.membw_probe(d_win, d_other, window, 5)
+    del d_other
+    h_pin = torch.empty(min(window, 256 << 20), dtype=torch.uint8).pin_memory()
+    link = []
+    for _ in range(3):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        h_pin.copy_(d_win[:h_pin.numel()], non_blocking=True)
+        torch.cuda.synchronize()
+        link.append(h_pin.numel() / (time.perf_counter() - t0) / 1e9)
+    out = {"bench": "sam_text", "n": n, "sigma": sigma, "reads": R, "read_length": L, "window_bytes": window,
+           "membw_probe_GBps": {"read": round(probe["read"], 1), "fill": round(probe["fill"], 1), "copy": round(probe["copy"], 1)},
+           "pinned_d2h_copy_GBps": round(max(link), 2)}
+
+    for k in [int(x) for x in args.ks.split(",")]:
+        total = ctx.bwt_approx_search_dev(d_c, d_o, d_ro, N, sigma, d_pat, d_off, R, k, d_hoff)
+        d_hits = torch.zeros(max(total, 1) * 32, dtype=torch.uint8, device="cuda")
+        d_boff = torch.zeros(total + 1, dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        _, _, search_ms = profiled("search", lambda: ctx.bwt_approx_search_dev(d_c, d_o, d_ro, N, sigma, d_pat, d_off, R, k,
+                                                                             d_hoff, d_hits, total))
+        batch = ctx.sam_batch(d_hits, total, d_sa, N, d_names, d_name_off, d_seqs, d_off, d_quals, d_off, R, d_rname,
+                              d_rname_off, 1)
+        ctx.sam_layout_dev(batch, d_boff)  # warm-up
+        nbytes, _, layout_ms = profiled("sam", lambda: ctx.sam_layout_dev(batch, d_boff))
+        words = d_hits[:total * 32].view(torch.int32).reshape(-1, 8)  # (query, L, R, ...)
+        lines = int(((words[:, 2].to(torch.int64) & 0xFFFFFFFF) - (words[:, 1].to(torch.int64) & 0xFFFFFFFF)).sum().item())
+        del words
+
+        def emit_all():
+            for lo in range(0, nbytes, window):
+                ctx.sam_emit_dev(batch, d_boff, nbytes, lo, min(nbytes, lo + window), d_win)
+
+        ctx.sam_emit_dev(batch, d_boff, nbytes, 0, min(nbytes, window), d_win)  # warm-up
+        _, emit_wall, emit_ms = profiled("sam", emit_all)
+        layout_bytes = total * (32 + 16) + lines * 4
+        emit_bytes = nbytes + lines * 4 + total * 32
+        out[f"k{k}"] = {"hits": int(total), "lines": lines, "text_bytes": int(nbytes),
+                        "search_kernel_ms": round(search_ms, 3),
+                        "layout_ms": round(layout_ms, 3), "layout_bytes": int(layout_bytes),
+                        "layout_GBps": round(layout_bytes / (layout_ms * 1e-3) / 1e9, 1),
+                        "emit_ms": round(emit_ms, 3), "emit_wall_ms": round(emit_wall * 1e3, 3), "emit_bytes": int(emit_bytes),
+                        "emit_GBps": round(emit_bytes / (emit_ms * 1e-3) / 1e9, 1),
+                        "emit_fraction_of_fill": round(emit_bytes / (emit_ms * 1e-3) / 1e9 / probe["fill"], 3),
+                        "lines_per_s": round(lines / ((layout_ms + emit_ms) * 1e-3), 1)}
+        del d_hits, d_boff
+        torch.cuda.empty_cache()
+    # ---- the streamed form: sx_map_reads_stream (host tables and FASTQ image in, SAM text out through a sink that discards)
+    from stralg_amd import _lib, api
+    fastq = b"".join(b"@%s\n%s\n+\n%s\n" % (names[q], row.tobytes(), b"~" * L)
+                     for q, row in enumerate(np.frombuffer(b"\0ACGT", np.uint8)[reads]))
+    fq = _lib.Fastq()
+    img = np.frombuffer(fastq, np.uint8)
+    t0 = time.perf_counter()
+    assert ctx.lib.sx_fastq_index(img.ctypes.data, img.size, C.byref(fq)) == 0 and fq.count == R
+    index_s = time.perf_counter() - t0
+    ctx.lib.sx_fastq_free(C.byref(fq))
+    out["fastq_index_host"] = {"image_bytes": len(fastq), "ms": round(index_s * 1e3, 2), "GBps": round(len(fastq) / index_s / 1e9, 2)}
+    torch.cuda.synchronize()
+    table = np.full(256, -1, np.int16)
+    table[0] = 0
+    table[np.frombuffer(b"ACGT", np.uint8)] = [1, 2, 3, 4]
+    rev = np.full(128, -1, np.int16)
+    rec = api.BwtTable(api.RemapTable(sigma, table, rev), api.SuffixArray(None, d_sa.cpu().numpy().view(np.uint32)),
+                       d_c.cpu().numpy().view(np.uint32), d_o.cpu().numpy().view(np.uint32),
+                       d_ro.cpu().numpy().view(np.uint32))
+    del d_sa, d_o, d_ro, d_win
+    torch.cuda.empty_cache()
+    for k in [int(x) for x in args.ks.split(",")]:
+        t0 = time.perf_counter()
+        seen = ctx.map_reads_stream([(b"chr1", rec)], fastq, k, None)
+        wall = time.perf_counter() - t0
+        nbytes = sum(b for _, b in seen)
+        assert nbytes == out[f"k{k}"]["text_bytes"], (nbytes, out[f"k{k}"]["text_bytes"])
+        # the windows' own rate: from the first window's arrival at the sink to the last one's (the first window's
+        # emit and copy, the table upload and the search of the first batch lie in front of it)
+        span = seen[-1][0] - seen[0][0]
+        rate = (nbytes - seen[0][1]) / span / 1e9 if span > 0 else None
+        out[f"k{k}"]["streamed"] = {"call_wall_ms": round(wall * 1e3, 1), "windows": len(seen),
+                                    "first_to_last_window_ms": round(span * 1e3, 2),
+                                    "windows_GBps": None if rate is None else round(rate, 2),
+                                    "fraction_of_pinned_copy": None if rate is None else round(rate / max(link), 3),
+                                    "call_GBps": round(nbytes / wall / 1e9, 2)}
+    if args.reference_lines_per_s:
+        out["reference_mapper_one_core"] = {"lines_per_s": args.reference_lines_per_s,
+                                            "what": "unmodified bwt_readmapper -d 2, hg38-10000.fa, reads-100-10-0.fq (408 980 lines, "
+                                                    "24.1 MB), whole program, page cache warm",
+                                            "host": "the CPU-only build machine, not the GPU box"}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
