@@ -248,7 +248,8 @@ int sx_bwt_approx_search(sx_ctx *ctx, const uint32_t *c_table, const uint32_t *o
 /* sink(user, section, data, bytes): consecutive chunks of one section after the other; data is only valid
  * during the call; a non-zero return aborts the build. */
 typedef int (*sx_sink_fn)(void *user, int section, const void *data, size_t bytes);
-enum { SX_SECTION_SA = 0, SX_SECTION_C = 1, SX_SECTION_O = 2, SX_SECTION_SAM = 3 /* sx_map_reads_stream */ };
+enum { SX_SECTION_SA = 0, SX_SECTION_C = 1, SX_SECTION_O = 2, SX_SECTION_SAM = 3 /* sx_map_reads_stream */,
+       SX_SECTION_INDEX = 4 /* sx_index_write */ };
 /* sx_build_tables, but the suffix array (when want_sa), the C table and the O table leave the device through
  * `sink` in 32 MiB chunks from pinned staging memory, in this order (the order of stralg/serialise.c:7-18 around
  * the remap table); the copy of a chunk overlaps the sink's work on the previous one. */
@@ -328,6 +329,71 @@ typedef struct sx_map_record {
  * (pattern length + edits < 2^15), so that limit cannot be met here. */
 int sx_map_reads_stream(sx_ctx *ctx, const sx_map_record *records, uint32_t n_records, const uint8_t *fastq, size_t fastq_len,
                         int edits, sx_sink_fn sink, void *user);
+
+/* ---- a device-resident index: build from FASTA once, map many read sets ---------------- */
+/* sx_fastq_index on the device: the FASTQ image lies in device memory (len bytes), the six arrays of sx_fastq are
+ * written to device memory that the call allocates (release with sx_fastq_dev_free; names, seqs and quals are 16-byte
+ * aligned and followed by 16 readable bytes).  Contract, limits and error codes are exactly those of sx_fastq_index;
+ * after an error *out holds no memory.  The same image gives the same bytes from run to run. */
+typedef struct sx_fastq_dev {
+    uint32_t count;
+    uint8_t *d_names, *d_seqs, *d_quals;
+    uint32_t *d_name_off, *d_seq_off, *d_qual_off; /* count + 1 entries each */
+    uint64_t name_bytes, seq_bytes, qual_bytes;     /* = the offsets' last entries */
+} sx_fastq_dev;
+int sx_fastq_index_dev(sx_ctx *ctx, const uint8_t *d_image, uint64_t len, sx_fastq_dev *out);
+void sx_fastq_dev_free(sx_fastq_dev *fq);
+
+/* The index: for every record, in FASTA file order, its name, N (symbols + sentinel), sigma, remap table, the remapped
+ * string (N bytes, the sentinel last) and SA, C, O and, when built with the reverse, RO as sx_bwt_tables_dev writes
+ * them, in device allocations of its own: sx_ctx_trim and other builds on the same context leave it intact.
+ * N x (5 + 8 sigma) bytes a record with RO.  It belongs to the device of the context that made it; a call with a
+ * context on another device returns SX_E_ARG.  One index must not be used from two threads at once. */
+typedef struct sx_index sx_index;
+/* From a host FASTA image: upload through the pinned staging buffers, sx_fasta_pack_dev, then per record remap, suffix
+ * array + BWT, C and O from the BWT and, with include_reverse, the same for the reversed string, whose suffix array is
+ * dropped.  No table crosses to the host.  Errors are those of the calls it is made of: SX_E_MALFORMED (FASTA), SX_E_ARG
+ * (an image of 2^31 - 1 bytes or more, more than 127 letters in a record), SX_E_NOMEM (host or device memory); nothing is
+ * left allocated then.  A record with an empty sequence becomes what build_complete_table makes of an empty string: N = 1,
+ * sigma = 1, SA = {0}; the index builds, saves and loads, and mapping against it answers SX_E_ARG as sx_map_reads_stream
+ * does for such a table (sigma < 2). */
+int sx_index_build_fasta(sx_ctx *ctx, const uint8_t *fasta, uint64_t len, int include_reverse, sx_index **out);
+/* From host tables: the upload that sx_map_reads_stream performs, once.  `string` (optional): the N - 1 remapped symbols;
+ * an index with a record that lacks it cannot be written (SX_E_ARG). */
+typedef struct sx_index_source {
+    sx_map_record record;
+    const uint8_t *string;
+} sx_index_source;
+int sx_index_from_tables(sx_ctx *ctx, const sx_map_record *records, uint32_t n_records, sx_index **out);
+int sx_index_from_sources(sx_ctx *ctx, const sx_index_source *sources, uint32_t n_records, sx_index **out);
+/* one more record, behind the others or (at_front) in front of them: a loader goes record by record with one host copy */
+int sx_index_add_record(sx_ctx *ctx, sx_index *idx, const sx_index_source *source, int at_front);
+/* sx_map_reads_stream against the resident tables: the FASTQ image is uploaded and indexed on the device
+ * (sx_fastq_index_dev).  Output, order, batch and window flags, limits and error codes are those of
+ * sx_map_reads_stream. */
+int sx_index_map_reads(sx_ctx *ctx, const sx_index *idx, const uint8_t *fastq, size_t fastq_len, int edits, sx_sink_fn sink,
+                       void *user);
+typedef struct sx_index_record {
+    const char *name; /* valid until the index changes or is destroyed */
+    uint64_t N;
+    uint32_t sigma;
+    int has_ro, has_string;
+    const signed char *remap; /* host, 256 entries */
+    /* device memory, exposed for tests */
+    const uint8_t *d_string;
+    const uint32_t *d_sa, *d_c, *d_o, *d_ro;
+} sx_index_record;
+int sx_index_info(const sx_index *idx, uint32_t *n_records_out, int *device_out, int *has_ro_out, uint64_t *device_bytes_out);
+int sx_index_record_info(const sx_index *idx, uint32_t record, sx_index_record *out);
+void sx_index_destroy(sx_index *idx);
+/* indexes alive in this process (created minus destroyed) */
+int sx_index_live_count(void);
+/* The read mapper's index file from the resident buffers, through sink(user, SX_SECTION_INDEX, ..) in chunks of at most
+ * 32 MiB from pinned staging: a u32 record count, then, last record first, a u32 name length, the name with its NUL and
+ * the image of stralg/serialise.c (string, suffix array, remap table, C, O, a flag byte, RO). */
+int sx_index_write(sx_ctx *ctx, const sx_index *idx, sx_sink_fn sink, void *user);
+/* bytes of device memory to the host on the context's stream, then a sync (the tests read the index's buffers back) */
+int sx_download(sx_ctx *ctx, void *h_dst, const void *d_src, size_t bytes);
 
 /* ---- FASTA ingest and remap on the device ---------------- */
 /* bioinf/fasta.c:92-135 load_fasta_records' packing of a file image in device memory into

@@ -253,6 +253,18 @@ void stralg_amd_free_approx_result(struct stralg_amd_approx_result *result);
  * sx_map_reads_stream (SX_E_MALFORMED for a FASTQ stream outside the contract of sx_fastq_index) with a line on stderr. */
 int stralg_amd_map_reads(struct bwt_table *const *tables, const char *const *names, size_t n, FILE *fastq, int edits, FILE *sam);
 
+/* A device-resident index (stralg_amd.h sx_index) on the calling thread's context: index a genome once, map many read
+ * sets.  _from_fasta_image builds every record's tables on the device from the bytes of a FASTA file; _read loads the
+ * mapper's .bwttables stream (record by record, one record's host copy at a time), _write produces that stream, byte for
+ * byte what `-p` writes; _map is stralg_amd_map_reads against the resident tables (the FASTQ image is indexed on the
+ * device).  NULL / a non-zero code with a line on stderr on failure.  Free the index on the thread that made it, before
+ * stralg_amd_release. */
+struct sx_index *stralg_amd_index_from_fasta_image(const uint8_t *fasta, size_t len, bool include_reverse);
+struct sx_index *stralg_amd_index_read(FILE *f);
+int stralg_amd_index_write(FILE *f, const struct sx_index *idx);
+int stralg_amd_index_map(const struct sx_index *idx, FILE *fastq, int edits, FILE *sam);
+void stralg_amd_index_free(struct sx_index *idx);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,7 @@ work is done by libstralg_amd.so (HIP kernels for gfx950) through the C-ABI of
 include/stralg_amd.h.  There is no CPU fallback.
 """
 from .api import (  # noqa: F401
-    Context, SuffixArray, BwtTable, RemapTable, StralgAmdError,
+    Context, Index, SuffixArray, BwtTable, RemapTable, StralgAmdError,
     sa_is_construction, sa_is_mem_construction, skew_sa_construction,
     remap_string, alloc_remap_table, remap, init_bwt_table, build_complete_table, bwt_approx_search, map_reads,
     default_context,

@@ -62,6 +62,26 @@ class MapRecord(C.Structure):
                 ("ro_table", C.c_void_p), ("N", C.c_uint64), ("sigma", C.c_uint32), ("remap", C.c_void_p)]
 
 
+class FastqDev(C.Structure):
+    """include/stralg_amd.h sx_fastq_dev (device pointers)"""
+    _fields_ = [("count", C.c_uint32), ("d_names", C.c_void_p), ("d_seqs", C.c_void_p), ("d_quals", C.c_void_p),
+                ("d_name_off", C.c_void_p), ("d_seq_off", C.c_void_p), ("d_qual_off", C.c_void_p),
+                ("name_bytes", C.c_uint64), ("seq_bytes", C.c_uint64), ("qual_bytes", C.c_uint64)]
+
+
+class IndexSource(C.Structure):
+    """include/stralg_amd.h sx_index_source"""
+    _fields_ = [("record", MapRecord), ("string", C.c_void_p)]
+
+
+class IndexRecord(C.Structure):
+    """include/stralg_amd.h sx_index_record"""
+    _fields_ = [("name", C.c_char_p), ("N", C.c_uint64), ("sigma", C.c_uint32), ("has_ro", C.c_int), ("has_string", C.c_int),
+                ("remap", C.c_void_p), ("d_string", C.c_void_p), ("d_sa", C.c_void_p), ("d_c", C.c_void_p), ("d_o", C.c_void_p),
+                ("d_ro", C.c_void_p)]
+
+
+SX_SECTION_INDEX = 4
 SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t)
 
 
@@ -111,6 +131,19 @@ def load(path=None):
         "sx_fastq_index": (C.c_int, [u8p, C.c_size_t, C.POINTER(Fastq)]),
         "sx_fastq_free": (None, [C.POINTER(Fastq)]),
         "sx_map_reads_stream": (C.c_int, [vp, C.POINTER(MapRecord), C.c_uint32, u8p, C.c_size_t, C.c_int, SINK_FN, C.c_void_p]),
+        "sx_fastq_index_dev": (C.c_int, [vp, u8p, C.c_uint64, C.POINTER(FastqDev)]),
+        "sx_fastq_dev_free": (None, [C.POINTER(FastqDev)]),
+        "sx_index_build_fasta": (C.c_int, [vp, u8p, C.c_uint64, C.c_int, C.POINTER(vp)]),
+        "sx_index_from_tables": (C.c_int, [vp, C.POINTER(MapRecord), C.c_uint32, C.POINTER(vp)]),
+        "sx_index_from_sources": (C.c_int, [vp, C.POINTER(IndexSource), C.c_uint32, C.POINTER(vp)]),
+        "sx_index_add_record": (C.c_int, [vp, vp, C.POINTER(IndexSource), C.c_int]),
+        "sx_index_map_reads": (C.c_int, [vp, vp, u8p, C.c_size_t, C.c_int, SINK_FN, C.c_void_p]),
+        "sx_index_info": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
+        "sx_index_record_info": (C.c_int, [vp, C.c_uint32, C.POINTER(IndexRecord)]),
+        "sx_index_destroy": (None, [vp]),
+        "sx_index_live_count": (C.c_int, []),
+        "sx_index_write": (C.c_int, [vp, vp, SINK_FN, C.c_void_p]),
+        "sx_download": (C.c_int, [vp, vp, vp, C.c_size_t]),
         "sx_fasta_pack_dev": (C.c_int, [vp, u8p, C.c_uint64, u8p, C.POINTER(C.c_uint64), u32p, C.c_uint64,
                                         C.POINTER(C.c_uint32)]),
         "sx_fasta_pack": (C.c_int, [vp, u8p, C.c_uint64, u8p, C.POINTER(C.c_uint64), u32p, C.c_uint64,
@@ -147,7 +180,10 @@ def load(path=None):
 EXPORTS = ["sx_device_count", "sx_device_numa_node", "sx_ctx_create", "sx_ctx_destroy", "sx_ctx_live_count", "sx_last_error", "sx_ctx_trim", "sx_ctx_set_flag",
            "sx_sa_build", "sx_sa_build_dev", "sx_sa_bwt_build_dev", "sx_bwt_tables", "sx_bwt_tables_dev",
            "sx_bwt_tables_from_bwt_dev", "sx_build_tables", "sx_sa_inverse_dev", "sx_sa_lcp_dev", "sx_sa_inverse_lcp",
-           "sx_bwt_exact_search_dev", "sx_bwt_approx_search_dev", "sx_bwt_approx_search", "sx_build_tables_stream", "sx_sam_layout_dev", "sx_sam_emit_dev", "sx_fastq_index", "sx_fastq_free", "sx_map_reads_stream", "sx_fasta_pack_dev", "sx_fasta_pack", "sx_remap_dev", "sx_reverse_dev", "sx_profile_enable", "sx_profile_only",
+           "sx_bwt_exact_search_dev", "sx_bwt_approx_search_dev", "sx_bwt_approx_search", "sx_build_tables_stream", "sx_sam_layout_dev", "sx_sam_emit_dev", "sx_fastq_index", "sx_fastq_free", "sx_map_reads_stream",
+           "sx_fastq_index_dev", "sx_fastq_dev_free", "sx_index_build_fasta", "sx_index_from_tables", "sx_index_from_sources",
+           "sx_index_add_record", "sx_index_map_reads", "sx_index_info", "sx_index_record_info", "sx_index_destroy",
+           "sx_index_live_count", "sx_index_write", "sx_download", "sx_fasta_pack_dev", "sx_fasta_pack", "sx_remap_dev", "sx_reverse_dev", "sx_profile_enable", "sx_profile_only",
            "sx_profile_reset", "sx_profile_read", "sx_kernel_class_name", "sx_last_stats",
            "sx_synth_dev", "sx_membw_probe", "sx_prim_sort_pairs_dev", "sx_prim_exclusive_sum_dev", "sx_prim_classify_dev"]
 

@@ -214,6 +214,32 @@ class Context:
         finally:
             self.lib.sx_fastq_free(C.byref(fq))
 
+    def download(self, address, count, dtype=np.uint8):
+        """sx_download: `count` entries of `dtype` of device memory at a raw address, as a numpy array"""
+        out = np.empty(int(count), dtype=dtype)
+        if out.size:
+            self._check(self.lib.sx_download(self.h, _ptr(out), int(address), out.nbytes), "sx_download")
+        return out
+
+    def fastq_index_dev(self, d_image, length):
+        """sx_fastq_index_dev of a FASTQ image in device memory (a tensor, an array the device can read, or an address):
+        ((names, name_off, seqs, seq_off, quals, qual_off), count) -- the six device arrays, read back as numpy arrays as
+        Context.fastq_index returns the host function's; raises StralgAmdError with the host function's code outside
+        the contract."""
+        fq = _lib.FastqDev()
+        self._check(self.lib.sx_fastq_index_dev(self.h, _ptr(d_image) if length else None, int(length), C.byref(fq)),
+                    "sx_fastq_index_dev")
+        try:
+            n = int(fq.count)
+            out = []
+            for data_p, off_p, nbytes in ((fq.d_names, fq.d_name_off, fq.name_bytes), (fq.d_seqs, fq.d_seq_off, fq.seq_bytes),
+                                          (fq.d_quals, fq.d_qual_off, fq.qual_bytes)):
+                out.append(self.download(data_p, nbytes, np.uint8))
+                out.append(self.download(off_p, n + 1, np.uint32))
+            return tuple(out), n
+        finally:
+            self.lib.sx_fastq_dev_free(C.byref(fq))
+
     def set_sam_batch_reads(self, reads):
         """sx_map_reads_stream: at most this many reads in one search batch (0: the default)"""
         self._check(self.lib.sx_ctx_set_flag(self.h, _lib.SX_FLAG_SAM_BATCH_READS, int(reads)), "sx_ctx_set_flag")
@@ -229,14 +255,7 @@ class Context:
         recs = (_lib.MapRecord * max(1, len(records)))()
         keep = []
         for r, (name, t) in enumerate(records):
-            sa = np.ascontiguousarray(t.sa.array, dtype=np.uint32)
-            c = np.ascontiguousarray(t.c_table, dtype=np.uint32)
-            o = np.ascontiguousarray(t.o_table, dtype=np.uint32)
-            ro = None if t.ro_table is None else np.ascontiguousarray(t.ro_table, dtype=np.uint32)
-            tab = np.ascontiguousarray(np.clip(t.remap_table.table, -1, 127), dtype=np.int8)
-            keep.append((sa, c, o, ro, tab))
-            recs[r] = _lib.MapRecord(bytes(name), _ptr(sa), _ptr(c), _ptr(o), _ptr(ro), sa.size, t.remap_table.alphabet_size,
-                                     _ptr(tab))
+            recs[r] = _map_record(name, t, keep)
         buf = np.frombuffer(bytes(fastq), dtype=np.uint8)
         failure = []
 
@@ -419,6 +438,227 @@ class Context:
         self.lib.stralg_amd_bind_thread_to_device.argtypes = [C.c_int]
         self.lib.stralg_amd_bind_thread_to_device.restype = C.c_int
         return int(self.lib.stralg_amd_bind_thread_to_device(self.device))
+
+
+def _map_record(name, t, keep):
+    """(name bytes, BwtTable) -> _lib.MapRecord over arrays that `keep` holds alive"""
+    sa = np.ascontiguousarray(t.sa.array, dtype=np.uint32)
+    c = np.ascontiguousarray(t.c_table, dtype=np.uint32)
+    o = np.ascontiguousarray(t.o_table, dtype=np.uint32)
+    ro = None if t.ro_table is None else np.ascontiguousarray(t.ro_table, dtype=np.uint32)
+    tab = np.ascontiguousarray(np.clip(t.remap_table.table, -1, 127), dtype=np.int8)
+    keep.append((sa, c, o, ro, tab))
+    return _lib.MapRecord(bytes(name), _ptr(sa), _ptr(c), _ptr(o), _ptr(ro), sa.size, t.remap_table.alphabet_size, _ptr(tab))
+
+
+class Index:
+    """A device-resident index (sx_index): every FASTA record's remapped string, SA, C, O and RO stay on the GPU, in
+    allocations of the index's own; build it once, map many read sets.  Use one index from one thread at a time, with
+    contexts on its device."""
+
+    def __init__(self, ctx, handle):
+        self.ctx = ctx
+        self.h = handle
+
+    # ---- constructors -------------------------------------------------------------------------------------------
+    @classmethod
+    def from_fasta(cls, fasta_bytes, include_reverse=True, ctx=None):
+        """sx_index_build_fasta: the bytes of a FASTA file -> tables of every record, built on the device"""
+        ctx = ctx or default_context()
+        buf = np.frombuffer(bytes(fasta_bytes), dtype=np.uint8)
+        h = C.c_void_p()
+        ctx._check(ctx.lib.sx_index_build_fasta(ctx.h, _ptr(buf) if buf.size else None, buf.size, 1 if include_reverse else 0,
+                                                C.byref(h)), "sx_index_build_fasta")
+        return cls(ctx, h)
+
+    @classmethod
+    def from_tables(cls, records, ctx=None):
+        """sx_index_from_sources: records = [(name bytes, BwtTable), ...] in the mapper's list order (the FASTA file's), as
+        Context.map_reads_stream takes them; a table whose sa.string is set (remapped symbols + terminator) can be saved"""
+        ctx = ctx or default_context()
+        src = (_lib.IndexSource * max(1, len(records)))()
+        keep = []
+        for r, (name, t) in enumerate(records):
+            src[r].record = _map_record(name, t, keep)
+            string = getattr(t.sa, "string", None)
+            if string is not None:
+                string = np.ascontiguousarray(string, dtype=np.uint8)
+                keep.append(string)
+                src[r].string = _ptr(string)
+        h = C.c_void_p()
+        ctx._check(ctx.lib.sx_index_from_sources(ctx.h, src, len(records), C.byref(h)), "sx_index_from_sources")
+        return cls(ctx, h)
+
+    @classmethod
+    def load(cls, path_or_bytes, ctx=None):
+        """the read mapper's index file (genome.fa.bwttables; what .save writes): a path, or the bytes.  The file is
+        mapped, and its records go to the device one after the other."""
+        ctx = ctx or default_context()
+        if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+            blob = np.frombuffer(bytes(path_or_bytes), dtype=np.uint8)
+        else:
+            blob = np.memmap(path_or_bytes, dtype=np.uint8, mode="r")
+        at = [0]
+
+        def take(nbytes, dtype=np.uint8):
+            if at[0] + nbytes > blob.size:
+                raise StralgAmdError("Index.load: truncated index")
+            out = np.frombuffer(np.ascontiguousarray(blob[at[0]:at[0] + nbytes]).tobytes(), dtype=dtype)
+            at[0] += nbytes
+            return out
+
+        h = C.c_void_p()
+        ctx._check(ctx.lib.sx_index_from_tables(ctx.h, None, 0, C.byref(h)), "sx_index_from_tables")
+        idx = cls(ctx, h)
+        try:
+            n_rec = int(take(4, np.uint32)[0])
+            for _ in range(n_rec):  # (last FASTA record first)
+                name = take(int(take(4, np.uint32)[0])).tobytes()
+                if not name or name[-1] != 0:
+                    raise StralgAmdError("Index.load: a record's name lacks its terminator")
+                n = int(take(4, np.uint32)[0])
+                string = np.concatenate([take(n), np.zeros(1, np.uint8)])
+                sa = take(4 * (n + 1), np.uint32)
+                sigma = int(take(4, np.uint32)[0])
+                table, _rev = take(256, np.int8), take(128, np.int8)
+                if not 1 <= sigma <= 128:
+                    raise StralgAmdError("Index.load: a remap table of more than 127 letters")
+                c = take(4 * sigma, np.uint32)
+                o = take(4 * sigma * (n + 2), np.uint32)
+                ro = take(4 * sigma * (n + 2), np.uint32) if int(take(1)[0]) else None
+                src = _lib.IndexSource(_lib.MapRecord(name[:-1], _ptr(sa), _ptr(c), _ptr(o), _ptr(ro), n + 1, sigma, _ptr(table)),
+                                       _ptr(string))
+                ctx._check(ctx.lib.sx_index_add_record(ctx.h, idx.h, C.byref(src), 1), "sx_index_add_record")
+        except Exception:
+            idx.close()
+            raise
+        return idx
+
+    # ---- use ----------------------------------------------------------------------------------------------------
+    def _handle(self):
+        if not self.h:
+            raise StralgAmdError("the index is closed")
+        return self.h
+
+    def map_reads(self, fastq, edits, sink=None, ctx=None):
+        """sx_index_map_reads: the SAM text of every match of every read of a FASTQ image within `edits` edits, byte for
+        byte stralg_amd.map_reads' (the reference mapper's stdout).  sink=None returns the text; sink(bytes) receives it
+        window after window and None is returned."""
+        ctx = ctx or self.ctx
+        buf = np.frombuffer(bytes(fastq), dtype=np.uint8)
+        chunks, failure = [], []
+        put = chunks.append if sink is None else sink
+
+        def _sink(user, section, data, nbytes):
+            try:
+                put(C.string_at(data, nbytes))
+                return 0
+            except Exception as e:  # (an exception must not cross the C frames)
+                failure.append(e)
+                return 1
+
+        cb = _lib.SINK_FN(_sink)
+        rc = ctx.lib.sx_index_map_reads(ctx.h, self._handle(), _ptr(buf) if buf.size else None, buf.size, edits, cb, None)
+        if failure:
+            raise failure[0]
+        ctx._check(rc, "sx_index_map_reads")
+        return b"".join(chunks) if sink is None else None
+
+    def map_reads_discard(self, fastq, edits, ctx=None):
+        """the same with a sink that does not touch the text: [(time.perf_counter(), bytes)] per window (measurement)"""
+        ctx = ctx or self.ctx
+        buf = np.frombuffer(bytes(fastq), dtype=np.uint8)
+        seen = []
+
+        def _sink(user, section, data, nbytes):
+            seen.append((time.perf_counter(), nbytes))
+            return 0
+
+        cb = _lib.SINK_FN(_sink)
+        ctx._check(ctx.lib.sx_index_map_reads(ctx.h, self._handle(), _ptr(buf) if buf.size else None, buf.size, edits, cb, None),
+                   "sx_index_map_reads")
+        return seen
+
+    def write(self, sink, ctx=None):
+        """sx_index_write: the index file's bytes, chunk after chunk, to sink(bytes)"""
+        ctx = ctx or self.ctx
+        failure = []
+
+        def _sink(user, section, data, nbytes):
+            try:
+                sink(C.string_at(data, nbytes))
+                return 0
+            except Exception as e:
+                failure.append(e)
+                return 1
+
+        cb = _lib.SINK_FN(_sink)
+        rc = ctx.lib.sx_index_write(ctx.h, self._handle(), cb, None)
+        if failure:
+            raise failure[0]
+        ctx._check(rc, "sx_index_write")
+
+    def save(self, path):
+        """the read mapper's index file (what `stralg_amd_readmapper -p` writes), from the resident buffers"""
+        with open(path, "wb") as f:
+            self.write(f.write)
+
+    def _info(self):
+        n, dev, ro, nbytes = C.c_uint32(0), C.c_int(0), C.c_int(0), C.c_uint64(0)
+        self.ctx._check(self.ctx.lib.sx_index_info(self._handle(), C.byref(n), C.byref(dev), C.byref(ro), C.byref(nbytes)),
+                        "sx_index_info")
+        return int(n.value), int(dev.value), bool(ro.value), int(nbytes.value)
+
+    def record_info(self, r):
+        """sx_index_record_info of record r: the _lib.IndexRecord with the record's device addresses (for tests)"""
+        rec = _lib.IndexRecord()
+        self.ctx._check(self.ctx.lib.sx_index_record_info(self._handle(), r, C.byref(rec)), "sx_index_record_info")
+        return rec
+
+    @property
+    def records(self):
+        """[(name, N, sigma, has_ro)] in FASTA file order"""
+        out = []
+        for r in range(self._info()[0]):
+            rec = self.record_info(r)
+            out.append((bytes(rec.name), int(rec.N), int(rec.sigma), bool(rec.has_ro)))
+        return out
+
+    @property
+    def device(self):
+        return self._info()[1]
+
+    @property
+    def device_bytes(self):
+        return self._info()[3]
+
+    def device_tables(self, r, ctx=None):
+        """record r's device buffers read back (tests): dict(string, sa, c, o, ro) of numpy arrays; ro / string may be None"""
+        ctx = ctx or self.ctx
+        rec = self.record_info(r)
+        N, sigma = int(rec.N), int(rec.sigma)
+        return dict(string=ctx.download(rec.d_string, N, np.uint8) if rec.d_string else None,
+                    sa=ctx.download(rec.d_sa, N, np.uint32), c=ctx.download(rec.d_c, sigma, np.uint32),
+                    o=ctx.download(rec.d_o, (N + 1) * sigma, np.uint32).reshape(N + 1, sigma),
+                    ro=ctx.download(rec.d_ro, (N + 1) * sigma, np.uint32).reshape(N + 1, sigma) if rec.d_ro else None)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.sx_index_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            if getattr(self.ctx, "h", None):  # (a closed context has taken the device's state with it)
+                self.close()
+        except Exception:
+            pass
 
 
 _tls = threading.local()

@@ -1785,3 +1785,97 @@ done:
     free(image);
     return rc;
 }
+
+/* ---- a device-resident index behind FILE-level calls (sx_index.hip) ------------------------------------------------ */
+
+static uint8_t *read_rest(FILE *f, size_t *len_out)
+{
+    size_t cap = 1 << 20, len = 0;
+    uint8_t *image = malloc(cap);
+    while (image) { /* the rest of the stream */
+        len += fread(image + len, 1, cap - len, f);
+        if (len < cap) break;
+        uint8_t *grown = realloc(image, cap *= 2);
+        if (!grown) free(image);
+        image = grown;
+    }
+    *len_out = len;
+    return image;
+}
+
+sx_index *stralg_amd_index_from_fasta_image(const uint8_t *fasta, size_t len, bool include_reverse)
+{
+    sx_ctx *ctx = thread_ctx();
+    sx_index *idx = NULL;
+    const int rc = sx_index_build_fasta(ctx, fasta, len, include_reverse, &idx);
+    if (rc != 0) {
+        fprintf(stderr, "stralg_amd_index_from_fasta_image: failed (code %d): %s\n", rc, sx_last_error(ctx));
+        return NULL;
+    }
+    return idx;
+}
+
+/* the mapper's index file (tools/stralg_amd_readmapper.c): record by record through read_complete_bwt_info, one
+ * record's host copy at a time; the file lists the records last first */
+sx_index *stralg_amd_index_read(FILE *f)
+{
+    if (!f) return NULL;
+    sx_ctx *ctx = thread_ctx();
+    uint32_t n = 0;
+    if (fread(&n, sizeof n, 1, f) != 1) return NULL;
+    sx_index *idx = NULL;
+    if (sx_index_from_tables(ctx, NULL, 0, &idx) != 0) return NULL;
+    for (uint32_t r = 0; r < n; ++r) {
+        uint32_t name_bytes = 0;
+        char *name = NULL;
+        struct bwt_table *t = NULL;
+        int rc = SX_E_MALFORMED;
+        if (fread(&name_bytes, sizeof name_bytes, 1, f) == 1 && name_bytes != 0 && (name = malloc(name_bytes)) != NULL &&
+            fread(name, 1, name_bytes, f) == name_bytes && name[name_bytes - 1] == '\0' && (t = read_complete_bwt_info(f)) != NULL) {
+            const sx_index_source src = {{name, t->sa->array, t->c_table, t->o_table, t->ro_table, t->sa->length,
+                                          t->remap_table->alphabet_size, t->remap_table->table}, t->sa->string};
+            rc = sx_index_add_record(ctx, idx, &src, 1);
+            if (rc != 0) fprintf(stderr, "stralg_amd_index_read: failed (code %d): %s\n", rc, sx_last_error(ctx));
+        }
+        if (t) completely_free_bwt_table(t);
+        free(name);
+        if (rc != 0) {
+            sx_index_destroy(idx);
+            return NULL;
+        }
+    }
+    return idx;
+}
+
+static int index_to_file(void *user, int section, const void *data, size_t bytes)
+{
+    (void)section;
+    return fwrite(data, 1, bytes, (FILE *)user) == bytes ? 0 : 1;
+}
+
+int stralg_amd_index_write(FILE *f, const sx_index *idx)
+{
+    if (!f || !idx) return SX_E_ARG;
+    sx_ctx *ctx = thread_ctx();
+    const int rc = sx_index_write(ctx, idx, index_to_file, f);
+    if (rc != 0) fprintf(stderr, "stralg_amd_index_write: failed (code %d): %s\n", rc, sx_last_error(ctx));
+    return rc;
+}
+
+int stralg_amd_index_map(const sx_index *idx, FILE *fastq, int edits, FILE *sam)
+{
+    if (!idx || !fastq || !sam) {
+        fprintf(stderr, "stralg_amd_index_map: malformed arguments\n");
+        return SX_E_ARG;
+    }
+    size_t len = 0;
+    uint8_t *image = read_rest(fastq, &len);
+    if (!image) return SX_E_NOMEM;
+    sx_ctx *ctx = thread_ctx();
+    const int rc = sx_index_map_reads(ctx, idx, image, len, edits, sam_to_file, sam);
+    if (rc != 0) fprintf(stderr, "stralg_amd_index_map: failed (code %d): %s\n", rc, sx_last_error(ctx));
+    free(image);
+    return rc;
+}
+
+void stralg_amd_index_free(sx_index *idx) { sx_index_destroy(idx); }

@@ -1,0 +1,43 @@
+// sx_index.hpp -- the device-resident index (sx_index.hip) and what the mapper's loop (sx_sam.hip) reads of it.
+#pragma once
+#include "sx_common.hpp"
+
+#include <string>
+#include <vector>
+
+struct sx_index_rec {
+    std::string name;
+    uint64_t N = 0;
+    uint32_t sigma = 0;
+    signed char remap[256];
+    uint8_t *d_string = nullptr; // N bytes (the sentinel last), or null
+    uint32_t *d_sa = nullptr, *d_c = nullptr, *d_o = nullptr, *d_ro = nullptr;
+};
+
+struct sx_index {
+    int device = 0;
+    std::vector<sx_index_rec> recs; // FASTA file order
+    size_t device_bytes = 0;
+    // the mapper's view of the records (rebuilt whenever a record is added): names and their offsets, one 256-byte
+    // symbol table a record, the suffix arrays' addresses and lengths
+    uint8_t *d_rnames = nullptr, *d_tabs = nullptr;
+    uint32_t *d_rname_off = nullptr;
+    const uint32_t **d_sa_list = nullptr;
+    uint64_t *d_sa_lens = nullptr;
+    size_t view_bytes = 0;
+};
+
+// the reads of one call on the device; h_seq_off: the host's copy of d_seq_off, or null (the loop then reads the two
+// entries a batch needs back)
+struct sx_reads_dev {
+    uint32_t count = 0;
+    const uint8_t *d_names = nullptr, *d_seqs = nullptr, *d_quals = nullptr;
+    const uint32_t *d_name_off = nullptr, *d_seq_off = nullptr, *d_qual_off = nullptr;
+    const uint32_t *h_seq_off = nullptr;
+    uint64_t seq_bytes = 0;
+};
+
+// sx_sam.hip: the mapper's loop over reads and an index that both lie on ctx's device
+int sx_map_reads_core(sx_ctx *ctx, const sx_index *idx, const sx_reads_dev &reads, int edits, sx_sink_fn sink, void *user);
+// sx_index.hip: an index of host tables without the checks of the public call (sx_map_reads_stream has made them)
+int sx_index_from_records_impl(sx_ctx *ctx, const sx_map_record *records, uint32_t n_records, sx_index **out);

@@ -18,6 +18,7 @@
 #include "sx_common.hpp"
 #include "sx_device.hpp"
 #include "sx_scan.hpp"
+#include "sx_index.hpp"
 
 #include <stdlib.h>
 
@@ -625,48 +626,55 @@ int sx_map_reads_stream(sx_ctx *ctx, const sx_map_record *records, uint32_t n_re
     SX_CHECK(hipSetDevice(ctx->device));
     const uint32_t n_reads = fq.count;
     DevBufs B;
-    // resident for the whole call: the reads, and every record's suffix array and tables
-    // (N x (4 + 8 sigma) bytes a record with its RO table: DESIGN.md section 11)
-    uint8_t *d_names, *d_seqs, *d_quals, *d_pat, *d_rnames, *d_tabs;
-    uint32_t *d_name_off, *d_seq_off, *d_qual_off, *d_rname_off;
+    // the reads of this call, then a temporary index of the host tables (every record's suffix array and tables:
+    // N x (4 + 8 sigma) bytes a record with its RO table), the loop, and the index goes again
+    uint8_t *d_names, *d_seqs, *d_quals;
+    uint32_t *d_name_off, *d_seq_off, *d_qual_off;
     SX_TRY(upload(ctx, B, &d_names, (const uint8_t *)fq.names, fq.name_off[n_reads]));
     SX_TRY(upload(ctx, B, &d_seqs, (const uint8_t *)fq.seqs, fq.seq_off[n_reads]));
     SX_TRY(upload(ctx, B, &d_quals, (const uint8_t *)fq.quals, fq.qual_off[n_reads]));
     SX_TRY(upload(ctx, B, &d_name_off, (const uint32_t *)fq.name_off, (size_t)n_reads + 1));
     SX_TRY(upload(ctx, B, &d_seq_off, (const uint32_t *)fq.seq_off, (size_t)n_reads + 1));
     SX_TRY(upload(ctx, B, &d_qual_off, (const uint32_t *)fq.qual_off, (size_t)n_reads + 1));
-    SX_TRY(B.take(ctx, &d_pat, (size_t)fq.seq_off[n_reads] + 16));
-    std::vector<uint8_t> rnames, tabs((size_t)n_records * 256);
-    std::vector<uint32_t> rname_off(n_records + 1);
-    std::vector<uint32_t *> d_c(n_records), d_o(n_records), d_ro(n_records);
-    std::vector<const uint32_t *> sa_ptrs(n_records);
-    std::vector<uint64_t> sa_lens(n_records);
-    for (uint32_t r = 0; r < n_records; ++r) {
-        const sx_map_record &R = records[r];
-        rname_off[r] = (uint32_t)rnames.size();
-        rnames.insert(rnames.end(), (const uint8_t *)R.name, (const uint8_t *)R.name + strlen(R.name));
-        // remap.c:102-114: a byte the table lacks makes remap() return NULL and the mapper skip the record for this
-        // read; here it becomes symbol 0, for which the search has no hits
-        for (int b = 0; b < 256; ++b) tabs[(size_t)r * 256 + b] = R.remap[b] > 0 && (uint32_t)R.remap[b] < R.sigma ? (uint8_t)R.remap[b] : 0;
-        const size_t o_words = (size_t)(R.N + 1) * R.sigma;
-        uint32_t *d_sa;
-        SX_TRY(upload(ctx, B, &d_sa, R.sa, (size_t)R.N));
-        SX_TRY(upload(ctx, B, &d_c[r], R.c_table, (size_t)R.sigma));
-        SX_TRY(upload(ctx, B, &d_o[r], R.o_table, o_words));
-        d_ro[r] = nullptr;
-        if (R.ro_table) SX_TRY(upload(ctx, B, &d_ro[r], R.ro_table, o_words));
-        sa_ptrs[r] = d_sa;
-        sa_lens[r] = R.N;
-    }
-    rname_off[n_records] = (uint32_t)rnames.size();
-    const uint32_t **d_sa_list = nullptr;
-    uint64_t *d_sa_lens = nullptr;
-    SX_TRY(upload(ctx, B, &d_rnames, (const uint8_t *)rnames.data(), rnames.size()));
-    SX_TRY(upload(ctx, B, &d_rname_off, (const uint32_t *)rname_off.data(), rname_off.size()));
-    SX_TRY(upload(ctx, B, &d_tabs, (const uint8_t *)tabs.data(), tabs.size()));
-    SX_TRY(upload(ctx, B, &d_sa_list, (const uint32_t *const *)sa_ptrs.data(), sa_ptrs.size()));
-    SX_TRY(upload(ctx, B, &d_sa_lens, (const uint64_t *)sa_lens.data(), sa_lens.size()));
-    SX_TRY(sx_sync(ctx)); // (the host vectors above are pageable: their copies are done)
+    sx_index *idx = nullptr;
+    SX_TRY(sx_index_from_records_impl(ctx, records, n_records, &idx));
+    struct IdxFree {
+        sx_index *i;
+        ~IdxFree() { sx_index_destroy(i); }
+    } idx_free{idx};
+    sx_reads_dev reads;
+    reads.count = n_reads;
+    reads.d_names = d_names, reads.d_seqs = d_seqs, reads.d_quals = d_quals;
+    reads.d_name_off = d_name_off, reads.d_seq_off = d_seq_off, reads.d_qual_off = d_qual_off;
+    reads.h_seq_off = fq.seq_off;
+    reads.seq_bytes = fq.seq_off[n_reads];
+    return sx_map_reads_core(ctx, idx, reads, edits, sink, user);
+}
+
+} // extern "C"
+
+// The mapper's loop (bwt_readmapper.c:130-160, 257-266) over reads and tables that lie on the device: what
+// sx_map_reads_stream and sx_index_map_reads share.
+int sx_map_reads_core(sx_ctx *ctx, const sx_index *idx, const sx_reads_dev &reads, int edits, sx_sink_fn sink, void *user)
+{
+    const uint32_t n_reads = reads.count, n_records = (uint32_t)idx->recs.size();
+    if (n_reads == 0 || n_records == 0) return 0;
+    if ((uint64_t)n_reads * n_records > 0xFFFFFFFFull)
+        return sx_fail_msg(ctx, SX_E_ARG, "read mapping: reads x records must stay below 2^32");
+    for (const sx_index_rec &R : idx->recs)
+        if (R.N == 0 || R.N > 0xFFFFFFFFull || R.sigma < 2 || R.sigma > 128)
+            return sx_fail_msg(ctx, SX_E_ARG, "read mapping: a record lacks its name, suffix array, tables or remap table");
+    SX_CHECK(hipSetDevice(ctx->device));
+    DevBufs B;
+    const uint8_t *d_names = reads.d_names, *d_seqs = reads.d_seqs, *d_quals = reads.d_quals, *d_rnames = idx->d_rnames,
+                  *d_tabs = idx->d_tabs;
+    const uint32_t *d_name_off = reads.d_name_off, *d_seq_off = reads.d_seq_off, *d_qual_off = reads.d_qual_off,
+                   *d_rname_off = idx->d_rname_off;
+    const uint32_t *const *d_sa_list = idx->d_sa_list;
+    const uint64_t *d_sa_lens = idx->d_sa_lens;
+    uint8_t *d_pat;
+    SX_TRY(B.take(ctx, &d_pat, (size_t)reads.seq_bytes + 16));
+    SX_TRY(sx_sync(ctx)); // (the callers' uploads from pageable memory are done)
 
     uint32_t batch_max = ctx->sam_batch_reads > 0 ? (uint32_t)ctx->sam_batch_reads : (1u << 20);
     if (batch_max > n_reads) batch_max = n_reads;
@@ -717,14 +725,23 @@ int sx_map_reads_stream(sx_ctx *ctx, const sx_map_record *records, uint32_t n_re
         // the searches, record after record, into one hit array; too many hits: half the reads, or (one read) more room
         uint64_t used = 0;
         bool again = false;
-        const uint64_t p_lo = fq.seq_off[q0], p_hi = fq.seq_off[q0 + batch];
+        uint64_t p_lo, p_hi;
+        if (reads.h_seq_off) {
+            p_lo = reads.h_seq_off[q0], p_hi = reads.h_seq_off[q0 + batch];
+        } else { // (the offsets were made on the device: the two this batch needs come back)
+            const uint32_t *src[2] = {d_seq_off + q0, d_seq_off + q0 + batch};
+            const uint32_t one[2] = {1, 1};
+            uint32_t got[2];
+            SX_TRY(sx_readback_ranges(ctx, src, one, 2, got));
+            p_lo = got[0], p_hi = got[1];
+        }
         for (uint32_t r = 0; r < n_records && !again; ++r) {
-            const sx_map_record &R = records[r];
+            const sx_index_rec &R = idx->recs[r];
             if (p_hi > p_lo)
                 sx_launch(ctx, SX_KC_REMAP, 2 * (p_hi - p_lo), sam_remap_kernel, dim3(sx_div_up(p_hi - p_lo, kBlock)), dim3(kBlock),
                           (const uint8_t *)d_seqs, (const uint8_t *)(d_tabs + (size_t)r * 256), d_pat, p_lo, p_hi);
             uint64_t tot = 0;
-            const int rc = sx_bwt_approx_search_dev(ctx, d_c[r], d_o[r], d_ro[r], R.N, R.sigma, d_pat, d_seq_off + q0, batch, edits,
+            const int rc = sx_bwt_approx_search_dev(ctx, R.d_c, R.d_o, R.d_ro, R.N, R.sigma, d_pat, d_seq_off + q0, batch, edits,
                                                     d_ho + r * stride, d_raw + used, cap - used, &tot);
             if (rc == SX_E_CAPACITY) {
                 const uint64_t need = used + tot;
@@ -802,5 +819,3 @@ int sx_map_reads_stream(sx_ctx *ctx, const sx_map_record *records, uint32_t n_re
     }
     return sx_sync(ctx);
 }
-
-} // extern "C"

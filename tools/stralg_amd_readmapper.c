@@ -3,12 +3,17 @@
  * stralg's tools/readmappers/bwt_readmapper.
  *
  *   stralg_amd_readmapper -p genome.fa              writes genome.fa.bwttables
- *   stralg_amd_readmapper -d K genome.fa reads.fq   prints the SAM lines of every match with at most K edits
- *   (--preprocess and --edits are accepted for -p and -d)
+ *   stralg_amd_readmapper -d K genome.fa reads.fq [more.fq ...]
+ *                                                   prints the SAM lines of every match with at most K edits, file after
+ *                                                   file; the index is loaded once and stays on the device
+ *   stralg_amd_readmapper -i -d K genome.fa reads.fq [more.fq ...]
+ *                                                   the same with the index built on the device from genome.fa: no
+ *                                                   genome.fa.bwttables is read or written
+ *   (--preprocess, --edits and --in-memory are accepted for -p, -d and -i)
  *
  * Index file: u32 record count; per record, last FASTA record first, its name as u32 length + bytes + NUL, then the
  * table image of stralg/serialise.c.  Indexing packs the FASTA image with sx_fasta_pack and lets the library stream
- * each record's tables from the device into the file; mapping is stralg_amd_map_reads.
+ * each record's tables from the device into the file; mapping is stralg_amd_index_read / stralg_amd_index_map.
  */
 #include "stralg_amd.h"
 #include "stralg_compat.h"
@@ -91,36 +96,34 @@ static int build_index(const char *fasta)
     return EXIT_SUCCESS;
 }
 
-static int map_reads(const char *fasta, const char *reads, int k)
+/* -d: the index is loaded once (from genome.fa.bwttables, or, with -i, built on the device from genome.fa itself) and
+ * stays on the device; every FASTQ file is mapped against it, stdout is the files' texts one behind the other */
+static int map_reads(const char *fasta, char *const *reads, int n_reads, int k, int in_memory)
 {
-    char *path = index_path(fasta);
-    FILE *in = fopen(path, "rb");
-    if (!in) fail("cannot read (run -p first)", path);
-    uint32_t n = 0;
-    if (fread(&n, sizeof n, 1, in) != 1) fail("empty index", path);
-    struct bwt_table **tables = calloc((size_t)n + 1, sizeof *tables);
-    char **names = calloc((size_t)n + 1, sizeof *names);
-    if (!tables || !names) fail("out of memory", path);
-    /* the lines of one read list the records last-in-file first */
-    for (uint32_t at = n; at-- > 0;) {
-        uint32_t name_bytes = 0;
-        if (fread(&name_bytes, sizeof name_bytes, 1, in) != 1 || name_bytes == 0 || !(names[at] = malloc(name_bytes)) ||
-            fread(names[at], 1, name_bytes, in) != name_bytes || names[at][name_bytes - 1] != '\0' ||
-            !(tables[at] = read_complete_bwt_info(in)))
-            fail("truncated index", path);
+    struct sx_index *idx = NULL;
+    if (in_memory) {
+        size_t len = 0;
+        uint8_t *image = slurp(fasta, &len);
+        idx = stralg_amd_index_from_fasta_image(image, len, true);
+        free(image);
+        if (!idx) fail("could not index", fasta);
+    } else {
+        char *path = index_path(fasta);
+        FILE *in = fopen(path, "rb");
+        if (!in) fail("cannot read (run -p first)", path);
+        idx = stralg_amd_index_read(in);
+        if (!idx) fail("empty or truncated index", path);
+        fclose(in);
+        free(path);
     }
-    fclose(in);
-    FILE *fq = fopen(reads, "rb");
-    if (!fq) fail("cannot read", reads);
-    const int rc = stralg_amd_map_reads(tables, (const char *const *)names, n, fq, k, stdout);
-    fclose(fq);
-    for (uint32_t r = 0; r < n; ++r) {
-        completely_free_bwt_table(tables[r]);
-        free(names[r]);
+    int rc = 0;
+    for (int f = 0; f < n_reads && rc == 0; ++f) {
+        FILE *fq = fopen(reads[f], "rb");
+        if (!fq) fail("cannot read", reads[f]);
+        rc = stralg_amd_index_map(idx, fq, k, stdout);
+        fclose(fq);
     }
-    free(tables);
-    free(names);
-    free(path);
+    stralg_amd_index_free(idx);
     stralg_amd_release();
     return rc == 0 && fflush(stdout) == 0 ? EXIT_SUCCESS : EXIT_FAILURE;
 }
@@ -128,19 +131,24 @@ static int map_reads(const char *fasta, const char *reads, int k)
 static int usage(const char *self, int status)
 {
     fprintf(stderr, "usage: %s -p genome.fa               build genome.fa" INDEX_EXT "\n", self);
-    fprintf(stderr, "       %s -d K genome.fa reads.fq    SAM lines of all matches within K edits, on stdout\n", self);
+    fprintf(stderr, "       %s -d K genome.fa reads.fq ...  SAM lines of all matches within K edits, on stdout\n", self);
+    fprintf(stderr, "       %s -i -d K genome.fa reads.fq ...  the same, the index built in memory from genome.fa\n", self);
     return status;
 }
 
 int main(int argc, char **argv)
 {
-    const char *to_index = NULL, *rest[2] = {NULL, NULL};
-    int k = -1, n_rest = 0;
+    const char *to_index = NULL;
+    char **rest = calloc((size_t)argc + 1, sizeof *rest);
+    int k = -1, n_rest = 0, in_memory = 0;
+    if (!rest) fail("out of memory", NULL);
     for (int a = 1; a < argc; ++a) {
         const char *s = argv[a];
         const int wants_p = !strcmp(s, "-p") || !strcmp(s, "--preprocess"), wants_d = !strcmp(s, "-d") || !strcmp(s, "--edits");
         if (!strcmp(s, "-h") || !strcmp(s, "--help")) return usage(argv[0], EXIT_SUCCESS);
-        if (wants_p || wants_d) {
+        if (!strcmp(s, "-i") || !strcmp(s, "--in-memory")) {
+            in_memory = 1;
+        } else if (wants_p || wants_d) {
             if (++a >= argc) return usage(argv[0], EXIT_FAILURE);
             if (wants_p) to_index = argv[a];
             else k = (int)strtol(argv[a], NULL, 10);
@@ -148,13 +156,11 @@ int main(int argc, char **argv)
             k = (int)strtol(s + 2, NULL, 10);
         } else if (s[0] == '-' && s[1]) {
             return usage(argv[0], EXIT_FAILURE);
-        } else if (n_rest < 2) {
-            rest[n_rest++] = s;
         } else {
-            return usage(argv[0], EXIT_FAILURE);
+            rest[n_rest++] = argv[a];
         }
     }
     if (to_index) return build_index(to_index);
-    if (n_rest != 2 || k < 0) return usage(argv[0], EXIT_FAILURE);
-    return map_reads(rest[0], rest[1], k);
+    if (n_rest < 2 || k < 0) return usage(argv[0], EXIT_FAILURE);
+    return map_reads(rest[0], rest + 1, n_rest - 1, k, in_memory);
 }
