@@ -1,7 +1,7 @@
 """The device-resident index (sx_index.hip: stralg_amd.Index) and the FASTQ ingest on the device (sx_fastq_index_dev)
 through the CPU execution harness: the reference read mapper's stdout in tests/golden/golden_sam.npz, the reference
-writer's byte streams in tests/golden/golden_fasta.npz, and the host's sx_fastq_index as the second opinion on every
-FASTQ image."""
+writer's byte streams in tests/golden/golden_fasta.npz, and, on every FASTQ image (tests/fastq_cases.py), the contract
+restated in Python and the host's sx_fastq_index beside the device function."""
 import struct
 
 import numpy as np
@@ -9,7 +9,9 @@ import pytest
 
 import approx_model
 from approx_cases import remapped
+import fastq_cases as fq
 from conftest import serial_cases
+from device_memory import HarnessMemory
 from sam_cases import check_case, sam_cases, subset_fastq
 from stralg_amd import Index, api
 
@@ -145,179 +147,74 @@ def test_limits_and_errors_are_those_of_the_stream_call(emu_ctx, cases, index_of
     check_case(c, idx.map_reads(c["fastq"], c["k"]))  # (and it still works)
 
 
-# ---- sx_fastq_index_dev against the host's sx_fastq_index ---------------------------------------------------------------
-def aligned_copy(data, shift=0):
-    """the bytes in an array whose first byte lies `shift` bytes behind a 16-byte boundary"""
-    raw = np.zeros(len(data) + 64, np.uint8)
-    at = (-raw.ctypes.data) % 16 + shift
-    raw[at:at + len(data)] = np.frombuffer(data, np.uint8)
-    return raw[at:at + len(data)] if len(data) else raw[:1]
+# ---- sx_fastq_index_dev against the contract's restatement and the host's sx_fastq_index (tests/fastq_cases.py; the GPU
+# runs the same images) ------------------------------------------------------------------------------------------------
+MEM = HarnessMemory()
 
 
-def host_result(ctx, data):
-    try:
-        return ctx.fastq_index(data), None
-    except api.StralgAmdError as e:
-        return None, str(e).rsplit("code ", 1)[1].split(":")[0].split()[0]
-
-
-def dev_result(ctx, data, shift=0):
-    try:
-        arrays, count = ctx.fastq_index_dev(aligned_copy(data, shift), len(data))
-        return (arrays, count), None
-    except api.StralgAmdError as e:
-        return None, str(e).split("code ", 1)[1].split(":")[0].split()[0]
-
-
-def agree(ctx, data, shift=0, expect=None):
-    want, werr = host_result(ctx, data)
-    got, gerr = dev_result(ctx, data, shift)
-    assert werr == gerr, (data[:80], werr, gerr)
-    if expect is not None:
-        assert (werr is None) == expect, (data[:80], werr)
-    if want is not None:
-        arrays, count = got
-        assert count == want[1].size - 1
-        for g, w in zip(arrays, want):
-            assert g.dtype == w.dtype and g.size == w.size and (g == w).all(), data[:80]
-    return werr
-
-
-IN_CONTRACT = b"@r0 desc x\nCC\n+\n~~\n@r1\nAAA\n+r1 again\nIII\n@@\n@\n+\n+\n@last\tname\nNN\n\n##"
-LONGEST = b"@" + b"n" * 2045 + b"\n" + b"A" * 2046 + b"\n+\n" + b"I" * 2046
-
-OUT_OF_CONTRACT = [  # the images of test_sam_cpu.test_fastq_index_out_of_contract
-    b"@" + b"n" * 2046 + b"\nA\n+\nI\n",
-    b"@r\n" + b"A" * 2047 + b"\n+\n" + b"I" * 2047 + b"\n",
-    b"@\nA\n+\nI\n",
-    b"@r\n\n+\nI\n",
-    b"@r\nA\n+\n\n",
-    b"@r\nA\n+\n",
-    b"@r\nA\n+",
-    b"@r\nA\n",
-    b"@r\n",
-    b"@r\nA\n+\nI\n\n",
-    b"\n@r\nA\n+\nI\n",
-    b"@r\nA\0\n+\nI\n",
-]
+def test_fastq_reference_reproduces_the_golden_sam_text(cases):
+    """every line of the reference mapper's SAM text shows a read's name, sequence and quality: fastq_reference gives
+    exactly those for the golden FASTQ images, reads in the text's order (the 24 MB case: its first 200 lines)"""
+    checked = 0
+    for name, c in cases.items():
+        ref = fq.fastq_reference(c["fastq"])
+        assert ref is not None, name
+        names, seqs, quals, no, so, qo = ref
+        reads = [(names[no[i]:no[i + 1]], seqs[so[i]:so[i + 1]], quals[qo[i]:qo[i + 1]]) for i in range(len(no) - 1)]
+        at = 0
+        for line in (c["sam"] if "sam" in c else c["head"]).split(b"\n")[:-1]:
+            f = line.split(b"\t")
+            while reads[at][0] != f[0]:  # (reads without a line are passed over; the order is the file's)
+                at += 1
+            assert (f[0], f[9], f[10]) == reads[at], (name, f[0])
+            checked += 1
+    assert checked > 1000
 
 
 def test_fastq_dev_on_the_fixture_images(emu_ctx, cases):
-    seen = set()
-    for c in cases.values():
-        if c["fastq"] not in seen:
-            seen.add(c["fastq"])
-            agree(emu_ctx, c["fastq"], expect=True)
-            agree(emu_ctx, c["fastq"].rstrip(b"\n"), shift=3, expect=True)
-    assert len(seen) >= 4
+    images = fq.fixture_images(cases)
+    for case in images:
+        fq.check_image(emu_ctx, MEM, case)
+    assert len(images) >= 2 * 4
 
 
 def test_fastq_dev_in_contract(emu_ctx):
-    for data in (IN_CONTRACT, IN_CONTRACT + b"\n", b"", LONGEST, LONGEST + b"\n"):
-        for shift in (0, 1, 4):
-            agree(emu_ctx, data, shift, expect=True)
-    (names, no, seqs, so, quals, qo), count = emu_ctx.fastq_index_dev(aligned_copy(IN_CONTRACT), len(IN_CONTRACT))
-    split = lambda d, o: [d[o[i]:o[i + 1]].tobytes() for i in range(o.size - 1)]
-    assert count == 4 and split(names, no) == [b"r0 desc x", b"r1", b"@", b"last\tname"]
-    assert split(seqs, so) == [b"CC", b"AAA", b"@", b"NN"] and split(quals, qo) == [b"~~", b"III", b"+", b"##"]
+    for case in fq.in_contract_images():
+        fq.check_image(emu_ctx, MEM, case)
+    fq.check_in_contract_fields(emu_ctx, MEM)
 
 
-@pytest.mark.parametrize("data", OUT_OF_CONTRACT)
+@pytest.mark.parametrize("data", fq.OUT_OF_CONTRACT)
 def test_fastq_dev_out_of_contract(emu_ctx, data, cases, index_of):
-    assert agree(emu_ctx, data, expect=False) == "-4"
+    assert fq.agree(emu_ctx, MEM, data, expect=False) == "-4"
     with pytest.raises(api.StralgAmdError) as e:
         index_of(cases["test-out/k0"]["fasta"]).map_reads(data, 1)
     assert "code -4" in str(e.value)
 
 
-def random_record(rng, edge):
-    """four lines of a record inside the contract; `edge`: line lengths near the limit"""
-    alphabet = np.frombuffer(b"ACGTN@+ \t~!IJ>", np.uint8)
-
-    def line(lo):
-        n = int(rng.integers(2040, 2047)) if edge and rng.integers(0, 3) == 0 else int(rng.integers(lo, 40))
-        return rng.choice(alphabet, n).tobytes()
-
-    return [line(2), line(1), line(0), line(1)]
-
-
-def image_of(records, final_newline):
-    return b"\n".join(b"\n".join(r) for r in records) + (b"\n" if final_newline and records else b"")
-
-
 def test_fastq_dev_generated_images(emu_ctx):
-    rng = np.random.default_rng(11)
-    for k in range(60):
-        recs = [random_record(rng, edge=k % 3 == 0) for _ in range(int(rng.integers(1, 30)))]
-        agree(emu_ctx, image_of(recs, k % 2 == 0), shift=int(rng.integers(0, 16)) if k % 4 == 0 else 0, expect=True)
-    # lengths around multiples of 16 and of the 4096-byte tile: the last record's quality line is stretched or cut
-    base = [random_record(rng, False) for _ in range(150)]
-    for target in (4096, 8192, 4096 * 3):
-        for delta in (-17, -16, -15, -2, -1, 0, 1, 2, 15, 16, 17):
-            for final in (False, True):
-                recs, size = [], 0
-                for r in base:
-                    recs.append(list(r))
-                    size = len(image_of(recs, final))
-                    if size >= target + delta - 30:
-                        break
-                pad = target + delta - size
-                if pad >= 0:
-                    recs[-1][3] += b"I" * pad
-                else:
-                    recs[-2][3] = recs[-2][3] + b"I" * 60
-                    recs[-1][3] = (recs[-1][3] + b"I" * 60)[:max(1, len(recs[-1][3]) + 60 + pad)]
-                agree(emu_ctx, image_of(recs, final), expect=True)
-    # a newline as the last byte of a tile, the first byte of the next, and the one behind it
-    filler = [b"@" + b"n" * 14, b"A" * 15, b"+" + b"x" * 14, b"I" * 15]  # 64 bytes with its newlines
-    for at in (4095, 4096, 4097):
-        seq = b"C" * (at - 63 * 64 - 3)
-        data = image_of([filler] * 63 + [[b"@n", seq, b"+", b"#" * len(seq)]] + [filler] * 70, True)
-        assert data[at] == 10 and data[at - 1] == ord("C")
-        agree(emu_ctx, data, expect=True)
-
-
-DEFECTS = ["long_line", "empty_name", "one_byte_name", "empty_seq", "empty_qual", "cut", "blank_before", "blank_between",
-           "blank_behind", "nul", "none"]
+    for case in fq.generated_images():
+        fq.check_image(emu_ctx, MEM, case)
 
 
 def test_fastq_dev_soups_with_one_defect(emu_ctx):
-    rng = np.random.default_rng(12)
-    seen = {}
-    for k in range(330):
-        recs = [random_record(rng, edge=False) for _ in range(int(rng.integers(1, 120)))]
-        at = int(rng.integers(0, len(recs)))
-        defect = DEFECTS[k % len(DEFECTS)]
-        lines = [l for r in recs for l in r]
-        final = bool(rng.integers(0, 2))
-        if defect == "long_line":
-            lines[4 * at + int(rng.integers(0, 4))] = b"@" + b"x" * int(rng.integers(2046, 2050))
-        elif defect == "empty_name":
-            lines[4 * at] = b""
-        elif defect == "one_byte_name":
-            lines[4 * at] = b"@"
-        elif defect == "empty_seq":
-            lines[4 * at + 1] = b""
-        elif defect == "empty_qual":
-            lines[4 * at + 3] = b""
-        elif defect == "cut":
-            lines = lines[:len(lines) - int(rng.integers(1, 4))]
-        elif defect == "blank_before":
-            lines.insert(0, b"")
-        elif defect == "blank_between":
-            lines.insert(4 * at, b"")
-        elif defect == "blank_behind":
-            lines.append(b"")
-            final = True
-        elif defect == "nul":
-            j = 4 * at + int(rng.integers(0, 4))
-            lines[j] = lines[j] + b"\0" + lines[j]
-        data = b"\n".join(lines) + (b"\n" if final else b"")
-        err = agree(emu_ctx, data)
-        seen.setdefault(defect, set()).add(err)
-    # (an empty quality line at the very end without a final newline reads as a record cut off: malformed either way)
-    assert seen.pop("none") == {None}
-    assert all(v == {"-4"} for v in seen.values()), seen
+    fq.check_defects(emu_ctx, MEM, fq.soups())
+
+
+@pytest.mark.parametrize("family", ["line_role_edge_images", "long_line_images", "dense_tile_images",
+                                    "shifted_tile_multiple_images"])
+def test_fastq_dev_at_the_tiles_edges(emu_ctx, family):
+    for case in getattr(fq, family)():
+        fq.check_image(emu_ctx, MEM, case)
+
+
+def test_fastq_dev_defects_at_the_tiles_edges(emu_ctx):
+    fq.check_defects(emu_ctx, MEM, fq.defects_at_tile_edges())
+
+
+def test_fastq_dev_twice_the_same_bytes(emu_ctx):
+    for case in fq.determinism_images():
+        fq.check_deterministic(emu_ctx, MEM, case)
 
 
 # ---- saving and loading -----------------------------------------------------------------------------------------------

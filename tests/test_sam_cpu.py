@@ -6,15 +6,14 @@ lines straddle slices in every case here; windows are set per test (SX_FLAG_SAM_
 
 The 24 MB case (reads-100-10-0.fq, 2 edits) is not run whole here: its first reads are, and their lines are compared with
 the fixture's first 200 lines.  tests/test_gpu_sam.py checks that case by its SHA-256."""
-import itertools
-
-import numpy as np
 import pytest
 
 import approx_model
+import sam_kernel_cases as skc
 from approx_cases import remapped
+from device_memory import HarnessMemory
 from sam_cases import check_case, sam_cases, subset_fastq
-from stralg_amd import _lib, api
+from stralg_amd import api
 
 
 @pytest.fixture(scope="module")
@@ -81,136 +80,46 @@ def test_small_read_batches(emu_ctx, cases):
         check_case(c, b"".join(run(emu_ctx, c["fasta"], c["fastq"], c["k"], batch=batch, window=4096)))
 
 
-# ---- sx_sam_layout_dev / sx_sam_emit_dev on made-up hits ------------------------------------------------------------
-def aligned_bytes(n):
-    raw = np.zeros(n + 32, np.uint8)
-    at = (-raw.ctypes.data) % 16
-    return raw[at:at + n]
-
-
-def flat(items):
-    off = np.zeros(len(items) + 1, np.uint32)
-    off[1:] = np.cumsum([len(x) for x in items])
-    data = np.frombuffer(b"".join(items) + b"\0", np.uint8).copy()
-    return data, off
-
-
-class Batch:
-    def __init__(self, ctx, hits, sa, names, seqs, quals, rnames):
-        self.ctx = ctx
-        self.keep = [np.ascontiguousarray(hits), np.ascontiguousarray(sa, dtype=np.uint32)]
-        self.keep += list(flat(names) + flat(seqs) + flat(quals) + flat(rnames))
-        h, s, nm, no, sq, so, ql, qo, rn, ro = self.keep
-        self.n_hits = h.size
-        self.batch = ctx.sam_batch(h, h.size, s, s.size, nm, no, sq, so, ql, qo, len(names), rn, ro, len(rnames))
-        self.off = np.zeros(h.size + 1, np.uint64)
-        self.total = ctx.sam_layout_dev(self.batch, self.off)
-
-    def text(self, window=None):
-        window = window or max(self.total, 1)
-        out = b""
-        for lo in range(0, self.total, window):
-            hi = min(self.total, lo + window)
-            buf = aligned_bytes(hi - lo + 16)
-            buf[:] = 0xEE
-            self.ctx.sam_emit_dev(self.batch, self.off, self.total, lo, hi, buf)
-            assert (buf[hi - lo:] == 0xEE).all(), "bytes behind the window were written"
-            out += buf[:hi - lo].tobytes()
-        return out
-
-
-def make_hits(rows):
-    """rows: (query, L, R, gaps)"""
-    hits = np.zeros(len(rows), dtype=_lib.APPROX_HIT_DTYPE)
-    for k, (q, L, R, gaps) in enumerate(rows):
-        hits[k]["query"], hits[k]["L"], hits[k]["R"] = q, L, R
-        hits[k]["n_gaps"] = len(gaps)
-        hits[k]["gap"][:len(gaps)] = gaps
-    return hits
-
-
-def gap_patterns(m, max_gaps):
-    """every edit string over M / I / D of a pattern of m symbols with at most max_gaps I / D: its gap[] list"""
-    out = []
-    for n_i in range(max_gaps + 1):
-        for n_d in range(max_gaps + 1 - n_i):
-            length = m + n_d
-            for where in itertools.combinations(range(length), n_i + n_d):
-                for d_set in itertools.combinations(where, n_d):
-                    out.append([w | (_lib.APPROX_GAP_D if w in d_set else 0) for w in where])
-    return out
+# ---- sx_sam_layout_dev / sx_sam_emit_dev on made-up hits (tests/sam_kernel_cases.py; the GPU runs the same cases) -------------
+MEM = HarnessMemory()
 
 
 def test_cigar_on_the_device(emu_ctx):
-    rng = np.random.default_rng(8)
-    gaps6 = gap_patterns(6, 3)
-    rows = [(0, 0, 1, g) for g in gaps6]
-    want = [api.approx_cigar(6, g) for g in gaps6]
-    long_m = 300
-    for _ in range(40):  # k = 8
-        n_d = int(rng.integers(0, 9))
-        where = sorted(rng.choice(long_m + n_d, 8, replace=False).tolist())
-        if _ % 4 == 0:  # (runs of adjacent operations)
-            where = list(range(where[0] % 200, where[0] % 200 + 8))
-        d_set = set(rng.choice(where, n_d, replace=False).tolist())
-        g = [w | (_lib.APPROX_GAP_D if w in d_set else 0) for w in where]
-        rows.append((1, 0, 1, g))
-        want.append(api.approx_cigar(long_m, g))
-    b = Batch(emu_ctx, make_hits(rows), [41], [b"six", b"long"], [b"ACGTAC", b"A" * long_m], [b"~" * 6, b"!" * long_m], [b"rec"])
-    lines = b.text().split(b"\n")[:-1]
-    assert len(lines) == len(rows)
-    for line, cigar, row in zip(lines, want, rows):
-        f = line.split(b"\t")
-        assert f[5].decode() == cigar, row
-        assert f[0] == (b"six", b"long")[row[0]] and f[2] == b"rec" and f[3] == b"42"
-        assert line == b"\t".join([f[0], b"0", b"rec", b"42", b"0", cigar.encode(), b"*", b"0", b"0", f[9], f[10]])
-    assert sum(len(l) + 1 for l in lines) == b.total
-    assert b.off[-1] == b.total and (np.diff(b.off.astype(np.int64)) == [len(l) + 1 for l in lines]).all()
-
-
-POSITIONS = [1, 9, 10, 99_999, 100_000, 2 ** 32 - 1]
-
-
-def digit_batch(ctx):
-    sa = [p - 1 for p in POSITIONS] + [7] * 70 + [123456]
-    rows = [(1, 0, 6, []), (0, 2, 4, [2]), (1, 6, 77, [1 | _lib.APPROX_GAP_D])]  # (the last: a long interval)
-    return Batch(ctx, make_hits(rows), sa, [b"a b", b"r1"], [b"ACG", b"TT"], [b"III", b"##"], [b"chr"]), sa, rows
-
-
-def expected_text(sa, rows, names, seqs, quals, rname):
-    out = b""
-    for q, L, R, g in rows:
-        for i in range(L, R):
-            out += b"%s\t0\t%s\t%d\t0\t%s\t*\t0\t0\t%s\t%s\n" % (names[q], rname, sa[i] + 1,
-                                                             api.approx_cigar(len(seqs[q]), g).encode(), seqs[q], quals[q])
-    return out
+    skc.check_cigars(emu_ctx, MEM, skc.cigar_case())
 
 
 def test_position_digits(emu_ctx):
-    b, sa, rows = digit_batch(emu_ctx)
-    want = expected_text(sa, rows, [b"a b", b"r1"], [b"ACG", b"TT"], [b"III", b"##"], b"chr")
-    got = b.text()
-    assert got == want
-    assert [l.split(b"\t")[3] for l in got.split(b"\n")[:6]] == [str(p).encode() for p in POSITIONS]
-    assert b.total == len(want)
+    skc.check_position_digits(emu_ctx, MEM, skc.digit_case())
 
 
-@pytest.mark.parametrize("window", [1, 15, 16, 17, 255, 256, 257])
+@pytest.mark.parametrize("window", skc.WINDOWS)
 def test_emit_window_sizes(emu_ctx, window):
-    b, sa, rows = digit_batch(emu_ctx)
-    assert b.text(window) == b.text()
+    skc.check_window(emu_ctx, MEM, skc.digit_case(), window)
 
 
 def test_layout_rejects_hits_outside_the_batch(emu_ctx):
-    for row in [(2, 0, 1, []), (0, 0, 9, []), (0, 3, 2, [])]:
-        with pytest.raises(api.StralgAmdError) as e:
-            Batch(emu_ctx, make_hits([row]), [1, 2, 3], [b"a", b"b"], [b"A", b"C"], [b"!", b"!"], [b"r"])
-        assert "code -1" in str(e.value)
+    for case in skc.refused_cases():
+        skc.check_refused(emu_ctx, MEM, case)
 
 
 def test_empty_batch(emu_ctx):
-    b = Batch(emu_ctx, make_hits([]), [0], [b"a"], [b"A"], [b"!"], [b"r"])
-    assert b.total == 0 and b.text() == b""
+    skc.check_empty(emu_ctx, MEM, skc.empty_case())
+
+
+@pytest.fixture(scope="module")
+def text_cases():
+    return skc.text_cases()
+
+
+@pytest.mark.parametrize("name", skc.TEXT_CASE_NAMES)
+def test_layout_and_emit_at_the_kernels_thresholds(emu_ctx, text_cases, name):
+    case = text_cases[name]
+    assert not case.get("gpu_only")
+    skc.check_text(emu_ctx, MEM, case)
+
+
+def test_text_case_names_are_the_modules(text_cases):
+    assert list(text_cases) == skc.TEXT_CASE_NAMES
 
 
 # ---- sx_fastq_index --------------------------------------------------------------------------------------------------
