@@ -14,6 +14,7 @@
 #include "sx_internal.hpp"
 #include "sx_window.hpp"
 #include "sx_pager.hpp"
+#include "sx_hostio.hpp"
 
 #include <chrono>
 #include <cmath>
@@ -406,39 +407,6 @@ int sx_build_tables(sx_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t sigma
     return sx_sync(ctx);
 }
 
-// device -> sink in chunks through two pinned staging buffers: the copy of chunk k+1 runs while the sink
-// (typically fwrite) consumes chunk k; nothing of the array's size exists on the host
-static int stream_out(sx_ctx *ctx, int section, const void *d_src, size_t bytes, sx_sink_fn sink, void *user)
-{
-    constexpr size_t kChunk = (size_t)32 << 20;
-    if (!ctx->h_stage[0]) {
-        for (int b = 0; b < 2; ++b)
-            if (hipHostMalloc((void **)&ctx->h_stage[b], kChunk, hipHostMallocDefault) != hipSuccess)
-                return sx_fail_msg(ctx, SX_E_NOMEM, "pinned staging buffers");
-    }
-    const char *src = (const char *)d_src;
-    size_t off = 0, pending = 0;
-    int cur = 0;
-    if (bytes) {
-        pending = bytes < kChunk ? bytes : kChunk;
-        SX_CHECK(hipMemcpyAsync(ctx->h_stage[0], src, pending, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    while (pending) {
-        SX_CHECK(hipStreamSynchronize(ctx->stream));
-        const size_t have = pending;
-        off += have;
-        const size_t next = bytes - off < kChunk ? bytes - off : kChunk;
-        if (next) SX_CHECK(hipMemcpyAsync(ctx->h_stage[cur ^ 1], src + off, next, hipMemcpyDeviceToHost, ctx->stream));
-        if (sink(user, section, ctx->h_stage[cur], have) != 0) {
-            (void)hipStreamSynchronize(ctx->stream);
-            return sx_fail_msg(ctx, SX_E_ARG, "the sink refused a chunk");
-        }
-        pending = next;
-        cur ^= 1;
-    }
-    return 0;
-}
-
 int sx_build_tables_stream(sx_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t sigma, int want_sa, sx_sink_fn sink,
                            void *user)
 {
@@ -459,9 +427,9 @@ int sx_build_tables_stream(sx_ctx *ctx, const uint8_t *text, uint64_t n, uint32_
     if (n) SX_CHECK(hipMemcpyAsync(d_text, text, n, hipMemcpyHostToDevice, ctx->stream));
     SX_TRY(sx_sa_build_impl(ctx, d_text, n, sigma, d_sa, d_bwt));
     SX_TRY(sx_tables_from_bwt_impl(ctx, d_bwt, N, sigma, d_c, d_o));
-    if (want_sa) SX_TRY(stream_out(ctx, SX_SECTION_SA, d_sa, N * sizeof(uint32_t), sink, user));
-    SX_TRY(stream_out(ctx, SX_SECTION_C, d_c, (size_t)sigma * 4, sink, user));
-    SX_TRY(stream_out(ctx, SX_SECTION_O, d_o, o_bytes, sink, user));
+    if (want_sa) SX_TRY(sx_stream_to_sink(ctx, SX_SECTION_SA, d_sa, N * sizeof(uint32_t), sink, user));
+    SX_TRY(sx_stream_to_sink(ctx, SX_SECTION_C, d_c, (size_t)sigma * 4, sink, user));
+    SX_TRY(sx_stream_to_sink(ctx, SX_SECTION_O, d_o, o_bytes, sink, user));
     return sx_sync(ctx);
 }
 

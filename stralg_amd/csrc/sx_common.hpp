@@ -63,6 +63,11 @@ enum {
     SX_NSLABS = 7
 };
 
+#ifndef SX_STAGE_BYTES
+#define SX_STAGE_BYTES (32u << 20) // one of a context's two pinned staging buffers: the chunk of every staged copy
+#endif
+constexpr size_t sx_stage_bytes = SX_STAGE_BYTES;
+
 struct sx_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -70,7 +75,7 @@ struct sx_ctx {
     sx_slab slab[SX_NSLABS];
     uint32_t *h_pin = nullptr; // pinned read-back page (4 KiB) + word 1024: the sequence number of the last read-back
     uint32_t readback_seq = 0;
-    char *h_stage[2] = {nullptr, nullptr}; // pinned staging of the streaming downloads (allocated on first use)
+    char *h_stage[2] = {nullptr, nullptr}; // pinned staging, SX_STAGE_BYTES each (sx_hostio.hpp: allocated on first use)
     // profiling
     uint32_t chain_epoch = 0; // look-back status epoch (24 bits), see sx_device.hpp
     int64_t chain_max_override = -1; // SX_FLAG_CHAIN_MAX_ENTRIES; -1 = choose by alphabet size

@@ -2,7 +2,6 @@
 #include <atomic>
 #include <chrono>
 #include "sx_common.hpp"
-#include "sx_scan.hpp"
 
 #include <new>
 
@@ -40,17 +39,6 @@ int sx_slab_ensure(sx_ctx *ctx, int which, size_t bytes)
     SX_CHECK(hipMalloc(&s.p, want));
     s.cap = want;
     return 0;
-}
-
-uint32_t *sx::sx_scan_scratch(sx_ctx *ctx, uint32_t ntiles)
-{
-    // tile totals of the scan in flight; a slab of its own so that growing it
-    // never moves a caller's data
-    const size_t need = (size_t)ntiles * sizeof(uint32_t);
-    if (ctx->slab[SX_SLAB_SCAN].cap < need) {
-        if (sx_slab_ensure(ctx, SX_SLAB_SCAN, need) != 0) return nullptr;
-    }
-    return (uint32_t *)ctx->slab[SX_SLAB_SCAN].p;
 }
 
 int sx_chain_slab(sx_ctx *ctx, int which, size_t bytes)

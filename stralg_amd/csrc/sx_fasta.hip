@@ -18,6 +18,7 @@
 // histogram, a 256-entry table built on the host, and a streaming lookup.
 #include "sx_common.hpp"
 #include "sx_device.hpp"
+#include "sx_bytes16.hpp"
 #include "sx_scan.hpp"
 #include "sx_internal.hpp"
 
@@ -26,30 +27,8 @@ namespace sx {
 __device__ __forceinline__ bool fasta_space(uint32_t c) { return c == ' ' || (c >= '\t' && c <= '\r'); }
 
 // ---- packing: three passes over tiles of 4096 bytes, 16 bytes per thread in registers ------------------------
-constexpr int kFaPer = 16, kFaTile = kBlock * kFaPer;
+constexpr int kFaPer = kBytes16, kFaTile = kBlock * kFaPer;
 
-// the thread's 16 bytes (zero beyond `end`: position `end` itself is the terminating NUL of the reference's buffer).  In two
-// steps, so that a workgroup can ask for the bytes of several tiles before it looks at the first (round 5): fasta_fetch16
-// issues the load where one aligned 16-byte load does (everywhere but at the image's end), fasta_unpack16 spreads the bytes
-// -- or reads them one by one.
-__device__ __forceinline__ bool fasta_fetch16(const uint8_t *__restrict__ file, uint64_t i0, uint64_t end, uint4 &v)
-{
-    const bool fast = i0 + kFaPer <= end && ((uintptr_t)(file + i0) & 15u) == 0;
-    if (fast) v = *reinterpret_cast<const uint4 *>(file + i0);
-    return fast;
-}
-__device__ __forceinline__ void fasta_unpack16(const uint8_t *__restrict__ file, uint64_t i0, uint64_t end, bool fast, const uint4 &v,
-                                               uint32_t (&b)[kFaPer])
-{
-    if (fast) {
-        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int k = 0; k < kFaPer; ++k) b[k] = (w[k >> 2] >> (8 * (k & 3))) & 0xFFu;
-    } else {
-#pragma unroll
-        for (int k = 0; k < kFaPer; ++k) b[k] = i0 + k < end ? (uint32_t)file[i0 + k] : 0u;
-    }
-}
 // tiles a workgroup takes, one after the other, all of their loads in flight from the start.  Measured (round 5, 1 GiB image):
 // 1, 2, 4 tiles a workgroup 2.2 ms each, 8: 2.4 -- the two kernels are not waiting for their loads: a tile costs each of its
 // four waves some 600 vector instructions (the walk in both states, five block-wide reductions), 4 KiB per 1200 cycles of a
@@ -60,22 +39,11 @@ __device__ __forceinline__ void fasta_unpack16(const uint8_t *__restrict__ file,
 constexpr int kFaSub = SX_FASTA_SUB;
 
 // Which of a thread's 16 bytes are '\n', '>', white space (what a sequence drops: isspace()), ' ' or '\t' (what a header line
-// drops besides '>'), NUL: bit k for byte k.  Where the 16 bytes came as one load they are classified four at a time in their
-// words -- equality with a constant and "at least a constant" per byte without carries between the bytes, the four flag bits of
-// a word gathered by a dot product (sx_classify.hip does the same for the type bits) --, 170 instructions where a compare and
-// a shift for each byte and each class were 340 (round 5; the two kernels are bound by their instructions, 1.06 and 1.0 ms a GiB).
+// drops besides '>'), NUL: bit k for byte k (sx_bytes16.hpp; zero beyond `end`: position `end` itself is the terminating NUL
+// of the reference's buffer).
 struct fa_masks {
     uint32_t nl, gt, sp, hdrop, zero;
 };
-__device__ __forceinline__ uint32_t fa_eq4(uint32_t w, uint32_t k4) // 0x80 in every byte of w that equals k4's
-{
-    const uint32_t x = w ^ k4;
-    return ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u;
-}
-__device__ __forceinline__ uint32_t fa_ge4(uint32_t w, uint32_t k4) // 0x80 in every byte of w that is >= k4's (which are < 0x80)
-{
-    return (w | ((w | 0x80808080u) - k4)) & 0x80808080u;
-}
 __device__ __forceinline__ fa_masks fasta_masks16(const uint8_t *__restrict__ file, uint64_t i0, uint64_t end, bool fast, const uint4 &v)
 {
     fa_masks m = {0, 0, 0, 0, 0};
@@ -84,11 +52,11 @@ __device__ __forceinline__ fa_masks fasta_masks16(const uint8_t *__restrict__ fi
         uint32_t nl[4], gt[4], sp[4], hd[4], ze[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const uint32_t spc = fa_eq4(w[j], 0x20202020u), tab = fa_eq4(w[j], 0x09090909u);
-            nl[j] = fa_eq4(w[j], 0x0A0A0A0Au);
-            gt[j] = fa_eq4(w[j], 0x3E3E3E3Eu);
-            ze[j] = fa_eq4(w[j], 0u);
-            sp[j] = spc | (fa_ge4(w[j], 0x09090909u) & ~fa_ge4(w[j], 0x0E0E0E0Eu)); // ' ', or 9 ... 13
+            const uint32_t spc = eq4(w[j], 0x20202020u), tab = eq4(w[j], 0x09090909u);
+            nl[j] = eq4(w[j], 0x0A0A0A0Au);
+            gt[j] = eq4(w[j], 0x3E3E3E3Eu);
+            ze[j] = eq4(w[j], 0u);
+            sp[j] = spc | (ge4(w[j], 0x09090909u) & ~ge4(w[j], 0x0E0E0E0Eu)); // ' ', or 9 ... 13
             hd[j] = spc | tab;
         }
         m.nl = gather16(nl[0], nl[1], nl[2], nl[3], 7);
@@ -96,7 +64,7 @@ __device__ __forceinline__ fa_masks fasta_masks16(const uint8_t *__restrict__ fi
         m.sp = gather16(sp[0], sp[1], sp[2], sp[3], 7);
         m.hdrop = gather16(hd[0], hd[1], hd[2], hd[3], 7);
         m.zero = gather16(ze[0], ze[1], ze[2], ze[3], 7);
-    } else { // (the image's last bytes, or an image that does not start on a 16-byte boundary: zero beyond `end`)
+    } else {
 #pragma unroll
         for (int k = 0; k < kFaPer; ++k) {
             const uint32_t c = i0 + k < end ? (uint32_t)file[i0 + k] : 0u;
@@ -179,7 +147,7 @@ __global__ __launch_bounds__(kBlock) void fasta_scan_kernel(const uint8_t *__res
 #pragma unroll
     for (int sub = 0; sub < kFaSub; ++sub) {
         raw[sub] = {0, 0, 0, 0};
-        fast[sub] = fasta_fetch16(file, (((uint64_t)blockIdx.x * kFaSub + sub) * kBlock + threadIdx.x) * kFaPer, end, raw[sub]);
+        fast[sub] = fetch16(file, (((uint64_t)blockIdx.x * kFaSub + sub) * kBlock + threadIdx.x) * kFaPer, end, raw[sub]);
     }
 #pragma unroll
     for (int sub = 0; sub < kFaSub; ++sub) {
@@ -264,7 +232,7 @@ __global__ __launch_bounds__(kBlock) void fasta_write_kernel(const uint8_t *__re
 #pragma unroll
     for (int sub = 0; sub < kFaSub; ++sub) {
         raw[sub] = {0, 0, 0, 0};
-        fast[sub] = fasta_fetch16(file, (((uint64_t)blockIdx.x * kFaSub + sub) * kBlock + threadIdx.x) * kFaPer, end, raw[sub]);
+        fast[sub] = fetch16(file, (((uint64_t)blockIdx.x * kFaSub + sub) * kBlock + threadIdx.x) * kFaPer, end, raw[sub]);
     }
 #pragma unroll
     for (int sub = 0; sub < kFaSub; ++sub) {
@@ -272,7 +240,7 @@ __global__ __launch_bounds__(kBlock) void fasta_write_kernel(const uint8_t *__re
     if (tile >= tiles) break; // uniform
     const uint64_t i0 = ((uint64_t)tile * kBlock + threadIdx.x) * kFaPer;
     uint32_t b[kFaPer];
-    fasta_unpack16(file, i0, end, fast[sub], raw[sub], b);
+    unpack16(file, i0, end, fast[sub], raw[sub], b);
     const fa_masks m = fasta_masks16(file, i0, end, fast[sub], raw[sub]);
     const bool in_seq = fasta_enter_state(m, i0, end, tile_carry[tile], lds);
     const fa_chunk c = fasta_walk(m, i0, end, in_seq);

@@ -17,6 +17,8 @@
 // Where a byte goes is a function of the scans alone (no atomics place anything): the same image gives the same bytes.
 #include "sx_common.hpp"
 #include "sx_device.hpp"
+#include "sx_bytes16.hpp"
+#include "sx_hostio.hpp"
 #include "sx_scan.hpp"
 #include "sx_index.hpp"
 
@@ -28,26 +30,20 @@
 namespace sx {
 
 // ---- FASTQ image -> the six arrays of sx_fastq ---------------------------------------------------------------------
-constexpr int kFqPer = 16, kFqTile = kBlock * kFqPer;
+constexpr int kFqPer = kBytes16, kFqTile = kBlock * kFqPer;
 constexpr uint32_t kFqLineMax = 2047; // fgets(buffer, 2048): a line's content must be shorter than this
 enum { FQ_ERR_NUL = 1, FQ_ERR_LINE = 2 };
 
-__device__ __forceinline__ uint32_t fq_eq4(uint32_t w, uint32_t k4) // 0x80 in every byte of w that equals k4's
-{
-    const uint32_t x = w ^ k4;
-    return ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u;
-}
-
-// which of the lane's 16 bytes (those in front of `len`) are newlines / NULs: bit k for byte k
+// which of the lane's 16 bytes (those in front of `len`) are newlines / NULs: bit k for byte k (sx_bytes16.hpp)
 __device__ __forceinline__ void fq_masks16(const uint8_t *__restrict__ img, uint64_t i0, uint64_t len, uint32_t &nl, uint32_t &zero)
 {
     nl = 0, zero = 0;
     if (i0 >= len) return;
-    if (i0 + kFqPer <= len && ((uintptr_t)(img + i0) & 15u) == 0) {
-        const uint4 v = *reinterpret_cast<const uint4 *>(img + i0);
-        nl = gather16(fq_eq4(v.x, 0x0A0A0A0Au), fq_eq4(v.y, 0x0A0A0A0Au), fq_eq4(v.z, 0x0A0A0A0Au), fq_eq4(v.w, 0x0A0A0A0Au), 7);
-        zero = gather16(fq_eq4(v.x, 0u), fq_eq4(v.y, 0u), fq_eq4(v.z, 0u), fq_eq4(v.w, 0u), 7);
-    } else { // (the image's last bytes, or an image that does not start on a 16-byte boundary)
+    uint4 v = {0, 0, 0, 0};
+    if (fetch16(img, i0, len, v)) {
+        nl = eq16(v, 0x0A0A0A0Au);
+        zero = eq16(v, 0u);
+    } else { // (nothing beyond `len` counts as a NUL here)
         for (int k = 0; k < kFqPer && i0 + k < len; ++k) {
             const uint32_t c = img[i0 + k];
             nl |= (c == '\n' ? 1u : 0u) << k;
@@ -167,110 +163,6 @@ __global__ __launch_bounds__(kBlock) void fq_scatter_kernel(const uint8_t *__res
 }
 
 static std::atomic<int> g_live_indexes{0};
-constexpr size_t kStage = (size_t)32 << 20; // the context's pinned staging buffers (sx_build.hip: stream_out)
-
-static int stage_buffers(sx_ctx *ctx)
-{
-    for (int b = 0; b < 2; ++b)
-        if (!ctx->h_stage[b] && hipHostMalloc((void **)&ctx->h_stage[b], kStage, hipHostMallocDefault) != hipSuccess) {
-            ctx->h_stage[b] = nullptr;
-            (void)hipGetLastError();
-            return sx_fail_msg(ctx, SX_E_NOMEM, "pinned staging buffers");
-        }
-    return 0;
-}
-
-// host -> device in 32 MiB chunks through the two pinned staging buffers: the copy of a chunk runs while the host fills
-// the next one
-static int upload_staged(sx_ctx *ctx, void *d_dst, const void *h_src, size_t bytes)
-{
-    if (!bytes) return 0;
-    SX_TRY(stage_buffers(ctx));
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    int rc = 0;
-    for (int b = 0; b < 2 && rc == 0; ++b)
-        if (hipEventCreate(&ev[b]) != hipSuccess) rc = sx_fail_msg(ctx, SX_E_INTERNAL, "event for a staged upload");
-    size_t off = 0;
-    for (int k = 0; rc == 0 && off < bytes; ++k) {
-        const size_t n = bytes - off < kStage ? bytes - off : kStage;
-        const int b = k & 1;
-        if (k >= 2 && hipEventSynchronize(ev[b]) != hipSuccess) rc = sx_fail_msg(ctx, SX_E_INTERNAL, "staged upload");
-        if (rc) break;
-        memcpy(ctx->h_stage[b], (const char *)h_src + off, n);
-        if (hipMemcpyAsync((char *)d_dst + off, ctx->h_stage[b], n, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-            hipEventRecord(ev[b], ctx->stream) != hipSuccess)
-            rc = sx_fail_msg(ctx, SX_E_INTERNAL, "staged upload");
-        off += n;
-    }
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == 0) rc = sx_fail_msg(ctx, SX_E_INTERNAL, "staged upload");
-    for (int b = 0; b < 2; ++b)
-        if (ev[b]) (void)hipEventDestroy(ev[b]);
-    return rc;
-}
-
-// device -> sink in chunks of at most 32 MiB through the pinned staging buffers: the copy of a chunk runs while the sink
-// works on the one before
-static int download_to_sink(sx_ctx *ctx, const void *d_src, size_t bytes, sx_sink_fn sink, void *user)
-{
-    SX_TRY(stage_buffers(ctx));
-    const char *src = (const char *)d_src;
-    size_t off = 0, pending = 0;
-    int cur = 0;
-    if (bytes) {
-        pending = bytes < kStage ? bytes : kStage;
-        SX_CHECK(hipMemcpyAsync(ctx->h_stage[0], src, pending, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    while (pending) {
-        SX_CHECK(hipStreamSynchronize(ctx->stream));
-        const size_t have = pending;
-        off += have;
-        const size_t next = bytes - off < kStage ? bytes - off : kStage;
-        if (next) SX_CHECK(hipMemcpyAsync(ctx->h_stage[cur ^ 1], src + off, next, hipMemcpyDeviceToHost, ctx->stream));
-        if (sink(user, SX_SECTION_INDEX, ctx->h_stage[cur], have) != 0) {
-            (void)hipStreamSynchronize(ctx->stream);
-            return sx_fail_msg(ctx, SX_E_ARG, "the sink refused a chunk");
-        }
-        pending = next;
-        cur ^= 1;
-    }
-    return 0;
-}
-
-// device allocations that are released unless someone keeps them
-struct Scoped {
-    std::vector<void *> p;
-    ~Scoped()
-    {
-        for (void *q : p) (void)hipFree(q);
-    }
-    template <class T> int take(sx_ctx *ctx, T **out, size_t count, size_t *bytes_out = nullptr)
-    {
-        void *q = nullptr;
-        *out = nullptr;
-        const size_t bytes = ((count * sizeof(T) + 255) & ~(size_t)255) + 256; // (readable a little beyond the end)
-        if (hipMalloc(&q, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            return sx_fail_msg(ctx, SX_E_NOMEM, "index: device memory");
-        }
-        p.push_back(q);
-        *out = (T *)q;
-        if (bytes_out) *bytes_out += bytes;
-        return 0;
-    }
-    void drop(void *q)
-    {
-        for (size_t k = 0; k < p.size(); ++k)
-            if (p[k] == q) {
-                (void)hipFree(q);
-                p.erase(p.begin() + (long)k);
-                return;
-            }
-    }
-    void keep() { p.clear(); }
-};
-
-static int nomem_of(int rc) { return rc == (int)hipErrorOutOfMemory ? SX_E_NOMEM : rc; }
-
 static void free_rec(sx_index_rec &R)
 {
     (void)hipFree(R.d_string), (void)hipFree(R.d_sa), (void)hipFree(R.d_c), (void)hipFree(R.d_o), (void)hipFree(R.d_ro);
@@ -307,7 +199,7 @@ static int make_view(sx_ctx *ctx, sx_index *idx)
     }
     rname_off[n] = (uint32_t)rnames.size();
     rnames.push_back(0);
-    Scoped S;
+    sx_dev_scope S;
     size_t bytes = 0;
     uint8_t *d_rnames, *d_tabs;
     uint32_t *d_rname_off;
@@ -349,7 +241,7 @@ static int add_tables(sx_ctx *ctx, sx_index *idx, const sx_map_record &M, const 
     R.sigma = M.sigma;
     memcpy(R.remap, M.remap, 256);
     const size_t o_words = (size_t)(M.N + 1) * M.sigma;
-    Scoped S;
+    sx_dev_scope S;
     size_t bytes = 0;
     SX_TRY(S.take(ctx, &R.d_sa, (size_t)M.N, &bytes));
     SX_TRY(S.take(ctx, &R.d_c, (size_t)M.sigma, &bytes));
@@ -371,13 +263,16 @@ static int add_tables(sx_ctx *ctx, sx_index *idx, const sx_map_record &M, const 
     return 0;
 }
 
-static bool record_ok(const sx_map_record &R)
+static int record_check(sx_ctx *ctx, const sx_map_record &R)
 {
-    return R.name && R.sa && R.c_table && R.o_table && R.remap && R.N != 0 && R.N <= 0xFFFFFFFFull && R.sigma >= 1 && R.sigma <= 128;
+    if (sx_map_record_check(R, 1)) return 0;
+    return sx_fail_msg(ctx, SX_E_ARG, "index: a record lacks its name, suffix array, tables or remap table");
 }
 
+// an index of host tables, given as records (no strings) or as sources; every record is checked first
 static int from_sources(sx_ctx *ctx, const sx_map_record *records, const sx_index_source *sources, uint32_t n, sx_index **out)
 {
+    for (uint32_t r = 0; r < n; ++r) SX_TRY(record_check(ctx, records ? records[r] : sources[r].record));
     SX_CHECK(hipSetDevice(ctx->device));
     sx_index *idx = new_index(ctx);
     if (!idx) return sx_fail_msg(ctx, SX_E_NOMEM, "index");
@@ -400,7 +295,7 @@ static int build_record(sx_ctx *ctx, sx_index *idx, const uint8_t *d_seq, uint64
     sx_index_rec R;
     R.name = name;
     R.N = n + 1;
-    Scoped S, T; // S: what the record keeps, T: temporaries
+    sx_dev_scope S, T; // S: what the record keeps, T: temporaries
     size_t bytes = 0;
     int16_t t16[256];
     SX_TRY(S.take(ctx, &R.d_string, (size_t)n + 1, &bytes));
@@ -414,8 +309,8 @@ static int build_record(sx_ctx *ctx, sx_index *idx, const uint8_t *d_seq, uint64
     SX_TRY(S.take(ctx, &R.d_c, (size_t)sigma, &bytes));
     SX_TRY(S.take(ctx, &R.d_o, o_words, &bytes));
     SX_TRY(T.take(ctx, &d_bwt, (size_t)N));
-    SX_TRY(nomem_of(sx_sa_bwt_build_dev(ctx, R.d_string, n, sigma, R.d_sa, d_bwt)));
-    SX_TRY(nomem_of(sx_bwt_tables_from_bwt_dev(ctx, d_bwt, N, sigma, R.d_c, R.d_o)));
+    SX_TRY(sx_nomem_of(sx_sa_bwt_build_dev(ctx, R.d_string, n, sigma, R.d_sa, d_bwt)));
+    SX_TRY(sx_nomem_of(sx_bwt_tables_from_bwt_dev(ctx, d_bwt, N, sigma, R.d_c, R.d_o)));
     if (include_reverse) { // bwt.c:147-158: the reversed string's suffix array is temporary, its O table is RO
         uint8_t *d_rev;
         uint32_t *d_rsa, *d_rc;
@@ -424,8 +319,8 @@ static int build_record(sx_ctx *ctx, sx_index *idx, const uint8_t *d_seq, uint64
         SX_TRY(T.take(ctx, &d_rsa, (size_t)N));
         SX_TRY(T.take(ctx, &d_rc, (size_t)sigma));
         SX_TRY(sx_reverse_dev(ctx, R.d_string, n, d_rev));
-        SX_TRY(nomem_of(sx_sa_bwt_build_dev(ctx, d_rev, n, sigma, d_rsa, d_bwt)));
-        SX_TRY(nomem_of(sx_bwt_tables_from_bwt_dev(ctx, d_bwt, N, sigma, d_rc, R.d_ro)));
+        SX_TRY(sx_nomem_of(sx_sa_bwt_build_dev(ctx, d_rev, n, sigma, d_rsa, d_bwt)));
+        SX_TRY(sx_nomem_of(sx_bwt_tables_from_bwt_dev(ctx, d_bwt, N, sigma, d_rc, R.d_ro)));
     }
     SX_TRY(sx_sync(ctx));
     S.keep();
@@ -440,16 +335,16 @@ static int build_fasta(sx_ctx *ctx, sx_index *idx, const uint8_t *fasta, uint64_
     uint64_t starts = 1;
     for (const uint8_t *p = fasta, *end = fasta + len; p < end && (p = (const uint8_t *)memchr(p, '>', (size_t)(end - p))) != nullptr; ++p) ++starts;
     const uint64_t term_cap = 2 * starts + 2;
-    Scoped T;
+    sx_dev_scope T;
     uint8_t *d_file, *d_packed;
     uint32_t *d_term;
     SX_TRY(T.take(ctx, &d_file, (size_t)len + 16));
     SX_TRY(T.take(ctx, &d_packed, (size_t)len + 17));
     SX_TRY(T.take(ctx, &d_term, (size_t)term_cap));
-    SX_TRY(upload_staged(ctx, d_file, fasta, (size_t)len));
+    SX_TRY(sx_upload_staged(ctx, d_file, fasta, (size_t)len));
     uint64_t packed_len = 0;
     uint32_t n_rec = 0;
-    SX_TRY(nomem_of(sx_fasta_pack_dev(ctx, d_file, len, d_packed, &packed_len, d_term, term_cap, &n_rec)));
+    SX_TRY(sx_nomem_of(sx_fasta_pack_dev(ctx, d_file, len, d_packed, &packed_len, d_term, term_cap, &n_rec)));
     T.drop(d_file);
     if (2ull * n_rec > term_cap) return sx_fail_msg(ctx, SX_E_INTERNAL, "index: more records than '>' bytes");
     std::vector<uint32_t> term(2 * (size_t)n_rec + 1);
@@ -485,22 +380,9 @@ void sx_fastq_dev_free(sx_fastq_dev *fq)
     memset(fq, 0, sizeof *fq);
 }
 
-static int fastq_index_dev(sx_ctx *ctx, const uint8_t *d_image, uint64_t len, sx_fastq_dev *out);
-
-int sx_fastq_index_dev(sx_ctx *ctx, const uint8_t *d_image, uint64_t len, sx_fastq_dev *out)
-{
-    if (!ctx || !out || (len && !d_image)) return SX_E_ARG;
-    memset(out, 0, sizeof *out);
-    if (len > 0xFFFFFFFEull) return sx_fail_msg(ctx, SX_E_ARG, "FASTQ image must be shorter than 2^32 - 1 bytes");
-    SX_CHECK(hipSetDevice(ctx->device));
-    const int rc = fastq_index_dev(ctx, d_image, len, out);
-    if (rc != 0) memset(out, 0, sizeof *out); // (what was allocated has been released)
-    return nomem_of(rc);
-}
-
 static int fastq_index_dev(sx_ctx *ctx, const uint8_t *d_image, uint64_t len, sx_fastq_dev *out)
 {
-    Scoped S;
+    sx_dev_scope S;
     const uint32_t ntiles = sx_div_up(len, kFqTile);
     // scratch: a few scalars and two u32 a tile (slab M); the line ends and the lengths (slab N, sized once the lines are counted)
     SX_TRY(sx_slab_ensure(ctx, SX_SLAB_M, 256 + 2 * (size_t)(ntiles + 1) * sizeof(uint32_t)));
@@ -564,6 +446,17 @@ static int fastq_index_dev(sx_ctx *ctx, const uint8_t *d_image, uint64_t len, sx
     return 0;
 }
 
+int sx_fastq_index_dev(sx_ctx *ctx, const uint8_t *d_image, uint64_t len, sx_fastq_dev *out)
+{
+    if (!ctx || !out || (len && !d_image)) return SX_E_ARG;
+    memset(out, 0, sizeof *out);
+    if (len > 0xFFFFFFFEull) return sx_fail_msg(ctx, SX_E_ARG, "FASTQ image must be shorter than 2^32 - 1 bytes");
+    SX_CHECK(hipSetDevice(ctx->device));
+    const int rc = fastq_index_dev(ctx, d_image, len, out);
+    if (rc != 0) memset(out, 0, sizeof *out); // (what was allocated has been released)
+    return sx_nomem_of(rc);
+}
+
 int sx_index_live_count(void) { return g_live_indexes.load(); }
 
 int sx_download(sx_ctx *ctx, void *h_dst, const void *d_src, size_t bytes)
@@ -598,7 +491,7 @@ int sx_index_build_fasta(sx_ctx *ctx, const uint8_t *fasta, uint64_t len, int in
     if (rc != 0) {
         (void)hipStreamSynchronize(ctx->stream);
         sx_index_destroy(idx);
-        return nomem_of(rc);
+        return sx_nomem_of(rc);
     }
     *out = idx;
     return 0;
@@ -608,8 +501,6 @@ int sx_index_from_tables(sx_ctx *ctx, const sx_map_record *records, uint32_t n_r
 {
     if (!ctx || !out || (n_records && !records)) return SX_E_ARG;
     *out = nullptr;
-    for (uint32_t r = 0; r < n_records; ++r)
-        if (!record_ok(records[r])) return sx_fail_msg(ctx, SX_E_ARG, "index: a record lacks its name, suffix array, tables or remap table");
     return from_sources(ctx, records, nullptr, n_records, out);
 }
 
@@ -617,8 +508,6 @@ int sx_index_from_sources(sx_ctx *ctx, const sx_index_source *sources, uint32_t 
 {
     if (!ctx || !out || (n_records && !sources)) return SX_E_ARG;
     *out = nullptr;
-    for (uint32_t r = 0; r < n_records; ++r)
-        if (!record_ok(sources[r].record)) return sx_fail_msg(ctx, SX_E_ARG, "index: a record lacks its name, suffix array, tables or remap table");
     return from_sources(ctx, nullptr, sources, n_records, out);
 }
 
@@ -626,7 +515,7 @@ int sx_index_add_record(sx_ctx *ctx, sx_index *idx, const sx_index_source *sourc
 {
     if (!ctx || !idx || !source) return SX_E_ARG;
     if (idx->device != ctx->device) return sx_fail_msg(ctx, SX_E_ARG, "index: it lives on another device than this context");
-    if (!record_ok(source->record)) return sx_fail_msg(ctx, SX_E_ARG, "index: a record lacks its name, suffix array, tables or remap table");
+    SX_TRY(record_check(ctx, source->record));
     SX_CHECK(hipSetDevice(ctx->device));
     const int rc = add_tables(ctx, idx, source->record, source->string, at_front != 0);
     if (rc != 0) {
@@ -675,24 +564,22 @@ int sx_index_map_reads(sx_ctx *ctx, const sx_index *idx, const uint8_t *fastq, s
     sx_fastq_dev fq;
     memset(&fq, 0, sizeof fq);
     {
-        Scoped T;
+        sx_dev_scope T;
         uint8_t *d_image;
         SX_TRY(T.take(ctx, &d_image, fastq_len + 16));
-        SX_TRY(upload_staged(ctx, d_image, fastq, fastq_len));
+        SX_TRY(sx_upload_staged(ctx, d_image, fastq, fastq_len));
         const int frc = sx_fastq_index_dev(ctx, d_image, fastq_len, &fq);
         if (frc == SX_E_MALFORMED || frc == SX_E_ARG) return sx_fail_msg(ctx, frc, "read mapping: malformed FASTQ image (see sx_fastq_index)");
         if (frc != 0) return frc;
     }
-    struct FqFree {
-        sx_fastq_dev *f;
-        ~FqFree() { sx_fastq_dev_free(f); }
-    } fq_free{&fq};
     sx_reads_dev reads;
     reads.count = fq.count;
     reads.d_names = fq.d_names, reads.d_seqs = fq.d_seqs, reads.d_quals = fq.d_quals;
     reads.d_name_off = fq.d_name_off, reads.d_seq_off = fq.d_seq_off, reads.d_qual_off = fq.d_qual_off;
     reads.seq_bytes = fq.seq_bytes;
-    return sx_map_reads_core(ctx, idx, reads, edits, sink, user);
+    const int rc = sx_map_reads_core(ctx, idx, reads, edits, sink, user);
+    sx_fastq_dev_free(&fq);
+    return rc;
 }
 
 int sx_index_write(sx_ctx *ctx, const sx_index *idx, sx_sink_fn sink, void *user)
@@ -713,8 +600,8 @@ int sx_index_write(sx_ctx *ctx, const sx_index *idx, sx_sink_fn sink, void *user
         SX_TRY(put(R.name.c_str(), name_bytes));
         // stralg/serialise.c:7-18: string (u32 length, bytes), suffix array, remap table, C, O, flag, RO
         SX_TRY(put(&n, 4));
-        SX_TRY(download_to_sink(ctx, R.d_string, n, sink, user));
-        SX_TRY(download_to_sink(ctx, R.d_sa, (size_t)R.N * 4, sink, user));
+        SX_TRY(sx_stream_to_sink(ctx, SX_SECTION_INDEX, R.d_string, n, sink, user));
+        SX_TRY(sx_stream_to_sink(ctx, SX_SECTION_INDEX, R.d_sa, (size_t)R.N * 4, sink, user));
         struct { // stralg/remap.h:9-19
             uint32_t alphabet_size;
             signed char table[256], rev_table[128];
@@ -726,11 +613,11 @@ int sx_index_write(sx_ctx *ctx, const sx_index *idx, sx_sink_fn sink, void *user
         for (int c = 1; c < 256; ++c)
             if (R.remap[c] > 0) rt.rev_table[(int)R.remap[c]] = (signed char)c;
         SX_TRY(put(&rt, sizeof rt));
-        SX_TRY(download_to_sink(ctx, R.d_c, (size_t)R.sigma * 4, sink, user));
-        SX_TRY(download_to_sink(ctx, R.d_o, o_bytes, sink, user));
+        SX_TRY(sx_stream_to_sink(ctx, SX_SECTION_INDEX, R.d_c, (size_t)R.sigma * 4, sink, user));
+        SX_TRY(sx_stream_to_sink(ctx, SX_SECTION_INDEX, R.d_o, o_bytes, sink, user));
         const uint8_t has_ro = R.d_ro ? 1 : 0; // (a bool in the reference: one byte)
         SX_TRY(put(&has_ro, 1));
-        if (R.d_ro) SX_TRY(download_to_sink(ctx, R.d_ro, o_bytes, sink, user));
+        if (R.d_ro) SX_TRY(sx_stream_to_sink(ctx, SX_SECTION_INDEX, R.d_ro, o_bytes, sink, user));
     }
     return sx_sync(ctx);
 }

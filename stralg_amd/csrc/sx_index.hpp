@@ -37,7 +37,18 @@ struct sx_reads_dev {
     uint64_t seq_bytes = 0;
 };
 
+// A record's host tables as an index takes them (min_sigma 1: the record without symbols has N = 1, sigma = 1) or as the
+// mapper searches them (min_sigma 2): N and sigma in range, and every array there
+static inline bool sx_map_dims_ok(uint64_t N, uint32_t sigma, uint32_t min_sigma)
+{
+    return N != 0 && N <= 0xFFFFFFFFull && sigma >= min_sigma && sigma <= 128;
+}
+static inline bool sx_map_record_check(const sx_map_record &R, uint32_t min_sigma)
+{
+    return R.name && R.sa && R.c_table && R.o_table && R.remap && sx_map_dims_ok(R.N, R.sigma, min_sigma);
+}
+
 // sx_sam.hip: the mapper's loop over reads and an index that both lie on ctx's device
 int sx_map_reads_core(sx_ctx *ctx, const sx_index *idx, const sx_reads_dev &reads, int edits, sx_sink_fn sink, void *user);
-// sx_index.hip: an index of host tables without the checks of the public call (sx_map_reads_stream has made them)
+// sx_index.hip: sx_index_from_tables without the checks of its arguments (sx_map_reads_stream has made them)
 int sx_index_from_records_impl(sx_ctx *ctx, const sx_map_record *records, uint32_t n_records, sx_index **out);

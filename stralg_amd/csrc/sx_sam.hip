@@ -18,6 +18,7 @@
 #include "sx_common.hpp"
 #include "sx_device.hpp"
 #include "sx_scan.hpp"
+#include "sx_hostio.hpp"
 #include "sx_index.hpp"
 
 #include <stdlib.h>
@@ -38,7 +39,6 @@ constexpr uint32_t kSlice = SX_SAM_SLICE_BYTES;
 constexpr uint32_t kCigarMax = 80;  // 9 runs of M (5 digits) and 8 of I / D (1 digit) take 70 bytes; longer ones are cut
 constexpr uint32_t kInlineMatches = 32;
 constexpr uint32_t kWalk = 4; // matches per lane in one step of the walk inside a long hit
-constexpr size_t kStageBytes = (size_t)32 << 20; // the context's pinned staging buffers (sx_build.hip: stream_out)
 
 struct SamArgs {
     const uint4 *hits; // sx_approx_hit as two 16-byte words
@@ -157,29 +157,6 @@ __device__ __forceinline__ uint32_t fixed_bytes(const HitInfo &I)
     return I.name_l + I.rn_l + I.cig_len + I.seq_l + I.qual_l + 16u;
 }
 
-// exclusive sum over the workgroup's 256 lanes, 64-bit with carries; ends with a barrier (lds: kWavesPerBlock words)
-__device__ __forceinline__ uint64_t block_exclusive_sum_u64(uint64_t v, uint64_t *lds, uint64_t &total)
-{
-    const int lane = lane_id(), w = wave_id();
-    unsigned long long inc = v;
-    for (unsigned d = 1; d < (unsigned)kWave; d <<= 1) {
-        const unsigned long long up = __shfl_up(inc, d, kWave);
-        if (lane >= (int)d) inc += up;
-    }
-    if (lane == kWave - 1) lds[w] = inc;
-    __syncthreads();
-    uint64_t base = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < kWavesPerBlock; ++i) {
-        const uint64_t x = lds[i];
-        if (i < w) base += x;
-        tot += x;
-    }
-    __syncthreads();
-    total = tot;
-    return base + inc - v;
-}
-
 // ---- layout: bytes per hit ---------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void sam_size_kernel(SamArgs A, uint64_t *len_out, uint32_t *err)
 {
@@ -218,73 +195,6 @@ __global__ __launch_bounds__(kBlock) void sam_size_kernel(SamArgs A, uint64_t *l
         if (u == t) bytes += tot;
     }
     if (h < A.n_hits) len_out[h] = bytes;
-}
-
-// ---- 64-bit exclusive scan in place: d[0 .. n) -> prefixes, d[n] <- total -------------------------
-constexpr int kScan64Items = 8;
-constexpr int kScan64Tile = kBlock * kScan64Items;
-
-__global__ __launch_bounds__(kBlock) void scan64_reduce_kernel(const uint64_t *d, uint64_t n, uint64_t *tile_tot)
-{
-    __shared__ uint64_t red[kWavesPerBlock];
-    const uint64_t base = (uint64_t)blockIdx.x * kScan64Tile + (uint64_t)threadIdx.x * kScan64Items;
-    uint64_t acc = 0;
-#pragma unroll
-    for (int k = 0; k < kScan64Items; ++k)
-        if (base + k < n) acc += d[base + k];
-    uint64_t tot;
-    (void)block_exclusive_sum_u64(acc, red, tot);
-    if (threadIdx.x == 0) tile_tot[blockIdx.x] = tot;
-}
-
-__global__ __launch_bounds__(kBlock) void scan64_spine_kernel(uint64_t *tile_tot, uint32_t ntiles, uint64_t *total_out)
-{
-    __shared__ uint64_t red[kWavesPerBlock];
-    uint64_t carry = 0;
-    for (uint64_t start = 0; start < ntiles; start += kBlock) { // uniform trip count
-        const uint64_t i = start + threadIdx.x;
-        const uint64_t v = i < ntiles ? tile_tot[i] : 0;
-        uint64_t tot;
-        const uint64_t ex = block_exclusive_sum_u64(v, red, tot);
-        if (i < ntiles) tile_tot[i] = carry + ex;
-        carry += tot;
-    }
-    if (threadIdx.x == 0) *total_out = carry;
-}
-
-__global__ __launch_bounds__(kBlock) void scan64_apply_kernel(uint64_t *d, uint64_t n, const uint64_t *tile_pre)
-{
-    __shared__ uint64_t red[kWavesPerBlock];
-    const uint64_t base = (uint64_t)blockIdx.x * kScan64Tile + (uint64_t)threadIdx.x * kScan64Items;
-    uint64_t v[kScan64Items];
-    uint64_t acc = 0;
-#pragma unroll
-    for (int k = 0; k < kScan64Items; ++k) {
-        v[k] = base + k < n ? d[base + k] : 0;
-        acc += v[k];
-    }
-    uint64_t tot;
-    uint64_t run = tile_pre[blockIdx.x] + block_exclusive_sum_u64(acc, red, tot);
-#pragma unroll
-    for (int k = 0; k < kScan64Items; ++k) {
-        if (base + k < n) d[base + k] = run;
-        run += v[k];
-    }
-}
-
-static int scan64_inplace(sx_ctx *ctx, uint64_t *d, uint64_t n)
-{
-    if (n == 0) {
-        SX_CHECK(hipMemsetAsync(d, 0, sizeof(uint64_t), ctx->stream));
-        return 0;
-    }
-    const uint32_t ntiles = sx_div_up(n, kScan64Tile);
-    uint64_t *tile_tot = (uint64_t *)sx_scan_scratch(ctx, 2 * ntiles + 2);
-    if (!tile_tot) return sx_fail_msg(ctx, SX_E_NOMEM, "scan scratch");
-    sx_launch(ctx, SX_KC_SAM, n * 8, scan64_reduce_kernel, dim3(ntiles), dim3(kBlock), (const uint64_t *)d, n, tile_tot);
-    sx_launch(ctx, SX_KC_SAM, 0, scan64_spine_kernel, dim3(1), dim3(kBlock), tile_tot, ntiles, d + n);
-    sx_launch(ctx, SX_KC_SAM, n * 16, scan64_apply_kernel, dim3(ntiles), dim3(kBlock), d, n, (const uint64_t *)tile_tot);
-    return 0;
 }
 
 // ---- emit ---------------------------------------------------------------------------------------
@@ -483,6 +393,13 @@ __global__ __launch_bounds__(kBlock) void sam_merge_kernel(const uint4 *src, uin
     dst[2 * at + 1] = src[2 * j + 1];
 }
 
+// what the kernels get of a batch (SamArgs has sx_sam_batch's fields in its order)
+static SamArgs sam_args_of(const sx_sam_batch &b)
+{
+    return SamArgs{(const uint4 *)b.d_hits, b.n_hits,     b.d_sa,       b.sa_len,     b.d_sa_list, b.d_sa_len_list, b.d_names,   b.d_seqs,
+                   b.d_quals,               b.d_name_off, b.d_seq_off,  b.d_qual_off, b.n_reads,   b.d_rnames,      b.d_rname_off, b.n_records};
+}
+
 static int sam_args(sx_ctx *ctx, const sx_sam_batch *b, SamArgs &A)
 {
     if (!ctx || !b) return SX_E_ARG;
@@ -491,22 +408,7 @@ static int sam_args(sx_ctx *ctx, const sx_sam_batch *b, SamArgs &A)
     if (!b->d_name_off || !b->d_seq_off || !b->d_qual_off || !b->d_rname_off || b->n_records == 0 ||
         (uint64_t)b->n_reads * b->n_records > 0xFFFFFFFFull)
         return sx_fail_msg(ctx, SX_E_ARG, "SAM text: offsets of the reads and record names; reads x records below 2^32");
-    A.hits = (const uint4 *)b->d_hits;
-    A.n_hits = b->n_hits;
-    A.sa = b->d_sa;
-    A.sa_len = b->sa_len;
-    A.sa_list = b->d_sa_list;
-    A.sa_len_list = b->d_sa_len_list;
-    A.names = b->d_names;
-    A.seqs = b->d_seqs;
-    A.quals = b->d_quals;
-    A.name_off = b->d_name_off;
-    A.seq_off = b->d_seq_off;
-    A.qual_off = b->d_qual_off;
-    A.n_reads = b->n_reads;
-    A.rnames = b->d_rnames;
-    A.rname_off = b->d_rname_off;
-    A.n_records = b->n_records;
+    A = sam_args_of(*b);
     return 0;
 }
 
@@ -519,7 +421,7 @@ static int sam_layout(sx_ctx *ctx, const SamArgs &A, uint64_t *d_byte_off, uint6
     if (A.n_hits)
         sx_launch(ctx, SX_KC_SAM, A.n_hits * 40, sam_size_kernel, dim3(sx_div_up(A.n_hits, kBlock)), dim3(kBlock), A, d_byte_off,
                   d_err);
-    SX_TRY(scan64_inplace(ctx, d_byte_off, A.n_hits));
+    SX_TRY(device_scan64_inplace(ctx, d_byte_off, A.n_hits, SX_KC_SAM));
     uint32_t h[2] = {0, 0}, e = 0;
     SX_TRY(sx_readback(ctx, (const uint32_t *)(d_byte_off + A.n_hits), 2, h));
     SX_TRY(sx_readback(ctx, d_err, 1, &e));
@@ -539,40 +441,147 @@ static int sam_emit(sx_ctx *ctx, const SamArgs &A, const uint64_t *d_byte_off, u
     return 0;
 }
 
-struct DevBufs { // device and pinned allocations of one sx_map_reads_stream call
-    std::vector<void *> dev;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~DevBufs()
+template <class T, class H> static int upload(sx_ctx *ctx, sx_dev_scope &B, const T **d, const H *h, size_t count)
+{
+    T *p;
+    SX_TRY(B.take(ctx, &p, count));
+    if (count) SX_CHECK(hipMemcpyAsync(p, h, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+    *d = p;
+    return 0;
+}
+
+// ---- the pieces of the mapper's loop (sx_map_reads_core) -----------------------------------------------------------
+// what a mapping call asks of its reads and records; records_ok: sx_map_dims_ok / sx_map_record_check with sigma >= 2
+static int map_check(sx_ctx *ctx, uint64_t n_reads, uint64_t n_records, bool records_ok)
+{
+    if (n_reads * n_records > 0xFFFFFFFFull) return sx_fail_msg(ctx, SX_E_ARG, "read mapping: reads x records must stay below 2^32");
+    if (!records_ok) return sx_fail_msg(ctx, SX_E_ARG, "read mapping: a record lacks its name, suffix array, tables or remap table");
+    return 0;
+}
+
+// Room for the hits of a batch's searches: a guess to start with; a batch that needs more makes it
+// grow, up to 2^27 hits or what a quarter of the free memory holds (72 bytes a hit: the searches' array, the merged one,
+// the byte offsets), before the batch is halved -- a search over few reads leaves most of its lanes idle
+struct HitRoom {
+    uint64_t cap = 0, cap_max = 1ull << 26;
+    sx_approx_hit *d_raw = nullptr;
+    sx_dev_scope own;
+    int init(sx_ctx *ctx, uint64_t guess)
     {
-        for (void *p : dev) (void)hipFree(p);
-        for (int k = 0; k < 2; ++k)
-            if (ev[k]) (void)hipEventDestroy(ev[k]);
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b) cap_max = free_b / 4 / 72 < (1ull << 27) ? free_b / 4 / 72 : 1ull << 27;
+        else (void)hipGetLastError();
+        if (cap_max < (1u << 16)) cap_max = 1u << 16;
+        cap = guess < (1u << 16) ? 1u << 16 : guess > cap_max ? cap_max : guess;
+        return own.take(ctx, &d_raw, (size_t)cap);
     }
-    template <class T> int take(sx_ctx *ctx, T **out, size_t count)
+    // the searches of `batch` reads need room for `need` hits: it grows where that is allowed (one read alone gets whatever
+    // it needs); otherwise *halve, and the caller goes on with half the reads
+    int grow_or_halve(sx_ctx *ctx, uint64_t need, uint32_t batch, bool *halve)
     {
-        void *p = nullptr;
-        const size_t bytes = (count * sizeof(T) + 255) & ~(size_t)255;
-        if (hipMalloc(&p, bytes ? bytes : 256) != hipSuccess) return sx_fail_msg(ctx, SX_E_NOMEM, "read mapping: device memory");
-        dev.push_back(p);
-        *out = (T *)p;
-        return 0;
-    }
-    void drop(void *p)
-    {
-        for (size_t k = 0; k < dev.size(); ++k)
-            if (dev[k] == p) {
-                (void)hipFree(p);
-                dev.erase(dev.begin() + (long)k);
-                return;
-            }
+        *halve = need > cap_max && batch > 1;
+        if (*halve) return 0;
+        cap = need + need / 4 > 2 * cap ? need + need / 4 : 2 * cap;
+        if (cap > cap_max && need <= cap_max) cap = cap_max;
+        own.drop(d_raw);
+        return own.take(ctx, &d_raw, (size_t)cap);
     }
 };
 
-template <class T> static int upload(sx_ctx *ctx, DevBufs &B, T **d, const T *h, size_t count)
+struct MapBufs { // what a mapping call holds on the device beside the hits' room
+    uint8_t *d_pat, *d_win[2];
+    uint64_t *d_ho, *d_vbase, *d_seg, *d_byte_off = nullptr;
+    uint32_t *d_err;
+    sx_approx_hit *d_merged = nullptr;
+    uint64_t merged_cap = 0, stride = 0; // stride: entries of a record's hit offsets in d_ho
+    size_t window = 0;
+    sx_dev_scope own;
+};
+
+// The searches of reads q0 .. q0 + batch, record after record, into the room: seg[r] <- where record r's hits start,
+// seg[records] <- how many there are.  SX_E_CAPACITY: the room is too small for the *need_out hits known of so far.
+static int search_batch(sx_ctx *ctx, const sx_index *idx, const sx_reads_dev &reads, const MapBufs &M, const HitRoom &room, uint32_t q0,
+                        uint32_t batch, int edits, std::vector<uint64_t> &seg, uint64_t *need_out)
 {
-    SX_TRY(B.take(ctx, d, count + 16));
-    if (count) SX_CHECK(hipMemcpyAsync(*d, h, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+    uint64_t p_lo, p_hi;
+    if (reads.h_seq_off) {
+        p_lo = reads.h_seq_off[q0], p_hi = reads.h_seq_off[q0 + batch];
+    } else { // (the offsets were made on the device: the two this batch needs come back)
+        const uint32_t *src[2] = {reads.d_seq_off + q0, reads.d_seq_off + q0 + batch};
+        const uint32_t one[2] = {1, 1};
+        uint32_t got[2];
+        SX_TRY(sx_readback_ranges(ctx, src, one, 2, got));
+        p_lo = got[0], p_hi = got[1];
+    }
+    const uint32_t n_records = (uint32_t)idx->recs.size();
+    uint64_t used = 0;
+    for (uint32_t r = 0; r < n_records; ++r) {
+        const sx_index_rec &R = idx->recs[r];
+        if (p_hi > p_lo)
+            sx_launch(ctx, SX_KC_REMAP, 2 * (p_hi - p_lo), sam_remap_kernel, dim3(sx_div_up(p_hi - p_lo, kBlock)), dim3(kBlock), reads.d_seqs,
+                      (const uint8_t *)(idx->d_tabs + (size_t)r * 256), M.d_pat, p_lo, p_hi);
+        uint64_t tot = 0;
+        const int rc = sx_bwt_approx_search_dev(ctx, R.d_c, R.d_o, R.d_ro, R.N, R.sigma, M.d_pat, reads.d_seq_off + q0, batch, edits,
+                                                M.d_ho + r * M.stride, room.d_raw + used, room.cap - used, &tot);
+        if (rc == SX_E_CAPACITY) *need_out = used + tot;
+        if (rc != 0) return rc;
+        seg[r] = used;
+        used += tot;
+    }
+    seg[n_records] = used;
     return 0;
+}
+
+// The hits of the batch's searches in (read, record rank, hit) order: M.d_merged, query <- read x records + rank
+static int merge_batch(sx_ctx *ctx, MapBufs &M, const HitRoom &room, const std::vector<uint64_t> &seg, uint32_t batch)
+{
+    const uint32_t n_records = (uint32_t)seg.size() - 1;
+    const uint64_t used = seg[n_records];
+    if (used > M.merged_cap) {
+        if (M.d_merged) M.own.drop(M.d_merged), M.own.drop(M.d_byte_off);
+        M.merged_cap = used > room.cap ? used : room.cap;
+        SX_TRY(M.own.take(ctx, &M.d_merged, (size_t)M.merged_cap));
+        SX_TRY(M.own.take(ctx, &M.d_byte_off, (size_t)M.merged_cap + 1));
+    }
+    SX_CHECK(hipMemcpyAsync(M.d_seg, seg.data(), seg.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    SX_CHECK(hipStreamSynchronize(ctx->stream)); // (seg is reused by the next batch)
+    const uint64_t nvq = (uint64_t)batch * n_records;
+    sx_launch(ctx, SX_KC_SAM, nvq * 24, sam_vq_count_kernel, dim3(sx_div_up(nvq, kBlock)), dim3(kBlock), (const uint64_t *)M.d_ho, M.stride,
+              batch, n_records, M.d_vbase);
+    SX_TRY(device_scan64_inplace(ctx, M.d_vbase, nvq, SX_KC_SAM));
+    sx_launch(ctx, SX_KC_SAM, used * 64, sam_merge_kernel, dim3(sx_div_up(used, kBlock)), dim3(kBlock), (const uint4 *)room.d_raw, used,
+              (const uint64_t *)M.d_seg, n_records, (const uint64_t *)M.d_ho, M.stride, batch, (const uint64_t *)M.d_vbase,
+              (uint4 *)M.d_merged, M.d_err);
+    uint32_t e = 0;
+    SX_TRY(sx_readback(ctx, M.d_err, 1, &e));
+    if (e) return sx_fail_msg(ctx, SX_E_INTERNAL, "read mapping: the hits of a batch do not add up");
+    return 0;
+}
+
+// The batch's text: its layout, then window after window through the two device windows and the context's staging
+// buffers: emit and copy of window w are queued, then the sink works on window w - 1
+static int emit_windows(sx_ctx *ctx, const SamArgs &A, const MapBufs &M, const sx_stage_events &E, sx_sink_fn sink, void *user)
+{
+    uint64_t total = 0;
+    SX_TRY(sam_layout(ctx, A, M.d_byte_off, &total));
+    const uint64_t window = M.window, n_win = (total + window - 1) / window;
+    for (uint64_t w = 0; w <= n_win; ++w) {
+        if (w < n_win) {
+            const uint64_t lo = w * window, hi = total - lo < window ? total : lo + window;
+            SX_TRY(sam_emit(ctx, A, M.d_byte_off, lo, hi, M.d_win[w & 1]));
+            SX_CHECK(hipMemcpyAsync(ctx->h_stage[w & 1], M.d_win[w & 1], (size_t)(hi - lo), hipMemcpyDeviceToHost, ctx->stream));
+            SX_CHECK(hipEventRecord(E.ev[w & 1], ctx->stream));
+        }
+        if (w > 0) {
+            const uint64_t lo = (w - 1) * window, hi = total - lo < window ? total : lo + window;
+            SX_CHECK(hipEventSynchronize(E.ev[(w - 1) & 1]));
+            if (sink(user, SX_SECTION_SAM, ctx->h_stage[(w - 1) & 1], (size_t)(hi - lo)) != 0) {
+                (void)hipStreamSynchronize(ctx->stream);
+                return sx_fail_msg(ctx, SX_E_ARG, "the sink refused a chunk");
+            }
+        }
+    }
+    return sx_sync(ctx);
 }
 
 } // namespace sx
@@ -616,204 +625,87 @@ int sx_map_reads_stream(sx_ctx *ctx, const sx_map_record *records, uint32_t n_re
         ~FqFree() { sx_fastq_free(f); }
     } fq_free{&fq};
     if (fq.count == 0 || n_records == 0) return 0;
-    if ((uint64_t)fq.count * n_records > 0xFFFFFFFFull)
-        return sx_fail_msg(ctx, SX_E_ARG, "read mapping: reads x records must stay below 2^32");
-    for (uint32_t r = 0; r < n_records; ++r) {
-        const sx_map_record &R = records[r];
-        if (!R.name || !R.sa || !R.c_table || !R.o_table || !R.remap || R.N == 0 || R.N > 0xFFFFFFFFull || R.sigma < 2 || R.sigma > 128)
-            return sx_fail_msg(ctx, SX_E_ARG, "read mapping: a record lacks its name, suffix array, tables or remap table");
-    }
+    bool records_ok = true;
+    for (uint32_t r = 0; r < n_records; ++r) records_ok = records_ok && sx_map_record_check(records[r], 2);
+    SX_TRY(map_check(ctx, fq.count, n_records, records_ok));
     SX_CHECK(hipSetDevice(ctx->device));
-    const uint32_t n_reads = fq.count;
-    DevBufs B;
     // the reads of this call, then a temporary index of the host tables (every record's suffix array and tables:
     // N x (4 + 8 sigma) bytes a record with its RO table), the loop, and the index goes again
-    uint8_t *d_names, *d_seqs, *d_quals;
-    uint32_t *d_name_off, *d_seq_off, *d_qual_off;
-    SX_TRY(upload(ctx, B, &d_names, (const uint8_t *)fq.names, fq.name_off[n_reads]));
-    SX_TRY(upload(ctx, B, &d_seqs, (const uint8_t *)fq.seqs, fq.seq_off[n_reads]));
-    SX_TRY(upload(ctx, B, &d_quals, (const uint8_t *)fq.quals, fq.qual_off[n_reads]));
-    SX_TRY(upload(ctx, B, &d_name_off, (const uint32_t *)fq.name_off, (size_t)n_reads + 1));
-    SX_TRY(upload(ctx, B, &d_seq_off, (const uint32_t *)fq.seq_off, (size_t)n_reads + 1));
-    SX_TRY(upload(ctx, B, &d_qual_off, (const uint32_t *)fq.qual_off, (size_t)n_reads + 1));
-    sx_index *idx = nullptr;
-    SX_TRY(sx_index_from_records_impl(ctx, records, n_records, &idx));
-    struct IdxFree {
-        sx_index *i;
-        ~IdxFree() { sx_index_destroy(i); }
-    } idx_free{idx};
+    const uint32_t n_reads = fq.count;
+    sx_dev_scope B;
     sx_reads_dev reads;
     reads.count = n_reads;
-    reads.d_names = d_names, reads.d_seqs = d_seqs, reads.d_quals = d_quals;
-    reads.d_name_off = d_name_off, reads.d_seq_off = d_seq_off, reads.d_qual_off = d_qual_off;
+    SX_TRY(upload(ctx, B, &reads.d_names, fq.names, fq.name_off[n_reads]));
+    SX_TRY(upload(ctx, B, &reads.d_seqs, fq.seqs, fq.seq_off[n_reads]));
+    SX_TRY(upload(ctx, B, &reads.d_quals, fq.quals, fq.qual_off[n_reads]));
+    SX_TRY(upload(ctx, B, &reads.d_name_off, fq.name_off, (size_t)n_reads + 1));
+    SX_TRY(upload(ctx, B, &reads.d_seq_off, fq.seq_off, (size_t)n_reads + 1));
+    SX_TRY(upload(ctx, B, &reads.d_qual_off, fq.qual_off, (size_t)n_reads + 1));
     reads.h_seq_off = fq.seq_off;
     reads.seq_bytes = fq.seq_off[n_reads];
-    return sx_map_reads_core(ctx, idx, reads, edits, sink, user);
+    sx_index *idx = nullptr;
+    SX_TRY(sx_index_from_records_impl(ctx, records, n_records, &idx));
+    const int rc = sx_map_reads_core(ctx, idx, reads, edits, sink, user);
+    sx_index_destroy(idx);
+    return rc;
 }
 
 } // extern "C"
 
 // The mapper's loop (bwt_readmapper.c:130-160, 257-266) over reads and tables that lie on the device: what
-// sx_map_reads_stream and sx_index_map_reads share.
+// sx_map_reads_stream and sx_index_map_reads share.  A batch: search (on capacity: grow_or_halve, again), merge, emit.
 int sx_map_reads_core(sx_ctx *ctx, const sx_index *idx, const sx_reads_dev &reads, int edits, sx_sink_fn sink, void *user)
 {
     const uint32_t n_reads = reads.count, n_records = (uint32_t)idx->recs.size();
     if (n_reads == 0 || n_records == 0) return 0;
-    if ((uint64_t)n_reads * n_records > 0xFFFFFFFFull)
-        return sx_fail_msg(ctx, SX_E_ARG, "read mapping: reads x records must stay below 2^32");
-    for (const sx_index_rec &R : idx->recs)
-        if (R.N == 0 || R.N > 0xFFFFFFFFull || R.sigma < 2 || R.sigma > 128)
-            return sx_fail_msg(ctx, SX_E_ARG, "read mapping: a record lacks its name, suffix array, tables or remap table");
+    bool records_ok = true;
+    for (const sx_index_rec &R : idx->recs) records_ok = records_ok && sx_map_dims_ok(R.N, R.sigma, 2);
+    SX_TRY(map_check(ctx, n_reads, n_records, records_ok));
     SX_CHECK(hipSetDevice(ctx->device));
-    DevBufs B;
-    const uint8_t *d_names = reads.d_names, *d_seqs = reads.d_seqs, *d_quals = reads.d_quals, *d_rnames = idx->d_rnames,
-                  *d_tabs = idx->d_tabs;
-    const uint32_t *d_name_off = reads.d_name_off, *d_seq_off = reads.d_seq_off, *d_qual_off = reads.d_qual_off,
-                   *d_rname_off = idx->d_rname_off;
-    const uint32_t *const *d_sa_list = idx->d_sa_list;
-    const uint64_t *d_sa_lens = idx->d_sa_lens;
-    uint8_t *d_pat;
-    SX_TRY(B.take(ctx, &d_pat, (size_t)reads.seq_bytes + 16));
+    MapBufs M;
+    SX_TRY(M.own.take(ctx, &M.d_pat, (size_t)reads.seq_bytes));
     SX_TRY(sx_sync(ctx)); // (the callers' uploads from pageable memory are done)
 
     uint32_t batch_max = ctx->sam_batch_reads > 0 ? (uint32_t)ctx->sam_batch_reads : (1u << 20);
     if (batch_max > n_reads) batch_max = n_reads;
-    size_t window = ctx->sam_window_bytes > 0 ? ((size_t)ctx->sam_window_bytes + 15) & ~(size_t)15 : (size_t)SX_SAM_WINDOW_BYTES;
-    if (window > kStageBytes) window = kStageBytes;
-    for (int b = 0; b < 2; ++b)
-        if (!ctx->h_stage[b] && hipHostMalloc((void **)&ctx->h_stage[b], kStageBytes, hipHostMallocDefault) != hipSuccess) {
-            ctx->h_stage[b] = nullptr;
-            return sx_fail_msg(ctx, SX_E_NOMEM, "pinned staging buffers");
-        }
-    uint8_t *d_win[2];
-    for (int b = 0; b < 2; ++b) {
-        SX_TRY(B.take(ctx, &d_win[b], window));
-        SX_CHECK(hipEventCreate(&B.ev[b]));
-    }
-    const uint64_t stride = (uint64_t)batch_max + 1;
-    uint64_t *d_ho, *d_vbase, *d_seg, *d_byte_off = nullptr;
-    uint32_t *d_err;
-    SX_TRY(B.take(ctx, &d_ho, (size_t)stride * n_records));
-    SX_TRY(B.take(ctx, &d_vbase, (size_t)batch_max * n_records + 1));
-    SX_TRY(B.take(ctx, &d_seg, (size_t)n_records + 1));
-    SX_TRY(B.take(ctx, &d_err, 64));
-    SX_CHECK(hipMemsetAsync(d_err, 0, 256, ctx->stream));
-    // room for hits: a guess to start with; a batch that needs more makes it grow, up to 2^27 hits or what a quarter of the
-    // free memory holds (72 bytes a hit: the searches' array, the merged one, the byte offsets), before the batch is halved
-    // -- a search over few reads leaves most of its lanes idle, so batches stay as long as memory allows
-    uint64_t cap = (uint64_t)batch_max * n_records * 4, cap_max = 1ull << 26;
-    {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b) {
-            cap_max = free_b / 4 / 72;
-            if (cap_max > (1ull << 27)) cap_max = 1ull << 27;
-        } else {
-            (void)hipGetLastError();
-        }
-        if (cap_max < (1u << 16)) cap_max = 1u << 16;
-    }
-    if (cap < (1u << 16)) cap = 1u << 16;
-    if (cap > cap_max) cap = cap_max;
-    sx_approx_hit *d_raw = nullptr, *d_merged = nullptr;
-    uint64_t merged_cap = 0;
-    SX_TRY(B.take(ctx, &d_raw, (size_t)cap));
+    M.window = ctx->sam_window_bytes > 0 ? ((size_t)ctx->sam_window_bytes + 15) & ~(size_t)15 : (size_t)SX_SAM_WINDOW_BYTES;
+    if (M.window > sx_stage_bytes) M.window = sx_stage_bytes;
+    SX_TRY(sx_stage_ensure(ctx));
+    sx_stage_events E;
+    for (uint8_t *&w : M.d_win) SX_TRY(M.own.take(ctx, &w, M.window));
+    SX_TRY(E.create(ctx));
+    M.stride = (uint64_t)batch_max + 1;
+    SX_TRY(M.own.take(ctx, &M.d_ho, (size_t)M.stride * n_records));
+    SX_TRY(M.own.take(ctx, &M.d_vbase, (size_t)batch_max * n_records + 1));
+    SX_TRY(M.own.take(ctx, &M.d_seg, (size_t)n_records + 1));
+    SX_TRY(M.own.take(ctx, &M.d_err, 64));
+    SX_CHECK(hipMemsetAsync(M.d_err, 0, 256, ctx->stream));
+    HitRoom room;
+    SX_TRY(room.init(ctx, (uint64_t)batch_max * n_records * 4));
     std::vector<uint64_t> seg(n_records + 1);
+    sx_sam_batch text = {}; // the batch whose text is emitted: what is the same for every batch here
+    text.d_sa_list = idx->d_sa_list, text.d_sa_len_list = idx->d_sa_lens;
+    text.d_names = reads.d_names, text.d_seqs = reads.d_seqs, text.d_quals = reads.d_quals;
+    text.d_rnames = idx->d_rnames, text.d_rname_off = idx->d_rname_off, text.n_records = n_records;
 
     uint32_t q0 = 0, batch = batch_max;
     while (q0 < n_reads) {
         if (batch > n_reads - q0) batch = n_reads - q0;
-        // the searches, record after record, into one hit array; too many hits: half the reads, or (one read) more room
-        uint64_t used = 0;
-        bool again = false;
-        uint64_t p_lo, p_hi;
-        if (reads.h_seq_off) {
-            p_lo = reads.h_seq_off[q0], p_hi = reads.h_seq_off[q0 + batch];
-        } else { // (the offsets were made on the device: the two this batch needs come back)
-            const uint32_t *src[2] = {d_seq_off + q0, d_seq_off + q0 + batch};
-            const uint32_t one[2] = {1, 1};
-            uint32_t got[2];
-            SX_TRY(sx_readback_ranges(ctx, src, one, 2, got));
-            p_lo = got[0], p_hi = got[1];
+        uint64_t need = 0;
+        const int rc = search_batch(ctx, idx, reads, M, room, q0, batch, edits, seg, &need);
+        if (rc == SX_E_CAPACITY) {
+            bool halve;
+            SX_TRY(room.grow_or_halve(ctx, need, batch, &halve));
+            if (halve) batch_max = batch = (batch + 1) / 2; // (it is not tried longer again)
+            continue;
         }
-        for (uint32_t r = 0; r < n_records && !again; ++r) {
-            const sx_index_rec &R = idx->recs[r];
-            if (p_hi > p_lo)
-                sx_launch(ctx, SX_KC_REMAP, 2 * (p_hi - p_lo), sam_remap_kernel, dim3(sx_div_up(p_hi - p_lo, kBlock)), dim3(kBlock),
-                          (const uint8_t *)d_seqs, (const uint8_t *)(d_tabs + (size_t)r * 256), d_pat, p_lo, p_hi);
-            uint64_t tot = 0;
-            const int rc = sx_bwt_approx_search_dev(ctx, R.d_c, R.d_o, R.d_ro, R.N, R.sigma, d_pat, d_seq_off + q0, batch, edits,
-                                                    d_ho + r * stride, d_raw + used, cap - used, &tot);
-            if (rc == SX_E_CAPACITY) {
-                const uint64_t need = used + tot;
-                if (need <= cap_max || batch == 1) { // more room (one read alone gets whatever it needs)
-                    cap = need + need / 4 > 2 * cap ? need + need / 4 : 2 * cap;
-                    if (cap > cap_max && need <= cap_max) cap = cap_max;
-                    B.drop(d_raw);
-                    SX_TRY(B.take(ctx, &d_raw, (size_t)cap));
-                } else {
-                    batch = (batch + 1) / 2;
-                    batch_max = batch; // (it is not tried longer again)
-                }
-                again = true;
-                break;
-            }
-            if (rc != 0) return rc;
-            seg[r] = used;
-            used += tot;
-        }
-        if (again) continue;
-        seg[n_records] = used;
-        if (used) {
-            if (used > merged_cap) {
-                if (d_merged) B.drop(d_merged), B.drop(d_byte_off);
-                merged_cap = used > cap ? used : cap;
-                SX_TRY(B.take(ctx, &d_merged, (size_t)merged_cap));
-                SX_TRY(B.take(ctx, &d_byte_off, (size_t)merged_cap + 1));
-            }
-            SX_CHECK(hipMemcpyAsync(d_seg, seg.data(), seg.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-            SX_CHECK(hipStreamSynchronize(ctx->stream)); // (seg is reused by the next batch)
-            const uint64_t nvq = (uint64_t)batch * n_records;
-            sx_launch(ctx, SX_KC_SAM, nvq * 24, sam_vq_count_kernel, dim3(sx_div_up(nvq, kBlock)), dim3(kBlock), (const uint64_t *)d_ho,
-                      stride, batch, n_records, d_vbase);
-            SX_TRY(scan64_inplace(ctx, d_vbase, nvq));
-            sx_launch(ctx, SX_KC_SAM, used * 64, sam_merge_kernel, dim3(sx_div_up(used, kBlock)), dim3(kBlock), (const uint4 *)d_raw, used,
-                      (const uint64_t *)d_seg, n_records, (const uint64_t *)d_ho, stride, batch, (const uint64_t *)d_vbase,
-                      (uint4 *)d_merged, d_err);
-            uint32_t e = 0;
-            SX_TRY(sx_readback(ctx, d_err, 1, &e));
-            if (e) return sx_fail_msg(ctx, SX_E_INTERNAL, "read mapping: the hits of a batch do not add up");
-            SamArgs A{};
-            A.hits = (const uint4 *)d_merged;
-            A.n_hits = used;
-            A.sa_list = d_sa_list;
-            A.sa_len_list = d_sa_lens;
-            A.names = d_names, A.seqs = d_seqs, A.quals = d_quals;
-            A.name_off = d_name_off + q0, A.seq_off = d_seq_off + q0, A.qual_off = d_qual_off + q0;
-            A.n_reads = batch;
-            A.rnames = d_rnames;
-            A.rname_off = d_rname_off;
-            A.n_records = n_records;
-            uint64_t total = 0;
-            SX_TRY(sam_layout(ctx, A, d_byte_off, &total));
-            // windows: emit and copy of window w are queued, then the sink works on window w - 1
-            const uint64_t n_win = (total + window - 1) / window;
-            for (uint64_t w = 0; w <= n_win; ++w) {
-                if (w < n_win) {
-                    const uint64_t lo = w * window, hi = total - lo < window ? total : lo + window;
-                    SX_TRY(sam_emit(ctx, A, d_byte_off, lo, hi, d_win[w & 1]));
-                    SX_CHECK(hipMemcpyAsync(ctx->h_stage[w & 1], d_win[w & 1], (size_t)(hi - lo), hipMemcpyDeviceToHost, ctx->stream));
-                    SX_CHECK(hipEventRecord(B.ev[w & 1], ctx->stream));
-                }
-                if (w > 0) {
-                    const uint64_t lo = (w - 1) * window, hi = total - lo < window ? total : lo + window;
-                    SX_CHECK(hipEventSynchronize(B.ev[(w - 1) & 1]));
-                    if (sink(user, SX_SECTION_SAM, ctx->h_stage[(w - 1) & 1], (size_t)(hi - lo)) != 0) {
-                        (void)hipStreamSynchronize(ctx->stream);
-                        return sx_fail_msg(ctx, SX_E_ARG, "the sink refused a chunk");
-                    }
-                }
-            }
-            SX_TRY(sx_sync(ctx));
+        if (rc != 0) return rc;
+        if (seg[n_records]) {
+            SX_TRY(merge_batch(ctx, M, room, seg, batch));
+            text.d_hits = M.d_merged, text.n_hits = seg[n_records];
+            text.d_name_off = reads.d_name_off + q0, text.d_seq_off = reads.d_seq_off + q0, text.d_qual_off = reads.d_qual_off + q0;
+            text.n_reads = batch;
+            SX_TRY(emit_windows(ctx, sam_args_of(text), M, E, sink, user));
         }
         q0 += batch;
     }

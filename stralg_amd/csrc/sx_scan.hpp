@@ -189,6 +189,33 @@ static inline int device_compact(sx_ctx *ctx, uint64_t n, Flag flag, Out out, ui
     return 0;
 }
 
+// exclusive sum over the workgroup's 256 lanes, 64-bit with carries; ends with a barrier (lds: kWavesPerBlock words)
+__device__ __forceinline__ uint64_t block_exclusive_sum_u64(uint64_t v, uint64_t *lds, uint64_t &total)
+{
+    const int lane = lane_id(), w = wave_id();
+    unsigned long long inc = v;
+    for (unsigned d = 1; d < (unsigned)kWave; d <<= 1) {
+        const unsigned long long up = __shfl_up(inc, d, kWave);
+        if (lane >= (int)d) inc += up;
+    }
+    if (lane == kWave - 1) lds[w] = inc;
+    __syncthreads();
+    uint64_t base = 0, tot = 0;
+#pragma unroll
+    for (int i = 0; i < kWavesPerBlock; ++i) {
+        const uint64_t x = lds[i];
+        if (i < w) base += x;
+        tot += x;
+    }
+    __syncthreads();
+    total = tot;
+    return base + inc - v;
+}
+
+// 64-bit exclusive sum in place (sx_scan.hip): d[0 .. n) -> prefixes, d[n] <- total.  The same three launches over plain
+// 64-bit words; not folded into device_scan, whose DPP steps are 32-bit.
+int device_scan64_inplace(sx_ctx *ctx, uint64_t *d, uint64_t n, int kclass);
+
 // ---- common functors ------------------------------------------------------
 struct InU32 {
     const uint32_t *p;

@@ -159,6 +159,41 @@ def test_at_size_exact_matches_checked_with_numpy(gpu_ctx):
     assert all(f[10] == b"I" * m for f in fields)
 
 
+def test_write_streams_several_chunks(gpu_ctx):
+    """one record of 2^22 symbols of synthetic DNA (sigma 5) with RO: its O and RO tables are 84 MB each, three chunks of
+    the 32 MiB staging buffers, so both buffers are used a second time.  The written stream, walked by the layout of
+    the reference's serialise.c, holds at each array's place what single copies of the device buffers give."""
+    n = 1 << 22
+    seq = np.frombuffer(b"\0ACGT", np.uint8)[stralg_amd.synth(n, 5, 303)]
+    chunks = []
+    with Index.from_fasta(fasta_of([(b"chrW", seq)]), ctx=gpu_ctx) as idx:
+        assert idx.records == [(b"chrW", n + 1, 5, True)]
+        idx.write(chunks.append)
+        want = idx.device_tables(0)
+    stream = np.frombuffer(b"".join(chunks), np.uint8)
+    N, sigma, at = n + 1, 5, 0
+
+    def take(count, dtype=np.uint8):
+        nonlocal at
+        out = stream[at:at + count * np.dtype(dtype).itemsize].view(dtype)
+        assert out.size == count, "the stream ends early"
+        at += out.nbytes
+        return out
+
+    assert take(1, np.uint32)[0] == 1  # records
+    assert take(1, np.uint32)[0] == 5 and take(5).tobytes() == b"chrW\0"  # the name with its terminator
+    assert take(1, np.uint32)[0] == n and (take(n) == want["string"][:-1]).all()
+    assert (take(N, np.uint32) == want["sa"]).all()
+    remap = take(4 + 256 + 128)  # remap.h: alphabet size, table, reverse table
+    assert remap[:4].view(np.uint32)[0] == sigma and remap[4 + 256:4 + 256 + sigma].tobytes() == b"\0ACGT"
+    assert (take(sigma, np.uint32) == want["c"]).all()
+    assert (take((N + 1) * sigma, np.uint32) == want["o"].ravel()).all()
+    assert take(1)[0] == 1  # the flag: RO follows
+    assert (take((N + 1) * sigma, np.uint32) == want["ro"].ravel()).all()
+    assert at == stream.size
+    assert (N + 1) * sigma * 4 > 2 * (32 << 20)  # (a third chunk)
+
+
 def test_at_size_agrees_with_the_stream_call(gpu_ctx):
     """a record of 2^24 symbols, 10^5 reads with up to one substitution, k = 1: the index path's text has the SHA-256 of
     Context.map_reads_stream's, fed host tables from build_complete_table"""
