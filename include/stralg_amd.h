@@ -395,6 +395,54 @@ int sx_index_write(sx_ctx *ctx, const sx_index *idx, sx_sink_fn sink, void *user
 /* bytes of device memory to the host on the context's stream, then a sync (the tests read the index's buffers back) */
 int sx_download(sx_ctx *ctx, void *h_dst, const void *d_src, size_t bytes);
 
+/* ---- the compact form of the O / RO tables ---------------- */
+/* BWT blocks with occurrence counts sampled every 64 rows, one layout for every sigma in [1, 128]: rows 0 .. N in blocks
+ * of 64; block b is sigma_pad u32 counters (sigma rounded up to a multiple of 16; counter a = O(a, 64 b), the counters
+ * from sigma on are 0) followed by the 64 bytes bwt[64 b .. 64 b + 64), bytes from N on 0xFF.  N / 64 + 1 blocks of
+ * 4 sigma_pad + 64 bytes; the first starts on a 16-byte boundary at least (the calls below answer SX_E_ARG otherwise; an
+ * index allocates its blocks on 256-byte boundaries, so that a block of sigma <= 16 is one 128-byte line).  O(a, row) is counter a of block row / 64 plus the
+ * number of bytes equal to a among the block's first row % 64: 4 N bytes for O and RO of DNA where the full tables take
+ * 40 N.  The same BWT gives the same bytes from run to run. */
+/* bytes of the blocks of a table of N rows + 1 (0 for N or sigma out of range) */
+uint64_t sx_occ_compact_bytes(uint64_t N, uint32_t sigma);
+/* blocks from a BWT on the device (N bytes, as sx_sa_bwt_build_dev leaves it); d_blocks_out: sx_occ_compact_bytes bytes */
+int sx_occ_compact_build_dev(sx_ctx *ctx, const uint8_t *d_bwt, uint64_t N, uint32_t sigma, uint8_t *d_blocks_out);
+/* rows [row_lo, row_hi) of the full table (row_hi <= N + 1) from the blocks: d_rows_out[(row - row_lo) * sigma + a] */
+int sx_occ_compact_expand_dev(sx_ctx *ctx, const uint8_t *d_blocks, uint64_t N, uint32_t sigma, uint64_t row_lo, uint64_t row_hi,
+                              uint32_t *d_rows_out);
+/* sx_bwt_exact_search_dev and sx_bwt_approx_search_dev over blocks in place of the full tables (d_rocc may be NULL as
+ * d_ro_table may): the same intervals, hits, offsets and order; sigma <= 128 */
+int sx_bwt_exact_search_compact_dev(sx_ctx *ctx, const uint32_t *d_c_table, const uint8_t *d_occ, uint64_t N, uint32_t sigma,
+                                    const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, uint32_t *d_l_out,
+                                    uint32_t *d_r_out);
+int sx_bwt_approx_search_compact_dev(sx_ctx *ctx, const uint32_t *d_c_table, const uint8_t *d_occ, const uint8_t *d_rocc, uint64_t N,
+                                     uint32_t sigma, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, int max_edits,
+                                     uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t hit_capacity, uint64_t *total_hits_out);
+/* An index in the compact form (flags: SX_INDEX_COMPACT): every record keeps blocks in place of O and RO, about
+ * N x (5 + 2 (1 + sigma_pad / 16)) bytes with RO (9 N for DNA in place of 45 N); no buffer of (N + 1) x sigma words exists
+ * during the build (the BWT goes into the block builder; tables that arrive as full tables come up in windows through
+ * the staging buffers).  Mapping gives the same text, sx_index_write the same file (the tables are expanded window by
+ * window), sx_index_add_record follows the index's form; sx_index_record_info reports d_o = d_ro = NULL for such a
+ * record and sx_index_record_occ its blocks.  Errors as sx_index_build_fasta / sx_index_from_sources; flags with unknown
+ * bits: SX_E_ARG. */
+enum { SX_INDEX_COMPACT = 1 };
+int sx_index_build_fasta_ex(sx_ctx *ctx, const uint8_t *fasta, uint64_t len, int include_reverse, uint32_t flags, sx_index **out);
+int sx_index_from_sources_ex(sx_ctx *ctx, const sx_index_source *sources, uint32_t n_records, uint32_t flags, sx_index **out);
+typedef struct sx_index_occ {
+    int compact;                  /* 0: the record has full tables and the rest is 0 */
+    const uint8_t *d_occ, *d_rocc; /* device memory; d_rocc NULL without the reverse */
+    uint32_t stride, sigma_pad;   /* bytes a block, counters a block */
+    uint64_t n_blocks;
+} sx_index_occ;
+int sx_index_record_occ(const sx_index *idx, uint32_t record, sx_index_occ *out);
+/* 1 for an index in the compact form */
+int sx_index_is_compact(const sx_index *idx);
+/* rows [row_lo, row_hi) of a compact record's O table (reverse: of RO) to host memory, (row_hi - row_lo) x sigma words:
+ * expanded on the device window by window (sx_occ_compact_expand_dev).  SX_E_ARG: a record with full tables, or without
+ * the reverse, rows outside [0, N + 1]. */
+int sx_index_expand_o(sx_ctx *ctx, const sx_index *idx, uint32_t record, int reverse, uint64_t row_lo, uint64_t row_hi,
+                      uint32_t *rows_out);
+
 /* ---- FASTA ingest and remap on the device ---------------- */
 /* bioinf/fasta.c:92-135 load_fasta_records' packing of a file image in device memory into
  * "name\0sequence\0name\0sequence\0..." (file order; the reference's record list is the reverse).

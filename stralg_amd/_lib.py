@@ -81,7 +81,14 @@ class IndexRecord(C.Structure):
                 ("d_ro", C.c_void_p)]
 
 
+class IndexOcc(C.Structure):
+    """include/stralg_amd.h sx_index_occ"""
+    _fields_ = [("compact", C.c_int), ("d_occ", C.c_void_p), ("d_rocc", C.c_void_p), ("stride", C.c_uint32),
+                ("sigma_pad", C.c_uint32), ("n_blocks", C.c_uint64)]
+
+
 SX_SECTION_INDEX = 4
+SX_INDEX_COMPACT = 1
 SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t)
 
 
@@ -144,6 +151,17 @@ def load(path=None):
         "sx_index_live_count": (C.c_int, []),
         "sx_index_write": (C.c_int, [vp, vp, SINK_FN, C.c_void_p]),
         "sx_download": (C.c_int, [vp, vp, vp, C.c_size_t]),
+        "sx_occ_compact_bytes": (C.c_uint64, [C.c_uint64, C.c_uint32]),
+        "sx_occ_compact_build_dev": (C.c_int, [vp, u8p, C.c_uint64, C.c_uint32, u8p]),
+        "sx_occ_compact_expand_dev": (C.c_int, [vp, u8p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, u32p]),
+        "sx_bwt_exact_search_compact_dev": (C.c_int, [vp, u32p, u8p, C.c_uint64, C.c_uint32, u8p, u32p, C.c_uint32, u32p, u32p]),
+        "sx_bwt_approx_search_compact_dev": (C.c_int, [vp, u32p, u8p, u8p, C.c_uint64, C.c_uint32, u8p, u32p, C.c_uint32, C.c_int,
+                                                       u64p, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+        "sx_index_build_fasta_ex": (C.c_int, [vp, u8p, C.c_uint64, C.c_int, C.c_uint32, C.POINTER(vp)]),
+        "sx_index_from_sources_ex": (C.c_int, [vp, C.POINTER(IndexSource), C.c_uint32, C.c_uint32, C.POINTER(vp)]),
+        "sx_index_record_occ": (C.c_int, [vp, C.c_uint32, C.POINTER(IndexOcc)]),
+        "sx_index_is_compact": (C.c_int, [vp]),
+        "sx_index_expand_o": (C.c_int, [vp, vp, C.c_uint32, C.c_int, C.c_uint64, C.c_uint64, u32p]),
         "sx_fasta_pack_dev": (C.c_int, [vp, u8p, C.c_uint64, u8p, C.POINTER(C.c_uint64), u32p, C.c_uint64,
                                         C.POINTER(C.c_uint32)]),
         "sx_fasta_pack": (C.c_int, [vp, u8p, C.c_uint64, u8p, C.POINTER(C.c_uint64), u32p, C.c_uint64,
@@ -185,6 +203,9 @@ EXPORTS = ["sx_device_count", "sx_device_numa_node", "sx_ctx_create", "sx_ctx_de
            "sx_index_add_record", "sx_index_map_reads", "sx_index_info", "sx_index_record_info", "sx_index_destroy",
            "sx_index_live_count", "sx_index_write", "sx_download", "sx_fasta_pack_dev", "sx_fasta_pack", "sx_remap_dev", "sx_reverse_dev", "sx_profile_enable", "sx_profile_only",
            "sx_profile_reset", "sx_profile_read", "sx_kernel_class_name", "sx_last_stats",
+           "sx_occ_compact_bytes", "sx_occ_compact_build_dev", "sx_occ_compact_expand_dev", "sx_bwt_exact_search_compact_dev",
+           "sx_bwt_approx_search_compact_dev", "sx_index_build_fasta_ex", "sx_index_from_sources_ex", "sx_index_record_occ",
+           "sx_index_is_compact", "sx_index_expand_o",
            "sx_synth_dev", "sx_membw_probe", "sx_prim_sort_pairs_dev", "sx_prim_exclusive_sum_dev", "sx_prim_classify_dev"]
 
 

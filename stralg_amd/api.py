@@ -171,6 +171,33 @@ class Context:
             _libc_free(hp.value)
         return hit_off, hits
 
+    # ---- the compact form of the O table (sx_occ.hpp) ------------------------------------------
+    def occ_compact_bytes(self, N, sigma):
+        """sx_occ_compact_bytes: bytes of the blocks of a table of N + 1 rows"""
+        return int(self.lib.sx_occ_compact_bytes(N, sigma))
+
+    def occ_compact_build_dev(self, d_bwt, N, sigma, d_blocks):
+        self._check(self.lib.sx_occ_compact_build_dev(self.h, _ptr(d_bwt), N, sigma, _ptr(d_blocks)), "sx_occ_compact_build_dev")
+
+    def occ_compact_expand_dev(self, d_blocks, N, sigma, row_lo, row_hi, d_rows):
+        self._check(self.lib.sx_occ_compact_expand_dev(self.h, _ptr(d_blocks), N, sigma, row_lo, row_hi, _ptr(d_rows)),
+                    "sx_occ_compact_expand_dev")
+
+    def bwt_exact_search_compact_dev(self, d_c, d_occ, N, sigma, d_patterns, d_offsets, count, d_l, d_r):
+        self._check(self.lib.sx_bwt_exact_search_compact_dev(self.h, _ptr(d_c), _ptr(d_occ), N, sigma, _ptr(d_patterns),
+                                                             _ptr(d_offsets), count, _ptr(d_l), _ptr(d_r)),
+                    "sx_bwt_exact_search_compact_dev")
+
+    def bwt_approx_search_compact_dev(self, d_c, d_occ, d_rocc, N, sigma, d_patterns, d_offsets, count, max_edits, d_hit_offsets,
+                                      d_hits=None, hit_capacity=0):
+        """sx_bwt_approx_search_compact_dev: Context.bwt_approx_search_dev over blocks in place of the full tables"""
+        total = C.c_uint64(0)
+        self._check(self.lib.sx_bwt_approx_search_compact_dev(self.h, _ptr(d_c), _ptr(d_occ), _ptr(d_rocc), N, sigma,
+                                                              _ptr(d_patterns), _ptr(d_offsets), count, max_edits,
+                                                              _ptr(d_hit_offsets), _ptr(d_hits), hit_capacity, C.byref(total)),
+                    "sx_bwt_approx_search_compact_dev")
+        return int(total.value)
+
     # ---- SAM text of search hits (the read mapper's output) ---------------------------------
     def sam_batch(self, d_hits, n_hits, d_sa, sa_len, d_names, d_name_off, d_seqs, d_seq_off, d_quals, d_qual_off, n_reads,
                   d_rnames, d_rname_off, n_records=1, d_sa_list=None, d_sa_len_list=None):
@@ -462,19 +489,21 @@ class Index:
 
     # ---- constructors -------------------------------------------------------------------------------------------
     @classmethod
-    def from_fasta(cls, fasta_bytes, include_reverse=True, ctx=None):
-        """sx_index_build_fasta: the bytes of a FASTA file -> tables of every record, built on the device"""
+    def from_fasta(cls, fasta_bytes, include_reverse=True, ctx=None, compact=False):
+        """sx_index_build_fasta_ex: the bytes of a FASTA file -> tables of every record, built on the device; compact=True:
+        BWT blocks with sampled counts in place of the O / RO tables (a fifth of the memory for DNA, the same results)"""
         ctx = ctx or default_context()
         buf = np.frombuffer(bytes(fasta_bytes), dtype=np.uint8)
         h = C.c_void_p()
-        ctx._check(ctx.lib.sx_index_build_fasta(ctx.h, _ptr(buf) if buf.size else None, buf.size, 1 if include_reverse else 0,
-                                                C.byref(h)), "sx_index_build_fasta")
+        ctx._check(ctx.lib.sx_index_build_fasta_ex(ctx.h, _ptr(buf) if buf.size else None, buf.size, 1 if include_reverse else 0,
+                                                   _lib.SX_INDEX_COMPACT if compact else 0, C.byref(h)), "sx_index_build_fasta")
         return cls(ctx, h)
 
     @classmethod
-    def from_tables(cls, records, ctx=None):
-        """sx_index_from_sources: records = [(name bytes, BwtTable), ...] in the mapper's list order (the FASTA file's), as
-        Context.map_reads_stream takes them; a table whose sa.string is set (remapped symbols + terminator) can be saved"""
+    def from_tables(cls, records, ctx=None, compact=False):
+        """sx_index_from_sources_ex: records = [(name bytes, BwtTable), ...] in the mapper's list order (the FASTA file's), as
+        Context.map_reads_stream takes them; a table whose sa.string is set (remapped symbols + terminator) can be saved.
+        compact=True: the tables go up in windows and stay as blocks"""
         ctx = ctx or default_context()
         src = (_lib.IndexSource * max(1, len(records)))()
         keep = []
@@ -486,13 +515,14 @@ class Index:
                 keep.append(string)
                 src[r].string = _ptr(string)
         h = C.c_void_p()
-        ctx._check(ctx.lib.sx_index_from_sources(ctx.h, src, len(records), C.byref(h)), "sx_index_from_sources")
+        ctx._check(ctx.lib.sx_index_from_sources_ex(ctx.h, src, len(records), _lib.SX_INDEX_COMPACT if compact else 0, C.byref(h)),
+                   "sx_index_from_sources")
         return cls(ctx, h)
 
     @classmethod
-    def load(cls, path_or_bytes, ctx=None):
+    def load(cls, path_or_bytes, ctx=None, compact=False):
         """the read mapper's index file (genome.fa.bwttables; what .save writes): a path, or the bytes.  The file is
-        mapped, and its records go to the device one after the other."""
+        mapped, and its records go to the device one after the other (compact=True: as blocks)."""
         ctx = ctx or default_context()
         if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
             blob = np.frombuffer(bytes(path_or_bytes), dtype=np.uint8)
@@ -508,7 +538,8 @@ class Index:
             return out
 
         h = C.c_void_p()
-        ctx._check(ctx.lib.sx_index_from_tables(ctx.h, None, 0, C.byref(h)), "sx_index_from_tables")
+        ctx._check(ctx.lib.sx_index_from_sources_ex(ctx.h, None, 0, _lib.SX_INDEX_COMPACT if compact else 0, C.byref(h)),
+                   "sx_index_from_sources")
         idx = cls(ctx, h)
         try:
             n_rec = int(take(4, np.uint32)[0])
@@ -633,14 +664,52 @@ class Index:
         return self._info()[3]
 
     def device_tables(self, r, ctx=None):
-        """record r's device buffers read back (tests): dict(string, sa, c, o, ro) of numpy arrays; ro / string may be None"""
+        """record r's device buffers read back (tests): dict(string, sa, c, o, ro) of numpy arrays; ro / string may be None
+        (and o, in a compact index: see device_occ and expand_o)"""
         ctx = ctx or self.ctx
         rec = self.record_info(r)
         N, sigma = int(rec.N), int(rec.sigma)
         return dict(string=ctx.download(rec.d_string, N, np.uint8) if rec.d_string else None,
                     sa=ctx.download(rec.d_sa, N, np.uint32), c=ctx.download(rec.d_c, sigma, np.uint32),
-                    o=ctx.download(rec.d_o, (N + 1) * sigma, np.uint32).reshape(N + 1, sigma),
+                    o=ctx.download(rec.d_o, (N + 1) * sigma, np.uint32).reshape(N + 1, sigma) if rec.d_o else None,
                     ro=ctx.download(rec.d_ro, (N + 1) * sigma, np.uint32).reshape(N + 1, sigma) if rec.d_ro else None)
+
+    def record_occ(self, r):
+        """sx_index_record_occ of record r: the _lib.IndexOcc with the addresses and the shape of the record's blocks"""
+        occ = _lib.IndexOcc()
+        self.ctx._check(self.ctx.lib.sx_index_record_occ(self._handle(), r, C.byref(occ)), "sx_index_record_occ")
+        return occ
+
+    @property
+    def compact(self):
+        """whether the records keep BWT blocks with sampled counts in place of the O / RO tables"""
+        return bool(self.ctx.lib.sx_index_is_compact(self._handle()))
+
+    def _occ_address(self, r, reverse):
+        occ = self.record_occ(r)
+        if not occ.compact:
+            raise StralgAmdError("the index keeps full tables: it has no blocks")
+        address = occ.d_rocc if reverse else occ.d_occ
+        if not address:
+            raise StralgAmdError("the record was built without the reverse")
+        return occ, address
+
+    def device_occ(self, r, reverse=False, ctx=None):
+        """record r's raw blocks (of RO with reverse=True) read back: a uint8 array of n_blocks x stride"""
+        ctx = ctx or self.ctx
+        occ, address = self._occ_address(r, reverse)
+        return ctx.download(address, int(occ.n_blocks) * int(occ.stride), np.uint8).reshape(int(occ.n_blocks), int(occ.stride))
+
+    def expand_o(self, r, reverse=False, rows=None, ctx=None):
+        """sx_index_expand_o: the (N + 1, sigma) O table of record r (RO with reverse=True) from its blocks, through the
+        expand kernel; rows=(lo, hi): only the rows [lo, hi)"""
+        ctx = ctx or self.ctx
+        rec = self.record_info(r)
+        N, sigma = int(rec.N), int(rec.sigma)
+        lo, hi = (0, N + 1) if rows is None else rows
+        out = np.zeros((max(0, hi - lo), sigma), dtype=np.uint32)
+        ctx._check(ctx.lib.sx_index_expand_o(ctx.h, self._handle(), r, 1 if reverse else 0, lo, hi, _ptr(out)), "sx_index_expand_o")
+        return out
 
     def close(self):
         if getattr(self, "h", None):

@@ -1805,9 +1805,14 @@ static uint8_t *read_rest(FILE *f, size_t *len_out)
 
 sx_index *stralg_amd_index_from_fasta_image(const uint8_t *fasta, size_t len, bool include_reverse)
 {
+    return stralg_amd_index_from_fasta_image_ex(fasta, len, include_reverse, 0);
+}
+
+sx_index *stralg_amd_index_from_fasta_image_ex(const uint8_t *fasta, size_t len, bool include_reverse, uint32_t flags)
+{
     sx_ctx *ctx = thread_ctx();
     sx_index *idx = NULL;
-    const int rc = sx_index_build_fasta(ctx, fasta, len, include_reverse, &idx);
+    const int rc = sx_index_build_fasta_ex(ctx, fasta, len, include_reverse, flags, &idx);
     if (rc != 0) {
         fprintf(stderr, "stralg_amd_index_from_fasta_image: failed (code %d): %s\n", rc, sx_last_error(ctx));
         return NULL;
@@ -1817,14 +1822,16 @@ sx_index *stralg_amd_index_from_fasta_image(const uint8_t *fasta, size_t len, bo
 
 /* the mapper's index file (tools/stralg_amd_readmapper.c): record by record through read_complete_bwt_info, one
  * record's host copy at a time; the file lists the records last first */
-sx_index *stralg_amd_index_read(FILE *f)
+sx_index *stralg_amd_index_read(FILE *f) { return stralg_amd_index_read_ex(f, 0); }
+
+sx_index *stralg_amd_index_read_ex(FILE *f, uint32_t flags)
 {
     if (!f) return NULL;
     sx_ctx *ctx = thread_ctx();
     uint32_t n = 0;
     if (fread(&n, sizeof n, 1, f) != 1) return NULL;
     sx_index *idx = NULL;
-    if (sx_index_from_tables(ctx, NULL, 0, &idx) != 0) return NULL;
+    if (sx_index_from_sources_ex(ctx, NULL, 0, flags, &idx) != 0) return NULL;
     for (uint32_t r = 0; r < n; ++r) {
         uint32_t name_bytes = 0;
         char *name = NULL;

@@ -23,6 +23,7 @@
 //    its pattern takes the next one from a counter, so it does not wait for the rest of its wave.
 #include "sx_common.hpp"
 #include "sx_device.hpp"
+#include "sx_occ.hpp"
 #include "sx_scan.hpp"
 
 #include <stdlib.h>
@@ -36,8 +37,11 @@ namespace sx {
 constexpr int kApproxBlock = 256;
 constexpr int kMaxEdits = SX_APPROX_MAX_EDITS;
 
-struct ApproxArgs {
-    const uint32_t *c, *o, *ro;
+// Occ: how O(a, row) is read (sx_occ.hpp); OccFull is one pointer, so ApproxArgs is laid out as it was before the
+// accessor came
+template <class Occ> struct ApproxArgsT {
+    const uint32_t *c;
+    Occ o, ro;
     uint64_t N;
     uint32_t sigma;
     const uint8_t *pat;
@@ -54,6 +58,8 @@ struct ApproxArgs {
     uint64_t cap;
 };
 
+using ApproxArgs = ApproxArgsT<OccFull>;
+
 enum : uint32_t { kFetch = 0, kScan = 1, kChain = 2 };
 
 __device__ __forceinline__ uint4 u4(uint32_t x, uint32_t y, uint32_t z, uint32_t w)
@@ -66,15 +72,15 @@ __device__ __forceinline__ uint4 u4(uint32_t x, uint32_t y, uint32_t z, uint32_t
     return v;
 }
 
-template <bool kEmit>
-__global__ __launch_bounds__(kApproxBlock) void bwt_approx_kernel(ApproxArgs A)
+template <bool kEmit, class Occ>
+__global__ __launch_bounds__(kApproxBlock) void bwt_approx_kernel(ApproxArgsT<Occ> A)
 {
     const uint32_t t = blockIdx.x * kApproxBlock + threadIdx.x;
     if (t >= A.lanes) return;
     const uint32_t sigma = A.sigma;
     const uint32_t nI = sigma - 1; // child index of I; M(a) is a - 1, D(a) is sigma - 1 + a
     const uint32_t *__restrict__ C = A.c;
-    const uint32_t *__restrict__ O = A.o;
+    const Occ O = A.o;
     uint4 *stack = A.stack + t;
 
     uint32_t mode = kFetch, q = 0, m = 0, cnt = 0;
@@ -96,8 +102,8 @@ __global__ __launch_bounds__(kApproxBlock) void bwt_approx_kernel(ApproxArgs A)
         if (mode == kChain) {
             if (j >= 0 && L2 < R2) {
                 const uint32_t a = p[j];
-                L2 = C[a] + O[(uint64_t)L2 * sigma + a];
-                R2 = C[a] + O[(uint64_t)R2 * sigma + a];
+                L2 = C[a] + O.rank(a, L2, sigma);
+                R2 = C[a] + O.rank(a, R2, sigma);
                 --j;
                 continue;
             }
@@ -140,8 +146,8 @@ __global__ __launch_bounds__(kApproxBlock) void bwt_approx_kernel(ApproxArgs A)
                     if (c < nI) ce = e - (a == (uint32_t)p[i] ? 0 : 1);
                     else ci = i;
                     if (ce >= 0) {
-                        nL = C[a] + O[(uint64_t)L * sigma + a];
-                        nR = C[a] + O[(uint64_t)R * sigma + a];
+                        nL = C[a] + O.rank(a, L, sigma);
+                        nR = C[a] + O.rank(a, R, sigma);
                         take = nL < nR;
                     }
                 } else {
@@ -234,9 +240,9 @@ __global__ __launch_bounds__(kApproxBlock) void bwt_approx_kernel(ApproxArgs A)
                 ok = false;
                 break;
             }
-            if (A.ro && me <= A.k) {
-                rL = C[a] + A.ro[(uint64_t)rL * sigma + a];
-                rR = C[a] + A.ro[(uint64_t)rR * sigma + a];
+            if (A.ro.present() && me <= A.k) {
+                rL = C[a] + A.ro.rank(a, rL, sigma);
+                rR = C[a] + A.ro.rank(a, rR, sigma);
                 if (rL >= rR) {
                     ++me;
 #pragma unroll
@@ -288,7 +294,7 @@ static uint32_t approx_lanes(uint32_t count)
 }
 
 // count pass + offsets; the workspace (stack, counts, counters) stays in the N slab for the emit pass
-static int approx_count(sx_ctx *ctx, ApproxArgs &A, uint64_t *d_hit_off, uint64_t *total_out)
+template <class Occ> static int approx_count(sx_ctx *ctx, ApproxArgsT<Occ> &A, uint64_t *d_hit_off, uint64_t *total_out)
 {
     // the longest pattern (the stack's depth, the 2^15 limit)
     SX_TRY(sx_slab_ensure(ctx, SX_SLAB_BWT, 4096));
@@ -307,7 +313,7 @@ static int approx_count(sx_ctx *ctx, ApproxArgs &A, uint64_t *d_hit_off, uint64_
     A.stack = (uint4 *)((char *)ctx->slab[SX_SLAB_N].p + cnt_b);
     A.total = (unsigned long long *)(scal + 2);
     A.next = scal + 4;
-    sx_launch(ctx, SX_KC_SEARCH, 0, bwt_approx_kernel<false>, dim3(A.lanes / kApproxBlock), dim3(kApproxBlock), A);
+    sx_launch(ctx, SX_KC_SEARCH, 0, bwt_approx_kernel<false, Occ>, dim3(A.lanes / kApproxBlock), dim3(kApproxBlock), A);
     SX_TRY((device_scan<OpAdd>(ctx, A.count, InU32{A.counts}, OutOffsets64{d_hit_off}, nullptr, SX_KC_SEARCH, (uint64_t)A.count * 12)));
     sx_launch(ctx, SX_KC_SEARCH, 0, approx_finish_offsets_kernel, dim3(1), dim3(64), (const unsigned long long *)A.total, d_hit_off, A.count);
     uint32_t h[4] = {0, 0, 0, 0};
@@ -319,13 +325,13 @@ static int approx_count(sx_ctx *ctx, ApproxArgs &A, uint64_t *d_hit_off, uint64_
     return 0;
 }
 
-static int approx_emit(sx_ctx *ctx, ApproxArgs &A, const uint64_t *d_hit_off, sx_approx_hit *d_hits, uint64_t total)
+template <class Occ> static int approx_emit(sx_ctx *ctx, ApproxArgsT<Occ> &A, const uint64_t *d_hit_off, sx_approx_hit *d_hits, uint64_t total)
 {
     A.hit_off = d_hit_off;
     A.hits = (uint4 *)d_hits;
     A.cap = total;
     SX_CHECK(hipMemsetAsync(A.next, 0, 8, ctx->stream));
-    sx_launch(ctx, SX_KC_SEARCH, total * sizeof(sx_approx_hit), bwt_approx_kernel<true>, dim3(A.lanes / kApproxBlock),
+    sx_launch(ctx, SX_KC_SEARCH, total * sizeof(sx_approx_hit), bwt_approx_kernel<true, Occ>, dim3(A.lanes / kApproxBlock),
               dim3(kApproxBlock), A);
     uint32_t h[2] = {0, 0};
     SX_TRY(sx_readback(ctx, A.next, 2, h));
@@ -333,12 +339,13 @@ static int approx_emit(sx_ctx *ctx, ApproxArgs &A, const uint64_t *d_hit_off, sx
     return 0;
 }
 
-static int approx_args(sx_ctx *ctx, ApproxArgs &A, const uint32_t *c, const uint32_t *o, const uint32_t *ro, uint64_t N,
-                       uint32_t sigma, const uint8_t *pat, const uint32_t *off, uint32_t count, int k)
+template <class Occ>
+static int approx_args(sx_ctx *ctx, ApproxArgsT<Occ> &A, const uint32_t *c, Occ o, Occ ro, uint64_t N, uint32_t sigma, const uint8_t *pat,
+                       const uint32_t *off, uint32_t count, int k)
 {
     (void)ctx;
-    if (!c || !o || !off || N == 0 || N > 0xFFFFFFFFull || sigma < 2 || sigma > 256 || k > kMaxEdits) return SX_E_ARG;
-    A = ApproxArgs{};
+    if (!c || !o.p || !off || N == 0 || N > 0xFFFFFFFFull || sigma < 2 || sigma > 256 || k > kMaxEdits) return SX_E_ARG;
+    A = ApproxArgsT<Occ>{};
     A.c = c;
     A.o = o;
     A.ro = ro;
@@ -355,16 +362,15 @@ static int approx_args(sx_ctx *ctx, ApproxArgs &A, const uint32_t *c, const uint
 
 using namespace sx;
 
-extern "C" {
-
-int sx_bwt_approx_search_dev(sx_ctx *ctx, const uint32_t *d_c_table, const uint32_t *d_o_table,
-                             const uint32_t *d_ro_table, uint64_t N, uint32_t sigma, const uint8_t *d_patterns,
-                             const uint32_t *d_offsets, uint32_t count, int max_edits, uint64_t *d_hit_offsets,
-                             sx_approx_hit *d_hits, uint64_t hit_capacity, uint64_t *total_hits_out)
+// sx_bwt_approx_search_dev in either form of the tables
+template <class Occ>
+static int approx_search_dev(sx_ctx *ctx, const uint32_t *d_c_table, Occ o, Occ ro, uint64_t N, uint32_t sigma, const uint8_t *d_patterns,
+                             const uint32_t *d_offsets, uint32_t count, int max_edits, uint64_t *d_hit_offsets, sx_approx_hit *d_hits,
+                             uint64_t hit_capacity, uint64_t *total_hits_out)
 {
     if (!ctx || !d_hit_offsets || !total_hits_out || ((uintptr_t)d_hits & 15)) return SX_E_ARG;
-    ApproxArgs A;
-    SX_TRY(approx_args(ctx, A, d_c_table, d_o_table, d_ro_table, N, sigma, d_patterns, d_offsets, count, max_edits));
+    ApproxArgsT<Occ> A;
+    SX_TRY(approx_args(ctx, A, d_c_table, o, ro, N, sigma, d_patterns, d_offsets, count, max_edits));
     SX_CHECK(hipSetDevice(ctx->device));
     *total_hits_out = 0;
     if (max_edits < 0 || count == 0) { // no search: every offset 0
@@ -384,6 +390,27 @@ int sx_bwt_approx_search_dev(sx_ctx *ctx, const uint32_t *d_c_table, const uint3
     return sx_sync(ctx);
 }
 
+extern "C" {
+
+int sx_bwt_approx_search_dev(sx_ctx *ctx, const uint32_t *d_c_table, const uint32_t *d_o_table,
+                             const uint32_t *d_ro_table, uint64_t N, uint32_t sigma, const uint8_t *d_patterns,
+                             const uint32_t *d_offsets, uint32_t count, int max_edits, uint64_t *d_hit_offsets,
+                             sx_approx_hit *d_hits, uint64_t hit_capacity, uint64_t *total_hits_out)
+{
+    return approx_search_dev(ctx, d_c_table, OccFull{d_o_table}, OccFull{d_ro_table}, N, sigma, d_patterns, d_offsets, count, max_edits,
+                             d_hit_offsets, d_hits, hit_capacity, total_hits_out);
+}
+
+int sx_bwt_approx_search_compact_dev(sx_ctx *ctx, const uint32_t *d_c_table, const uint8_t *d_occ, const uint8_t *d_rocc, uint64_t N,
+                                     uint32_t sigma, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, int max_edits,
+                                     uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t hit_capacity, uint64_t *total_hits_out)
+{
+    if (sigma > 128 || (((uintptr_t)d_occ | (uintptr_t)d_rocc) & 15u)) return SX_E_ARG; // (the layout of sx_occ.hpp)
+    const uint32_t stride = occ_stride(sigma);
+    return approx_search_dev(ctx, d_c_table, OccCompact{d_occ, stride}, OccCompact{d_rocc, stride}, N, sigma, d_patterns, d_offsets, count,
+                             max_edits, d_hit_offsets, d_hits, hit_capacity, total_hits_out);
+}
+
 int sx_bwt_approx_search(sx_ctx *ctx, const uint32_t *c_table, const uint32_t *o_table, const uint32_t *ro_table,
                          uint64_t N, uint32_t sigma, const uint8_t *patterns, const uint32_t *offsets, uint32_t count,
                          int max_edits, uint64_t *hit_offsets, sx_approx_hit **hits_out, uint64_t *total_hits_out)
@@ -392,7 +419,7 @@ int sx_bwt_approx_search(sx_ctx *ctx, const uint32_t *c_table, const uint32_t *o
     *hits_out = nullptr;
     *total_hits_out = 0;
     ApproxArgs A;
-    SX_TRY(approx_args(ctx, A, c_table, o_table, ro_table, N, sigma, patterns, offsets, count, max_edits));
+    SX_TRY(approx_args(ctx, A, c_table, OccFull{o_table}, OccFull{ro_table}, N, sigma, patterns, offsets, count, max_edits));
     if (max_edits < 0 || count == 0) {
         memset(hit_offsets, 0, ((size_t)count + 1) * sizeof(uint64_t));
         return 0;
@@ -417,8 +444,8 @@ int sx_bwt_approx_search(sx_ctx *ctx, const uint32_t *c_table, const uint32_t *o
     if (plen) SX_CHECK(hipMemcpyAsync(d_p, patterns, plen, hipMemcpyHostToDevice, ctx->stream));
     SX_CHECK(hipMemcpyAsync(d_off, offsets, ((size_t)count + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
     A.c = d_c;
-    A.o = d_o;
-    A.ro = d_ro;
+    A.o = OccFull{d_o};
+    A.ro = OccFull{d_ro};
     A.pat = d_p;
     A.off = d_off;
     uint64_t total = 0;

@@ -21,6 +21,7 @@
 #include "sx_hostio.hpp"
 #include "sx_scan.hpp"
 #include "sx_index.hpp"
+#include "sx_occ.hpp"
 
 #include <stdlib.h>
 
@@ -166,7 +167,8 @@ static std::atomic<int> g_live_indexes{0};
 static void free_rec(sx_index_rec &R)
 {
     (void)hipFree(R.d_string), (void)hipFree(R.d_sa), (void)hipFree(R.d_c), (void)hipFree(R.d_o), (void)hipFree(R.d_ro);
-    R.d_string = nullptr, R.d_sa = R.d_c = R.d_o = R.d_ro = nullptr;
+    (void)hipFree(R.d_occ), (void)hipFree(R.d_rocc);
+    R.d_string = R.d_occ = R.d_rocc = nullptr, R.d_sa = R.d_c = R.d_o = R.d_ro = nullptr;
 }
 
 static void free_view(sx_index *idx)
@@ -223,11 +225,12 @@ static int make_view(sx_ctx *ctx, sx_index *idx)
     return 0;
 }
 
-static sx_index *new_index(sx_ctx *ctx)
+static sx_index *new_index(sx_ctx *ctx, bool compact)
 {
     sx_index *idx = new (std::nothrow) sx_index;
     if (!idx) return nullptr;
     idx->device = ctx->device;
+    idx->compact = compact;
     g_live_indexes.fetch_add(1);
     return idx;
 }
@@ -245,13 +248,23 @@ static int add_tables(sx_ctx *ctx, sx_index *idx, const sx_map_record &M, const 
     size_t bytes = 0;
     SX_TRY(S.take(ctx, &R.d_sa, (size_t)M.N, &bytes));
     SX_TRY(S.take(ctx, &R.d_c, (size_t)M.sigma, &bytes));
-    SX_TRY(S.take(ctx, &R.d_o, o_words, &bytes));
-    if (M.ro_table) SX_TRY(S.take(ctx, &R.d_ro, o_words, &bytes));
+    if (idx->compact) {
+        SX_TRY(S.take(ctx, &R.d_occ, (size_t)occ_bytes(M.N, M.sigma), &bytes));
+        if (M.ro_table) SX_TRY(S.take(ctx, &R.d_rocc, (size_t)occ_bytes(M.N, M.sigma), &bytes));
+    } else {
+        SX_TRY(S.take(ctx, &R.d_o, o_words, &bytes));
+        if (M.ro_table) SX_TRY(S.take(ctx, &R.d_ro, o_words, &bytes));
+    }
     if (string) SX_TRY(S.take(ctx, &R.d_string, (size_t)M.N, &bytes));
     SX_CHECK(hipMemcpyAsync(R.d_sa, M.sa, (size_t)M.N * 4, hipMemcpyHostToDevice, ctx->stream));
     SX_CHECK(hipMemcpyAsync(R.d_c, M.c_table, (size_t)M.sigma * 4, hipMemcpyHostToDevice, ctx->stream));
-    SX_CHECK(hipMemcpyAsync(R.d_o, M.o_table, o_words * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (M.ro_table) SX_CHECK(hipMemcpyAsync(R.d_ro, M.ro_table, o_words * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (idx->compact) { // the full rows come up in windows and leave as blocks: no table of o_words exists on the device
+        SX_TRY(sx_nomem_of(sx_occ_from_rows_impl(ctx, M.o_table, M.N, M.sigma, R.d_occ)));
+        if (M.ro_table) SX_TRY(sx_nomem_of(sx_occ_from_rows_impl(ctx, M.ro_table, M.N, M.sigma, R.d_rocc)));
+    } else {
+        SX_CHECK(hipMemcpyAsync(R.d_o, M.o_table, o_words * 4, hipMemcpyHostToDevice, ctx->stream));
+        if (M.ro_table) SX_CHECK(hipMemcpyAsync(R.d_ro, M.ro_table, o_words * 4, hipMemcpyHostToDevice, ctx->stream));
+    }
     if (string) {
         if (M.N > 1) SX_CHECK(hipMemcpyAsync(R.d_string, string, (size_t)M.N - 1, hipMemcpyHostToDevice, ctx->stream));
         SX_CHECK(hipMemsetAsync(R.d_string + (M.N - 1), 0, 1, ctx->stream));
@@ -270,11 +283,11 @@ static int record_check(sx_ctx *ctx, const sx_map_record &R)
 }
 
 // an index of host tables, given as records (no strings) or as sources; every record is checked first
-static int from_sources(sx_ctx *ctx, const sx_map_record *records, const sx_index_source *sources, uint32_t n, sx_index **out)
+static int from_sources(sx_ctx *ctx, const sx_map_record *records, const sx_index_source *sources, uint32_t n, bool compact, sx_index **out)
 {
     for (uint32_t r = 0; r < n; ++r) SX_TRY(record_check(ctx, records ? records[r] : sources[r].record));
     SX_CHECK(hipSetDevice(ctx->device));
-    sx_index *idx = new_index(ctx);
+    sx_index *idx = new_index(ctx, compact);
     if (!idx) return sx_fail_msg(ctx, SX_E_NOMEM, "index");
     int rc = 0;
     for (uint32_t r = 0; r < n && rc == 0; ++r)
@@ -307,20 +320,27 @@ static int build_record(sx_ctx *ctx, sx_index *idx, const uint8_t *d_seq, uint64
     uint8_t *d_bwt;
     SX_TRY(S.take(ctx, &R.d_sa, (size_t)N, &bytes));
     SX_TRY(S.take(ctx, &R.d_c, (size_t)sigma, &bytes));
-    SX_TRY(S.take(ctx, &R.d_o, o_words, &bytes));
+    // compact: the BWT goes straight into the block builder and the table call makes C alone
+    const bool compact = idx->compact;
+    const size_t occ_b = (size_t)occ_bytes(N, sigma);
+    if (compact) SX_TRY(S.take(ctx, &R.d_occ, occ_b, &bytes));
+    else SX_TRY(S.take(ctx, &R.d_o, o_words, &bytes));
     SX_TRY(T.take(ctx, &d_bwt, (size_t)N));
     SX_TRY(sx_nomem_of(sx_sa_bwt_build_dev(ctx, R.d_string, n, sigma, R.d_sa, d_bwt)));
     SX_TRY(sx_nomem_of(sx_bwt_tables_from_bwt_dev(ctx, d_bwt, N, sigma, R.d_c, R.d_o)));
+    if (compact) SX_TRY(sx_nomem_of(sx_occ_build_impl(ctx, d_bwt, N, sigma, R.d_occ)));
     if (include_reverse) { // bwt.c:147-158: the reversed string's suffix array is temporary, its O table is RO
         uint8_t *d_rev;
         uint32_t *d_rsa, *d_rc;
-        SX_TRY(S.take(ctx, &R.d_ro, o_words, &bytes));
+        if (compact) SX_TRY(S.take(ctx, &R.d_rocc, occ_b, &bytes));
+        else SX_TRY(S.take(ctx, &R.d_ro, o_words, &bytes));
         SX_TRY(T.take(ctx, &d_rev, (size_t)N));
         SX_TRY(T.take(ctx, &d_rsa, (size_t)N));
         SX_TRY(T.take(ctx, &d_rc, (size_t)sigma));
         SX_TRY(sx_reverse_dev(ctx, R.d_string, n, d_rev));
         SX_TRY(sx_nomem_of(sx_sa_bwt_build_dev(ctx, d_rev, n, sigma, d_rsa, d_bwt)));
         SX_TRY(sx_nomem_of(sx_bwt_tables_from_bwt_dev(ctx, d_bwt, N, sigma, d_rc, R.d_ro)));
+        if (compact) SX_TRY(sx_nomem_of(sx_occ_build_impl(ctx, d_bwt, N, sigma, R.d_rocc)));
     }
     SX_TRY(sx_sync(ctx));
     S.keep();
@@ -367,7 +387,7 @@ using namespace sx;
 
 int sx_index_from_records_impl(sx_ctx *ctx, const sx_map_record *records, uint32_t n_records, sx_index **out)
 {
-    return from_sources(ctx, records, nullptr, n_records, out);
+    return from_sources(ctx, records, nullptr, n_records, false, out);
 }
 
 extern "C" {
@@ -481,11 +501,17 @@ void sx_index_destroy(sx_index *idx)
 
 int sx_index_build_fasta(sx_ctx *ctx, const uint8_t *fasta, uint64_t len, int include_reverse, sx_index **out)
 {
+    return sx_index_build_fasta_ex(ctx, fasta, len, include_reverse, 0, out);
+}
+
+int sx_index_build_fasta_ex(sx_ctx *ctx, const uint8_t *fasta, uint64_t len, int include_reverse, uint32_t flags, sx_index **out)
+{
     if (!ctx || !out || (len && !fasta)) return SX_E_ARG;
     *out = nullptr;
+    if (flags & ~(uint32_t)SX_INDEX_COMPACT) return sx_fail_msg(ctx, SX_E_ARG, "index: unknown flags");
     if (len >= 0x7FFFFFFFull) return sx_fail_msg(ctx, SX_E_ARG, "FASTA image must be shorter than 2^31 - 1 bytes");
     SX_CHECK(hipSetDevice(ctx->device));
-    sx_index *idx = new_index(ctx);
+    sx_index *idx = new_index(ctx, (flags & SX_INDEX_COMPACT) != 0);
     if (!idx) return sx_fail_msg(ctx, SX_E_NOMEM, "index");
     const int rc = build_fasta(ctx, idx, fasta, len, include_reverse != 0);
     if (rc != 0) {
@@ -501,14 +527,22 @@ int sx_index_from_tables(sx_ctx *ctx, const sx_map_record *records, uint32_t n_r
 {
     if (!ctx || !out || (n_records && !records)) return SX_E_ARG;
     *out = nullptr;
-    return from_sources(ctx, records, nullptr, n_records, out);
+    return from_sources(ctx, records, nullptr, n_records, false, out);
 }
 
 int sx_index_from_sources(sx_ctx *ctx, const sx_index_source *sources, uint32_t n_records, sx_index **out)
 {
     if (!ctx || !out || (n_records && !sources)) return SX_E_ARG;
     *out = nullptr;
-    return from_sources(ctx, nullptr, sources, n_records, out);
+    return from_sources(ctx, nullptr, sources, n_records, false, out);
+}
+
+int sx_index_from_sources_ex(sx_ctx *ctx, const sx_index_source *sources, uint32_t n_records, uint32_t flags, sx_index **out)
+{
+    if (!ctx || !out || (n_records && !sources)) return SX_E_ARG;
+    *out = nullptr;
+    if (flags & ~(uint32_t)SX_INDEX_COMPACT) return sx_fail_msg(ctx, SX_E_ARG, "index: unknown flags");
+    return sx_nomem_of(from_sources(ctx, nullptr, sources, n_records, (flags & SX_INDEX_COMPACT) != 0, out));
 }
 
 int sx_index_add_record(sx_ctx *ctx, sx_index *idx, const sx_index_source *source, int at_front)
@@ -520,7 +554,7 @@ int sx_index_add_record(sx_ctx *ctx, sx_index *idx, const sx_index_source *sourc
     const int rc = add_tables(ctx, idx, source->record, source->string, at_front != 0);
     if (rc != 0) {
         (void)hipStreamSynchronize(ctx->stream);
-        return rc;
+        return sx_nomem_of(rc);
     }
     return make_view(ctx, idx);
 }
@@ -533,7 +567,7 @@ int sx_index_info(const sx_index *idx, uint32_t *n_records_out, int *device_out,
     if (has_ro_out) {
         *has_ro_out = idx->recs.empty() ? 0 : 1;
         for (const sx_index_rec &R : idx->recs)
-            if (!R.d_ro) *has_ro_out = 0;
+            if (!R.has_ro()) *has_ro_out = 0;
     }
     if (device_bytes_out) *device_bytes_out = idx->device_bytes;
     return 0;
@@ -546,12 +580,49 @@ int sx_index_record_info(const sx_index *idx, uint32_t record, sx_index_record *
     out->name = R.name.c_str();
     out->N = R.N;
     out->sigma = R.sigma;
-    out->has_ro = R.d_ro ? 1 : 0;
+    out->has_ro = R.has_ro() ? 1 : 0;
     out->has_string = R.d_string ? 1 : 0;
     out->remap = R.remap;
     out->d_string = R.d_string;
     out->d_sa = R.d_sa, out->d_c = R.d_c, out->d_o = R.d_o, out->d_ro = R.d_ro;
     return 0;
+}
+
+int sx_index_record_occ(const sx_index *idx, uint32_t record, sx_index_occ *out)
+{
+    if (!idx || !out || record >= idx->recs.size()) return SX_E_ARG;
+    const sx_index_rec &R = idx->recs[record];
+    memset(out, 0, sizeof *out);
+    out->compact = R.d_occ ? 1 : 0;
+    if (R.d_occ) {
+        out->d_occ = R.d_occ, out->d_rocc = R.d_rocc;
+        out->stride = occ_stride(R.sigma), out->sigma_pad = occ_sigma_pad(R.sigma);
+        out->n_blocks = occ_blocks(R.N);
+    }
+    return 0;
+}
+
+int sx_index_is_compact(const sx_index *idx) { return idx && idx->compact ? 1 : 0; }
+
+static int expand_sink(void *user, int, const void *data, size_t bytes)
+{
+    char **at = (char **)user;
+    memcpy(*at, data, bytes);
+    *at += bytes;
+    return 0;
+}
+
+int sx_index_expand_o(sx_ctx *ctx, const sx_index *idx, uint32_t record, int reverse, uint64_t row_lo, uint64_t row_hi, uint32_t *rows_out)
+{
+    if (!ctx || !idx || record >= idx->recs.size()) return SX_E_ARG;
+    if (idx->device != ctx->device) return sx_fail_msg(ctx, SX_E_ARG, "index: it lives on another device than this context");
+    const sx_index_rec &R = idx->recs[record];
+    const uint8_t *blocks = reverse ? R.d_rocc : R.d_occ;
+    if (!blocks) return sx_fail_msg(ctx, SX_E_ARG, "index: the record has no blocks of this table");
+    if (row_lo > row_hi || row_hi > R.N + 1 || (row_hi > row_lo && !rows_out)) return sx_fail_msg(ctx, SX_E_ARG, "index: the rows to expand lie in [0, N]");
+    SX_CHECK(hipSetDevice(ctx->device));
+    char *at = (char *)rows_out;
+    return sx_nomem_of(sx_occ_stream_rows(ctx, SX_SECTION_INDEX, blocks, R.N, R.sigma, row_lo, row_hi, expand_sink, &at));
 }
 
 int sx_index_map_reads(sx_ctx *ctx, const sx_index *idx, const uint8_t *fastq, size_t fastq_len, int edits, sx_sink_fn sink, void *user)
@@ -614,10 +685,13 @@ int sx_index_write(sx_ctx *ctx, const sx_index *idx, sx_sink_fn sink, void *user
             if (R.remap[c] > 0) rt.rev_table[(int)R.remap[c]] = (signed char)c;
         SX_TRY(put(&rt, sizeof rt));
         SX_TRY(sx_stream_to_sink(ctx, SX_SECTION_INDEX, R.d_c, (size_t)R.sigma * 4, sink, user));
-        SX_TRY(sx_stream_to_sink(ctx, SX_SECTION_INDEX, R.d_o, o_bytes, sink, user));
-        const uint8_t has_ro = R.d_ro ? 1 : 0; // (a bool in the reference: one byte)
+        // (a compact record's tables are expanded window by window: the same bytes)
+        if (R.d_occ) SX_TRY(sx_nomem_of(sx_occ_stream_rows(ctx, SX_SECTION_INDEX, R.d_occ, R.N, R.sigma, 0, R.N + 1, sink, user)));
+        else SX_TRY(sx_stream_to_sink(ctx, SX_SECTION_INDEX, R.d_o, o_bytes, sink, user));
+        const uint8_t has_ro = R.has_ro() ? 1 : 0; // (a bool in the reference: one byte)
         SX_TRY(put(&has_ro, 1));
-        if (R.d_ro) SX_TRY(sx_stream_to_sink(ctx, SX_SECTION_INDEX, R.d_ro, o_bytes, sink, user));
+        if (R.d_rocc) SX_TRY(sx_nomem_of(sx_occ_stream_rows(ctx, SX_SECTION_INDEX, R.d_rocc, R.N, R.sigma, 0, R.N + 1, sink, user)));
+        else if (R.d_ro) SX_TRY(sx_stream_to_sink(ctx, SX_SECTION_INDEX, R.d_ro, o_bytes, sink, user));
     }
     return sx_sync(ctx);
 }

@@ -12,10 +12,14 @@ struct sx_index_rec {
     signed char remap[256];
     uint8_t *d_string = nullptr; // N bytes (the sentinel last), or null
     uint32_t *d_sa = nullptr, *d_c = nullptr, *d_o = nullptr, *d_ro = nullptr;
+    // a record of a compact index has the blocks of sx_occ.hpp in place of d_o / d_ro (d_rocc null: no reverse)
+    uint8_t *d_occ = nullptr, *d_rocc = nullptr;
+    bool has_ro() const { return d_ro || d_rocc; }
 };
 
 struct sx_index {
     int device = 0;
+    bool compact = false; // SX_INDEX_COMPACT: every record it has or gets is in the compact form
     std::vector<sx_index_rec> recs; // FASTA file order
     size_t device_bytes = 0;
     // the mapper's view of the records (rebuilt whenever a record is added): names and their offsets, one 256-byte

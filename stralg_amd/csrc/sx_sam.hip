@@ -521,8 +521,11 @@ static int search_batch(sx_ctx *ctx, const sx_index *idx, const sx_reads_dev &re
             sx_launch(ctx, SX_KC_REMAP, 2 * (p_hi - p_lo), sam_remap_kernel, dim3(sx_div_up(p_hi - p_lo, kBlock)), dim3(kBlock), reads.d_seqs,
                       (const uint8_t *)(idx->d_tabs + (size_t)r * 256), M.d_pat, p_lo, p_hi);
         uint64_t tot = 0;
-        const int rc = sx_bwt_approx_search_dev(ctx, R.d_c, R.d_o, R.d_ro, R.N, R.sigma, M.d_pat, reads.d_seq_off + q0, batch, edits,
-                                                M.d_ho + r * M.stride, room.d_raw + used, room.cap - used, &tot);
+        // (whichever form the record has: the hits and their order are the same)
+        const int rc = R.d_occ ? sx_bwt_approx_search_compact_dev(ctx, R.d_c, R.d_occ, R.d_rocc, R.N, R.sigma, M.d_pat, reads.d_seq_off + q0, batch,
+                                                                  edits, M.d_ho + r * M.stride, room.d_raw + used, room.cap - used, &tot)
+                               : sx_bwt_approx_search_dev(ctx, R.d_c, R.d_o, R.d_ro, R.N, R.sigma, M.d_pat, reads.d_seq_off + q0, batch, edits,
+                                                          M.d_ho + r * M.stride, room.d_raw + used, room.cap - used, &tot);
         if (rc == SX_E_CAPACITY) *need_out = used + tot;
         if (rc != 0) return rc;
         seg[r] = used;

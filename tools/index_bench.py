@@ -10,7 +10,13 @@ profiles/index_bench_2p28.json), everything measured in this one run:
   fastq      sx_fastq_index_dev, kernels only (HIP events of the class) and upload + kernels (wall), against the host's
              sx_fastq_index on the same image; the device pass as a fraction of sx_membw_probe's read rate
 
+  --compact  the full index against the compact one (BWT blocks with sampled counts in place of O / RO, DESIGN.md section
+             13) of the same record and reads, in one run: resident bytes, build time, a mapping call per k, the search
+             kernels' share of it (HIP events of the class), and the ratio of the two forms' search times; nothing else
+             is measured then (kept in profiles/compact_index_2p28.json)
+
     python tools/index_bench.py [--log2n 28] [--reads 1000000] [--reps 3]
+    python tools/index_bench.py --compact [--form compact --trace-only]
     rocprofv3 --kernel-trace --stats -d out -- python tools/index_bench.py --trace-only     (profiles/index_rocprofv3_summary.txt)
 """
 import argparse
@@ -36,6 +42,58 @@ def best(fn, reps):
     return res, min(times), times
 
 
+def compact_leg(args, ctx, Index, fasta, fastq, out):
+    """both forms of the index of the same record, one after the other in this process: what each keeps resident, what its
+    build takes, a mapping call per k and the search kernels' part of one such call"""
+    out["bench"] = "compact_index"
+    ks = [int(x) for x in args.ks.split(",")]
+    forms = ("full", "compact") if args.form == "both" else (args.form,)
+    for form in forms:
+        compact = form == "compact"
+        if args.trace_only:
+            with Index.from_fasta(fasta, ctx=ctx, compact=compact) as idx:
+                for _ in range(2):
+                    idx.map_reads_discard(fastq, ks[0])
+            continue
+
+        def build():
+            Index.from_fasta(fasta, ctx=ctx, compact=compact).close()
+
+        build()  # warm-up (workspace)
+        _, build_s, build_all = best(build, args.reps)
+        res = {"build_ms": round(build_s * 1e3, 1), "build_all_ms": [round(t * 1e3, 1) for t in build_all]}
+        with Index.from_fasta(fasta, ctx=ctx, compact=compact) as idx:
+            res["device_bytes"] = idx.device_bytes
+            for k in ks:
+                seen = idx.map_reads_discard(fastq, k)  # warm-up
+                _, call_s, call_all = best(lambda: idx.map_reads_discard(fastq, k), args.reps if k < 2 else max(1, args.reps - 1))
+                ctx.profile_only("search")
+                ctx.profile_enable(True)
+                ctx.profile_reset()
+                t0 = time.perf_counter()
+                idx.map_reads_discard(fastq, k)
+                timed_s = time.perf_counter() - t0
+                stat = ctx.profile_read()["search"]
+                ctx.profile_enable(False)
+                ctx.profile_only(None)
+                res[f"k{k}"] = {"text_bytes": sum(b for _, b in seen), "call_ms": round(call_s * 1e3, 1),
+                                "call_all_ms": [round(t * 1e3, 1) for t in call_all], "search_kernels_ms": round(stat["ms"], 2),
+                                "search_launches": stat["launches"], "profiled_call_ms": round(timed_s * 1e3, 1),
+                                "search_share_of_call": round(stat["ms"] * 1e-3 / timed_s, 4)}
+        out[form] = res
+        ctx.trim()
+    if not args.trace_only:
+        if len(forms) == 2:
+            out["compact_over_full"] = {
+                "device_bytes": round(out["compact"]["device_bytes"] / out["full"]["device_bytes"], 4),
+                "build": round(out["compact"]["build_ms"] / out["full"]["build_ms"], 3),
+                **{f"k{k}_search_kernels": round(out["compact"][f"k{k}"]["search_kernels_ms"] / out["full"][f"k{k}"]["search_kernels_ms"], 3)
+                   for k in ks},
+                **{f"k{k}_call": round(out["compact"][f"k{k}"]["call_ms"] / out["full"][f"k{k}"]["call_ms"], 3) for k in ks}}
+            assert all(out["compact"][f"k{k}"]["text_bytes"] == out["full"][f"k{k}"]["text_bytes"] for k in ks)
+        print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--log2n", type=int, default=28)
@@ -46,6 +104,8 @@ def main():
     ap.add_argument("--skip-parent", action="store_true", help="no host tables: only the index's own figures")
     ap.add_argument("--trace-only", action="store_true",
                     help="build the index, map the reads twice at the first k and stop (for a rocprofv3 --kernel-trace --stats run)")
+    ap.add_argument("--compact", action="store_true", help="the full and the compact index side by side, nothing else")
+    ap.add_argument("--form", default="both", choices=["both", "full", "compact"], help="with --compact: only this form")
     args = ap.parse_args()
     import torch
 
@@ -75,6 +135,9 @@ def main():
     fastq = b"".join(b"@read%d\n%s\n+\n%s\n" % (q, row.tobytes(), b"~" * L) for q, row in enumerate(letters[reads]))
     out = {"bench": "index", "n": n, "reads": R, "read_length": L, "fasta_bytes": len(fasta), "fastq_bytes": len(fastq),
            "reps": args.reps}
+
+    if args.compact:
+        return compact_leg(args, ctx, Index, fasta, fastq, out)
 
     if args.trace_only:
         with Index.from_fasta(fasta, ctx=ctx) as idx:

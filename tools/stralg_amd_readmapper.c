@@ -9,6 +9,10 @@
  *   stralg_amd_readmapper -i -d K genome.fa reads.fq [more.fq ...]
  *                                                   the same with the index built on the device from genome.fa: no
  *                                                   genome.fa.bwttables is read or written
+ *   --compact                                       with -d (and -i or a saved index): the index keeps BWT blocks with
+ *                                                   sampled counts in place of the O / RO tables, a fifth of the device
+ *                                                   memory for DNA; the output is the same.  -p writes the same file
+ *                                                   with or without it
  *   (--preprocess, --edits and --in-memory are accepted for -p, -d and -i)
  *
  * Index file: u32 record count; per record, last FASTA record first, its name as u32 length + bytes + NUL, then the
@@ -98,20 +102,20 @@ static int build_index(const char *fasta)
 
 /* -d: the index is loaded once (from genome.fa.bwttables, or, with -i, built on the device from genome.fa itself) and
  * stays on the device; every FASTQ file is mapped against it, stdout is the files' texts one behind the other */
-static int map_reads(const char *fasta, char *const *reads, int n_reads, int k, int in_memory)
+static int map_reads(const char *fasta, char *const *reads, int n_reads, int k, int in_memory, uint32_t flags)
 {
     struct sx_index *idx = NULL;
     if (in_memory) {
         size_t len = 0;
         uint8_t *image = slurp(fasta, &len);
-        idx = stralg_amd_index_from_fasta_image(image, len, true);
+        idx = stralg_amd_index_from_fasta_image_ex(image, len, true, flags);
         free(image);
         if (!idx) fail("could not index", fasta);
     } else {
         char *path = index_path(fasta);
         FILE *in = fopen(path, "rb");
         if (!in) fail("cannot read (run -p first)", path);
-        idx = stralg_amd_index_read(in);
+        idx = stralg_amd_index_read_ex(in, flags);
         if (!idx) fail("empty or truncated index", path);
         fclose(in);
         free(path);
@@ -133,6 +137,7 @@ static int usage(const char *self, int status)
     fprintf(stderr, "usage: %s -p genome.fa               build genome.fa" INDEX_EXT "\n", self);
     fprintf(stderr, "       %s -d K genome.fa reads.fq ...  SAM lines of all matches within K edits, on stdout\n", self);
     fprintf(stderr, "       %s -i -d K genome.fa reads.fq ...  the same, the index built in memory from genome.fa\n", self);
+    fprintf(stderr, "       --compact                          with -d: BWT blocks in place of the O tables on the device\n");
     return status;
 }
 
@@ -141,6 +146,7 @@ int main(int argc, char **argv)
     const char *to_index = NULL;
     char **rest = calloc((size_t)argc + 1, sizeof *rest);
     int k = -1, n_rest = 0, in_memory = 0;
+    uint32_t flags = 0;
     if (!rest) fail("out of memory", NULL);
     for (int a = 1; a < argc; ++a) {
         const char *s = argv[a];
@@ -148,6 +154,8 @@ int main(int argc, char **argv)
         if (!strcmp(s, "-h") || !strcmp(s, "--help")) return usage(argv[0], EXIT_SUCCESS);
         if (!strcmp(s, "-i") || !strcmp(s, "--in-memory")) {
             in_memory = 1;
+        } else if (!strcmp(s, "--compact")) {
+            flags |= SX_INDEX_COMPACT;
         } else if (wants_p || wants_d) {
             if (++a >= argc) return usage(argv[0], EXIT_FAILURE);
             if (wants_p) to_index = argv[a];
@@ -162,5 +170,5 @@ int main(int argc, char **argv)
     }
     if (to_index) return build_index(to_index);
     if (n_rest < 2 || k < 0) return usage(argv[0], EXIT_FAILURE);
-    return map_reads(rest[0], rest + 1, n_rest - 1, k, in_memory);
+    return map_reads(rest[0], rest + 1, n_rest - 1, k, in_memory, flags);
 }
