@@ -154,6 +154,10 @@ enum {
                                        tests set small values so that one run takes several batches) */
     ,SX_FLAG_SAM_WINDOW_BYTES = 19 /* sx_map_reads_stream: bytes of SAM text per window, rounded up to 16 (0: the default and the
                                        most, 32 MiB, one pinned staging buffer) */
+    ,SX_FLAG_LOCATE_CHUNK_ROWS = 20 /* mapping against an index with a sampled suffix array: the hits of a batch are located and
+                                       printed in runs of consecutive hits whose lines fit this many positions (0: the default,
+                                       2^28, a buffer of 1 GiB; a single hit with more lines gets a buffer of its own length;
+                                       tests set small values) */
 };
 int sx_ctx_set_flag(sx_ctx *ctx, int flag, int value);
 
@@ -442,6 +446,45 @@ int sx_index_is_compact(const sx_index *idx);
  * the reverse, rows outside [0, N + 1]. */
 int sx_index_expand_o(sx_ctx *ctx, const sx_index *idx, uint32_t record, int reverse, uint64_t row_lo, uint64_t row_hi,
                       uint32_t *rows_out);
+
+/* ---- a sampled suffix array for the compact index ---------------- */
+/* SA values kept at a sampling distance s = 2^q, q in 1 .. 10, the others recovered by walking LF over the forward blocks.
+ * Sampling is by text position: row r is marked iff SA[r] % s == 0, so a record of N rows has (N + s - 1) / s samples.
+ * Rows are cut into the blocks of the compact table (N / 64 + 1 of them).  Marks: one 16-byte entry a block, a u64 whose
+ * bit j is set iff row 64 b + j is marked (rows from N on are clear), a u32 `before`, the number of marked rows in all
+ * earlier blocks, and a u32 zero.  Values: SA[r] of the marked rows in row order, so the value of the marked row 64 b + j
+ * is values[before + popcount(bits & ((1 << j) - 1))].  SA[row]: while the row is not marked, a = the row's BWT byte,
+ * row = C[a] + O(a, row), one more step; the marked row's value plus the steps.  The same suffix array gives the same
+ * bytes from run to run. */
+/* bytes of the marks and of the values of a record of N rows; SX_E_ARG for N or q out of range */
+int sx_sa_sample_bytes(uint64_t N, uint32_t q, uint64_t *marks_bytes_out, uint64_t *values_bytes_out);
+/* marks and values from a suffix array on the device (N entries); d_marks_out 16-byte aligned.  SX_E_ARG when the array
+ * does not hold (N + s - 1) / s multiples of s (it is no suffix array); nothing behind the buffers' ends is written */
+int sx_sa_sample_build_dev(sx_ctx *ctx, const uint32_t *d_sa, uint64_t N, uint32_t q, void *d_marks_out, uint32_t *d_values_out);
+/* SA[row_lo .. row_hi) (row_hi <= N) into d_out[0 .. row_hi - row_lo) from the C table, the forward blocks
+ * (sx_occ_compact_build_dev), marks and values.  A walk is bounded at s steps: samples that do not belong to the blocks
+ * end with SX_E_INTERNAL, not with a hang.  SX_E_ARG: misaligned blocks or marks, rows outside [0, N]. */
+int sx_sa_locate_rows_dev(sx_ctx *ctx, const uint32_t *d_c_table, const uint8_t *d_occ, uint64_t N, uint32_t sigma, const void *d_marks,
+                          const uint32_t *d_values, uint32_t q, uint64_t row_lo, uint64_t row_hi, uint32_t *d_out);
+/* An index with a sampled suffix array: bits 8 .. 15 of the flags of sx_index_build_fasta_ex / sx_index_from_sources_ex
+ * carry q (0: the whole suffix array, as before); q in 1 .. 10 needs SX_INDEX_COMPACT, anything else is SX_E_ARG.  Every
+ * record keeps marks and values in place of its suffix array: about N x (5 + 1/4 + 4/s) + 4 N bytes of blocks for DNA with
+ * RO, 5.4 N at s = 32 where the compact index takes 9 N.  A build from FASTA samples the suffix array and releases it before
+ * the record is finished; tables that arrive from the host come up in windows.  Mapping locates the hits of a batch in
+ * runs (SX_FLAG_LOCATE_CHUNK_ROWS) before their text is laid out and gives the same text; sx_index_write the same file
+ * (the suffix array is located window by window); sx_index_add_record follows the index's form; sx_index_record_info
+ * reports d_sa = NULL for such a record and sx_index_record_samples its marks and values. */
+#define SX_INDEX_SA_SAMPLE_LOG2(q) ((uint32_t)(q) << 8)
+typedef struct sx_index_samples {
+    const void *d_marks;      /* device memory; NULL (and the rest 0) for a record with its whole suffix array */
+    const uint32_t *d_values;
+    uint32_t sa_log2;         /* q */
+    uint64_t n_samples, n_blocks;
+} sx_index_samples;
+int sx_index_record_samples(const sx_index *idx, uint32_t record, sx_index_samples *out);
+/* rows [row_lo, row_hi) of a sampled record's suffix array to host memory, located on the device window by window.
+ * SX_E_ARG: a record with its whole suffix array, row_hi > N, row_lo > row_hi; row_lo == row_hi writes nothing. */
+int sx_index_expand_sa(sx_ctx *ctx, const sx_index *idx, uint32_t record, uint64_t row_lo, uint64_t row_hi, uint32_t *rows_out);
 
 /* ---- FASTA ingest and remap on the device ---------------- */
 /* bioinf/fasta.c:92-135 load_fasta_records' packing of a file image in device memory into

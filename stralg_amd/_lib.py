@@ -37,8 +37,10 @@ APPROX_GAP_D = 0x8000
 APPROX_HIT_DTYPE = [("query", "<u4"), ("L", "<u4"), ("R", "<u4"), ("match_length", "<u2"), ("n_gaps", "<u2"),
                     ("gap", "<u2", (APPROX_MAX_EDITS,))]
 SX_E_ARG, SX_E_MALFORMED, SX_E_CAPACITY = -1, -4, -5
+SX_E_INTERNAL = -3
 SX_SECTION_SAM = 3
 SX_FLAG_SAM_BATCH_READS, SX_FLAG_SAM_WINDOW_BYTES = 18, 19
+SX_FLAG_LOCATE_CHUNK_ROWS = 20
 
 
 class SamBatch(C.Structure):
@@ -87,8 +89,29 @@ class IndexOcc(C.Structure):
                 ("sigma_pad", C.c_uint32), ("n_blocks", C.c_uint64)]
 
 
+class IndexSamples(C.Structure):
+    """include/stralg_amd.h sx_index_samples"""
+    _fields_ = [("d_marks", C.c_void_p), ("d_values", C.c_void_p), ("sa_log2", C.c_uint32), ("n_samples", C.c_uint64),
+                ("n_blocks", C.c_uint64)]
+
+
 SX_SECTION_INDEX = 4
 SX_INDEX_COMPACT = 1
+SA_SAMPLE_MAX_LOG2 = 10
+
+
+def index_flags(compact, sa_sample=0):
+    """the flags of sx_index_build_fasta_ex / sx_index_from_sources_ex; sa_sample: 0, or a power of two in 2 .. 1024 (with
+    compact): checked here, before anything is built"""
+    sa_sample = int(sa_sample)
+    if sa_sample == 0:
+        return SX_INDEX_COMPACT if compact else 0
+    q = sa_sample.bit_length() - 1
+    if sa_sample < 2 or sa_sample != 1 << q or q > SA_SAMPLE_MAX_LOG2:
+        raise ValueError(f"sa_sample must be 0 or a power of two in 2 .. 1024, not {sa_sample}")
+    if not compact:
+        raise ValueError("sa_sample needs compact=True: the walks read the BWT blocks")
+    return SX_INDEX_COMPACT | (q << 8)
 SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t)
 
 
@@ -162,6 +185,11 @@ def load(path=None):
         "sx_index_record_occ": (C.c_int, [vp, C.c_uint32, C.POINTER(IndexOcc)]),
         "sx_index_is_compact": (C.c_int, [vp]),
         "sx_index_expand_o": (C.c_int, [vp, vp, C.c_uint32, C.c_int, C.c_uint64, C.c_uint64, u32p]),
+        "sx_sa_sample_bytes": (C.c_int, [C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "sx_sa_sample_build_dev": (C.c_int, [vp, u32p, C.c_uint64, C.c_uint32, vp, u32p]),
+        "sx_sa_locate_rows_dev": (C.c_int, [vp, u32p, u8p, C.c_uint64, C.c_uint32, vp, u32p, C.c_uint32, C.c_uint64, C.c_uint64, u32p]),
+        "sx_index_record_samples": (C.c_int, [vp, C.c_uint32, C.POINTER(IndexSamples)]),
+        "sx_index_expand_sa": (C.c_int, [vp, vp, C.c_uint32, C.c_uint64, C.c_uint64, u32p]),
         "sx_fasta_pack_dev": (C.c_int, [vp, u8p, C.c_uint64, u8p, C.POINTER(C.c_uint64), u32p, C.c_uint64,
                                         C.POINTER(C.c_uint32)]),
         "sx_fasta_pack": (C.c_int, [vp, u8p, C.c_uint64, u8p, C.POINTER(C.c_uint64), u32p, C.c_uint64,
@@ -206,6 +234,7 @@ EXPORTS = ["sx_device_count", "sx_device_numa_node", "sx_ctx_create", "sx_ctx_de
            "sx_occ_compact_bytes", "sx_occ_compact_build_dev", "sx_occ_compact_expand_dev", "sx_bwt_exact_search_compact_dev",
            "sx_bwt_approx_search_compact_dev", "sx_index_build_fasta_ex", "sx_index_from_sources_ex", "sx_index_record_occ",
            "sx_index_is_compact", "sx_index_expand_o",
+           "sx_sa_sample_bytes", "sx_sa_sample_build_dev", "sx_sa_locate_rows_dev", "sx_index_record_samples", "sx_index_expand_sa",
            "sx_synth_dev", "sx_membw_probe", "sx_prim_sort_pairs_dev", "sx_prim_exclusive_sum_dev", "sx_prim_classify_dev"]
 
 

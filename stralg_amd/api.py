@@ -275,6 +275,26 @@ class Context:
         """sx_map_reads_stream: bytes of SAM text per window (0: the default, 32 MiB)"""
         self._check(self.lib.sx_ctx_set_flag(self.h, _lib.SX_FLAG_SAM_WINDOW_BYTES, int(nbytes)), "sx_ctx_set_flag")
 
+    def set_locate_chunk_rows(self, rows):
+        """mapping against an index with a sampled suffix array: the hits of a batch are located and printed in runs whose
+        lines fit this many positions (0: the default, 2^28)"""
+        self._check(self.lib.sx_ctx_set_flag(self.h, _lib.SX_FLAG_LOCATE_CHUNK_ROWS, int(rows)), "sx_ctx_set_flag")
+
+    # ---- the sampled suffix array (sx_locate.hpp) -----------------------------------------------
+    def sa_sample_bytes(self, N, sa_sample):
+        """sx_sa_sample_bytes: (bytes of the marks, bytes of the values) of a record of N rows sampled at this distance"""
+        marks, values = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.sx_sa_sample_bytes(N, int(sa_sample).bit_length() - 1, C.byref(marks), C.byref(values)), "sx_sa_sample_bytes")
+        return int(marks.value), int(values.value)
+
+    def sa_sample_build_dev(self, d_sa, N, sa_sample, d_marks, d_values):
+        self._check(self.lib.sx_sa_sample_build_dev(self.h, _ptr(d_sa), N, int(sa_sample).bit_length() - 1, _ptr(d_marks), _ptr(d_values)),
+                    "sx_sa_sample_build_dev")
+
+    def sa_locate_rows_dev(self, d_c, d_occ, N, sigma, d_marks, d_values, sa_sample, row_lo, row_hi, d_out):
+        self._check(self.lib.sx_sa_locate_rows_dev(self.h, _ptr(d_c), _ptr(d_occ), N, sigma, _ptr(d_marks), _ptr(d_values),
+                                                   int(sa_sample).bit_length() - 1, row_lo, row_hi, _ptr(d_out)), "sx_sa_locate_rows_dev")
+
     def map_reads_stream(self, records, fastq, edits, sink):
         """sx_map_reads_stream: records = [(name bytes, BwtTable), ...] in the mapper's list order; sink(bytes) receives the
         SAM text window after window.  sink=None discards the text without touching it and returns [(time.perf_counter(),
@@ -489,21 +509,26 @@ class Index:
 
     # ---- constructors -------------------------------------------------------------------------------------------
     @classmethod
-    def from_fasta(cls, fasta_bytes, include_reverse=True, ctx=None, compact=False):
+    def from_fasta(cls, fasta_bytes, include_reverse=True, ctx=None, compact=False, sa_sample=0):
         """sx_index_build_fasta_ex: the bytes of a FASTA file -> tables of every record, built on the device; compact=True:
-        BWT blocks with sampled counts in place of the O / RO tables (a fifth of the memory for DNA, the same results)"""
+        BWT blocks with sampled counts in place of the O / RO tables (a fifth of the memory for DNA, the same results);
+        sa_sample=32 (a power of two in 2 .. 1024, with compact): SA values at that distance in place of the suffix array,
+        the others located by walks over the blocks (5.4 bytes a symbol in place of 9 for DNA, the same results)"""
+        flags = _lib.index_flags(compact, sa_sample)
         ctx = ctx or default_context()
         buf = np.frombuffer(bytes(fasta_bytes), dtype=np.uint8)
         h = C.c_void_p()
         ctx._check(ctx.lib.sx_index_build_fasta_ex(ctx.h, _ptr(buf) if buf.size else None, buf.size, 1 if include_reverse else 0,
-                                                   _lib.SX_INDEX_COMPACT if compact else 0, C.byref(h)), "sx_index_build_fasta")
+                                                   flags, C.byref(h)), "sx_index_build_fasta")
         return cls(ctx, h)
 
     @classmethod
-    def from_tables(cls, records, ctx=None, compact=False):
+    def from_tables(cls, records, ctx=None, compact=False, sa_sample=0):
         """sx_index_from_sources_ex: records = [(name bytes, BwtTable), ...] in the mapper's list order (the FASTA file's), as
         Context.map_reads_stream takes them; a table whose sa.string is set (remapped symbols + terminator) can be saved.
-        compact=True: the tables go up in windows and stay as blocks"""
+        compact=True: the tables go up in windows and stay as blocks; sa_sample: as from_fasta (the suffix arrays go up in
+        windows too and stay as samples)"""
+        flags = _lib.index_flags(compact, sa_sample)
         ctx = ctx or default_context()
         src = (_lib.IndexSource * max(1, len(records)))()
         keep = []
@@ -515,14 +540,15 @@ class Index:
                 keep.append(string)
                 src[r].string = _ptr(string)
         h = C.c_void_p()
-        ctx._check(ctx.lib.sx_index_from_sources_ex(ctx.h, src, len(records), _lib.SX_INDEX_COMPACT if compact else 0, C.byref(h)),
+        ctx._check(ctx.lib.sx_index_from_sources_ex(ctx.h, src, len(records), flags, C.byref(h)),
                    "sx_index_from_sources")
         return cls(ctx, h)
 
     @classmethod
-    def load(cls, path_or_bytes, ctx=None, compact=False):
+    def load(cls, path_or_bytes, ctx=None, compact=False, sa_sample=0):
         """the read mapper's index file (genome.fa.bwttables; what .save writes): a path, or the bytes.  The file is
-        mapped, and its records go to the device one after the other (compact=True: as blocks)."""
+        mapped, and its records go to the device one after the other (compact=True: as blocks; sa_sample: as from_fasta)."""
+        flags = _lib.index_flags(compact, sa_sample)
         ctx = ctx or default_context()
         if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
             blob = np.frombuffer(bytes(path_or_bytes), dtype=np.uint8)
@@ -538,7 +564,7 @@ class Index:
             return out
 
         h = C.c_void_p()
-        ctx._check(ctx.lib.sx_index_from_sources_ex(ctx.h, None, 0, _lib.SX_INDEX_COMPACT if compact else 0, C.byref(h)),
+        ctx._check(ctx.lib.sx_index_from_sources_ex(ctx.h, None, 0, flags, C.byref(h)),
                    "sx_index_from_sources")
         idx = cls(ctx, h)
         try:
@@ -665,12 +691,12 @@ class Index:
 
     def device_tables(self, r, ctx=None):
         """record r's device buffers read back (tests): dict(string, sa, c, o, ro) of numpy arrays; ro / string may be None
-        (and o, in a compact index: see device_occ and expand_o)"""
+        (and o, in a compact index: see device_occ and expand_o; and sa, in a sampled one: see device_samples and expand_sa)"""
         ctx = ctx or self.ctx
         rec = self.record_info(r)
         N, sigma = int(rec.N), int(rec.sigma)
         return dict(string=ctx.download(rec.d_string, N, np.uint8) if rec.d_string else None,
-                    sa=ctx.download(rec.d_sa, N, np.uint32), c=ctx.download(rec.d_c, sigma, np.uint32),
+                    sa=ctx.download(rec.d_sa, N, np.uint32) if rec.d_sa else None, c=ctx.download(rec.d_c, sigma, np.uint32),
                     o=ctx.download(rec.d_o, (N + 1) * sigma, np.uint32).reshape(N + 1, sigma) if rec.d_o else None,
                     ro=ctx.download(rec.d_ro, (N + 1) * sigma, np.uint32).reshape(N + 1, sigma) if rec.d_ro else None)
 
@@ -709,6 +735,39 @@ class Index:
         lo, hi = (0, N + 1) if rows is None else rows
         out = np.zeros((max(0, hi - lo), sigma), dtype=np.uint32)
         ctx._check(ctx.lib.sx_index_expand_o(ctx.h, self._handle(), r, 1 if reverse else 0, lo, hi, _ptr(out)), "sx_index_expand_o")
+        return out
+
+    def record_samples(self, r):
+        """sx_index_record_samples of record r: the _lib.IndexSamples with the addresses of the record's marks and values,
+        the log2 of its sampling distance, its samples and its blocks (all 0 for a record with its whole suffix array)"""
+        smp = _lib.IndexSamples()
+        self.ctx._check(self.ctx.lib.sx_index_record_samples(self._handle(), r, C.byref(smp)), "sx_index_record_samples")
+        return smp
+
+    @property
+    def sa_sample(self):
+        """the sampling distance of the records' suffix arrays, 0 when they are kept whole"""
+        if self._info()[0] == 0:
+            return 0
+        q = int(self.record_samples(0).sa_log2)
+        return 1 << q if q else 0
+
+    def device_samples(self, r, ctx=None):
+        """record r's marks, a (blocks, 2) uint64 array of (bits, before), and values read back"""
+        ctx = ctx or self.ctx
+        smp = self.record_samples(r)
+        if not smp.sa_log2:
+            raise StralgAmdError("the index keeps whole suffix arrays: it has no samples")
+        return (ctx.download(smp.d_marks, 2 * int(smp.n_blocks), np.uint64).reshape(int(smp.n_blocks), 2),
+                ctx.download(smp.d_values, int(smp.n_samples), np.uint32))
+
+    def expand_sa(self, r, rows=None, ctx=None):
+        """sx_index_expand_sa: the suffix array of a sampled record r, located on the device; rows=(lo, hi): SA[lo .. hi)"""
+        ctx = ctx or self.ctx
+        N = int(self.record_info(r).N)
+        lo, hi = (0, N) if rows is None else rows
+        out = np.zeros(max(0, hi - lo), dtype=np.uint32)
+        ctx._check(ctx.lib.sx_index_expand_sa(ctx.h, self._handle(), r, lo, hi, _ptr(out)), "sx_index_expand_sa")
         return out
 
     def close(self):

@@ -393,6 +393,10 @@ int sx_ctx_set_flag(sx_ctx *ctx, int flag, int value)
         ctx->sam_window_bytes = value > 0 ? value : 0;
         return 0;
     }
+    if (flag == SX_FLAG_LOCATE_CHUNK_ROWS) {
+        ctx->locate_chunk_rows = value > 0 ? value : 0;
+        return 0;
+    }
     if (flag == SX_FLAG_INDUCE_NO_HOIST) {
         ctx->induce_no_hoist = value ? 1 : 0;
         return 0;

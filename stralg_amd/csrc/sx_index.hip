@@ -22,6 +22,7 @@
 #include "sx_scan.hpp"
 #include "sx_index.hpp"
 #include "sx_occ.hpp"
+#include "sx_locate.hpp"
 
 #include <stdlib.h>
 
@@ -167,14 +168,15 @@ static std::atomic<int> g_live_indexes{0};
 static void free_rec(sx_index_rec &R)
 {
     (void)hipFree(R.d_string), (void)hipFree(R.d_sa), (void)hipFree(R.d_c), (void)hipFree(R.d_o), (void)hipFree(R.d_ro);
-    (void)hipFree(R.d_occ), (void)hipFree(R.d_rocc);
-    R.d_string = R.d_occ = R.d_rocc = nullptr, R.d_sa = R.d_c = R.d_o = R.d_ro = nullptr;
+    (void)hipFree(R.d_occ), (void)hipFree(R.d_rocc), (void)hipFree(R.d_sa_marks), (void)hipFree(R.d_sa_values);
+    R.d_string = R.d_occ = R.d_rocc = R.d_sa_marks = nullptr, R.d_sa = R.d_c = R.d_o = R.d_ro = R.d_sa_values = nullptr;
 }
 
 static void free_view(sx_index *idx)
 {
     (void)hipFree(idx->d_rnames), (void)hipFree(idx->d_tabs), (void)hipFree(idx->d_rname_off), (void)hipFree((void *)idx->d_sa_list),
-        (void)hipFree(idx->d_sa_lens);
+        (void)hipFree(idx->d_sa_lens), (void)hipFree(idx->d_loc_list);
+    idx->d_loc_list = nullptr;
     idx->d_rnames = idx->d_tabs = nullptr, idx->d_rname_off = nullptr, idx->d_sa_list = nullptr, idx->d_sa_lens = nullptr;
     idx->device_bytes -= idx->view_bytes;
     idx->view_bytes = 0;
@@ -189,6 +191,7 @@ static int make_view(sx_ctx *ctx, sx_index *idx)
     std::vector<uint32_t> rname_off(n + 1);
     std::vector<const uint32_t *> sa_ptrs(n + 1);
     std::vector<uint64_t> sa_lens(n + 1);
+    std::vector<LocRec> locs(idx->sa_log2 ? n : 0);
     for (size_t r = 0; r < n; ++r) {
         const sx_index_rec &R = idx->recs[r];
         rname_off[r] = (uint32_t)rnames.size();
@@ -198,6 +201,7 @@ static int make_view(sx_ctx *ctx, sx_index *idx)
         for (int b = 0; b < 256; ++b) tabs[r * 256 + b] = R.remap[b] > 0 && (uint32_t)R.remap[b] < R.sigma ? (uint8_t)R.remap[b] : 0;
         sa_ptrs[r] = R.d_sa;
         sa_lens[r] = R.N;
+        if (idx->sa_log2) locs[r] = loc_rec_of(R.d_c, R.d_occ, R.N, R.sigma, R.d_sa_marks, R.d_sa_values, R.sa_log2);
     }
     rname_off[n] = (uint32_t)rnames.size();
     rnames.push_back(0);
@@ -212,6 +216,11 @@ static int make_view(sx_ctx *ctx, sx_index *idx)
     SX_TRY(S.take(ctx, &d_rname_off, rname_off.size(), &bytes));
     SX_TRY(S.take(ctx, &d_sa_list, sa_ptrs.size(), &bytes));
     SX_TRY(S.take(ctx, &d_sa_lens, sa_lens.size(), &bytes));
+    LocRec *d_locs = nullptr;
+    if (!locs.empty()) {
+        SX_TRY(S.take(ctx, &d_locs, locs.size(), &bytes));
+        SX_CHECK(hipMemcpyAsync(d_locs, locs.data(), locs.size() * sizeof(LocRec), hipMemcpyHostToDevice, ctx->stream));
+    }
     SX_CHECK(hipMemcpyAsync(d_rnames, rnames.data(), rnames.size(), hipMemcpyHostToDevice, ctx->stream));
     SX_CHECK(hipMemcpyAsync(d_tabs, tabs.data(), tabs.size(), hipMemcpyHostToDevice, ctx->stream));
     SX_CHECK(hipMemcpyAsync(d_rname_off, rname_off.data(), rname_off.size() * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -220,17 +229,28 @@ static int make_view(sx_ctx *ctx, sx_index *idx)
     SX_TRY(sx_sync(ctx)); // (the host vectors are pageable: their copies are done)
     S.keep();
     idx->d_rnames = d_rnames, idx->d_tabs = d_tabs, idx->d_rname_off = d_rname_off, idx->d_sa_list = d_sa_list, idx->d_sa_lens = d_sa_lens;
+    idx->d_loc_list = d_locs;
     idx->view_bytes = bytes;
     idx->device_bytes += bytes;
     return 0;
 }
 
-static sx_index *new_index(sx_ctx *ctx, bool compact)
+// the flags of the _ex builders: SX_INDEX_COMPACT, and in bits 8 .. 15 the log2 of a sampling distance, which needs it
+static bool index_flags_ok(uint32_t flags)
 {
+    const uint32_t q = (flags >> 8) & 0xFFu;
+    if (flags & ~((uint32_t)SX_INDEX_COMPACT | 0xFF00u)) return false;
+    return q == 0 || (sa_sample_log2_ok(q) && (flags & SX_INDEX_COMPACT));
+}
+
+static sx_index *new_index(sx_ctx *ctx, uint32_t flags)
+{
+    const bool compact = (flags & SX_INDEX_COMPACT) != 0;
     sx_index *idx = new (std::nothrow) sx_index;
     if (!idx) return nullptr;
     idx->device = ctx->device;
     idx->compact = compact;
+    idx->sa_log2 = (flags >> 8) & 0xFFu;
     g_live_indexes.fetch_add(1);
     return idx;
 }
@@ -246,7 +266,13 @@ static int add_tables(sx_ctx *ctx, sx_index *idx, const sx_map_record &M, const 
     const size_t o_words = (size_t)(M.N + 1) * M.sigma;
     sx_dev_scope S;
     size_t bytes = 0;
-    SX_TRY(S.take(ctx, &R.d_sa, (size_t)M.N, &bytes));
+    R.sa_log2 = idx->sa_log2;
+    if (R.sa_log2) {
+        SX_TRY(S.take(ctx, &R.d_sa_marks, (size_t)sa_mark_bytes(M.N), &bytes));
+        SX_TRY(S.take(ctx, &R.d_sa_values, (size_t)sa_sample_count(M.N, R.sa_log2), &bytes));
+    } else {
+        SX_TRY(S.take(ctx, &R.d_sa, (size_t)M.N, &bytes));
+    }
     SX_TRY(S.take(ctx, &R.d_c, (size_t)M.sigma, &bytes));
     if (idx->compact) {
         SX_TRY(S.take(ctx, &R.d_occ, (size_t)occ_bytes(M.N, M.sigma), &bytes));
@@ -256,7 +282,9 @@ static int add_tables(sx_ctx *ctx, sx_index *idx, const sx_map_record &M, const 
         if (M.ro_table) SX_TRY(S.take(ctx, &R.d_ro, o_words, &bytes));
     }
     if (string) SX_TRY(S.take(ctx, &R.d_string, (size_t)M.N, &bytes));
-    SX_CHECK(hipMemcpyAsync(R.d_sa, M.sa, (size_t)M.N * 4, hipMemcpyHostToDevice, ctx->stream));
+    // (a sampled record's suffix array comes up in windows and leaves as marks and values: it is never resident)
+    if (R.sa_log2) SX_TRY(sx_nomem_of(sx_sa_sample_host_impl(ctx, M.sa, M.N, R.sa_log2, R.d_sa_marks, R.d_sa_values)));
+    if (!R.sa_log2) SX_CHECK(hipMemcpyAsync(R.d_sa, M.sa, (size_t)M.N * 4, hipMemcpyHostToDevice, ctx->stream));
     SX_CHECK(hipMemcpyAsync(R.d_c, M.c_table, (size_t)M.sigma * 4, hipMemcpyHostToDevice, ctx->stream));
     if (idx->compact) { // the full rows come up in windows and leave as blocks: no table of o_words exists on the device
         SX_TRY(sx_nomem_of(sx_occ_from_rows_impl(ctx, M.o_table, M.N, M.sigma, R.d_occ)));
@@ -283,11 +311,11 @@ static int record_check(sx_ctx *ctx, const sx_map_record &R)
 }
 
 // an index of host tables, given as records (no strings) or as sources; every record is checked first
-static int from_sources(sx_ctx *ctx, const sx_map_record *records, const sx_index_source *sources, uint32_t n, bool compact, sx_index **out)
+static int from_sources(sx_ctx *ctx, const sx_map_record *records, const sx_index_source *sources, uint32_t n, uint32_t flags, sx_index **out)
 {
     for (uint32_t r = 0; r < n; ++r) SX_TRY(record_check(ctx, records ? records[r] : sources[r].record));
     SX_CHECK(hipSetDevice(ctx->device));
-    sx_index *idx = new_index(ctx, compact);
+    sx_index *idx = new_index(ctx, flags);
     if (!idx) return sx_fail_msg(ctx, SX_E_NOMEM, "index");
     int rc = 0;
     for (uint32_t r = 0; r < n && rc == 0; ++r)
@@ -318,7 +346,15 @@ static int build_record(sx_ctx *ctx, sx_index *idx, const uint8_t *d_seq, uint64
     const uint32_t sigma = R.sigma;
     const size_t o_words = (size_t)(N + 1) * sigma;
     uint8_t *d_bwt;
-    SX_TRY(S.take(ctx, &R.d_sa, (size_t)N, &bytes));
+    // sampled: the suffix array is an allocation of this call, sampled and released before the reverse is built
+    uint32_t *d_sa;
+    R.sa_log2 = idx->sa_log2;
+    if (R.sa_log2) {
+        SX_TRY(T.take(ctx, &d_sa, (size_t)N));
+    } else {
+        SX_TRY(S.take(ctx, &R.d_sa, (size_t)N, &bytes));
+        d_sa = R.d_sa;
+    }
     SX_TRY(S.take(ctx, &R.d_c, (size_t)sigma, &bytes));
     // compact: the BWT goes straight into the block builder and the table call makes C alone
     const bool compact = idx->compact;
@@ -326,9 +362,15 @@ static int build_record(sx_ctx *ctx, sx_index *idx, const uint8_t *d_seq, uint64
     if (compact) SX_TRY(S.take(ctx, &R.d_occ, occ_b, &bytes));
     else SX_TRY(S.take(ctx, &R.d_o, o_words, &bytes));
     SX_TRY(T.take(ctx, &d_bwt, (size_t)N));
-    SX_TRY(sx_nomem_of(sx_sa_bwt_build_dev(ctx, R.d_string, n, sigma, R.d_sa, d_bwt)));
+    SX_TRY(sx_nomem_of(sx_sa_bwt_build_dev(ctx, R.d_string, n, sigma, d_sa, d_bwt)));
     SX_TRY(sx_nomem_of(sx_bwt_tables_from_bwt_dev(ctx, d_bwt, N, sigma, R.d_c, R.d_o)));
     if (compact) SX_TRY(sx_nomem_of(sx_occ_build_impl(ctx, d_bwt, N, sigma, R.d_occ)));
+    if (R.sa_log2) {
+        SX_TRY(S.take(ctx, &R.d_sa_marks, (size_t)sa_mark_bytes(N), &bytes));
+        SX_TRY(S.take(ctx, &R.d_sa_values, (size_t)sa_sample_count(N, R.sa_log2), &bytes));
+        SX_TRY(sx_nomem_of(sx_sa_sample_dev_impl(ctx, d_sa, N, R.sa_log2, R.d_sa_marks, R.d_sa_values))); // (ends with a sync)
+        T.drop(d_sa);
+    }
     if (include_reverse) { // bwt.c:147-158: the reversed string's suffix array is temporary, its O table is RO
         uint8_t *d_rev;
         uint32_t *d_rsa, *d_rc;
@@ -387,7 +429,7 @@ using namespace sx;
 
 int sx_index_from_records_impl(sx_ctx *ctx, const sx_map_record *records, uint32_t n_records, sx_index **out)
 {
-    return from_sources(ctx, records, nullptr, n_records, false, out);
+    return from_sources(ctx, records, nullptr, n_records, 0, out);
 }
 
 extern "C" {
@@ -508,10 +550,10 @@ int sx_index_build_fasta_ex(sx_ctx *ctx, const uint8_t *fasta, uint64_t len, int
 {
     if (!ctx || !out || (len && !fasta)) return SX_E_ARG;
     *out = nullptr;
-    if (flags & ~(uint32_t)SX_INDEX_COMPACT) return sx_fail_msg(ctx, SX_E_ARG, "index: unknown flags");
+    if (!index_flags_ok(flags)) return sx_fail_msg(ctx, SX_E_ARG, "index: unknown flags, or a sampling distance without SX_INDEX_COMPACT or outside 2^1 .. 2^10");
     if (len >= 0x7FFFFFFFull) return sx_fail_msg(ctx, SX_E_ARG, "FASTA image must be shorter than 2^31 - 1 bytes");
     SX_CHECK(hipSetDevice(ctx->device));
-    sx_index *idx = new_index(ctx, (flags & SX_INDEX_COMPACT) != 0);
+    sx_index *idx = new_index(ctx, flags);
     if (!idx) return sx_fail_msg(ctx, SX_E_NOMEM, "index");
     const int rc = build_fasta(ctx, idx, fasta, len, include_reverse != 0);
     if (rc != 0) {
@@ -527,22 +569,22 @@ int sx_index_from_tables(sx_ctx *ctx, const sx_map_record *records, uint32_t n_r
 {
     if (!ctx || !out || (n_records && !records)) return SX_E_ARG;
     *out = nullptr;
-    return from_sources(ctx, records, nullptr, n_records, false, out);
+    return from_sources(ctx, records, nullptr, n_records, 0, out);
 }
 
 int sx_index_from_sources(sx_ctx *ctx, const sx_index_source *sources, uint32_t n_records, sx_index **out)
 {
     if (!ctx || !out || (n_records && !sources)) return SX_E_ARG;
     *out = nullptr;
-    return from_sources(ctx, nullptr, sources, n_records, false, out);
+    return from_sources(ctx, nullptr, sources, n_records, 0, out);
 }
 
 int sx_index_from_sources_ex(sx_ctx *ctx, const sx_index_source *sources, uint32_t n_records, uint32_t flags, sx_index **out)
 {
     if (!ctx || !out || (n_records && !sources)) return SX_E_ARG;
     *out = nullptr;
-    if (flags & ~(uint32_t)SX_INDEX_COMPACT) return sx_fail_msg(ctx, SX_E_ARG, "index: unknown flags");
-    return sx_nomem_of(from_sources(ctx, nullptr, sources, n_records, (flags & SX_INDEX_COMPACT) != 0, out));
+    if (!index_flags_ok(flags)) return sx_fail_msg(ctx, SX_E_ARG, "index: unknown flags, or a sampling distance without SX_INDEX_COMPACT or outside 2^1 .. 2^10");
+    return sx_nomem_of(from_sources(ctx, nullptr, sources, n_records, flags, out));
 }
 
 int sx_index_add_record(sx_ctx *ctx, sx_index *idx, const sx_index_source *source, int at_front)
@@ -604,6 +646,20 @@ int sx_index_record_occ(const sx_index *idx, uint32_t record, sx_index_occ *out)
 
 int sx_index_is_compact(const sx_index *idx) { return idx && idx->compact ? 1 : 0; }
 
+int sx_index_record_samples(const sx_index *idx, uint32_t record, sx_index_samples *out)
+{
+    if (!idx || !out || record >= idx->recs.size()) return SX_E_ARG;
+    const sx_index_rec &R = idx->recs[record];
+    memset(out, 0, sizeof *out);
+    if (R.sa_log2) {
+        out->d_marks = R.d_sa_marks, out->d_values = R.d_sa_values;
+        out->sa_log2 = R.sa_log2;
+        out->n_samples = sa_sample_count(R.N, R.sa_log2);
+        out->n_blocks = occ_blocks(R.N);
+    }
+    return 0;
+}
+
 static int expand_sink(void *user, int, const void *data, size_t bytes)
 {
     char **at = (char **)user;
@@ -623,6 +679,19 @@ int sx_index_expand_o(sx_ctx *ctx, const sx_index *idx, uint32_t record, int rev
     SX_CHECK(hipSetDevice(ctx->device));
     char *at = (char *)rows_out;
     return sx_nomem_of(sx_occ_stream_rows(ctx, SX_SECTION_INDEX, blocks, R.N, R.sigma, row_lo, row_hi, expand_sink, &at));
+}
+
+int sx_index_expand_sa(sx_ctx *ctx, const sx_index *idx, uint32_t record, uint64_t row_lo, uint64_t row_hi, uint32_t *rows_out)
+{
+    if (!ctx || !idx || record >= idx->recs.size()) return SX_E_ARG;
+    if (idx->device != ctx->device) return sx_fail_msg(ctx, SX_E_ARG, "index: it lives on another device than this context");
+    const sx_index_rec &R = idx->recs[record];
+    if (!R.sa_log2) return sx_fail_msg(ctx, SX_E_ARG, "index: the record keeps its whole suffix array");
+    if (row_lo > row_hi || row_hi > R.N || (row_hi > row_lo && !rows_out)) return sx_fail_msg(ctx, SX_E_ARG, "index: the rows to expand lie in [0, N)");
+    SX_CHECK(hipSetDevice(ctx->device));
+    char *at = (char *)rows_out;
+    return sx_nomem_of(sx_sa_stream_rows(ctx, SX_SECTION_INDEX, loc_rec_of(R.d_c, R.d_occ, R.N, R.sigma, R.d_sa_marks, R.d_sa_values, R.sa_log2), row_lo,
+                                         row_hi, expand_sink, &at));
 }
 
 int sx_index_map_reads(sx_ctx *ctx, const sx_index *idx, const uint8_t *fastq, size_t fastq_len, int edits, sx_sink_fn sink, void *user)
@@ -672,7 +741,11 @@ int sx_index_write(sx_ctx *ctx, const sx_index *idx, sx_sink_fn sink, void *user
         // stralg/serialise.c:7-18: string (u32 length, bytes), suffix array, remap table, C, O, flag, RO
         SX_TRY(put(&n, 4));
         SX_TRY(sx_stream_to_sink(ctx, SX_SECTION_INDEX, R.d_string, n, sink, user));
-        SX_TRY(sx_stream_to_sink(ctx, SX_SECTION_INDEX, R.d_sa, (size_t)R.N * 4, sink, user));
+        // (a sampled record's suffix array is located window by window: the same bytes)
+        if (R.sa_log2)
+            SX_TRY(sx_nomem_of(sx_sa_stream_rows(ctx, SX_SECTION_INDEX, loc_rec_of(R.d_c, R.d_occ, R.N, R.sigma, R.d_sa_marks, R.d_sa_values, R.sa_log2),
+                                                 0, R.N, sink, user)));
+        if (!R.sa_log2) SX_TRY(sx_stream_to_sink(ctx, SX_SECTION_INDEX, R.d_sa, (size_t)R.N * 4, sink, user));
         struct { // stralg/remap.h:9-19
             uint32_t alphabet_size;
             signed char table[256], rev_table[128];

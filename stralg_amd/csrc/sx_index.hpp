@@ -14,17 +14,24 @@ struct sx_index_rec {
     uint32_t *d_sa = nullptr, *d_c = nullptr, *d_o = nullptr, *d_ro = nullptr;
     // a record of a compact index has the blocks of sx_occ.hpp in place of d_o / d_ro (d_rocc null: no reverse)
     uint8_t *d_occ = nullptr, *d_rocc = nullptr;
+    // a record of a sampled index has the marks and values of sx_locate.hpp in place of d_sa (which is null then)
+    uint8_t *d_sa_marks = nullptr;
+    uint32_t *d_sa_values = nullptr;
+    uint32_t sa_log2 = 0;
     bool has_ro() const { return d_ro || d_rocc; }
 };
 
 struct sx_index {
     int device = 0;
     bool compact = false; // SX_INDEX_COMPACT: every record it has or gets is in the compact form
+    uint32_t sa_log2 = 0; // SX_INDEX_SA_SAMPLE_LOG2: 0, or every record keeps a suffix array sampled at this distance's log2
     std::vector<sx_index_rec> recs; // FASTA file order
     size_t device_bytes = 0;
     // the mapper's view of the records (rebuilt whenever a record is added): names and their offsets, one 256-byte
-    // symbol table a record, the suffix arrays' addresses and lengths
+    // symbol table a record, the suffix arrays' addresses and lengths and, in a sampled index, what a walk reads of every
+    // record (an array of sx::LocRec, sx_locate.hpp)
     uint8_t *d_rnames = nullptr, *d_tabs = nullptr;
+    void *d_loc_list = nullptr;
     uint32_t *d_rname_off = nullptr;
     const uint32_t **d_sa_list = nullptr;
     uint64_t *d_sa_lens = nullptr;

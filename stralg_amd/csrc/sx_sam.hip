@@ -20,6 +20,7 @@
 #include "sx_scan.hpp"
 #include "sx_hostio.hpp"
 #include "sx_index.hpp"
+#include "sx_locate.hpp"
 
 #include <stdlib.h>
 
@@ -53,6 +54,11 @@ struct SamArgs {
     const uint8_t *rnames;
     const uint32_t *rname_off;
     uint32_t n_records;
+    // an index with a sampled suffix array (the kernels' kLocated form): the positions of a run of hits, located before
+    // the layout; hit h's stand at positions[pos_off[h] - pos_base ..)
+    const uint32_t *positions;
+    const uint64_t *pos_off;
+    uint64_t pos_base;
 };
 
 struct HitInfo {
@@ -118,7 +124,7 @@ __device__ __forceinline__ uint32_t cigar_render(uint8_t *out, uint32_t cap, uin
 }
 
 // what the lines of hit h are made of; false: the hit does not fit the batch (its query, interval or offsets)
-__device__ __forceinline__ bool hit_info(const SamArgs &A, uint64_t h, HitInfo &I)
+template <bool kLocated> __device__ __forceinline__ bool hit_info(const SamArgs &A, uint64_t h, HitInfo &I)
 {
     const uint4 h0 = A.hits[2 * h];
     I.gaps = A.hits[2 * h + 1];
@@ -129,7 +135,7 @@ __device__ __forceinline__ bool hit_info(const SamArgs &A, uint64_t h, HitInfo &
     const uint32_t vq = h0.x, L = h0.y, R = h0.z;
     if ((uint64_t)vq >= (uint64_t)A.n_reads * A.n_records || L > R) return false;
     const uint32_t read = vq / A.n_records, rec = vq - read * A.n_records;
-    const uint32_t *sa = A.sa_list ? A.sa_list[rec] : A.sa;
+    const uint32_t *sa = kLocated ? nullptr : A.sa_list ? A.sa_list[rec] : A.sa;
     const uint64_t sa_len = A.sa_list ? A.sa_len_list[rec] : A.sa_len;
     if ((uint64_t)R > sa_len) return false;
     I.name_b = A.name_off[read];
@@ -146,7 +152,7 @@ __device__ __forceinline__ bool hit_info(const SamArgs &A, uint64_t h, HitInfo &
     I.m = I.seq_l;
     I.n_gaps = h0.w >> 16;
     if (I.n_gaps > SX_APPROX_MAX_EDITS) I.n_gaps = SX_APPROX_MAX_EDITS;
-    I.pos = sa + L;
+    I.pos = kLocated ? A.positions + (A.pos_off[h] - A.pos_base) : sa + L;
     I.cnt = R - L;
     return true;
 }
@@ -158,7 +164,7 @@ __device__ __forceinline__ uint32_t fixed_bytes(const HitInfo &I)
 }
 
 // ---- layout: bytes per hit ---------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void sam_size_kernel(SamArgs A, uint64_t *len_out, uint32_t *err)
+template <bool kLocated> __global__ __launch_bounds__(kBlock) void sam_size_kernel(SamArgs A, uint64_t *len_out, uint32_t *err)
 {
     __shared__ uint64_t red[kWavesPerBlock];
     __shared__ uint32_t long_cnt[kBlock];
@@ -169,7 +175,7 @@ __global__ __launch_bounds__(kBlock) void sam_size_kernel(SamArgs A, uint64_t *l
     long_cnt[t] = 0;
     if (h < A.n_hits) {
         HitInfo I = {};
-        if (!hit_info(A, h, I)) {
+        if (!hit_info<kLocated>(A, h, I)) {
             atomicOr(err, 1u);
         } else {
             I.cig_len = cigar_render(nullptr, kCigarMax, I.m, I.gaps, I.n_gaps);
@@ -212,7 +218,7 @@ __device__ __forceinline__ void put_bytes(uint8_t *obuf, int64_t &off, int64_t s
     off += n;
 }
 
-__global__ __launch_bounds__(kBlock) void sam_emit_kernel(SamArgs A, const uint64_t *byte_off, uint64_t lo, uint64_t hi,
+template <bool kLocated> __global__ __launch_bounds__(kBlock) void sam_emit_kernel(SamArgs A, const uint64_t *byte_off, uint64_t lo, uint64_t hi,
                                                           uint8_t *out)
 {
     __shared__ uint4 obuf4[kSlice / 16];
@@ -243,7 +249,7 @@ __global__ __launch_bounds__(kBlock) void sam_emit_kernel(SamArgs A, const uint6
     uint32_t i = 0;
     {   // the walk inside the hit: whole steps of 1024 lines that end at or before the slice's first byte are skipped
         HitInfo I = {};
-        if (hit_info(A, h, I)) {
+        if (hit_info<kLocated>(A, h, I)) {
             I.cig_len = cigar_render(nullptr, kCigarMax, I.m, I.gaps, I.n_gaps);
             const uint32_t fixed = fixed_bytes(I);
             while (I.cnt - i > kWalk * kBlock) {
@@ -263,7 +269,7 @@ __global__ __launch_bounds__(kBlock) void sam_emit_kernel(SamArgs A, const uint6
         // hits h .. h + 255: how many lines each has left, the first 256 lines' hits, their CIGARs
         HitInfo I = {};
         uint32_t c = 0;
-        if (h + t < A.n_hits && hit_info(A, h + t, I)) c = I.cnt - (t == 0 ? (i < I.cnt ? i : I.cnt) : 0u);
+        if (h + t < A.n_hits && hit_info<kLocated>(A, h + t, I)) c = I.cnt - (t == 0 ? (i < I.cnt ? i : I.cnt) : 0u);
         const uint32_t cc = c < (uint32_t)kBlock ? c : (uint32_t)kBlock;
         uint32_t total;
         const uint32_t ex = block_exclusive_scan<OpAdd>(cc, red32, total);
@@ -397,7 +403,8 @@ __global__ __launch_bounds__(kBlock) void sam_merge_kernel(const uint4 *src, uin
 static SamArgs sam_args_of(const sx_sam_batch &b)
 {
     return SamArgs{(const uint4 *)b.d_hits, b.n_hits,     b.d_sa,       b.sa_len,     b.d_sa_list, b.d_sa_len_list, b.d_names,   b.d_seqs,
-                   b.d_quals,               b.d_name_off, b.d_seq_off,  b.d_qual_off, b.n_reads,   b.d_rnames,      b.d_rname_off, b.n_records};
+                   b.d_quals,               b.d_name_off, b.d_seq_off,  b.d_qual_off, b.n_reads,   b.d_rnames,      b.d_rname_off, b.n_records,
+                   nullptr,                 nullptr,      0};
 }
 
 static int sam_args(sx_ctx *ctx, const sx_sam_batch *b, SamArgs &A)
@@ -419,8 +426,8 @@ static int sam_layout(sx_ctx *ctx, const SamArgs &A, uint64_t *d_byte_off, uint6
     uint32_t *d_err = (uint32_t *)ctx->slab[SX_SLAB_SORT].p;
     SX_CHECK(hipMemsetAsync(d_err, 0, 16, ctx->stream));
     if (A.n_hits)
-        sx_launch(ctx, SX_KC_SAM, A.n_hits * 40, sam_size_kernel, dim3(sx_div_up(A.n_hits, kBlock)), dim3(kBlock), A, d_byte_off,
-                  d_err);
+        sx_launch(ctx, SX_KC_SAM, A.n_hits * 40, A.positions ? sam_size_kernel<true> : sam_size_kernel<false>, dim3(sx_div_up(A.n_hits, kBlock)),
+                  dim3(kBlock), A, d_byte_off, d_err);
     SX_TRY(device_scan64_inplace(ctx, d_byte_off, A.n_hits, SX_KC_SAM));
     uint32_t h[2] = {0, 0}, e = 0;
     SX_TRY(sx_readback(ctx, (const uint32_t *)(d_byte_off + A.n_hits), 2, h));
@@ -437,7 +444,8 @@ static int sam_emit(sx_ctx *ctx, const SamArgs &A, const uint64_t *d_byte_off, u
     const uint64_t slices = (hi - lo + kSlice - 1) / kSlice;
     if (slices > 0x7FFFFFFFull) return sx_fail_msg(ctx, SX_E_ARG, "SAM text: window too long");
     // per line: its bytes out, 4 bytes of position in; the read's fields once a slice
-    sx_launch(ctx, SX_KC_SAM, hi - lo, sam_emit_kernel, dim3((uint32_t)slices), dim3(kBlock), A, d_byte_off, lo, hi, d_out);
+    sx_launch(ctx, SX_KC_SAM, hi - lo, A.positions ? sam_emit_kernel<true> : sam_emit_kernel<false>, dim3((uint32_t)slices), dim3(kBlock), A,
+              d_byte_off, lo, hi, d_out);
     return 0;
 }
 
@@ -493,6 +501,10 @@ struct MapBufs { // what a mapping call holds on the device beside the hits' roo
     uint64_t *d_ho, *d_vbase, *d_seg, *d_byte_off = nullptr;
     uint32_t *d_err;
     sx_approx_hit *d_merged = nullptr;
+    // an index with a sampled suffix array: the lines in front of every hit of the batch, the positions of a run of hits
+    uint64_t *d_pos_off = nullptr;
+    uint32_t *d_positions = nullptr;
+    uint64_t pos_cap = 0;
     uint64_t merged_cap = 0, stride = 0; // stride: entries of a record's hit offsets in d_ho
     size_t window = 0;
     sx_dev_scope own;
@@ -541,7 +553,8 @@ static int merge_batch(sx_ctx *ctx, MapBufs &M, const HitRoom &room, const std::
     const uint32_t n_records = (uint32_t)seg.size() - 1;
     const uint64_t used = seg[n_records];
     if (used > M.merged_cap) {
-        if (M.d_merged) M.own.drop(M.d_merged), M.own.drop(M.d_byte_off);
+        if (M.d_merged) M.own.drop(M.d_merged), M.own.drop(M.d_byte_off), M.own.drop(M.d_pos_off);
+        M.d_pos_off = nullptr;
         M.merged_cap = used > room.cap ? used : room.cap;
         SX_TRY(M.own.take(ctx, &M.d_merged, (size_t)M.merged_cap));
         SX_TRY(M.own.take(ctx, &M.d_byte_off, (size_t)M.merged_cap + 1));
@@ -585,6 +598,43 @@ static int emit_windows(sx_ctx *ctx, const SamArgs &A, const MapBufs &M, const s
         }
     }
     return sx_sync(ctx);
+}
+
+// The text of a batch against an index with a sampled suffix array: its hits are taken in runs of consecutive hits whose
+// lines fit the cap (SX_FLAG_LOCATE_CHUNK_ROWS; a hit is never split: one with more lines gets a buffer of its own length);
+// a run is located, laid out and emitted through its windows before the next one starts
+static int emit_located(sx_ctx *ctx, const sx_index *idx, sx_sam_batch text, MapBufs &M, const sx_stage_events &E, sx_sink_fn sink, void *user)
+{
+    const LocRec *d_recs = (const LocRec *)idx->d_loc_list;
+    const uint64_t n_hits = text.n_hits, cap = ctx->locate_chunk_rows > 0 ? (uint64_t)ctx->locate_chunk_rows : 1ull << 28;
+    const uint4 *d_hits = (const uint4 *)text.d_hits;
+    if (!M.d_pos_off) SX_TRY(M.own.take(ctx, &M.d_pos_off, (size_t)M.merged_cap + 1));
+    uint64_t total = 0;
+    SX_TRY(sx_sa_hits_offsets(ctx, d_recs, text.n_records, (uint64_t)text.n_reads * text.n_records, d_hits, n_hits, M.d_pos_off, &total));
+    uint32_t *d_loc_err = M.d_err + 4, *d_run = M.d_err + 8;
+    for (uint64_t h_lo = 0, base = 0; h_lo < n_hits;) {
+        uint64_t h_hi = n_hits, rows = total - base;
+        if (rows > cap) SX_TRY(sx_sa_hits_run(ctx, M.d_pos_off, n_hits, h_lo, base, cap, d_run, &h_hi, &rows));
+        if (rows > M.pos_cap) {
+            if (M.d_positions) M.own.drop(M.d_positions);
+            M.d_positions = nullptr, M.pos_cap = 0;
+            SX_TRY(M.own.take(ctx, &M.d_positions, (size_t)rows));
+            M.pos_cap = rows;
+        }
+        if (!M.d_positions) SX_TRY(M.own.take(ctx, &M.d_positions, 1)); // (hits without a line: the kernels still want an address)
+        SX_TRY(sx_sa_locate_hits(ctx, d_recs, text.n_records, d_hits, M.d_pos_off, h_lo, h_hi, base, rows, M.d_positions, d_loc_err));
+        uint32_t e = 0;
+        SX_TRY(sx_readback(ctx, d_loc_err, 1, &e));
+        if (e) return sx_fail_msg(ctx, SX_E_INTERNAL, "read mapping: a walk over a sampled suffix array met its bound");
+        sx_sam_batch run = text;
+        run.d_hits = text.d_hits + h_lo, run.n_hits = h_hi - h_lo;
+        SamArgs A = sam_args_of(run);
+        A.positions = M.d_positions, A.pos_off = M.d_pos_off + h_lo, A.pos_base = base;
+        SX_TRY(emit_windows(ctx, A, M, E, sink, user));
+        base += rows;
+        h_lo = h_hi;
+    }
+    return 0;
 }
 
 } // namespace sx
@@ -708,7 +758,8 @@ int sx_map_reads_core(sx_ctx *ctx, const sx_index *idx, const sx_reads_dev &read
             text.d_hits = M.d_merged, text.n_hits = seg[n_records];
             text.d_name_off = reads.d_name_off + q0, text.d_seq_off = reads.d_seq_off + q0, text.d_qual_off = reads.d_qual_off + q0;
             text.n_reads = batch;
-            SX_TRY(emit_windows(ctx, sam_args_of(text), M, E, sink, user));
+            if (idx->sa_log2) SX_TRY(emit_located(ctx, idx, text, M, E, sink, user));
+            else SX_TRY(emit_windows(ctx, sam_args_of(text), M, E, sink, user));
         }
         q0 += batch;
     }

@@ -10,6 +10,7 @@ profiles/index_bench_2p28.json), everything measured in this one run:
   fastq      sx_fastq_index_dev, kernels only (HIP events of the class) and upload + kernels (wall), against the host's
              sx_fastq_index on the same image; the device pass as a fraction of sx_membw_probe's read rate
 
+  --compact --sa-sample 8,32,128  the compact index against the same with a sampled suffix array
   --compact  the full index against the compact one (BWT blocks with sampled counts in place of O / RO, DESIGN.md section
              13) of the same record and reads, in one run: resident bytes, build time, a mapping call per k, the search
              kernels' share of it (HIP events of the class), and the ratio of the two forms' search times; nothing else
@@ -48,21 +49,26 @@ def compact_leg(args, ctx, Index, fasta, fastq, out):
     out["bench"] = "compact_index"
     ks = [int(x) for x in args.ks.split(",")]
     forms = ("full", "compact") if args.form == "both" else (args.form,)
+    samplings = [int(x) for x in args.sa_sample.split(",")] if args.sa_sample else []
+    if samplings:  # the compact index beside the sampled ones: the searches are the same, the locate pass is what differs
+        out["bench"] = "sampled_sa"
+        forms = (() if args.form == "sampled" else ("compact",)) + tuple(f"sampled{s}" for s in samplings)
     for form in forms:
-        compact = form == "compact"
+        compact = form != "full"
+        sa_sample = int(form[7:]) if form.startswith("sampled") else 0
         if args.trace_only:
-            with Index.from_fasta(fasta, ctx=ctx, compact=compact) as idx:
+            with Index.from_fasta(fasta, ctx=ctx, compact=compact, sa_sample=sa_sample) as idx:
                 for _ in range(2):
                     idx.map_reads_discard(fastq, ks[0])
             continue
 
         def build():
-            Index.from_fasta(fasta, ctx=ctx, compact=compact).close()
+            Index.from_fasta(fasta, ctx=ctx, compact=compact, sa_sample=sa_sample).close()
 
         build()  # warm-up (workspace)
         _, build_s, build_all = best(build, args.reps)
         res = {"build_ms": round(build_s * 1e3, 1), "build_all_ms": [round(t * 1e3, 1) for t in build_all]}
-        with Index.from_fasta(fasta, ctx=ctx, compact=compact) as idx:
+        with Index.from_fasta(fasta, ctx=ctx, compact=compact, sa_sample=sa_sample) as idx:
             res["device_bytes"] = idx.device_bytes
             for k in ks:
                 seen = idx.map_reads_discard(fastq, k)  # warm-up
@@ -80,10 +86,23 @@ def compact_leg(args, ctx, Index, fasta, fastq, out):
                                 "call_all_ms": [round(t * 1e3, 1) for t in call_all], "search_kernels_ms": round(stat["ms"], 2),
                                 "search_launches": stat["launches"], "profiled_call_ms": round(timed_s * 1e3, 1),
                                 "search_share_of_call": round(stat["ms"] * 1e-3 / timed_s, 4)}
+                if sa_sample and "compact" in out:
+                    # the locate kernel is timed in the searches' class: what that class takes beyond the compact index's same
+                    # searches is the locate pass (a launch a run beside the count, the scan and the run kernels)
+                    locate_ms = stat["ms"] - out["compact"][f"k{k}"]["search_kernels_ms"]
+                    res[f"k{k}"].update(locate_ms=round(locate_ms, 2), locate_share_of_call=round(locate_ms * 1e-3 / timed_s, 4),
+                                        locate_launches=stat["launches"] - out["compact"][f"k{k}"]["search_launches"])
         out[form] = res
         ctx.trim()
     if not args.trace_only:
-        if len(forms) == 2:
+        if samplings and "compact" in out:
+            out["sampled_over_compact"] = {
+                f"sampled{s}": {"device_bytes": round(out[f"sampled{s}"]["device_bytes"] / out["compact"]["device_bytes"], 4),
+                                "build": round(out[f"sampled{s}"]["build_ms"] / out["compact"]["build_ms"], 3),
+                                **{f"k{k}_call": round(out[f"sampled{s}"][f"k{k}"]["call_ms"] / out["compact"][f"k{k}"]["call_ms"], 3) for k in ks}}
+                for s in samplings}
+            assert all(out[f"sampled{s}"][f"k{k}"]["text_bytes"] == out["compact"][f"k{k}"]["text_bytes"] for k in ks for s in samplings)
+        elif len(forms) == 2:
             out["compact_over_full"] = {
                 "device_bytes": round(out["compact"]["device_bytes"] / out["full"]["device_bytes"], 4),
                 "build": round(out["compact"]["build_ms"] / out["full"]["build_ms"], 3),
@@ -105,7 +124,10 @@ def main():
     ap.add_argument("--trace-only", action="store_true",
                     help="build the index, map the reads twice at the first k and stop (for a rocprofv3 --kernel-trace --stats run)")
     ap.add_argument("--compact", action="store_true", help="the full and the compact index side by side, nothing else")
-    ap.add_argument("--form", default="both", choices=["both", "full", "compact"], help="with --compact: only this form")
+    ap.add_argument("--form", default="both", choices=["both", "full", "compact", "sampled"],
+                    help="with --compact: only this form (sampled: with --sa-sample, without the compact index beside it)")
+    ap.add_argument("--sa-sample", default="", help="with --compact: the compact index beside indexes with a suffix array sampled at "
+                    "these distances (8,32,128): DESIGN.md section 14, kept in profiles/sampled_sa_2p28.json")
     args = ap.parse_args()
     import torch
 

@@ -2,7 +2,8 @@
  * stralg_amd_readmapper -- a read mapper on libstralg_amd.so that takes the command line and the index file of
  * stralg's tools/readmappers/bwt_readmapper.
  *
- *   stralg_amd_readmapper -p genome.fa              writes genome.fa.bwttables
+ *   stralg_amd_readmapper -p genome.fa              writes genome.fa.bwttables (options may stand between -p and the
+ *                                                   file: -p --compact genome.fa)
  *   stralg_amd_readmapper -d K genome.fa reads.fq [more.fq ...]
  *                                                   prints the SAM lines of every match with at most K edits, file after
  *                                                   file; the index is loaded once and stays on the device
@@ -13,6 +14,11 @@
  *                                                   sampled counts in place of the O / RO tables, a fifth of the device
  *                                                   memory for DNA; the output is the same.  -p writes the same file
  *                                                   with or without it
+ *   --sa-sample S                                   with --compact and -d (and -i or a saved index): SA values at every
+ *                                                   S-th text position (a power of two in 2 .. 1024) in place of the
+ *                                                   suffix array, the others located by walks over the blocks: 5.4 bytes
+ *                                                   a symbol at S = 32 where --compact alone takes 9; the output is the
+ *                                                   same.  -p writes the same file with or without it
  *   (--preprocess, --edits and --in-memory are accepted for -p, -d and -i)
  *
  * Index file: u32 record count; per record, last FASTA record first, its name as u32 length + bytes + NUL, then the
@@ -138,6 +144,8 @@ static int usage(const char *self, int status)
     fprintf(stderr, "       %s -d K genome.fa reads.fq ...  SAM lines of all matches within K edits, on stdout\n", self);
     fprintf(stderr, "       %s -i -d K genome.fa reads.fq ...  the same, the index built in memory from genome.fa\n", self);
     fprintf(stderr, "       --compact                          with -d: BWT blocks in place of the O tables on the device\n");
+    fprintf(stderr, "       --sa-sample S                      with --compact and -d: SA values at every S-th position (a power of\n");
+    fprintf(stderr, "                                          two in 2 .. 1024) in place of the suffix array on the device\n");
     return status;
 }
 
@@ -145,8 +153,8 @@ int main(int argc, char **argv)
 {
     const char *to_index = NULL;
     char **rest = calloc((size_t)argc + 1, sizeof *rest);
-    int k = -1, n_rest = 0, in_memory = 0;
-    uint32_t flags = 0;
+    int k = -1, n_rest = 0, in_memory = 0, indexing = 0;
+    uint32_t flags = 0, sa_log2 = 0;
     if (!rest) fail("out of memory", NULL);
     for (int a = 1; a < argc; ++a) {
         const char *s = argv[a];
@@ -156,10 +164,17 @@ int main(int argc, char **argv)
             in_memory = 1;
         } else if (!strcmp(s, "--compact")) {
             flags |= SX_INDEX_COMPACT;
-        } else if (wants_p || wants_d) {
+        } else if (!strcmp(s, "--sa-sample")) {
             if (++a >= argc) return usage(argv[0], EXIT_FAILURE);
-            if (wants_p) to_index = argv[a];
-            else k = (int)strtol(argv[a], NULL, 10);
+            const long dist = strtol(argv[a], NULL, 10);
+            for (sa_log2 = 1; sa_log2 <= 10 && (1L << sa_log2) != dist; ++sa_log2) {}
+            if (sa_log2 > 10) fail("--sa-sample takes a power of two in 2 .. 1024, not", argv[a]);
+        } else if (wants_p) { /* the file follows, or, where options come first (-p --compact genome.fa), stands behind them */
+            indexing = 1;
+            if (a + 1 < argc && argv[a + 1][0] != '-') to_index = argv[++a];
+        } else if (wants_d) {
+            if (++a >= argc) return usage(argv[0], EXIT_FAILURE);
+            k = (int)strtol(argv[a], NULL, 10);
         } else if (s[0] == '-' && s[1] == 'd' && s[2]) { /* -dK */
             k = (int)strtol(s + 2, NULL, 10);
         } else if (s[0] == '-' && s[1]) {
@@ -168,7 +183,10 @@ int main(int argc, char **argv)
             rest[n_rest++] = argv[a];
         }
     }
-    if (to_index) return build_index(to_index);
+    if (sa_log2 && !(flags & SX_INDEX_COMPACT)) fail("--sa-sample needs --compact", NULL);
+    flags |= SX_INDEX_SA_SAMPLE_LOG2(sa_log2);
+    if (indexing && !to_index && n_rest) to_index = rest[0];
+    if (indexing) return to_index ? build_index(to_index) : usage(argv[0], EXIT_FAILURE);
     if (n_rest < 2 || k < 0) return usage(argv[0], EXIT_FAILURE);
     return map_reads(rest[0], rest + 1, n_rest - 1, k, in_memory, flags);
 }
