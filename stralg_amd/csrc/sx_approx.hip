@@ -23,6 +23,7 @@
 //    its pattern takes the next one from a counter, so it does not wait for the rest of its wave.
 #include "sx_common.hpp"
 #include "sx_device.hpp"
+#include "sx_index.hpp"
 #include "sx_occ.hpp"
 #include "sx_scan.hpp"
 
@@ -388,6 +389,16 @@ static int approx_search_dev(sx_ctx *ctx, const uint32_t *d_c_table, Occ o, Occ 
     }
     if (total) SX_TRY(approx_emit(ctx, A, d_hit_offsets, d_hits, total));
     return sx_sync(ctx);
+}
+
+// the search over a record of an index in whichever form its tables have (the mapper's loop, sx_sam.hip)
+int sx_approx_search_record(sx_ctx *ctx, const sx_index_rec &R, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, int max_edits,
+                            uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t hit_capacity, uint64_t *total_hits_out)
+{
+    return R.compact() ? sx_bwt_approx_search_compact_dev(ctx, R.d_c, R.d_occ, R.d_rocc, R.N, R.sigma, d_patterns, d_offsets, count, max_edits,
+                                                          d_hit_offsets, d_hits, hit_capacity, total_hits_out)
+                       : sx_bwt_approx_search_dev(ctx, R.d_c, R.d_o, R.d_ro, R.N, R.sigma, d_patterns, d_offsets, count, max_edits, d_hit_offsets,
+                                                  d_hits, hit_capacity, total_hits_out);
 }
 
 extern "C" {

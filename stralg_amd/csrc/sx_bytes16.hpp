@@ -2,7 +2,7 @@
 // four at a time in their words: equality with a constant and "at least a constant" per byte without carries between the
 // bytes, the flag bits of the four words gathered by dot products (gather16; sx_classify.hip does the same for the type
 // bits).  170 instructions for the five FASTA classes where a compare and a shift for each byte and class were 340 (round 5).
-// The FASTA packer (sx_fasta.hip) and the FASTQ indexer (sx_index.hip) name their classes with these.
+// The FASTA packer (sx_fasta.hip) and the FASTQ indexer (sx_fastq.hip) name their classes with these.
 #pragma once
 #include "sx_device.hpp"
 

@@ -1,0 +1,246 @@
+// sx_fastq.hip -- the FASTQ ingest on the device.
+//
+// sx_fastq_index_dev restates the host's sx_fastq_index (stralg_host.c; bioinf/fastq.c:17-35) as data-parallel passes
+// over 4096-byte tiles of the image.  A byte's line is the number of newlines in front of it; the line at rank j belongs
+// to record j / 4 and has role j % 4 (name, sequence, '+' line, quality):
+//   1. every tile counts its newlines (16 bytes a lane, classified in their words) and flags NUL bytes,
+//   2. a scan of the tile counts gives every tile the rank of its first line,
+//   3. the line-end table: the position of every line's newline (the image's end for a last line without one),
+//   4. one lane a record checks its four lines and writes the three lengths (or an error bit),
+//   5. three exclusive scans turn the lengths into the offset arrays,
+//   6. a pass over the image in order sends every byte of a first, second or fourth line to its place: a workgroup
+//      holds its tile's line starts in LDS, a lane finds the line of its four bytes by a search in them.
+// Where a byte goes is a function of the scans alone (no atomics place anything): the same image gives the same bytes.
+#include "sx_common.hpp"
+#include "sx_device.hpp"
+#include "sx_bytes16.hpp"
+#include "sx_hostio.hpp"
+#include "sx_scan.hpp"
+
+namespace sx {
+
+// ---- FASTQ image -> the six arrays of sx_fastq ---------------------------------------------------------------------
+constexpr int kFqPer = kBytes16, kFqTile = kBlock * kFqPer;
+constexpr uint32_t kFqLineMax = 2047; // fgets(buffer, 2048): a line's content must be shorter than this
+enum { FQ_ERR_NUL = 1, FQ_ERR_LINE = 2 };
+
+// which of the lane's 16 bytes (those in front of `len`) are newlines / NULs: bit k for byte k (sx_bytes16.hpp)
+__device__ __forceinline__ void fq_masks16(const uint8_t *__restrict__ img, uint64_t i0, uint64_t len, uint32_t &nl, uint32_t &zero)
+{
+    nl = 0, zero = 0;
+    if (i0 >= len) return;
+    uint4 v = {0, 0, 0, 0};
+    if (fetch16(img, i0, len, v)) {
+        nl = eq16(v, 0x0A0A0A0Au);
+        zero = eq16(v, 0u);
+    } else { // (nothing beyond `len` counts as a NUL here)
+        for (int k = 0; k < kFqPer && i0 + k < len; ++k) {
+            const uint32_t c = img[i0 + k];
+            nl |= (c == '\n' ? 1u : 0u) << k;
+            zero |= (c == 0u ? 1u : 0u) << k;
+        }
+    }
+}
+
+// pass 1: newlines of every tile; scal[0] |= FQ_ERR_NUL for a NUL byte; scal[1] <- 1 when the last byte is no newline
+__global__ __launch_bounds__(kBlock) void fq_count_kernel(const uint8_t *__restrict__ img, uint64_t len, uint32_t *__restrict__ tile_nl,
+                                                          uint32_t *__restrict__ scal)
+{
+    __shared__ uint32_t lds[kWavesPerBlock];
+    const uint64_t i0 = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) * kFqPer;
+    uint32_t nl, zero;
+    fq_masks16(img, i0, len, nl, zero);
+    if (zero) atomicOr(&scal[0], (uint32_t)FQ_ERR_NUL);
+    if (i0 < len && len - i0 <= (uint64_t)kFqPer) scal[1] = ((nl >> (uint32_t)(len - 1 - i0)) & 1u) ? 0u : 1u;
+    const uint32_t tot = block_reduce<OpAdd>((uint32_t)__popc(nl), lds);
+    if (threadIdx.x == 0) tile_nl[blockIdx.x] = tot;
+}
+
+// pass 3: line_end[j] <- position of the newline that ends line j; the last line of an image without a final newline
+// ends at len (n_lines > the number of newlines then)
+__global__ __launch_bounds__(kBlock) void fq_line_end_kernel(const uint8_t *__restrict__ img, uint64_t len, const uint32_t *__restrict__ tile_base,
+                                                             uint32_t *__restrict__ line_end, uint32_t n_newlines, uint32_t n_lines)
+{
+    __shared__ uint32_t lds[kWavesPerBlock];
+    const uint64_t i0 = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) * kFqPer;
+    uint32_t nl, zero;
+    fq_masks16(img, i0, len, nl, zero);
+    uint32_t tot;
+    uint32_t rank = tile_base[blockIdx.x] + block_exclusive_scan<OpAdd>((uint32_t)__popc(nl), lds, tot);
+    while (nl) {
+        const uint32_t k = (uint32_t)__ffs(nl) - 1u;
+        if (rank < n_newlines) line_end[rank] = (uint32_t)(i0 + k);
+        ++rank;
+        nl &= nl - 1u;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0 && n_lines > n_newlines) line_end[n_newlines] = (uint32_t)len;
+}
+
+// pass 4: record r's lines end at e[0 .. 4); lens[k][r] <- the bytes of its name, sequence and quality; entry `count`
+// of each is 0 so that the scans' entry `count` is the total
+__global__ __launch_bounds__(kBlock) void fq_record_kernel(const uint32_t *__restrict__ line_end, uint32_t count, uint32_t *__restrict__ name_len,
+                                                           uint32_t *__restrict__ seq_len, uint32_t *__restrict__ qual_len, uint32_t *__restrict__ scal)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (r > count) return;
+    uint32_t nlen = 0, slen = 0, qlen = 0;
+    if (r < count) {
+        const uint32_t start = r ? line_end[4 * r - 1] + 1u : 0u;
+        const uint32_t e0 = line_end[4 * r], e1 = line_end[4 * r + 1], e2 = line_end[4 * r + 2], e3 = line_end[4 * r + 3];
+        const uint32_t l0 = e0 - start, l1 = e1 - e0 - 1u, l2 = e2 - e1 - 1u, l3 = e3 - e2 - 1u;
+        // a line of 2047 bytes or more; a first line of fewer than 2 bytes; an empty second or fourth line
+        const bool bad = l0 >= kFqLineMax || l1 >= kFqLineMax || l2 >= kFqLineMax || l3 >= kFqLineMax || l0 < 2u || l1 == 0u || l3 == 0u;
+        if (bad) atomicOr(&scal[0], (uint32_t)FQ_ERR_LINE);
+        else nlen = l0 - 1u, slen = l1, qlen = l3;
+    }
+    name_len[r] = nlen;
+    seq_len[r] = slen;
+    qual_len[r] = qlen;
+}
+
+// pass 6: every byte to its place.  ls[m]: the first byte of the m-th line that touches this tile (ls[0]: the line
+// the tile's first byte lies in, which may start in an earlier tile).
+__global__ __launch_bounds__(kBlock) void fq_scatter_kernel(const uint8_t *__restrict__ img, uint64_t len, const uint32_t *__restrict__ tile_base,
+                                                            const uint32_t *__restrict__ tile_nl, const uint32_t *__restrict__ line_end,
+                                                            const uint32_t *__restrict__ name_off, const uint32_t *__restrict__ seq_off,
+                                                            const uint32_t *__restrict__ qual_off, uint8_t *__restrict__ names,
+                                                            uint8_t *__restrict__ seqs, uint8_t *__restrict__ quals, uint32_t n_lines)
+{
+    __shared__ uint32_t ls[kFqTile + 1];
+    const uint64_t tile0 = (uint64_t)blockIdx.x * kFqTile;
+    const uint32_t rank0 = tile_base[blockIdx.x], cnt = tile_nl[blockIdx.x]; // cnt <= kFqTile
+    for (uint32_t m = threadIdx.x; m <= cnt; m += kBlock) {
+        const uint32_t j = rank0 + m; // ls[m] = the start of line j = the end of line j - 1, plus one
+        ls[m] = j ? line_end[j - 1] + 1u : 0u;
+    }
+    __syncthreads();
+    const bool words = ((uintptr_t)img & 3u) == 0;
+    for (uint32_t it = 0; it < (uint32_t)kFqTile / (4u * kBlock); ++it) {
+        const uint64_t i = tile0 + 4ull * ((uint64_t)it * kBlock + threadIdx.x);
+        if (i >= len) break;
+        uint32_t w = 0;
+        if (words && i + 4 <= len) {
+            w = *reinterpret_cast<const uint32_t *>(img + i);
+        } else {
+            for (uint32_t k = 0; k < 4 && i + k < len; ++k) w |= (uint32_t)img[i + k] << (8u * k);
+        }
+        uint32_t m = 0;
+        { // the last m with ls[m] <= i (ls[0] <= tile0)
+            uint32_t hi = cnt + 1u;
+            while (hi - m > 1u) {
+                const uint32_t mid = (m + hi) / 2u;
+                if ((uint64_t)ls[mid] <= i) m = mid;
+                else hi = mid;
+            }
+        }
+        for (uint32_t k = 0; k < 4; ++k) {
+            const uint64_t pos = i + k;
+            if (pos >= len) break;
+            if (m < cnt && (uint64_t)ls[m + 1] <= pos) ++m;
+            const uint32_t c = (w >> (8u * k)) & 0xFFu;
+            const uint32_t j = rank0 + m;
+            if (c == '\n' || j >= n_lines) continue;
+            const uint32_t rec = j >> 2, role = j & 3u, off = (uint32_t)(pos - ls[m]);
+            if (role == 0) {
+                if (off) names[name_off[rec] + off - 1u] = (uint8_t)c; // (the record's first byte is dropped whatever it is)
+            } else if (role == 1) {
+                seqs[seq_off[rec] + off] = (uint8_t)c;
+            } else if (role == 3) {
+                quals[qual_off[rec] + off] = (uint8_t)c;
+            }
+        }
+    }
+}
+
+} // namespace sx
+
+using namespace sx;
+
+extern "C" {
+
+void sx_fastq_dev_free(sx_fastq_dev *fq)
+{
+    if (!fq) return;
+    (void)hipFree(fq->d_names), (void)hipFree(fq->d_seqs), (void)hipFree(fq->d_quals);
+    (void)hipFree(fq->d_name_off), (void)hipFree(fq->d_seq_off), (void)hipFree(fq->d_qual_off);
+    memset(fq, 0, sizeof *fq);
+}
+
+static int fastq_index_dev(sx_ctx *ctx, const uint8_t *d_image, uint64_t len, sx_fastq_dev *out)
+{
+    sx_dev_scope S;
+    const uint32_t ntiles = sx_div_up(len, kFqTile);
+    // scratch: a few scalars and two u32 a tile (slab M); the line ends and the lengths (slab N, sized once the lines are counted)
+    SX_TRY(sx_slab_ensure(ctx, SX_SLAB_M, 256 + 2 * (size_t)(ntiles + 1) * sizeof(uint32_t)));
+    uint32_t *scal = (uint32_t *)ctx->slab[SX_SLAB_M].p; // [0] error bits, [1] no final newline, [2] newlines, [4..6] totals
+    uint32_t *tile_nl = scal + 64, *tile_base = tile_nl + ntiles + 1;
+    SX_CHECK(hipMemsetAsync(scal, 0, 256, ctx->stream));
+    uint32_t h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (len) {
+        sx_launch(ctx, SX_KC_FASTA, len, fq_count_kernel, dim3(ntiles), dim3(kBlock), d_image, len, tile_nl, scal);
+        SX_TRY((device_scan<OpAdd>(ctx, ntiles, InU32{tile_nl}, OutExclusive{tile_base}, scal + 2, SX_KC_FASTA, 0)));
+        SX_TRY(sx_readback(ctx, scal, 3, h));
+    }
+    const uint64_t n_newlines = h[2], n_lines = n_newlines + h[1];
+    // a NUL inside a record; a line count that is no multiple of four (a record cut off, a blank line somewhere)
+    if (h[0] || (n_lines & 3u)) return sx_fail_msg(ctx, SX_E_MALFORMED, "malformed FASTQ image (see sx_fastq_index)");
+    const uint32_t count = (uint32_t)(n_lines / 4);
+    SX_TRY(S.take(ctx, &out->d_name_off, (size_t)count + 1));
+    SX_TRY(S.take(ctx, &out->d_seq_off, (size_t)count + 1));
+    SX_TRY(S.take(ctx, &out->d_qual_off, (size_t)count + 1));
+    if (count == 0) {
+        SX_CHECK(hipMemsetAsync(out->d_name_off, 0, 4, ctx->stream));
+        SX_CHECK(hipMemsetAsync(out->d_seq_off, 0, 4, ctx->stream));
+        SX_CHECK(hipMemsetAsync(out->d_qual_off, 0, 4, ctx->stream));
+        SX_TRY(S.take(ctx, &out->d_names, 16));
+        SX_TRY(S.take(ctx, &out->d_seqs, 16));
+        SX_TRY(S.take(ctx, &out->d_quals, 16));
+        SX_TRY(sx_sync(ctx));
+        S.keep();
+        return 0;
+    }
+    const size_t lens_b = (((size_t)count + 1) * 4 + 255) & ~(size_t)255;
+    int rc = sx_slab_ensure(ctx, SX_SLAB_N, (((size_t)n_lines * 4 + 255) & ~(size_t)255) + 3 * lens_b);
+    uint32_t *line_end = nullptr, *lens[3] = {nullptr, nullptr, nullptr};
+    if (rc == 0) {
+        line_end = (uint32_t *)ctx->slab[SX_SLAB_N].p;
+        for (int k = 0; k < 3; ++k) lens[k] = (uint32_t *)((char *)line_end + (((size_t)n_lines * 4 + 255) & ~(size_t)255) + (size_t)k * lens_b);
+        sx_launch(ctx, SX_KC_FASTA, len + n_lines * 4, fq_line_end_kernel, dim3(ntiles), dim3(kBlock), d_image, len,
+                  (const uint32_t *)tile_base, line_end, (uint32_t)n_newlines, (uint32_t)n_lines);
+        sx_launch(ctx, SX_KC_FASTA, (uint64_t)count * 28, fq_record_kernel, dim3(sx_div_up((uint64_t)count + 1, kBlock)), dim3(kBlock),
+                  (const uint32_t *)line_end, count, lens[0], lens[1], lens[2], scal);
+        uint32_t *offs[3] = {out->d_name_off, out->d_seq_off, out->d_qual_off};
+        for (int k = 0; k < 3 && rc == 0; ++k)
+            rc = device_scan<OpAdd>(ctx, (uint64_t)count + 1, InU32{lens[k]}, OutExclusive{offs[k]}, scal + 4 + k, SX_KC_FASTA, 0);
+        if (rc == 0) rc = sx_readback(ctx, scal, 7, h);
+        if (rc == 0 && h[0]) rc = sx_fail_msg(ctx, SX_E_MALFORMED, "malformed FASTQ image (see sx_fastq_index)");
+    }
+    if (rc == 0) rc = S.take(ctx, &out->d_names, (size_t)h[4] + 16);
+    if (rc == 0) rc = S.take(ctx, &out->d_seqs, (size_t)h[5] + 16);
+    if (rc == 0) rc = S.take(ctx, &out->d_quals, (size_t)h[6] + 16);
+    if (rc == 0) {
+        // (every line has passed its checks: each byte's place lies inside the three totals)
+        sx_launch(ctx, SX_KC_FASTA, 2 * len, fq_scatter_kernel, dim3(ntiles), dim3(kBlock), d_image, len, (const uint32_t *)tile_base,
+                  (const uint32_t *)tile_nl, (const uint32_t *)line_end, (const uint32_t *)out->d_name_off, (const uint32_t *)out->d_seq_off,
+                  (const uint32_t *)out->d_qual_off, out->d_names, out->d_seqs, out->d_quals, (uint32_t)n_lines);
+        rc = sx_sync(ctx);
+    }
+    if (rc != 0) return rc; // (S releases what was taken)
+    out->count = count;
+    out->name_bytes = h[4], out->seq_bytes = h[5], out->qual_bytes = h[6];
+    S.keep();
+    return 0;
+}
+
+int sx_fastq_index_dev(sx_ctx *ctx, const uint8_t *d_image, uint64_t len, sx_fastq_dev *out)
+{
+    if (!ctx || !out || (len && !d_image)) return SX_E_ARG;
+    memset(out, 0, sizeof *out);
+    if (len > 0xFFFFFFFEull) return sx_fail_msg(ctx, SX_E_ARG, "FASTQ image must be shorter than 2^32 - 1 bytes");
+    SX_CHECK(hipSetDevice(ctx->device));
+    const int rc = fastq_index_dev(ctx, d_image, len, out);
+    if (rc != 0) memset(out, 0, sizeof *out); // (what was allocated has been released)
+    return sx_nomem_of(rc);
+}
+
+} // extern "C"

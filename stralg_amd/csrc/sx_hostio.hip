@@ -1,4 +1,4 @@
-// sx_hostio.hip -- the pinned staging buffers of a context and the chunked copies through them (sx_hostio.hpp).
+// sx_hostio.hip -- the pinned staging buffers of a context, the chunked copies through them (sx_hostio.hpp), sx_download.
 #include "sx_hostio.hpp"
 
 int sx_stage_ensure(sx_ctx *ctx)
@@ -33,6 +33,14 @@ int sx_stream_to_sink(sx_ctx *ctx, int section, const void *d_src, size_t bytes,
         cur ^= 1;
     }
     return 0;
+}
+
+int sx_download(sx_ctx *ctx, void *h_dst, const void *d_src, size_t bytes)
+{
+    if (!ctx || (bytes && (!h_dst || !d_src))) return SX_E_ARG;
+    SX_CHECK(hipSetDevice(ctx->device));
+    if (bytes) SX_CHECK(hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    return sx_sync(ctx);
 }
 
 int sx_upload_staged(sx_ctx *ctx, void *d_dst, const void *h_src, size_t bytes)

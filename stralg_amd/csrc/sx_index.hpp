@@ -1,6 +1,7 @@
 // sx_index.hpp -- the device-resident index (sx_index.hip) and what the mapper's loop (sx_sam.hip) reads of it.
 #pragma once
 #include "sx_common.hpp"
+#include "sx_locate.hpp"
 
 #include <string>
 #include <vector>
@@ -18,7 +19,11 @@ struct sx_index_rec {
     uint8_t *d_sa_marks = nullptr;
     uint32_t *d_sa_values = nullptr;
     uint32_t sa_log2 = 0;
+    // the record's form: full (d_sa, d_o, d_ro), compact (blocks for d_o / d_ro) or compact and sampled
+    bool compact() const { return d_occ != nullptr; }
+    bool sampled() const { return sa_log2 != 0; }
     bool has_ro() const { return d_ro || d_rocc; }
+    sx::LocRec loc() const { return sx::loc_rec_of(d_c, d_occ, N, sigma, d_sa_marks, d_sa_values, sa_log2); } // what a walk reads of it
 };
 
 struct sx_index {
@@ -61,5 +66,6 @@ static inline bool sx_map_record_check(const sx_map_record &R, uint32_t min_sigm
 
 // sx_sam.hip: the mapper's loop over reads and an index that both lie on ctx's device
 int sx_map_reads_core(sx_ctx *ctx, const sx_index *idx, const sx_reads_dev &reads, int edits, sx_sink_fn sink, void *user);
-// sx_index.hip: sx_index_from_tables without the checks of its arguments (sx_map_reads_stream has made them)
-int sx_index_from_records_impl(sx_ctx *ctx, const sx_map_record *records, uint32_t n_records, sx_index **out);
+// sx_approx.hip: sx_bwt_approx_search_dev over the tables of a record, full or compact
+int sx_approx_search_record(sx_ctx *ctx, const sx_index_rec &R, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, int max_edits,
+                            uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t hit_capacity, uint64_t *total_hits_out);

@@ -186,24 +186,17 @@ int sx_sa_sample_dev_impl(sx_ctx *ctx, const uint32_t *d_sa, uint64_t N, uint32_
 
 int sx_sa_sample_host_impl(sx_ctx *ctx, const uint32_t *h_sa, uint64_t N, uint32_t q, void *d_marks, uint32_t *d_values)
 {
-    // a window: as many whole blocks' rows as a staging buffer holds, one block's at least
-    const uint64_t nblocks = occ_blocks(N);
-    uint64_t per = sx_stage_bytes / (4 * kOccRows) ? sx_stage_bytes / (4 * kOccRows) : 1;
-    if (per > nblocks) per = nblocks;
-    sx_dev_scope T;
-    uint32_t *d_win, *d_scal;
-    SX_TRY(T.take(ctx, &d_win, (size_t)(per * kOccRows)));
+    uint32_t *d_scal;
     SX_TRY(locate_scratch(ctx, &d_scal));
     uint64_t have = 0;
-    for (uint64_t b0 = 0; b0 < nblocks; b0 += per) {
-        const uint32_t nb = (uint32_t)(nblocks - b0 < per ? nblocks - b0 : per);
-        const uint64_t row_lo = b0 * kOccRows, row_hi = (b0 + nb) * kOccRows < N ? (b0 + nb) * kOccRows : N;
+    // a window: whole blocks' rows.  More samples than the array may have end the loop at once: the check fails then, and
+    // its failure is what the body returns (no more windows come up); otherwise the check is made behind the last window
+    SX_TRY(sx_upload_windows(ctx, h_sa, N, 4, kOccRows, 0, [&](const uint32_t *d_win, uint64_t b0, uint32_t nb, uint64_t) {
         uint32_t total = 0;
-        if (row_hi > row_lo) SX_TRY(sx_upload_staged(ctx, d_win, h_sa + row_lo, (size_t)(row_hi - row_lo) * 4));
         SX_TRY(sample_window(ctx, d_win, N, q, b0, nb, (uint32_t)have, (uint4 *)d_marks, d_values, d_scal, &total)); // (ends with a sync)
         have += total;
-        if (have > sa_sample_count(N, q)) break;
-    }
+        return have > sa_sample_count(N, q) ? sample_total_check(ctx, have, N, q) : 0;
+    }));
     return sample_total_check(ctx, have, N, q);
 }
 
@@ -219,22 +212,6 @@ int sx_sa_locate_rows_impl(sx_ctx *ctx, const LocRec &rec, uint64_t row_lo, uint
               row_lo, count, d_out, d_err);
     SX_TRY(sx_readback(ctx, d_err, 1, &e));
     if (e) return sx_fail_msg(ctx, SX_E_INTERNAL, "sampled suffix array: a walk met its bound (the samples do not belong to the blocks)");
-    return 0;
-}
-
-int sx_sa_stream_rows(sx_ctx *ctx, int section, const LocRec &rec, uint64_t row_lo, uint64_t row_hi, sx_sink_fn sink, void *user)
-{
-    if (row_hi <= row_lo) return 0;
-    uint64_t per = sx_stage_bytes / 4 ? sx_stage_bytes / 4 : 1;
-    if (per > row_hi - row_lo) per = row_hi - row_lo;
-    sx_dev_scope T;
-    uint32_t *d_win;
-    SX_TRY(T.take(ctx, &d_win, (size_t)per));
-    for (uint64_t lo = row_lo; lo < row_hi; lo += per) {
-        const uint64_t hi = row_hi - lo < per ? row_hi : lo + per;
-        SX_TRY(sx_sa_locate_rows_impl(ctx, rec, lo, hi, d_win));
-        SX_TRY(sx_stream_to_sink(ctx, section, d_win, (size_t)(hi - lo) * 4, sink, user)); // (synchronous: the window is free again)
-    }
     return 0;
 }
 

@@ -58,8 +58,6 @@ int sx_sa_sample_dev_impl(sx_ctx *ctx, const uint32_t *d_sa, uint64_t N, uint32_
 int sx_sa_sample_host_impl(sx_ctx *ctx, const uint32_t *h_sa, uint64_t N, uint32_t q, void *d_marks, uint32_t *d_values);
 // SA[row_lo .. row_hi) -> d_out[0 .. row_hi - row_lo); synchronous; SX_E_INTERNAL when a walk met its bound
 int sx_sa_locate_rows_impl(sx_ctx *ctx, const sx::LocRec &rec, uint64_t row_lo, uint64_t row_hi, uint32_t *d_out);
-// the same rows to a sink, located window by window through the staging buffers
-int sx_sa_stream_rows(sx_ctx *ctx, int section, const sx::LocRec &rec, uint64_t row_lo, uint64_t row_hi, sx_sink_fn sink, void *user);
 // The hits form, for the mapper (hits: sx_approx_hit as two 16-byte words, query = read x n_records + record rank):
 // d_pos_off[h] <- R - L of hit h (0 for a hit that does not fit its record), scanned in place: d_pos_off[n_hits] <- the sum
 int sx_sa_hits_offsets(sx_ctx *ctx, const sx::LocRec *d_recs, uint32_t n_records, uint64_t n_queries, const uint4 *d_hits, uint64_t n_hits,

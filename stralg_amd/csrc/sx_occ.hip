@@ -145,22 +145,13 @@ int sx_occ_build_impl(sx_ctx *ctx, const uint8_t *d_bwt, uint64_t N, uint32_t si
 
 int sx_occ_from_rows_impl(sx_ctx *ctx, const uint32_t *h_o_table, uint64_t N, uint32_t sigma, uint8_t *d_blocks)
 {
-    // a window: as many whole blocks' rows (and the row behind them) as a staging buffer holds, one block's at least
-    const uint64_t nblocks = occ_blocks(N), row_bytes = 4ull * sigma;
-    uint64_t per = sx_stage_bytes / row_bytes > kOccRows ? (sx_stage_bytes / row_bytes - 1) / kOccRows : 1;
-    if (per > nblocks) per = nblocks;
-    sx_dev_scope T;
-    uint32_t *d_win;
-    SX_TRY(T.take(ctx, &d_win, (size_t)((per * kOccRows + 1) * sigma)));
+    const uint64_t row_bytes = 4ull * sigma; // a window: whole blocks' rows and the row behind them
     const uint32_t stride = occ_stride(sigma);
-    for (uint64_t b0 = 0; b0 < nblocks; b0 += per) {
-        const uint32_t nb = (uint32_t)(nblocks - b0 < per ? nblocks - b0 : per);
-        const uint64_t row_lo = b0 * kOccRows, row_hi = (b0 + nb) * kOccRows < N ? (b0 + nb) * kOccRows : N; // inclusive
-        SX_TRY(sx_upload_staged(ctx, d_win, h_o_table + row_lo * sigma, (size_t)((row_hi - row_lo + 1) * row_bytes)));
-        sx_launch(ctx, SX_KC_OTABLE, (row_hi - row_lo + 1) * row_bytes, occ_from_rows_kernel, dim3(sx_div_up(nb, kWavesPerBlock)), dim3(kBlock),
-                  (const uint32_t *)d_win, N, sigma, b0, nb, d_blocks, stride);
-    }
-    return sx_sync(ctx); // (the window goes with this scope)
+    return sx_upload_windows(ctx, h_o_table, N, row_bytes, kOccRows, 1, [&](const uint32_t *d_win, uint64_t b0, uint32_t nb, uint64_t rows) {
+        sx_launch(ctx, SX_KC_OTABLE, rows * row_bytes, occ_from_rows_kernel, dim3(sx_div_up(nb, kWavesPerBlock)), dim3(kBlock), d_win, N, sigma, b0, nb,
+                  d_blocks, stride);
+        return 0;
+    }); // (ends with a sync, before the window goes)
 }
 
 int sx_occ_expand_impl(sx_ctx *ctx, const uint8_t *d_blocks, uint64_t N, uint32_t sigma, uint64_t row_lo, uint64_t row_hi, uint32_t *d_rows)
@@ -171,24 +162,6 @@ int sx_occ_expand_impl(sx_ctx *ctx, const uint8_t *d_blocks, uint64_t N, uint32_
     const uint64_t grid = (count + kBlock - 1) / kBlock;
     sx_launch(ctx, SX_KC_OTABLE, count * 4, occ_expand_kernel, dim3((uint32_t)(grid < (1u << 20) ? grid : (1u << 20))), dim3(kBlock),
               OccCompact{d_blocks, occ_stride(sigma)}, sigma, row_lo, count, d_rows);
-    return 0;
-}
-
-int sx_occ_stream_rows(sx_ctx *ctx, int section, const uint8_t *d_blocks, uint64_t N, uint32_t sigma, uint64_t row_lo, uint64_t row_hi,
-                       sx_sink_fn sink, void *user)
-{
-    if (row_hi <= row_lo) return 0;
-    const uint64_t rows = row_hi, row_bytes = 4ull * sigma;
-    uint64_t per = sx_stage_bytes / row_bytes ? sx_stage_bytes / row_bytes : 1;
-    if (per > row_hi - row_lo) per = row_hi - row_lo;
-    sx_dev_scope T;
-    uint32_t *d_win;
-    SX_TRY(T.take(ctx, &d_win, (size_t)(per * sigma)));
-    for (uint64_t lo = row_lo; lo < rows; lo += per) {
-        const uint64_t hi = rows - lo < per ? rows : lo + per;
-        SX_TRY(sx_occ_expand_impl(ctx, d_blocks, N, sigma, lo, hi, d_win));
-        SX_TRY(sx_stream_to_sink(ctx, section, d_win, (size_t)((hi - lo) * row_bytes), sink, user)); // (synchronous: the window is free again)
-    }
     return 0;
 }
 

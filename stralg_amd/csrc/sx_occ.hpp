@@ -59,7 +59,3 @@ struct OccCompact {
 int sx_occ_build_impl(sx_ctx *ctx, const uint8_t *d_bwt, uint64_t N, uint32_t sigma, uint8_t *d_blocks);
 int sx_occ_from_rows_impl(sx_ctx *ctx, const uint32_t *h_o_table, uint64_t N, uint32_t sigma, uint8_t *d_blocks);
 int sx_occ_expand_impl(sx_ctx *ctx, const uint8_t *d_blocks, uint64_t N, uint32_t sigma, uint64_t row_lo, uint64_t row_hi, uint32_t *d_rows);
-// rows [row_lo, row_hi) of the full table to a sink (all of them: the O table as the index file holds it): expanded window
-// by window through the staging buffers
-int sx_occ_stream_rows(sx_ctx *ctx, int section, const uint8_t *d_blocks, uint64_t N, uint32_t sigma, uint64_t row_lo, uint64_t row_hi,
-                       sx_sink_fn sink, void *user);

@@ -534,10 +534,8 @@ static int search_batch(sx_ctx *ctx, const sx_index *idx, const sx_reads_dev &re
                       (const uint8_t *)(idx->d_tabs + (size_t)r * 256), M.d_pat, p_lo, p_hi);
         uint64_t tot = 0;
         // (whichever form the record has: the hits and their order are the same)
-        const int rc = R.d_occ ? sx_bwt_approx_search_compact_dev(ctx, R.d_c, R.d_occ, R.d_rocc, R.N, R.sigma, M.d_pat, reads.d_seq_off + q0, batch,
-                                                                  edits, M.d_ho + r * M.stride, room.d_raw + used, room.cap - used, &tot)
-                               : sx_bwt_approx_search_dev(ctx, R.d_c, R.d_o, R.d_ro, R.N, R.sigma, M.d_pat, reads.d_seq_off + q0, batch, edits,
-                                                          M.d_ho + r * M.stride, room.d_raw + used, room.cap - used, &tot);
+        const int rc = sx_approx_search_record(ctx, R, M.d_pat, reads.d_seq_off + q0, batch, edits, M.d_ho + r * M.stride, room.d_raw + used,
+                                               room.cap - used, &tot);
         if (rc == SX_E_CAPACITY) *need_out = used + tot;
         if (rc != 0) return rc;
         seg[r] = used;
@@ -697,7 +695,7 @@ int sx_map_reads_stream(sx_ctx *ctx, const sx_map_record *records, uint32_t n_re
     reads.h_seq_off = fq.seq_off;
     reads.seq_bytes = fq.seq_off[n_reads];
     sx_index *idx = nullptr;
-    SX_TRY(sx_index_from_records_impl(ctx, records, n_records, &idx));
+    SX_TRY(sx_index_from_tables(ctx, records, n_records, &idx));
     const int rc = sx_map_reads_core(ctx, idx, reads, edits, sink, user);
     sx_index_destroy(idx);
     return rc;

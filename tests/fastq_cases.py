@@ -1,4 +1,4 @@
-"""FASTQ images for sx_fastq_index_dev (sx_index.hip), shared by the CPU-harness suite (tests/test_index_cpu.py) and the
+"""FASTQ images for sx_fastq_index_dev (sx_fastq.hip), shared by the CPU-harness suite (tests/test_index_cpu.py) and the
 GPU suite (tests/test_gpu_fastq.py), and the three parties every image is put to: fastq_reference below (Python, written
 from the contract in include/stralg_amd.h), the host's sx_fastq_index and the device's sx_fastq_index_dev.  `mem` is one
 of the two objects of tests/device_memory.py.  TEST INFRASTRUCTURE ONLY."""

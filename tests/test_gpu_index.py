@@ -1,4 +1,4 @@
-"""The device-resident index on the GPU (sx_index.hip: stralg_amd.Index, sx_fastq_index_dev, the tool's -i and several
+"""The device-resident index on the GPU (sx_index.hip: stralg_amd.Index, sx_fastq.hip: sx_fastq_index_dev, the tool's -i and several
 FASTQ files) against the reference mapper's stdout (tests/golden/golden_sam.npz), the reference's tables
 (tests/golden/golden_genomes.npz), and, at size, against what numpy says about reads cut at known places."""
 import hashlib
@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import check_against_sha, genome_cases
+import index_form_cases as forms
 from sam_cases import ROOT, check_case, sam_cases
 import stralg_amd
 from stralg_amd import Index, api
@@ -51,6 +52,12 @@ def index_of(gpu_ctx):
 def test_from_fasta_equals_the_reference(gpu_ctx, cases, index_of, name):
     c = cases[name]
     check_case(c, index_of(c["fasta"]).map_reads(c["fastq"], c["k"]))
+
+
+@pytest.mark.parametrize("form", list(forms.FORMS))
+@pytest.mark.parametrize("name", forms.CASES)
+def test_built_and_loaded_agree_in_every_form(gpu_ctx, cases, name, form):
+    forms.check_built_and_loaded_agree(gpu_ctx, Index, cases[name], form)
 
 
 @pytest.mark.parametrize("name", NAMES)

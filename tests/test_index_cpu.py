@@ -1,4 +1,4 @@
-"""The device-resident index (sx_index.hip: stralg_amd.Index) and the FASTQ ingest on the device (sx_fastq_index_dev)
+"""The device-resident index (sx_index.hip: stralg_amd.Index) and the FASTQ ingest on the device (sx_fastq.hip: sx_fastq_index_dev)
 through the CPU execution harness: the reference read mapper's stdout in tests/golden/golden_sam.npz, the reference
 writer's byte streams in tests/golden/golden_fasta.npz, and, on every FASTQ image (tests/fastq_cases.py), the contract
 restated in Python and the host's sx_fastq_index beside the device function."""
@@ -10,6 +10,7 @@ import pytest
 import approx_model
 from approx_cases import remapped
 import fastq_cases as fq
+import index_form_cases as forms
 from conftest import serial_cases
 from device_memory import HarnessMemory
 from sam_cases import check_case, sam_cases, subset_fastq
@@ -80,6 +81,12 @@ def test_device_tables_equal_the_oracle(emu_ctx, cases, index_of):
             assert (got["o"] == t.o_table).all() and (got["ro"] == t.ro_table).all()
             total += N * (5 + 8 * sigma)
         assert total <= idx.device_bytes <= total + 4096 * (5 * len(want) + 5)  # (allocations are rounded up to 256 + 256)
+
+
+@pytest.mark.parametrize("form", list(forms.FORMS))
+@pytest.mark.parametrize("name", forms.CASES)
+def test_built_and_loaded_agree_in_every_form(emu_ctx, cases, name, form):
+    forms.check_built_and_loaded_agree(emu_ctx, Index, cases[name], form)
 
 
 def test_one_index_several_read_sets(emu_ctx, cases, index_of):
