@@ -433,7 +433,7 @@ enum { SX_INDEX_COMPACT = 1 };
 int sx_index_build_fasta_ex(sx_ctx *ctx, const uint8_t *fasta, uint64_t len, int include_reverse, uint32_t flags, sx_index **out);
 int sx_index_from_sources_ex(sx_ctx *ctx, const sx_index_source *sources, uint32_t n_records, uint32_t flags, sx_index **out);
 typedef struct sx_index_occ {
-    int compact;                  /* 0: the record has full tables and the rest is 0 */
+    int compact;                  /* 0: the record has full tables and the rest is 0; 1: byte blocks; 2: packed blocks */
     const uint8_t *d_occ, *d_rocc; /* device memory; d_rocc NULL without the reverse */
     uint32_t stride, sigma_pad;   /* bytes a block, counters a block */
     uint64_t n_blocks;
@@ -446,6 +446,35 @@ int sx_index_is_compact(const sx_index *idx);
  * the reverse, rows outside [0, N + 1]. */
 int sx_index_expand_o(sx_ctx *ctx, const sx_index *idx, uint32_t record, int reverse, uint64_t row_lo, uint64_t row_hi,
                       uint32_t *rows_out);
+
+/* ---- the packed form of the compact tables, for alphabets of up to 8 symbols ---------------- */
+/* The same 64-row blocks with a nibble a row, one layout for every sigma in [1, 8]: block b is 64 bytes, 8 u32 counters
+ * (counter a = O(a, 64 b), the counters from sigma on are 0) followed by 32 bytes of 64 nibbles: row 64 b + j in byte j / 2,
+ * the low nibble for even j, the high one for odd j, nibbles from row N on 0xF.  N / 64 + 1 blocks; the first starts on a
+ * 16-byte boundary at least (SX_E_ARG otherwise; an index allocates on 256-byte boundaries, so that two blocks share a
+ * 128-byte line).  O(a, row) is counter a of block row / 64 plus the nibbles equal to a among the block's first row % 64:
+ * 2 N bytes for O and RO of DNA where the byte blocks take 4 N.  The same BWT gives the same bytes from run to run.  The
+ * calls are those of the compact form; each answers SX_E_ARG for sigma > 8 (sx_occ_packed_bytes answers 0). */
+uint64_t sx_occ_packed_bytes(uint64_t N, uint32_t sigma);
+int sx_occ_packed_build_dev(sx_ctx *ctx, const uint8_t *d_bwt, uint64_t N, uint32_t sigma, uint8_t *d_blocks_out);
+int sx_occ_packed_expand_dev(sx_ctx *ctx, const uint8_t *d_blocks, uint64_t N, uint32_t sigma, uint64_t row_lo, uint64_t row_hi,
+                             uint32_t *d_rows_out);
+int sx_bwt_exact_search_packed_dev(sx_ctx *ctx, const uint32_t *d_c_table, const uint8_t *d_occ, uint64_t N, uint32_t sigma,
+                                   const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, uint32_t *d_l_out,
+                                   uint32_t *d_r_out);
+int sx_bwt_approx_search_packed_dev(sx_ctx *ctx, const uint32_t *d_c_table, const uint8_t *d_occ, const uint8_t *d_rocc, uint64_t N,
+                                    uint32_t sigma, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, int max_edits,
+                                    uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t hit_capacity, uint64_t *total_hits_out);
+/* An index in the packed form (flags: SX_INDEX_COMPACT | SX_INDEX_PACKED, with or without SX_INDEX_SA_SAMPLE_LOG2(q);
+ * SX_INDEX_PACKED alone is SX_E_ARG): every record keeps packed blocks, about 7 N bytes with RO for DNA where the compact
+ * index takes 9 N, 3.4 N with a suffix array sampled at 32 where it takes 5.4 N.  Mapping gives the same text and
+ * sx_index_write the same file; sx_index_expand_o, sx_index_expand_sa and sx_index_add_record follow the index's form;
+ * sx_index_record_occ reports compact = 2, stride = 64 and sigma_pad = 8.  A record of more than 8 symbols (7 letters and
+ * the sentinel) has no place in such an index: a build or a load that meets one fails as a whole with SX_E_ARG and leaves
+ * nothing behind, sx_index_add_record answers SX_E_ARG and leaves the index as it was. */
+enum { SX_INDEX_PACKED = 4 };
+/* 1 for an index in the packed form */
+int sx_index_is_packed(const sx_index *idx);
 
 /* ---- a sampled suffix array for the compact index ---------------- */
 /* SA values kept at a sampling distance s = 2^q, q in 1 .. 10, the others recovered by walking LF over the forward blocks.

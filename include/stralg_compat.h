@@ -266,7 +266,8 @@ int stralg_amd_index_map(const struct sx_index *idx, FILE *fastq, int edits, FIL
 void stralg_amd_index_free(struct sx_index *idx);
 /* the same with the flags of sx_index_build_fasta_ex (SX_INDEX_COMPACT: the compact form of the O / RO tables; a saved
  * index is turned into blocks record by record while it is read; with it, SX_INDEX_SA_SAMPLE_LOG2(q): a suffix array
- * sampled at distance 2^q, made of a saved index's arrays window by window) */
+ * sampled at distance 2^q, made of a saved index's arrays window by window; with it, SX_INDEX_PACKED: a nibble a row in
+ * the blocks, for records of at most 7 letters -- NULL where a record has more) */
 struct sx_index *stralg_amd_index_from_fasta_image_ex(const uint8_t *fasta, size_t len, bool include_reverse, uint32_t flags);
 struct sx_index *stralg_amd_index_read_ex(FILE *f, uint32_t flags);
 

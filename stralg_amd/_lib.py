@@ -97,12 +97,19 @@ class IndexSamples(C.Structure):
 
 SX_SECTION_INDEX = 4
 SX_INDEX_COMPACT = 1
+SX_INDEX_PACKED = 4
 SA_SAMPLE_MAX_LOG2 = 10
 
 
-def index_flags(compact, sa_sample=0):
+def index_flags(compact, sa_sample=0, packed=False):
     """the flags of sx_index_build_fasta_ex / sx_index_from_sources_ex; sa_sample: 0, or a power of two in 2 .. 1024 (with
-    compact): checked here, before anything is built"""
+    compact); packed: a nibble a row in the blocks (with compact): checked here, before anything is built"""
+    if packed and not compact:
+        raise ValueError("packed needs compact=True: it is a form of the BWT blocks")
+    return _sample_flags(compact, sa_sample) | (SX_INDEX_PACKED if packed else 0)
+
+
+def _sample_flags(compact, sa_sample):
     sa_sample = int(sa_sample)
     if sa_sample == 0:
         return SX_INDEX_COMPACT if compact else 0
@@ -112,6 +119,8 @@ def index_flags(compact, sa_sample=0):
     if not compact:
         raise ValueError("sa_sample needs compact=True: the walks read the BWT blocks")
     return SX_INDEX_COMPACT | (q << 8)
+
+
 SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t)
 
 
@@ -180,6 +189,13 @@ def load(path=None):
         "sx_bwt_exact_search_compact_dev": (C.c_int, [vp, u32p, u8p, C.c_uint64, C.c_uint32, u8p, u32p, C.c_uint32, u32p, u32p]),
         "sx_bwt_approx_search_compact_dev": (C.c_int, [vp, u32p, u8p, u8p, C.c_uint64, C.c_uint32, u8p, u32p, C.c_uint32, C.c_int,
                                                        u64p, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+        "sx_occ_packed_bytes": (C.c_uint64, [C.c_uint64, C.c_uint32]),
+        "sx_occ_packed_build_dev": (C.c_int, [vp, u8p, C.c_uint64, C.c_uint32, u8p]),
+        "sx_occ_packed_expand_dev": (C.c_int, [vp, u8p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, u32p]),
+        "sx_bwt_exact_search_packed_dev": (C.c_int, [vp, u32p, u8p, C.c_uint64, C.c_uint32, u8p, u32p, C.c_uint32, u32p, u32p]),
+        "sx_bwt_approx_search_packed_dev": (C.c_int, [vp, u32p, u8p, u8p, C.c_uint64, C.c_uint32, u8p, u32p, C.c_uint32, C.c_int,
+                                                      u64p, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+        "sx_index_is_packed": (C.c_int, [vp]),
         "sx_index_build_fasta_ex": (C.c_int, [vp, u8p, C.c_uint64, C.c_int, C.c_uint32, C.POINTER(vp)]),
         "sx_index_from_sources_ex": (C.c_int, [vp, C.POINTER(IndexSource), C.c_uint32, C.c_uint32, C.POINTER(vp)]),
         "sx_index_record_occ": (C.c_int, [vp, C.c_uint32, C.POINTER(IndexOcc)]),
@@ -234,6 +250,8 @@ EXPORTS = ["sx_device_count", "sx_device_numa_node", "sx_ctx_create", "sx_ctx_de
            "sx_occ_compact_bytes", "sx_occ_compact_build_dev", "sx_occ_compact_expand_dev", "sx_bwt_exact_search_compact_dev",
            "sx_bwt_approx_search_compact_dev", "sx_index_build_fasta_ex", "sx_index_from_sources_ex", "sx_index_record_occ",
            "sx_index_is_compact", "sx_index_expand_o",
+           "sx_occ_packed_bytes", "sx_occ_packed_build_dev", "sx_occ_packed_expand_dev", "sx_bwt_exact_search_packed_dev",
+           "sx_bwt_approx_search_packed_dev", "sx_index_is_packed",
            "sx_sa_sample_bytes", "sx_sa_sample_build_dev", "sx_sa_locate_rows_dev", "sx_index_record_samples", "sx_index_expand_sa",
            "sx_synth_dev", "sx_membw_probe", "sx_prim_sort_pairs_dev", "sx_prim_exclusive_sum_dev", "sx_prim_classify_dev"]
 

@@ -198,6 +198,33 @@ class Context:
                     "sx_bwt_approx_search_compact_dev")
         return int(total.value)
 
+    # ---- the packed form of the compact table (sx_occ.hpp: a nibble a row, sigma <= 8) ---------
+    def occ_packed_bytes(self, N, sigma):
+        """sx_occ_packed_bytes: bytes of the packed blocks of a table of N + 1 rows (0 for sigma > 8)"""
+        return int(self.lib.sx_occ_packed_bytes(N, sigma))
+
+    def occ_packed_build_dev(self, d_bwt, N, sigma, d_blocks):
+        self._check(self.lib.sx_occ_packed_build_dev(self.h, _ptr(d_bwt), N, sigma, _ptr(d_blocks)), "sx_occ_packed_build_dev")
+
+    def occ_packed_expand_dev(self, d_blocks, N, sigma, row_lo, row_hi, d_rows):
+        self._check(self.lib.sx_occ_packed_expand_dev(self.h, _ptr(d_blocks), N, sigma, row_lo, row_hi, _ptr(d_rows)),
+                    "sx_occ_packed_expand_dev")
+
+    def bwt_exact_search_packed_dev(self, d_c, d_occ, N, sigma, d_patterns, d_offsets, count, d_l, d_r):
+        self._check(self.lib.sx_bwt_exact_search_packed_dev(self.h, _ptr(d_c), _ptr(d_occ), N, sigma, _ptr(d_patterns),
+                                                            _ptr(d_offsets), count, _ptr(d_l), _ptr(d_r)),
+                    "sx_bwt_exact_search_packed_dev")
+
+    def bwt_approx_search_packed_dev(self, d_c, d_occ, d_rocc, N, sigma, d_patterns, d_offsets, count, max_edits, d_hit_offsets,
+                                     d_hits=None, hit_capacity=0):
+        """sx_bwt_approx_search_packed_dev: Context.bwt_approx_search_dev over packed blocks in place of the full tables"""
+        total = C.c_uint64(0)
+        self._check(self.lib.sx_bwt_approx_search_packed_dev(self.h, _ptr(d_c), _ptr(d_occ), _ptr(d_rocc), N, sigma,
+                                                             _ptr(d_patterns), _ptr(d_offsets), count, max_edits,
+                                                             _ptr(d_hit_offsets), _ptr(d_hits), hit_capacity, C.byref(total)),
+                    "sx_bwt_approx_search_packed_dev")
+        return int(total.value)
+
     # ---- SAM text of search hits (the read mapper's output) ---------------------------------
     def sam_batch(self, d_hits, n_hits, d_sa, sa_len, d_names, d_name_off, d_seqs, d_seq_off, d_quals, d_qual_off, n_reads,
                   d_rnames, d_rname_off, n_records=1, d_sa_list=None, d_sa_len_list=None):
@@ -509,12 +536,14 @@ class Index:
 
     # ---- constructors -------------------------------------------------------------------------------------------
     @classmethod
-    def from_fasta(cls, fasta_bytes, include_reverse=True, ctx=None, compact=False, sa_sample=0):
+    def from_fasta(cls, fasta_bytes, include_reverse=True, ctx=None, compact=False, sa_sample=0, packed=False):
         """sx_index_build_fasta_ex: the bytes of a FASTA file -> tables of every record, built on the device; compact=True:
         BWT blocks with sampled counts in place of the O / RO tables (a fifth of the memory for DNA, the same results);
         sa_sample=32 (a power of two in 2 .. 1024, with compact): SA values at that distance in place of the suffix array,
-        the others located by walks over the blocks (5.4 bytes a symbol in place of 9 for DNA, the same results)"""
-        flags = _lib.index_flags(compact, sa_sample)
+        the others located by walks over the blocks (5.4 bytes a symbol in place of 9 for DNA, the same results);
+        packed=True (with compact): a nibble a row in the blocks, for records of at most 7 letters (7 bytes a symbol in
+        place of 9 for DNA, 3.4 in place of 5.4 with sa_sample=32, the same results; a record of more letters fails the build)"""
+        flags = _lib.index_flags(compact, sa_sample, packed)
         ctx = ctx or default_context()
         buf = np.frombuffer(bytes(fasta_bytes), dtype=np.uint8)
         h = C.c_void_p()
@@ -523,12 +552,12 @@ class Index:
         return cls(ctx, h)
 
     @classmethod
-    def from_tables(cls, records, ctx=None, compact=False, sa_sample=0):
+    def from_tables(cls, records, ctx=None, compact=False, sa_sample=0, packed=False):
         """sx_index_from_sources_ex: records = [(name bytes, BwtTable), ...] in the mapper's list order (the FASTA file's), as
         Context.map_reads_stream takes them; a table whose sa.string is set (remapped symbols + terminator) can be saved.
         compact=True: the tables go up in windows and stay as blocks; sa_sample: as from_fasta (the suffix arrays go up in
-        windows too and stay as samples)"""
-        flags = _lib.index_flags(compact, sa_sample)
+        windows too and stay as samples); packed: as from_fasta"""
+        flags = _lib.index_flags(compact, sa_sample, packed)
         ctx = ctx or default_context()
         src = (_lib.IndexSource * max(1, len(records)))()
         keep = []
@@ -545,10 +574,11 @@ class Index:
         return cls(ctx, h)
 
     @classmethod
-    def load(cls, path_or_bytes, ctx=None, compact=False, sa_sample=0):
+    def load(cls, path_or_bytes, ctx=None, compact=False, sa_sample=0, packed=False):
         """the read mapper's index file (genome.fa.bwttables; what .save writes): a path, or the bytes.  The file is
-        mapped, and its records go to the device one after the other (compact=True: as blocks; sa_sample: as from_fasta)."""
-        flags = _lib.index_flags(compact, sa_sample)
+        mapped, and its records go to the device one after the other (compact=True: as blocks; sa_sample and packed: as
+        from_fasta)."""
+        flags = _lib.index_flags(compact, sa_sample, packed)
         ctx = ctx or default_context()
         if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
             blob = np.frombuffer(bytes(path_or_bytes), dtype=np.uint8)
@@ -711,6 +741,11 @@ class Index:
         """whether the records keep BWT blocks with sampled counts in place of the O / RO tables"""
         return bool(self.ctx.lib.sx_index_is_compact(self._handle()))
 
+    @property
+    def packed(self):
+        """whether the records' blocks keep a nibble a row (the packed form of a compact index)"""
+        return bool(self.ctx.lib.sx_index_is_packed(self._handle()))
+
     def _occ_address(self, r, reverse):
         occ = self.record_occ(r)
         if not occ.compact:
@@ -721,7 +756,7 @@ class Index:
         return occ, address
 
     def device_occ(self, r, reverse=False, ctx=None):
-        """record r's raw blocks (of RO with reverse=True) read back: a uint8 array of n_blocks x stride"""
+        """record r's raw blocks (of RO with reverse=True) read back: a uint8 array of n_blocks x stride (x 64 in a packed index)"""
         ctx = ctx or self.ctx
         occ, address = self._occ_address(r, reverse)
         return ctx.download(address, int(occ.n_blocks) * int(occ.stride), np.uint8).reshape(int(occ.n_blocks), int(occ.stride))

@@ -363,7 +363,7 @@ static int approx_args(sx_ctx *ctx, ApproxArgsT<Occ> &A, const uint32_t *c, Occ 
 
 using namespace sx;
 
-// sx_bwt_approx_search_dev in either form of the tables
+// sx_bwt_approx_search_dev in any form of the tables
 template <class Occ>
 static int approx_search_dev(sx_ctx *ctx, const uint32_t *d_c_table, Occ o, Occ ro, uint64_t N, uint32_t sigma, const uint8_t *d_patterns,
                              const uint32_t *d_offsets, uint32_t count, int max_edits, uint64_t *d_hit_offsets, sx_approx_hit *d_hits,
@@ -395,6 +395,9 @@ static int approx_search_dev(sx_ctx *ctx, const uint32_t *d_c_table, Occ o, Occ 
 int sx_approx_search_record(sx_ctx *ctx, const sx_index_rec &R, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, int max_edits,
                             uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t hit_capacity, uint64_t *total_hits_out)
 {
+    if (R.packed)
+        return sx_bwt_approx_search_packed_dev(ctx, R.d_c, R.d_occ, R.d_rocc, R.N, R.sigma, d_patterns, d_offsets, count, max_edits, d_hit_offsets,
+                                               d_hits, hit_capacity, total_hits_out);
     return R.compact() ? sx_bwt_approx_search_compact_dev(ctx, R.d_c, R.d_occ, R.d_rocc, R.N, R.sigma, d_patterns, d_offsets, count, max_edits,
                                                           d_hit_offsets, d_hits, hit_capacity, total_hits_out)
                        : sx_bwt_approx_search_dev(ctx, R.d_c, R.d_o, R.d_ro, R.N, R.sigma, d_patterns, d_offsets, count, max_edits, d_hit_offsets,
@@ -420,6 +423,15 @@ int sx_bwt_approx_search_compact_dev(sx_ctx *ctx, const uint32_t *d_c_table, con
     const uint32_t stride = occ_stride(sigma);
     return approx_search_dev(ctx, d_c_table, OccCompact{d_occ, stride}, OccCompact{d_rocc, stride}, N, sigma, d_patterns, d_offsets, count,
                              max_edits, d_hit_offsets, d_hits, hit_capacity, total_hits_out);
+}
+
+int sx_bwt_approx_search_packed_dev(sx_ctx *ctx, const uint32_t *d_c_table, const uint8_t *d_occ, const uint8_t *d_rocc, uint64_t N,
+                                    uint32_t sigma, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, int max_edits,
+                                    uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t hit_capacity, uint64_t *total_hits_out)
+{
+    if (sigma > kOccPackedMaxSigma || (((uintptr_t)d_occ | (uintptr_t)d_rocc) & 15u)) return SX_E_ARG; // (the layout of sx_occ.hpp)
+    return approx_search_dev(ctx, d_c_table, OccPacked{d_occ}, OccPacked{d_rocc}, N, sigma, d_patterns, d_offsets, count, max_edits,
+                             d_hit_offsets, d_hits, hit_capacity, total_hits_out);
 }
 
 int sx_bwt_approx_search(sx_ctx *ctx, const uint32_t *c_table, const uint32_t *o_table, const uint32_t *ro_table,

@@ -423,7 +423,7 @@ __global__ __launch_bounds__(kBlock) void plcp_kernel(const uint8_t *__restrict_
 // positions) every step is a random 64-byte sector.  10^7 patterns x 30 symbols: 6.9 ms = 87 G look-ups/s = 5.5 TB/s
 // of sectors, the chip's random-access rate; taking the patterns in the order of their last symbols (a radix sort of
 // the pattern numbers) did not change the kernel's time and cost the sort.
-// Occ: how O(a, row) is read (sx_occ.hpp: the full table's word, or a rank in the compact blocks).
+// Occ: how O(a, row) is read (sx_occ.hpp: the full table's word, or a rank in the compact or the packed blocks).
 template <class Occ>
 __global__ __launch_bounds__(kBlock) void bwt_exact_search_kernel(const uint32_t *__restrict__ c_table,
                                                                   const Occ o_table, uint64_t N,
@@ -684,6 +684,19 @@ int sx_bwt_exact_search_compact_dev(sx_ctx *ctx, const uint32_t *d_c_table, cons
     SX_CHECK(hipSetDevice(ctx->device));
     sx_launch(ctx, SX_KC_SEARCH, 0, bwt_exact_search_kernel<OccCompact>, dim3(sx_div_up(count, kBlock)), dim3(kBlock), d_c_table,
               OccCompact{d_occ, occ_stride(sigma)}, N, sigma, d_patterns, d_offsets, count, d_l_out, d_r_out);
+    return sx_sync(ctx);
+}
+
+int sx_bwt_exact_search_packed_dev(sx_ctx *ctx, const uint32_t *d_c_table, const uint8_t *d_occ, uint64_t N, uint32_t sigma,
+                                   const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, uint32_t *d_l_out, uint32_t *d_r_out)
+{
+    if (!ctx || !d_c_table || !d_occ || ((uintptr_t)d_occ & 15u) || !d_offsets || !d_l_out || !d_r_out || N == 0 || N > 0xFFFFFFFFull ||
+        sigma < 1 || sigma > kOccPackedMaxSigma)
+        return SX_E_ARG;
+    if (count == 0) return 0;
+    SX_CHECK(hipSetDevice(ctx->device));
+    sx_launch(ctx, SX_KC_SEARCH, 0, bwt_exact_search_kernel<OccPacked>, dim3(sx_div_up(count, kBlock)), dim3(kBlock), d_c_table, OccPacked{d_occ}, N,
+              sigma, d_patterns, d_offsets, count, d_l_out, d_r_out);
     return sx_sync(ctx);
 }
 

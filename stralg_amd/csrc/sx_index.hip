@@ -83,13 +83,23 @@ static int make_view(sx_ctx *ctx, sx_index *idx)
     return 0;
 }
 
-// the flags of the _ex builders: SX_INDEX_COMPACT, and in bits 8 .. 15 the log2 of a sampling distance, which needs it
+// the flags of the _ex builders: SX_INDEX_COMPACT, SX_INDEX_PACKED, which needs it, and in bits 8 .. 15 the log2 of a
+// sampling distance, which needs it too
 static int flags_check(sx_ctx *ctx, uint32_t flags)
 {
     const uint32_t q = (flags >> 8) & 0xFFu;
-    const bool known = !(flags & ~((uint32_t)SX_INDEX_COMPACT | 0xFF00u));
-    if (known && (q == 0 || (sa_sample_log2_ok(q) && (flags & SX_INDEX_COMPACT)))) return 0;
-    return sx_fail_msg(ctx, SX_E_ARG, "index: unknown flags, or a sampling distance without SX_INDEX_COMPACT or outside 2^1 .. 2^10");
+    const bool known = !(flags & ~((uint32_t)SX_INDEX_COMPACT | (uint32_t)SX_INDEX_PACKED | 0xFF00u));
+    const bool compact = (flags & SX_INDEX_COMPACT) != 0;
+    if (known && (q == 0 || (sa_sample_log2_ok(q) && compact)) && (!(flags & SX_INDEX_PACKED) || compact)) return 0;
+    return sx_fail_msg(ctx, SX_E_ARG,
+                       "index: unknown flags, or SX_INDEX_PACKED or a sampling distance without SX_INDEX_COMPACT, or a distance outside 2^1 .. 2^10");
+}
+
+// a packed index holds records of at most 8 symbols (the sentinel among them): there is no other form for the others
+static int packed_sigma_check(sx_ctx *ctx, const sx_index *idx, uint32_t sigma)
+{
+    if (!idx->packed || sigma <= kOccPackedMaxSigma) return 0;
+    return sx_fail_msg(ctx, SX_E_ARG, "index: a record of more than 8 symbols (7 letters) does not fit the packed form");
 }
 
 static int device_check(sx_ctx *ctx, const sx_index *idx)
@@ -112,6 +122,7 @@ static sx_index *new_index(sx_ctx *ctx, uint32_t flags)
     if (!idx) return nullptr;
     idx->device = ctx->device;
     idx->compact = (flags & SX_INDEX_COMPACT) != 0;
+    idx->packed = (flags & SX_INDEX_PACKED) != 0;
     idx->sa_log2 = (flags >> 8) & 0xFFu;
     g_live_indexes.fetch_add(1);
     return idx;
@@ -121,7 +132,7 @@ static sx_index *new_index(sx_ctx *ctx, uint32_t flags)
 // grows by what they occupy.  Both ways to a record (host tables, a build from FASTA) allocate through this.
 static int take_arrays(sx_ctx *ctx, sx_dev_scope &S, sx_index_rec &R, bool compact, bool want_ro, bool want_string, size_t *bytes)
 {
-    const size_t o_words = (size_t)(R.N + 1) * R.sigma, occ_b = (size_t)occ_bytes(R.N, R.sigma);
+    const size_t o_words = (size_t)(R.N + 1) * R.sigma, occ_b = (size_t)occ_form_bytes(R.N, R.sigma, R.packed);
     if (R.sampled()) {
         SX_TRY(S.take(ctx, &R.d_sa_marks, (size_t)sa_mark_bytes(R.N), bytes));
         SX_TRY(S.take(ctx, &R.d_sa_values, (size_t)sa_sample_count(R.N, R.sa_log2), bytes));
@@ -145,7 +156,8 @@ static int add_tables(sx_ctx *ctx, sx_index *idx, const sx_map_record &M, const 
 {
     sx_index_rec R;
     R.name = M.name;
-    R.N = M.N, R.sigma = M.sigma, R.sa_log2 = idx->sa_log2;
+    R.N = M.N, R.sigma = M.sigma, R.sa_log2 = idx->sa_log2, R.packed = idx->packed;
+    SX_TRY(packed_sigma_check(ctx, idx, R.sigma));
     memcpy(R.remap, M.remap, 256);
     const size_t o_words = (size_t)(M.N + 1) * M.sigma;
     sx_dev_scope S;
@@ -156,8 +168,8 @@ static int add_tables(sx_ctx *ctx, sx_index *idx, const sx_map_record &M, const 
     else SX_CHECK(hipMemcpyAsync(R.d_sa, M.sa, (size_t)M.N * 4, hipMemcpyHostToDevice, ctx->stream));
     SX_CHECK(hipMemcpyAsync(R.d_c, M.c_table, (size_t)M.sigma * 4, hipMemcpyHostToDevice, ctx->stream));
     if (R.compact()) { // the full rows come up in windows and leave as blocks: no table of o_words exists on the device
-        SX_TRY(sx_nomem_of(sx_occ_from_rows_impl(ctx, M.o_table, M.N, M.sigma, R.d_occ)));
-        if (M.ro_table) SX_TRY(sx_nomem_of(sx_occ_from_rows_impl(ctx, M.ro_table, M.N, M.sigma, R.d_rocc)));
+        SX_TRY(sx_nomem_of(sx_occ_from_rows_impl(ctx, M.o_table, M.N, M.sigma, R.d_occ, R.packed)));
+        if (M.ro_table) SX_TRY(sx_nomem_of(sx_occ_from_rows_impl(ctx, M.ro_table, M.N, M.sigma, R.d_rocc, R.packed)));
     } else {
         SX_CHECK(hipMemcpyAsync(R.d_o, M.o_table, o_words * 4, hipMemcpyHostToDevice, ctx->stream));
         if (M.ro_table) SX_CHECK(hipMemcpyAsync(R.d_ro, M.ro_table, o_words * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -186,6 +198,10 @@ static int from_tables(sx_ctx *ctx, const sx_map_record *records, const sx_index
     *out = nullptr;
     SX_TRY(flags_check(ctx, flags));
     for (uint32_t r = 0; r < n; ++r) SX_TRY(record_check(ctx, records ? records[r] : sources[r].record));
+    if (flags & SX_INDEX_PACKED)
+        for (uint32_t r = 0; r < n; ++r)
+            if ((records ? records[r] : sources[r].record).sigma > kOccPackedMaxSigma)
+                return sx_fail_msg(ctx, SX_E_ARG, "index: a record of more than 8 symbols (7 letters) does not fit the packed form");
     SX_CHECK(hipSetDevice(ctx->device));
     sx_index *idx = new_index(ctx, flags);
     if (!idx) return sx_fail_msg(ctx, SX_E_NOMEM, "index");
@@ -202,13 +218,14 @@ static int build_record(sx_ctx *ctx, sx_index *idx, const uint8_t *d_seq, uint64
 {
     sx_index_rec R;
     R.name = name;
-    R.N = n + 1, R.sa_log2 = idx->sa_log2;
+    R.N = n + 1, R.sa_log2 = idx->sa_log2, R.packed = idx->packed;
     sx_dev_scope S, T; // S: what the record keeps, T: temporaries
     size_t bytes = 0;
     int16_t t16[256];
     SX_TRY(S.take(ctx, &R.d_string, (size_t)n + 1, &bytes));
     SX_TRY(sx_remap_dev(ctx, d_seq, n, R.d_string, t16, &R.sigma));
     for (int b = 0; b < 256; ++b) R.remap[b] = (signed char)t16[b];
+    SX_TRY(packed_sigma_check(ctx, idx, R.sigma)); // (the whole build fails: what it has made so far goes with the index)
     const uint64_t N = n + 1;
     const uint32_t sigma = R.sigma;
     SX_TRY(take_arrays(ctx, S, R, idx->compact, include_reverse, false, &bytes));
@@ -220,7 +237,7 @@ static int build_record(sx_ctx *ctx, sx_index *idx, const uint8_t *d_seq, uint64
     SX_TRY(sx_nomem_of(sx_sa_bwt_build_dev(ctx, R.d_string, n, sigma, d_sa, d_bwt)));
     // compact: the BWT goes straight into the block builder and the table call makes C alone (d_o and d_ro are null)
     SX_TRY(sx_nomem_of(sx_bwt_tables_from_bwt_dev(ctx, d_bwt, N, sigma, R.d_c, R.d_o)));
-    if (R.compact()) SX_TRY(sx_nomem_of(sx_occ_build_impl(ctx, d_bwt, N, sigma, R.d_occ)));
+    if (R.compact()) SX_TRY(sx_nomem_of(sx_occ_build_impl(ctx, d_bwt, N, sigma, R.d_occ, R.packed)));
     if (R.sampled()) {
         SX_TRY(sx_nomem_of(sx_sa_sample_dev_impl(ctx, d_sa, N, R.sa_log2, R.d_sa_marks, R.d_sa_values))); // (ends with a sync)
         T.drop(d_sa);
@@ -234,7 +251,7 @@ static int build_record(sx_ctx *ctx, sx_index *idx, const uint8_t *d_seq, uint64
         SX_TRY(sx_reverse_dev(ctx, R.d_string, n, d_rev));
         SX_TRY(sx_nomem_of(sx_sa_bwt_build_dev(ctx, d_rev, n, sigma, d_rsa, d_bwt)));
         SX_TRY(sx_nomem_of(sx_bwt_tables_from_bwt_dev(ctx, d_bwt, N, sigma, d_rc, R.d_ro)));
-        if (R.compact()) SX_TRY(sx_nomem_of(sx_occ_build_impl(ctx, d_bwt, N, sigma, R.d_rocc)));
+        if (R.compact()) SX_TRY(sx_nomem_of(sx_occ_build_impl(ctx, d_bwt, N, sigma, R.d_rocc, R.packed)));
     }
     SX_TRY(sx_sync(ctx));
     S.keep();
@@ -288,7 +305,7 @@ static int send_o_rows(sx_ctx *ctx, const sx_index_rec &R, bool reverse, uint64_
 {
     const size_t row_bytes = (size_t)R.sigma * 4;
     if (!R.compact()) return sx_stream_to_sink(ctx, SX_SECTION_INDEX, (reverse ? R.d_ro : R.d_o) + lo * R.sigma, (hi - lo) * row_bytes, sink, user);
-    const auto fill = [&](uint64_t a, uint64_t b, uint32_t *d_win) { return sx_occ_expand_impl(ctx, reverse ? R.d_rocc : R.d_occ, R.N, R.sigma, a, b, d_win); };
+    const auto fill = [&](uint64_t a, uint64_t b, uint32_t *d_win) { return sx_occ_expand_impl(ctx, reverse ? R.d_rocc : R.d_occ, R.N, R.sigma, a, b, d_win, R.packed); };
     return sx_nomem_of(sx_stream_windows(ctx, SX_SECTION_INDEX, lo, hi, row_bytes, sink, user, fill));
 }
 
@@ -392,16 +409,17 @@ int sx_index_record_occ(const sx_index *idx, uint32_t record, sx_index_occ *out)
     if (!idx || !out || record >= idx->recs.size()) return SX_E_ARG;
     const sx_index_rec &R = idx->recs[record];
     memset(out, 0, sizeof *out);
-    out->compact = R.compact() ? 1 : 0;
+    out->compact = R.compact() ? (R.packed ? 2 : 1) : 0;
     if (R.compact()) {
         out->d_occ = R.d_occ, out->d_rocc = R.d_rocc;
-        out->stride = occ_stride(R.sigma), out->sigma_pad = occ_sigma_pad(R.sigma);
+        out->stride = occ_form_stride(R.sigma, R.packed), out->sigma_pad = R.packed ? kOccPackedMaxSigma : occ_sigma_pad(R.sigma);
         out->n_blocks = occ_blocks(R.N);
     }
     return 0;
 }
 
 int sx_index_is_compact(const sx_index *idx) { return idx && idx->compact ? 1 : 0; }
+int sx_index_is_packed(const sx_index *idx) { return idx && idx->packed ? 1 : 0; }
 
 int sx_index_record_samples(const sx_index *idx, uint32_t record, sx_index_samples *out)
 {

@@ -13,22 +13,26 @@ struct sx_index_rec {
     signed char remap[256];
     uint8_t *d_string = nullptr; // N bytes (the sentinel last), or null
     uint32_t *d_sa = nullptr, *d_c = nullptr, *d_o = nullptr, *d_ro = nullptr;
-    // a record of a compact index has the blocks of sx_occ.hpp in place of d_o / d_ro (d_rocc null: no reverse)
+    // a record of a compact index has the blocks of sx_occ.hpp in place of d_o / d_ro (d_rocc null: no reverse); packed:
+    // they are the nibble blocks (sigma <= 8)
     uint8_t *d_occ = nullptr, *d_rocc = nullptr;
+    bool packed = false;
     // a record of a sampled index has the marks and values of sx_locate.hpp in place of d_sa (which is null then)
     uint8_t *d_sa_marks = nullptr;
     uint32_t *d_sa_values = nullptr;
     uint32_t sa_log2 = 0;
-    // the record's form: full (d_sa, d_o, d_ro), compact (blocks for d_o / d_ro) or compact and sampled
+    // the record's form: full (d_sa, d_o, d_ro), compact (byte or nibble blocks for d_o / d_ro) or compact
+    // and sampled
     bool compact() const { return d_occ != nullptr; }
     bool sampled() const { return sa_log2 != 0; }
     bool has_ro() const { return d_ro || d_rocc; }
-    sx::LocRec loc() const { return sx::loc_rec_of(d_c, d_occ, N, sigma, d_sa_marks, d_sa_values, sa_log2); } // what a walk reads of it
+    sx::LocRec loc() const { return sx::loc_rec_of(d_c, d_occ, N, sigma, d_sa_marks, d_sa_values, sa_log2, packed); } // what a walk reads of it
 };
 
 struct sx_index {
     int device = 0;
     bool compact = false; // SX_INDEX_COMPACT: every record it has or gets is in the compact form
+    bool packed = false;  // SX_INDEX_PACKED (with compact): every record's blocks are nibble blocks, and a record has sigma <= 8
     uint32_t sa_log2 = 0; // SX_INDEX_SA_SAMPLE_LOG2: 0, or every record keeps a suffix array sampled at this distance's log2
     std::vector<sx_index_rec> recs; // FASTA file order
     size_t device_bytes = 0;
@@ -66,6 +70,6 @@ static inline bool sx_map_record_check(const sx_map_record &R, uint32_t min_sigm
 
 // sx_sam.hip: the mapper's loop over reads and an index that both lie on ctx's device
 int sx_map_reads_core(sx_ctx *ctx, const sx_index *idx, const sx_reads_dev &reads, int edits, sx_sink_fn sink, void *user);
-// sx_approx.hip: sx_bwt_approx_search_dev over the tables of a record, full or compact
+// sx_approx.hip: sx_bwt_approx_search_dev over the tables of a record, full, compact or packed
 int sx_approx_search_record(sx_ctx *ctx, const sx_index_rec &R, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, int max_edits,
                             uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t hit_capacity, uint64_t *total_hits_out);

@@ -62,9 +62,14 @@ __global__ __launch_bounds__(kBlock) void sa_values_kernel(const uint32_t *__res
 // ---- locate ----------------------------------------------------------------------------------------------------------
 enum { LOC_ERR_BOUND = 1 };
 
-__device__ __forceinline__ uint32_t locate_row(const LocRec &T, uint32_t row, uint32_t *err)
+// the accessor of a record's blocks in the form of the launch
+template <class Occ> __device__ __forceinline__ Occ loc_occ(const LocRec &T);
+template <> __device__ __forceinline__ OccCompact loc_occ<OccCompact>(const LocRec &T) { return OccCompact{T.occ, T.stride}; }
+template <> __device__ __forceinline__ OccPacked loc_occ<OccPacked>(const LocRec &T) { return OccPacked{T.occ}; }
+
+template <class Occ> __device__ __forceinline__ uint32_t locate_row(const LocRec &T, uint32_t row, uint32_t *err)
 {
-    const OccCompact occ{T.occ, T.stride};
+    const Occ occ = loc_occ<Occ>(T);
     uint32_t steps = 0;
     bool bad = row >= T.N;
     while (!bad) {
@@ -76,7 +81,7 @@ __device__ __forceinline__ uint32_t locate_row(const LocRec &T, uint32_t row, ui
             if (at < T.n_samples) return T.values[at] + steps;
             break;
         }
-        const uint32_t a = T.occ[(uint64_t)b * T.stride + (T.stride - kOccRows) + j]; // the row's BWT byte: one load
+        const uint32_t a = occ.symbol(row); // the row's BWT symbol: one load
         if (steps == T.s || a >= T.sigma) break; // tables that do not belong together: the walk ends at its bound
         row = T.c[a] + occ.rank(a, row, T.sigma);
         ++steps;
@@ -87,13 +92,15 @@ __device__ __forceinline__ uint32_t locate_row(const LocRec &T, uint32_t row, ui
 }
 
 // rows [lo, lo + count) into out[0 .. count): the expansion
+template <class Occ>
 __global__ __launch_bounds__(kBlock) void locate_rows_kernel(LocRec T, uint64_t lo, uint64_t count, uint32_t *__restrict__ out, uint32_t *err)
 {
     for (uint64_t idx = (uint64_t)blockIdx.x * kBlock + threadIdx.x; idx < count; idx += (uint64_t)gridDim.x * kBlock)
-        out[idx] = locate_row(T, (uint32_t)(lo + idx), err);
+        out[idx] = locate_row<Occ>(T, (uint32_t)(lo + idx), err);
 }
 
 // the rows of a run of hits: slot pos_off[h] - base + i gets row L_h + i (pos_off: from the run's first hit on, n entries + 1)
+template <class Occ>
 __global__ __launch_bounds__(kBlock) void locate_hits_kernel(const LocRec *__restrict__ recs, uint32_t n_records, const uint4 *__restrict__ hits,
                                                              const uint64_t *__restrict__ pos_off, uint64_t n, uint64_t base, uint64_t count,
                                                              uint32_t *__restrict__ out, uint32_t *err)
@@ -108,7 +115,7 @@ __global__ __launch_bounds__(kBlock) void locate_hits_kernel(const LocRec *__res
         }
         const uint4 h0 = hits[2 * h];
         const LocRec T = recs[h0.x % n_records];
-        out[idx] = locate_row(T, h0.y + (uint32_t)(slot - pos_off[h]), err);
+        out[idx] = locate_row<Occ>(T, h0.y + (uint32_t)(slot - pos_off[h]), err);
     }
 }
 
@@ -208,8 +215,13 @@ int sx_sa_locate_rows_impl(sx_ctx *ctx, const LocRec &rec, uint64_t row_lo, uint
     SX_TRY(locate_scratch(ctx, &d_err));
     SX_CHECK(hipMemsetAsync(d_err, 0, 4, ctx->stream));
     // a row: half a sampling distance of steps, a step one block line and one mark entry
-    sx_launch(ctx, SX_KC_SEARCH, count * (4 + (uint64_t)rec.s / 2 * (rec.stride + 16)), locate_rows_kernel, dim3(locate_grid(count)), dim3(kBlock), rec,
-              row_lo, count, d_out, d_err);
+    const uint64_t alg_bytes = count * (4 + (uint64_t)rec.s / 2 * (rec.stride + 16));
+    if (rec.packed)
+        sx_launch(ctx, SX_KC_SEARCH, alg_bytes, locate_rows_kernel<OccPacked>, dim3(locate_grid(count)), dim3(kBlock), rec, row_lo, count, d_out,
+                  d_err);
+    else
+        sx_launch(ctx, SX_KC_SEARCH, alg_bytes, locate_rows_kernel<OccCompact>, dim3(locate_grid(count)), dim3(kBlock), rec, row_lo, count, d_out,
+                  d_err);
     SX_TRY(sx_readback(ctx, d_err, 1, &e));
     if (e) return sx_fail_msg(ctx, SX_E_INTERNAL, "sampled suffix array: a walk met its bound (the samples do not belong to the blocks)");
     return 0;
@@ -241,12 +253,16 @@ int sx_sa_hits_run(sx_ctx *ctx, const uint64_t *d_pos_off, uint64_t n_hits, uint
     return 0;
 }
 
-int sx_sa_locate_hits(sx_ctx *ctx, const LocRec *d_recs, uint32_t n_records, const uint4 *d_hits, const uint64_t *d_pos_off, uint64_t h_lo,
-                      uint64_t h_hi, uint64_t base, uint64_t rows, uint32_t *d_out, uint32_t *d_err)
+int sx_sa_locate_hits(sx_ctx *ctx, const LocRec *d_recs, uint32_t n_records, bool packed, const uint4 *d_hits, const uint64_t *d_pos_off,
+                      uint64_t h_lo, uint64_t h_hi, uint64_t base, uint64_t rows, uint32_t *d_out, uint32_t *d_err)
 {
     if (!rows) return 0;
-    sx_launch(ctx, SX_KC_SEARCH, rows * 4, locate_hits_kernel, dim3(locate_grid(rows)), dim3(kBlock), d_recs, n_records, d_hits + 2 * h_lo,
-              d_pos_off + h_lo, h_hi - h_lo, base, rows, d_out, d_err);
+    if (packed)
+        sx_launch(ctx, SX_KC_SEARCH, rows * 4, locate_hits_kernel<OccPacked>, dim3(locate_grid(rows)), dim3(kBlock), d_recs, n_records, d_hits + 2 * h_lo,
+                  d_pos_off + h_lo, h_hi - h_lo, base, rows, d_out, d_err);
+    else
+        sx_launch(ctx, SX_KC_SEARCH, rows * 4, locate_hits_kernel<OccCompact>, dim3(locate_grid(rows)), dim3(kBlock), d_recs, n_records, d_hits + 2 * h_lo,
+                  d_pos_off + h_lo, h_hi - h_lo, base, rows, d_out, d_err);
     return 0;
 }
 

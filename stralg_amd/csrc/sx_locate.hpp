@@ -11,7 +11,7 @@
 //           values[before + popcount(bits & ((1 << j) - 1))]
 // Both start on a 16-byte boundary at least (an index allocates them on 256-byte boundaries with a 256-byte tail).
 //
-// Locate.  SA[row]: while the row is not marked, a = the row's BWT byte (from the forward blocks), row = C[a] + O(a, row),
+// Locate.  SA[row]: while the row is not marked, a = the row's BWT symbol (from the forward blocks), row = C[a] + O(a, row),
 // one more step; the value of the marked row plus the steps.  At most s - 1 steps for tables that belong together; a walk
 // that reaches s steps, meets a byte that is no symbol or leaves [0, N) sets a bit in an error word and ends.
 #pragma once
@@ -39,14 +39,14 @@ struct LocRec {
     const uint4 *marks;
     const uint32_t *values;
     uint32_t N, sigma, stride, n_samples;
-    uint32_t s, pad;
+    uint32_t s, packed; // packed: the blocks are the nibble blocks of sx_occ.hpp (the walks read them through OccPacked)
 };
 
 static inline LocRec loc_rec_of(const uint32_t *d_c, const uint8_t *d_occ, uint64_t N, uint32_t sigma, const void *d_marks,
-                                const uint32_t *d_values, uint32_t q)
+                                const uint32_t *d_values, uint32_t q, bool packed = false)
 {
-    return LocRec{d_occ, d_c, (const uint4 *)d_marks, d_values, (uint32_t)N, sigma, occ_stride(sigma), (uint32_t)sa_sample_count(N, q),
-                  1u << q, 0u};
+    return LocRec{d_occ, d_c, (const uint4 *)d_marks, d_values, (uint32_t)N, sigma, occ_form_stride(sigma, packed),
+                  (uint32_t)sa_sample_count(N, q), 1u << q, packed ? 1u : 0u};
 }
 
 } // namespace sx
@@ -65,6 +65,7 @@ int sx_sa_hits_offsets(sx_ctx *ctx, const sx::LocRec *d_recs, uint32_t n_records
 // the run of hits that starts at h_lo and whose rows fit `cap` (one hit at least): *h_hi_out, *rows_out
 int sx_sa_hits_run(sx_ctx *ctx, const uint64_t *d_pos_off, uint64_t n_hits, uint64_t h_lo, uint64_t base, uint64_t cap, uint32_t *d_scratch4,
                    uint64_t *h_hi_out, uint64_t *rows_out);
-// slot d_pos_off[h] - base + i of d_out <- SA[L_h + i] for the hits [h_lo, h_hi) (asynchronous; d_err |= 1 at a bound)
-int sx_sa_locate_hits(sx_ctx *ctx, const sx::LocRec *d_recs, uint32_t n_records, const uint4 *d_hits, const uint64_t *d_pos_off, uint64_t h_lo,
-                      uint64_t h_hi, uint64_t base, uint64_t rows, uint32_t *d_out, uint32_t *d_err);
+// slot d_pos_off[h] - base + i of d_out <- SA[L_h + i] for the hits [h_lo, h_hi) (asynchronous; d_err |= 1 at a bound);
+// packed: the form of every record of d_recs (an index has one form as a whole)
+int sx_sa_locate_hits(sx_ctx *ctx, const sx::LocRec *d_recs, uint32_t n_records, bool packed, const uint4 *d_hits, const uint64_t *d_pos_off,
+                      uint64_t h_lo, uint64_t h_hi, uint64_t base, uint64_t rows, uint32_t *d_out, uint32_t *d_err);

@@ -620,7 +620,7 @@ static int emit_located(sx_ctx *ctx, const sx_index *idx, sx_sam_batch text, Map
             M.pos_cap = rows;
         }
         if (!M.d_positions) SX_TRY(M.own.take(ctx, &M.d_positions, 1)); // (hits without a line: the kernels still want an address)
-        SX_TRY(sx_sa_locate_hits(ctx, d_recs, text.n_records, d_hits, M.d_pos_off, h_lo, h_hi, base, rows, M.d_positions, d_loc_err));
+        SX_TRY(sx_sa_locate_hits(ctx, d_recs, text.n_records, idx->packed, d_hits, M.d_pos_off, h_lo, h_hi, base, rows, M.d_positions, d_loc_err));
         uint32_t e = 0;
         SX_TRY(sx_readback(ctx, d_loc_err, 1, &e));
         if (e) return sx_fail_msg(ctx, SX_E_INTERNAL, "read mapping: a walk over a sampled suffix array met its bound");

@@ -16,6 +16,10 @@ profiles/index_bench_2p28.json), everything measured in this one run:
              kernels' share of it (HIP events of the class), and the ratio of the two forms' search times; nothing else
              is measured then (kept in profiles/compact_index_2p28.json)
 
+  --compact --packed [--sa-sample 32]  the compact index against its packed form (a nibble a row in the blocks, DESIGN.md
+             section 15) of the same record and reads, in one run; with --sa-sample both forms keep a suffix array sampled at
+             these distances (kept in profiles/packed_index_2p28.json)
+
     python tools/index_bench.py [--log2n 28] [--reads 1000000] [--reps 3]
     python tools/index_bench.py --compact [--form compact --trace-only]
     rocprofv3 --kernel-trace --stats -d out -- python tools/index_bench.py --trace-only     (profiles/index_rocprofv3_summary.txt)
@@ -50,26 +54,35 @@ def compact_leg(args, ctx, Index, fasta, fastq, out):
     ks = [int(x) for x in args.ks.split(",")]
     forms = ("full", "compact") if args.form == "both" else (args.form,)
     samplings = [int(x) for x in args.sa_sample.split(",")] if args.sa_sample else []
-    if samplings:  # the compact index beside the sampled ones: the searches are the same, the locate pass is what differs
+    if args.packed:  # every byte-block form beside its packed form: the same searches and walks over the other blocks
+        out["bench"] = "packed_index"
+        pairs = [f"sampled{s}" for s in samplings] if samplings else ["compact"]
+        if args.form == "packed":
+            forms = tuple("packed_" + f if f != "compact" else "packed" for f in pairs)
+        else:
+            forms = tuple(f for pair in pairs for f in (pair, "packed_" + pair if pair != "compact" else "packed"))
+    elif samplings:  # the compact index beside the sampled ones: the searches are the same, the locate pass is what differs
         out["bench"] = "sampled_sa"
         forms = (() if args.form == "sampled" else ("compact",)) + tuple(f"sampled{s}" for s in samplings)
     for form in forms:
         compact = form != "full"
-        sa_sample = int(form[7:]) if form.startswith("sampled") else 0
+        packed = form.startswith("packed")
+        sa_sample = int(form.split("sampled")[1]) if "sampled" in form else 0
         if args.trace_only:
-            with Index.from_fasta(fasta, ctx=ctx, compact=compact, sa_sample=sa_sample) as idx:
+            with Index.from_fasta(fasta, ctx=ctx, compact=compact, sa_sample=sa_sample, packed=packed) as idx:
                 for _ in range(2):
                     idx.map_reads_discard(fastq, ks[0])
             continue
 
         def build():
-            Index.from_fasta(fasta, ctx=ctx, compact=compact, sa_sample=sa_sample).close()
+            Index.from_fasta(fasta, ctx=ctx, compact=compact, sa_sample=sa_sample, packed=packed).close()
 
         build()  # warm-up (workspace)
         _, build_s, build_all = best(build, args.reps)
         res = {"build_ms": round(build_s * 1e3, 1), "build_all_ms": [round(t * 1e3, 1) for t in build_all]}
-        with Index.from_fasta(fasta, ctx=ctx, compact=compact, sa_sample=sa_sample) as idx:
+        with Index.from_fasta(fasta, ctx=ctx, compact=compact, sa_sample=sa_sample, packed=packed) as idx:
             res["device_bytes"] = idx.device_bytes
+            res["device_bytes_a_symbol"] = round(idx.device_bytes / sum(N for _, N, _, _ in idx.records), 4)
             for k in ks:
                 seen = idx.map_reads_discard(fastq, k)  # warm-up
                 _, call_s, call_all = best(lambda: idx.map_reads_discard(fastq, k), args.reps if k < 2 else max(1, args.reps - 1))
@@ -86,7 +99,7 @@ def compact_leg(args, ctx, Index, fasta, fastq, out):
                                 "call_all_ms": [round(t * 1e3, 1) for t in call_all], "search_kernels_ms": round(stat["ms"], 2),
                                 "search_launches": stat["launches"], "profiled_call_ms": round(timed_s * 1e3, 1),
                                 "search_share_of_call": round(stat["ms"] * 1e-3 / timed_s, 4)}
-                if sa_sample and "compact" in out:
+                if sa_sample and not args.packed and "compact" in out:
                     # the locate kernel is timed in the searches' class: what that class takes beyond the compact index's same
                     # searches is the locate pass (a launch a run beside the count, the scan and the run kernels)
                     locate_ms = stat["ms"] - out["compact"][f"k{k}"]["search_kernels_ms"]
@@ -95,7 +108,17 @@ def compact_leg(args, ctx, Index, fasta, fastq, out):
         out[form] = res
         ctx.trim()
     if not args.trace_only:
-        if samplings and "compact" in out:
+        if args.packed and args.form != "packed":
+            out["packed_over_bytes"] = {}
+            for base in forms[0::2]:
+                pk = "packed" if base == "compact" else "packed_" + base
+                out["packed_over_bytes"][pk] = {
+                    "device_bytes": round(out[pk]["device_bytes"] / out[base]["device_bytes"], 4),
+                    "build": round(out[pk]["build_ms"] / out[base]["build_ms"], 3),
+                    **{f"k{k}_search_kernels": round(out[pk][f"k{k}"]["search_kernels_ms"] / out[base][f"k{k}"]["search_kernels_ms"], 3) for k in ks},
+                    **{f"k{k}_call": round(out[pk][f"k{k}"]["call_ms"] / out[base][f"k{k}"]["call_ms"], 3) for k in ks}}
+                assert all(out[pk][f"k{k}"]["text_bytes"] == out[base][f"k{k}"]["text_bytes"] for k in ks)
+        elif samplings and "compact" in out:
             out["sampled_over_compact"] = {
                 f"sampled{s}": {"device_bytes": round(out[f"sampled{s}"]["device_bytes"] / out["compact"]["device_bytes"], 4),
                                 "build": round(out[f"sampled{s}"]["build_ms"] / out["compact"]["build_ms"], 3),
@@ -124,11 +147,16 @@ def main():
     ap.add_argument("--trace-only", action="store_true",
                     help="build the index, map the reads twice at the first k and stop (for a rocprofv3 --kernel-trace --stats run)")
     ap.add_argument("--compact", action="store_true", help="the full and the compact index side by side, nothing else")
-    ap.add_argument("--form", default="both", choices=["both", "full", "compact", "sampled"],
-                    help="with --compact: only this form (sampled: with --sa-sample, without the compact index beside it)")
+    ap.add_argument("--form", default="both", choices=["both", "full", "compact", "sampled", "packed"],
+                    help="with --compact: only this form (sampled: with --sa-sample, without the compact index beside it; packed: with "
+                    "--packed, without the byte blocks beside it)")
+    ap.add_argument("--packed", action="store_true", help="with --compact: the compact index beside its packed form (DESIGN.md section 15), "
+                    "both with a sampled suffix array where --sa-sample is given; kept in profiles/packed_index_2p28.json")
     ap.add_argument("--sa-sample", default="", help="with --compact: the compact index beside indexes with a suffix array sampled at "
                     "these distances (8,32,128): DESIGN.md section 14, kept in profiles/sampled_sa_2p28.json")
     args = ap.parse_args()
+    if args.packed and not args.compact:
+        ap.error("--packed needs --compact")
     import torch
 
     import stralg_amd
