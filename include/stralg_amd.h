@@ -95,6 +95,8 @@ typedef struct sx_build_stats {
                                       the longest prefix key: from 300 on the prefix-key sort is not attempted */
     uint32_t long_subbuckets; /* hybrid prefix-key sort: sub-buckets too long for a workgroup's LDS (repeat families, AT-rich
                                  prefixes) that were ordered by HBM passes of their own */
+    uint32_t induce_early_s; /* induced-sort passes over at most 8 buckets: S-type entries that the L pass placed itself, as
+                                the predecessors of the L-type entries it was scanning (the S pass did not scan those again) */
 } sx_build_stats;
 
 /* ---- context ------------------------------------------------------------ */
@@ -158,6 +160,9 @@ enum {
                                        printed in runs of consecutive hits whose lines fit this many positions (0: the default,
                                        2^28, a buffer of 1 GiB; a single hit with more lines gets a buffer of its own length;
                                        tests set small values) */
+    ,SX_FLAG_INDUCE_EARLY_S_OFF = 21 /* induced-sort passes over at most 8 buckets: 1 = the S pass scans every bucket's whole L
+                                       region for the S-type predecessors (as before); 0 (default) = the L pass's large rounds
+                                       place them while they hold the entries, the S pass scans what those rounds left */
 };
 int sx_ctx_set_flag(sx_ctx *ctx, int flag, int value);
 

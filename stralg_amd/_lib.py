@@ -25,7 +25,8 @@ class BuildStats(C.Structure):
                 ("doubling_rounds", C.c_uint32), ("induce_rounds", C.c_uint32),
                 ("sort_passes", C.c_uint32), ("lms_path", C.c_uint32), ("sort_local", C.c_uint32), ("refine_tiers", C.c_uint32),
                 ("ms_total", C.c_double), ("induce_redo", C.c_uint32), ("long_runs", C.c_uint32),
-                ("recursion_levels", C.c_uint32), ("sample_tied_permille", C.c_uint32), ("long_subbuckets", C.c_uint32)]
+                ("recursion_levels", C.c_uint32), ("sample_tied_permille", C.c_uint32), ("long_subbuckets", C.c_uint32),
+                ("induce_early_s", C.c_uint32)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -41,6 +42,7 @@ SX_E_INTERNAL = -3
 SX_SECTION_SAM = 3
 SX_FLAG_SAM_BATCH_READS, SX_FLAG_SAM_WINDOW_BYTES = 18, 19
 SX_FLAG_LOCATE_CHUNK_ROWS = 20
+SX_FLAG_INDUCE_EARLY_S_OFF = 21
 
 
 class SamBatch(C.Structure):

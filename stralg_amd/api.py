@@ -465,6 +465,11 @@ class Context:
         finish is carried on by the host), 1 the host looks at every bucket's last range"""
         self._check(self.lib.sx_ctx_set_flag(self.h, 9, int(mode)), "sx_ctx_set_flag")
 
+    def set_induce_early_s(self, on=True):
+        """SX_FLAG_INDUCE_EARLY_S_OFF: texts of at most 8 symbols -- the L pass's large rounds place the S-type predecessors of
+        the entries they scan (default), or the S pass scans every L region again for them"""
+        self._check(self.lib.sx_ctx_set_flag(self.h, _lib.SX_FLAG_INDUCE_EARLY_S_OFF, 0 if on else 1), "sx_ctx_set_flag")
+
     def set_induce_hoist(self, on=True):
         """SX_FLAG_INDUCE_NO_HOIST: texts of more than 8 symbols -- all buckets' LMS seeds / L-type entries scanned at once, up
         front, placed by the text's bigram counts (default), or by launches of each bucket's own (rounds 1 - 3)"""

@@ -199,7 +199,8 @@ int sx_sa_build_impl(sx_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t si
     }
 
     sx_text_info ti;
-    SX_TRY(sx_classify(ctx, T, n, an, ti, src_tiles ? d_text : nullptr, src_tiles));
+    SX_TRY(sx_classify(ctx, T, n, an, ti, src_tiles ? d_text : nullptr, src_tiles,
+                       (sigma <= 8 && !ctx->induce_early_s_off) ? sigma : 0u));
     if (ti.maxc >= sigma) return sx_fail_msg(ctx, SX_E_ARG, "text holds a symbol >= alphabet_size");
     ctx->stats.n_lms = ti.m;
 

@@ -21,6 +21,14 @@
 namespace sx {
 
 
+// 16 positions whose symbol is A, from the three bit planes of their symbols: every plane agrees with A's bit (a truth
+// table with a single one)
+template <int A> __device__ __forceinline__ uint32_t plane_eq(uint32_t b0, uint32_t b1, uint32_t b2)
+{
+    return __builtin_amdgcn_bitop3_b32(b0, b1, b2, 1u << (((A & 1) << 2) | (A & 2) | ((A >> 2) & 1)));
+}
+constexpr uint32_t kClsAscAt = 3 * 256 + 16; // ascent counts [d * 8 + c] behind the histograms and the open-tile count
+
 __device__ __forceinline__ void load_chunk(const uint8_t *__restrict__ T, uint64_t p0, uint32_t (&c)[17])
 {
     const uint4 v = *reinterpret_cast<const uint4 *>(T + p0);
@@ -206,22 +214,37 @@ __device__ __forceinline__ uint32_t carry_from_right(bool has, uint32_t first_va
 // 0.38 ms of a 23 ms build, and this kernel reads every byte of the text anyway while it waits for its vector
 // unit: it reads the first src_tiles tiles (all but the text's last 32 bytes or so) from the caller's buffer and
 // stores them into the copy as it goes; only the tail was copied beforehand.  (src == nullptr: T is complete.)
+#ifndef SX_CLS_GRID
+#define SX_CLS_GRID 4096u // workgroups of cls_types_kernel (1 GiB of DNA: 1024 0.79 ms, 2048 0.75, 4096 0.655, 16384 0.66)
+#endif
+// ASC: the text's ascents are counted per symbol pair (d, c), d < c < ASC, as well (0: not; 5: four letters; 8).
+template <int ASC>
 __global__ __launch_bounds__(kBlock) void cls_types_kernel(
     uint8_t *__restrict__ T, uint64_t n, const uint8_t *__restrict__ tile_first, uint32_t ntiles,
     uint16_t *__restrict__ lmsbits, uint32_t *__restrict__ tile_lms, uint32_t *__restrict__ tile_last,
-    uint32_t *__restrict__ g_hist /* 3 * 256 */, const uint8_t *__restrict__ src, uint32_t src_tiles)
+    uint32_t *__restrict__ g_hist /* 3 * 256, kClsAscAt: 64 ascent counts */, const uint8_t *__restrict__ src, uint32_t src_tiles)
 {
     __shared__ uint32_t h[3][256];
+    __shared__ uint32_t h_asc[64];
     __shared__ uint32_t lds[2 * kWavesPerBlock];
     __shared__ uint32_t last_s[kBlock];
     const int t = (int)threadIdx.x;
     h[0][t] = 0;
     h[1][t] = 0;
     h[2][t] = 0;
+    if (t < 64) h_asc[t] = 0;
     __syncthreads();
     uint32_t cnt_all[8], cnt_s[8], cnt_lms[8]; // symbols below 8: all / S-type / LMS positions of this thread so far
 #pragma unroll
     for (int a = 0; a < 8; ++a) cnt_all[a] = cnt_s[a] = cnt_lms[a] = 0;
+    // ascents: positions q with text[q] = d < text[q + 1] = c, per pair (the induced-sort passes over at most 8 buckets
+    // place the S-type predecessors of L-type entries by them: sx_induce.hip); pair (d, c) at (c - 1)(c - 2) / 2 + d - 1,
+    // two pairs a register in 16-bit fields: a thread sees 16 positions of at most 256 tiles (2^20 tiles, SX_CLS_GRID
+    // workgroups; sx_classify does not ask where a workgroup would walk over 4095), and the kernel has no registers to spare (80 without these counts, 110 with one each for 21 pairs)
+    constexpr int kAscPairs = ASC > 2 ? (ASC - 1) * (ASC - 2) / 2 : 0;
+    uint32_t cnt_asc[kAscPairs / 2 + 1];
+#pragma unroll
+    for (int a = 0; a < kAscPairs / 2 + 1; ++a) cnt_asc[a] = 0;
     // A workgroup walks over many tiles and adds its histograms to the global ones once at the end: a global
     // atomic per tile and symbol (262 144 tiles on 15 addresses at 1 GiB of DNA) serialises at the memory side
     // and was most of this kernel's time.
@@ -326,6 +349,24 @@ __global__ __launch_bounds__(kBlock) void cls_types_kernel(
             SX_CLS_COUNT(0) SX_CLS_COUNT(1) SX_CLS_COUNT(2) SX_CLS_COUNT(3)
             SX_CLS_COUNT(4) SX_CLS_COUNT(5) SX_CLS_COUNT(6) SX_CLS_COUNT(7)
 #undef SX_CLS_COUNT
+            if constexpr (ASC > 2) {
+                // the planes of the right neighbours: one position down, the chunk's 17th symbol on top
+                const uint32_t n0 = ((b0 >> 1) & 0x7FFFu) | ((b16 & 1u) << 15), n1 = ((b1 >> 1) & 0x7FFFu) | (((b16 >> 1) & 1u) << 15),
+                               n2 = ((b2 >> 1) & 0x7FFFu) | (((b16 >> 2) & 1u) << 15);
+                const uint32_t is_d[7] = {0u, plane_eq<1>(b0, b1, b2) & 0xFFFFu, plane_eq<2>(b0, b1, b2) & 0xFFFFu,
+                                          plane_eq<3>(b0, b1, b2) & 0xFFFFu, plane_eq<4>(b0, b1, b2) & 0xFFFFu,
+                                          plane_eq<5>(b0, b1, b2) & 0xFFFFu, plane_eq<6>(b0, b1, b2) & 0xFFFFu};
+#define SX_CLS_ASC(C)                                                                                                  \
+    if constexpr ((C) < ASC) {                                                                                         \
+        const uint32_t nx = plane_eq<C>(n0, n1, n2);                                                                   \
+        _Pragma("unroll") for (int d = 1; d < (C); ++d) {                                                              \
+            constexpr int base = ((C) - 1) * ((C) - 2) / 2 - 1;                                                        \
+            cnt_asc[(base + d) >> 1] += (uint32_t)__popc(is_d[d] & nx) << (16 * ((base + d) & 1));                      \
+        }                                                                                                              \
+    }
+                SX_CLS_ASC(2) SX_CLS_ASC(3) SX_CLS_ASC(4) SX_CLS_ASC(5) SX_CLS_ASC(6) SX_CLS_ASC(7)
+#undef SX_CLS_ASC
+            }
         } else {
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
@@ -334,6 +375,8 @@ __global__ __launch_bounds__(kBlock) void cls_types_kernel(
                     atomicAdd(&h[0][ch], 1u);
                     if (!((smask >> i) & 1u)) atomicAdd(&h[1][ch], 1u);
                     if ((lmsmask >> i) & 1u) atomicAdd(&h[2][ch], 1u);
+                    const uint32_t nx = p0 + i + 1 < n ? (w[(i + 1) >> 2] >> (8 * ((i + 1) & 3))) & 0xFFu : 0u;
+                    if (ch != 0 && ch < nx && nx < (uint32_t)ASC) atomicAdd(&h_asc[ch * 8 + nx], 1u);
                 }
             }
         }
@@ -381,7 +424,21 @@ __global__ __launch_bounds__(kBlock) void cls_types_kernel(
             if (z) atomicAdd(&h[2][a], z);
         }
     }
+    if constexpr (ASC > 2) {
+#pragma unroll
+        for (int cc = 2; cc < ASC; ++cc) {
+#pragma unroll
+            for (int d = 1; d < cc; ++d) {
+                const int idx = (cc - 1) * (cc - 2) / 2 + d - 1;
+                uint32_t x = (cnt_asc[idx >> 1] >> (16 * (idx & 1))) & 0xFFFFu;
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, kWave);
+                if (lane_id() == 0 && x) atomicAdd(&h_asc[d * 8 + cc], x);
+            }
+        }
+    }
     __syncthreads();
+    if (t < 64 && h_asc[t]) atomicAdd(&g_hist[kClsAscAt + t], h_asc[t]);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const uint32_t v = h[k][t];
@@ -389,9 +446,6 @@ __global__ __launch_bounds__(kBlock) void cls_types_kernel(
     }
 }
 
-#ifndef SX_CLS_GRID
-#define SX_CLS_GRID 4096u // workgroups of cls_types_kernel (1 GiB of DNA: 1024 0.79 ms, 2048 0.75, 4096 0.655, 16384 0.66)
-#endif
 // ---- pass 4: sample flags ---------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void samp_flags_kernel(const uint16_t *__restrict__ lmsbits, uint64_t n,
                                                             const uint32_t *__restrict__ tile_prev, uint32_t W,
@@ -502,7 +556,7 @@ size_t sx_text_scratch_bytes(uint64_t n)
     b += 2 * (ntiles * kBlock * 2 + 256); // lmsbits, sampbits
     b += 5 * ntiles * 4 + 256;            // tile_u32
     b += ntiles + 256;                    // tile_first
-    b += 3 * 256 * 4 + 256 + 256;         // hist, scalars
+    b += 3 * 256 * 4 + 256 + 256 + 256;   // hist, ascent counts, scalars
     return b + 4096;
 }
 
@@ -537,7 +591,8 @@ int sx_symbol_histogram(sx_ctx *ctx, const uint8_t *T, uint64_t n, uint32_t *d_s
     return sx_readback(ctx, d_scratch256, 256, h_out);
 }
 
-int sx_classify(sx_ctx *ctx, uint8_t *T, uint64_t n, sx_arena &arena, sx_text_info &ti, const uint8_t *src, uint32_t src_tiles)
+int sx_classify(sx_ctx *ctx, uint8_t *T, uint64_t n, sx_arena &arena, sx_text_info &ti, const uint8_t *src, uint32_t src_tiles,
+                uint32_t asc_syms)
 {
     ti.T = T;
     ti.n = n;
@@ -547,23 +602,33 @@ int sx_classify(sx_ctx *ctx, uint8_t *T, uint64_t n, sx_arena &arena, sx_text_in
     ti.sampbits = arena.take<uint16_t>((size_t)ti.ntiles * kBlock);
     ti.tile_u32 = arena.take<uint32_t>((size_t)ti.ntiles * 5);
     ti.tile_first = arena.take<uint8_t>(ti.ntiles);
-    ti.d_hist = arena.take<uint32_t>(3 * 256 + 16); // (+ the count of open tiles)
+    ti.d_hist = arena.take<uint32_t>(kClsAscAt + 64); // (+ the count of open tiles, + the ascent counts)
     ti.d_scalar = arena.take<uint32_t>(16);
     if (!ti.lmsbits || !ti.sampbits || !ti.tile_u32 || !ti.tile_first || !ti.d_hist || !ti.d_scalar)
         return sx_fail_msg(ctx, SX_E_INTERNAL, "classify: arena too small");
     uint32_t *tile_lms = ti.tile_u32, *tile_last = ti.tile_u32 + ti.ntiles;
-    SX_CHECK(hipMemsetAsync(ti.d_hist, 0, (3 * 256 + 1) * sizeof(uint32_t), ctx->stream));
+    SX_CHECK(hipMemsetAsync(ti.d_hist, 0, (kClsAscAt + 64) * sizeof(uint32_t), ctx->stream));
+    const uint32_t cls_grid = ti.ntiles < SX_CLS_GRID ? ti.ntiles : SX_CLS_GRID;
+    // (more than 8 symbols: nobody asks; the kernel's 16-bit counts hold 16 positions of 4095 tiles a workgroup)
+    if (asc_syms > 8 || sx_div_up(ti.ntiles, cls_grid ? cls_grid : 1u) > 4095u) asc_syms = 0;
     const dim3 grid(ti.ntiles), block(kBlock);
     sx_launch(ctx, SX_KC_CLASSIFY, ti.N / 4, cls_first_kernel, grid, dim3(kWave), (const uint8_t *)T, n, ti.tile_first, ti.d_hist + 3 * 256, src, src_tiles);
     sx_launch(ctx, SX_KC_CLASSIFY, ti.ntiles, cls_resolve_kernel, dim3(sx_div_up(ti.ntiles, kBlock * 16)), block, ti.tile_first,
               ti.ntiles);
-    sx_launch(ctx, SX_KC_CLASSIFY, ti.N + ti.N / 8 + (src ? (uint64_t)src_tiles * kClsTile : 0), cls_types_kernel,
-              dim3(ti.ntiles < SX_CLS_GRID ? ti.ntiles : SX_CLS_GRID), block, T, n, (const uint8_t *)ti.tile_first, ti.ntiles, ti.lmsbits, tile_lms,
-              tile_last, ti.d_hist, src, src_tiles);
+#define SX_CLS_TYPES(ASC)                                                                                              \
+    sx_launch(ctx, SX_KC_CLASSIFY, ti.N + ti.N / 8 + (src ? (uint64_t)src_tiles * kClsTile : 0), cls_types_kernel<ASC>,   \
+              dim3(cls_grid), block, T, n, (const uint8_t *)ti.tile_first, ti.ntiles,                                  \
+              ti.lmsbits, tile_lms, tile_last, ti.d_hist, src, src_tiles)
+    if (asc_syms == 0) SX_CLS_TYPES(0);
+    else if (asc_syms <= 5) SX_CLS_TYPES(5);
+    else SX_CLS_TYPES(8);
+#undef SX_CLS_TYPES
     // read the three histograms back: the host drives the bucket loop
-    uint32_t h[3 * 256 + 1];
-    SX_TRY(sx_readback(ctx, ti.d_hist, 3 * 256 + 1, h));
+    uint32_t h[kClsAscAt + 64];
+    SX_TRY(sx_readback(ctx, ti.d_hist, kClsAscAt + 64, h));
     ti.open_tiles = h[3 * 256];
+    ti.asc_syms = asc_syms;
+    memcpy(ti.h_asc, h + kClsAscAt, sizeof ti.h_asc);
     memcpy(ti.h_all, h, sizeof ti.h_all);
     memcpy(ti.h_l, h + 256, sizeof ti.h_l);
     memcpy(ti.h_lms, h + 512, sizeof ti.h_lms);

@@ -87,6 +87,7 @@ struct sx_ctx {
     int induce_batch_off = 0; // SX_FLAG_INDUCE_BATCH_OFF
     int induce_attended = 0;  // SX_FLAG_INDUCE_ATTENDED
     int induce_no_hoist = 0;  // SX_FLAG_INDUCE_NO_HOIST
+    int induce_early_s_off = 0; // SX_FLAG_INDUCE_EARLY_S_OFF
     int text_keys_off = 0;    // SX_FLAG_TEXT_KEYS_OFF
     int long_subbuckets_off = 0; // SX_FLAG_LONG_SUBBUCKETS_OFF
     int local_sort_lean_off = 0; // SX_FLAG_LOCAL_SORT_LEAN_OFF

@@ -206,6 +206,7 @@ int sx_child_begin(sx_ctx *ctx, sx_ctx **out)
     c->induce_batch_min = ctx->induce_batch_min;
     c->induce_attended = ctx->induce_attended;
     c->induce_no_hoist = ctx->induce_no_hoist;
+    c->induce_early_s_off = ctx->induce_early_s_off;
     c->text_keys_off = ctx->text_keys_off;
     c->long_subbuckets_off = ctx->long_subbuckets_off;
     c->local_sort_lean_off = ctx->local_sort_lean_off;
@@ -395,6 +396,10 @@ int sx_ctx_set_flag(sx_ctx *ctx, int flag, int value)
     }
     if (flag == SX_FLAG_LOCATE_CHUNK_ROWS) {
         ctx->locate_chunk_rows = value > 0 ? value : 0;
+        return 0;
+    }
+    if (flag == SX_FLAG_INDUCE_EARLY_S_OFF) {
+        ctx->induce_early_s_off = value ? 1 : 0;
         return 0;
     }
     if (flag == SX_FLAG_INDUCE_NO_HOIST) {

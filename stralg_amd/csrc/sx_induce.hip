@@ -11,7 +11,9 @@
 //   bucket c, round k : the entries round k-1 induced into c itself
 //                       (same symbol to the left: a run of c's)
 //   then              : the bucket's other region (LMS seeds in the L pass,
-//                       the L region in the S pass)
+//                       the L region in the S pass -- at most 8 buckets: what is
+//                       left of it, the L pass's large rounds have placed the S-type
+//                       predecessors of the entries they scanned: sx_induce_small.hpp)
 //
 // A round is a stable multi-way split by text[SA[i]-1]: gather + per-tile
 // histogram, per-bucket offsets, stable scatter to the bucket cursors.  The
@@ -38,7 +40,7 @@ size_t sx_induce_scratch_bytes(uint64_t N, uint32_t sigma)
     // (at most 8 buckets: (round, bucket) count rows of the eight-rounds-at-a-time form, over the largest bucket's tiles)
     return (size_t)N * 8 + 256 + (size_t)(N / 2 + 2) * 8 + 256 + (size_t)N + 256 + (size_t)sigma * ntiles * 4 + 256 +
            (size_t)kBatchRows * (ntiles + 1) * 4 + 1024 +
-           (sigma > 8 ? (size_t)(wtiles + wtiles / 256 + 4) * 1024 + 512 : 0) + 16384 +
+           (sigma > 8 ? (size_t)(wtiles + wtiles / 256 + 4) * 1024 + 512 : 0) + 16384 + 1024 +
            // the up-front rounds of more than 8 buckets: tile counts of all buckets' regions, the bigram matrix and its tables
            (sigma > 8 ? ((size_t)N / kWideTile + 520) * 1024 + 5 * 65536 * 4 + 16384 : 0);
 }
@@ -86,6 +88,7 @@ template <class WT> struct induce_state {
     uint32_t *hoist_tot;     // the current pass's up-front entries from bucket c to bucket d, [c][d]
     uint32_t *hoist_err;     // set by bucket_begin_kernel when a cursor is not where the bigram counts put it
     uint32_t hoist_from;     // the last bucket of the pass that had rounds of its own (L pass: 0, S pass: nk - 1 before the first)
+    uint32_t *early;         // at most 8 buckets, early_s on: the words of sx_induce_small.hpp (kEarly*); else null
     int next_c;              // unattended pass: the next bucket with rounds of its own, whose head the tail kernel of this one takes (-1: none)
     int begun_c;             // the bucket whose rounds the last tail kernel has opened (-1: none)
 };
@@ -116,19 +119,21 @@ void launch_round(induce_state<WT> &st, const uint32_t *srcP, const WT *srcW, in
         // (entries of the suffix array have their symbol bytes next to them; the LMS seeds only their windows)
         const uint8_t *srcB = srcP == st.SA ? (const uint8_t *)st.BW : nullptr;
         const uint64_t src_len = srcP == st.SA ? st.N : st.m;
+        // (early_s: the L pass's rounds over an L region place the S-type predecessors too, while they continue its prefix)
+        uint32_t *early = mode == MODE_L_FROM_L ? st.early : nullptr;
         if (srcB)
             sx_launch(ctx, SX_KC_INDUCE_GATHER, 0, induce_count_bytes_kernel, dim3(grid), dim3(kBlock), srcB, (const uint32_t *)rin, rev,
-                      mode, c, st.hist, st.stride, st.nk, chain_max, src_len);
+                      mode, c, st.hist, st.stride, st.nk, chain_max, src_len, early ? 1 : 0);
         else
             sx_launch(ctx, SX_KC_INDUCE_GATHER, 0, induce_count_kernel<WT, 3>, dim3(grid), dim3(kBlock), srcW, srcB,
                       (const uint32_t *)rin, rev, mode, c, st.cfg, st.hist, st.stride, st.nk, chain_max, src_len);
         sx_launch(ctx, SX_KC_INDUCE_SCAN, (uint64_t)tiles_bound * st.nk * 8, induce_offsets_kernel, dim3(st.nk),
-                  dim3(kRowThreads), st.hist, st.stride, (const uint32_t *)rin, rout, cur, nxt, dir, c, chain_max, only3 ? 1 : 0);
+                  dim3(kRowThreads), st.hist, st.stride, (const uint32_t *)rin, rout, cur, nxt, dir, c, chain_max, only3 ? 1 : 0, early);
         {
 #define SX_SCATTER_SMALL(M)                                                                                            \
     sx_launch(ctx, SX_KC_INDUCE_SCATTER, 0, induce_scatter_small_kernel<WT, M>, dim3(grid), dim3(kBlock), srcP, srcW, \
               (const uint32_t *)rin, c, st.cfg, st.T, (const uint32_t *)st.hist, st.stride, cur, st.SA, st.WN, st.BW, st.nk, \
-              chain_max)
+              chain_max, (const uint32_t *)early)
             switch (mode) { // mode fixes the scan direction (rev) and the side the buckets grow to (dir)
             case MODE_L_FROM_L: SX_SCATTER_SMALL(MODE_L_FROM_L); break;
             case MODE_L_FROM_LMS: SX_SCATTER_SMALL(MODE_L_FROM_LMS); break;
@@ -284,6 +289,10 @@ int run_self_rounds(induce_state<WT> &st, uint32_t fixed_bound, uint32_t region_
         if (st.unattended && !resume) spec = by_share;
         else if (by_share > spec) spec = by_share;
     }
+    // early_s with the eight-rounds form switched off: every self round of the L pass is a launch of its own as far as the
+    // queue goes (only such rounds place S-type predecessors, and the first non-empty round the tail kernel takes ends that)
+    const bool place_rounds = st.early && mode == MODE_L_FROM_L && !st.batch_on;
+    if (place_rounds) spec = kMaxSpec;
     // Every batch ends with the tail kernel, which runs kTailIters rounds unless the range empties first, and a round
     // consumes one symbol of every run it follows: a bucket cannot need more batches than this (a device fault that
     // keeps the range alive must not keep the host here for ever).
@@ -345,7 +354,8 @@ int run_self_rounds(induce_state<WT> &st, uint32_t fixed_bound, uint32_t region_
             // that finds nothing to do still costs 5 us, and there were 20 of them per bucket)
             double expect = 2.0 * (double)bound_tiles;
             for (int i = 0; i < k; ++i) expect *= share;
-            const uint32_t likely = expect < (double)bound_tiles ? (uint32_t)expect : bound_tiles;
+            uint32_t likely = expect < (double)bound_tiles ? (uint32_t)expect : bound_tiles;
+            if (place_rounds && likely < 1) likely = 1;
             // (the first round of a large region is large beyond doubt: the three-launch form alone)
             const bool sure = first && k == 0 && (uint64_t)region_entries > 16ull * st.chain_max;
             launch_round<WT>(st, st.SA, st.WN, k, k + 1, tb, first && k == 0 ? bound_tiles : likely, rev, mode, c, dir, 1, 0, sure ? 1 : 0);
@@ -484,6 +494,27 @@ int induce_typed(sx_ctx *ctx, const sx_text_info &ti, uint32_t sigma, const uint
     st.poison = arena.take<uint32_t>(4);
     if (!st.poison) return sx_fail_msg(ctx, SX_E_INTERNAL, "induce: arena too small");
     st.host_poison = ctx->h_pin + 1040;
+    // early_s (sx_induce_small.hpp): the blocks of the S regions that the L pass fills, from the text's ascent counts
+    st.early = nullptr;
+    uint32_t h_early[kEarlyWords];
+    if (st.small_alphabet && !ctx->induce_early_s_off && ti.asc_syms >= nk) {
+        memset(h_early, 0, sizeof h_early);
+        for (uint32_t d = 1; d < nk; ++d) {
+            uint32_t below = begin[d + 1]; // block (c, d) ends where the blocks of the buckets above c begin
+            for (uint32_t c = nk - 1; c > d; --c) {
+                below -= ti.h_asc[d * 8 + c];
+                h_early[kEarlyCur + c * 8 + d] = h_early[kEarlyBase + c * 8 + d] = below;
+            }
+            if (begin[d + 1] - below > ti.h_all[d] - ti.h_l[d])
+                return sx_fail_msg(ctx, SX_E_INTERNAL, "induce: more ascents from a symbol than it has S-type positions");
+        }
+        for (uint32_t c = 0; c < nk; ++c)
+            for (uint32_t d = 0; d < 8; ++d) h_early[kEarlyUpto + c * 8 + d] = begin[c];
+        st.early = arena.take<uint32_t>(kEarlyWords);
+        if (!st.early) return sx_fail_msg(ctx, SX_E_INTERNAL, "induce: arena too small");
+        SX_CHECK(hipMemcpyAsync(st.early, h_early, sizeof h_early, hipMemcpyHostToDevice, ctx->stream));
+    }
+    uint64_t early_placed = 0, early_rescan = 0; // S-type entries the L pass placed; L-type entries the S pass still scanned
     // More than 8 buckets: every bucket's other-region round (its LMS seeds in the L pass, its L-type entries in the S
     // pass) up front, all buckets in one count / offsets / scatter, placed by the text's bigram counts (hoist_*_kernel)
     st.hoist = (!st.small_alphabet && !ctx->induce_no_hoist) ? 1 : 0;
@@ -557,10 +588,11 @@ int induce_typed(sx_ctx *ctx, const sx_text_info &ti, uint32_t sigma, const uint
     // behind the S pass the look-back time-out word and the hoisted rounds' error word
     auto pass_end = [&](int pass, bool with_stop, uint32_t (&rec)[4], uint32_t (&cur)[256], uint32_t (&tail)[3]) -> int {
         const uint32_t *src[4];
-        uint32_t cnt[4], page[4 + 256 + 3];
+        uint32_t cnt[4], page[4 + 256 + 3 + kEarlyFlag];
         int k = 0;
         if (with_stop) src[k] = (const uint32_t *)st.poison, cnt[k++] = 4;
         src[k] = (const uint32_t *)st.cursor[st.par], cnt[k++] = nk;
+        if (pass == 0 && st.early) src[k] = (const uint32_t *)st.early, cnt[k++] = kEarlyFlag; // (fills, bases, prefix ends)
         if (pass == 1) {
             src[k] = (const uint32_t *)st.status, cnt[k++] = 2;
             if (st.hoist) src[k] = (const uint32_t *)st.hoist_err, cnt[k++] = 1;
@@ -569,6 +601,13 @@ int induce_typed(sx_ctx *ctx, const sx_text_info &ti, uint32_t sigma, const uint
         const uint32_t *q = page;
         if (with_stop) memcpy(rec, q, sizeof rec), q += 4;
         memcpy(cur, q, nk * sizeof(uint32_t)), q += nk;
+        if (pass == 0 && st.early) {
+            early_placed = early_rescan = 0;
+            for (uint32_t c = 1; c < nk; ++c) {
+                for (uint32_t d = 1; d < c; ++d) early_placed += q[kEarlyCur + c * 8 + d] - q[kEarlyBase + c * 8 + d];
+                early_rescan += begin[c] + ti.h_l[c] - q[kEarlyUpto + c * 8 + c];
+            }
+        }
         tail[0] = tail[1] = tail[2] = 0;
         if (pass == 1) {
             tail[0] = q[0], tail[1] = q[1];
@@ -637,7 +676,16 @@ int induce_typed(sx_ctx *ctx, const sx_text_info &ti, uint32_t sigma, const uint
                     return sx_fail_msg(ctx, SX_E_INTERNAL, "induce S: bucket did not receive its S-type count");
                 st.unattended = unattended_ok ? 1 : 0;
             }
-            if (ti.h_l[c] && !st.hoist) {
+            if (ti.h_l[c] && !st.hoist && st.early) {
+                // what the L pass's placing rounds left of the L region (usually little: both forms are queued), then the
+                // cursors below c skip what those rounds placed
+                const uint32_t *stop = (const uint32_t *)(st.unattended ? st.poison : nullptr);
+                sx_launch(ctx, SX_KC_INDUCE_SCAN, 0, early_range_kernel, dim3(1), dim3(1), st.ranges, (const uint32_t *)st.early, c,
+                          begin[c] + ti.h_l[c], st.tickets, 1u, stop);
+                launch_round<WT>(st, SA, st.WN, 0, -1, sx_div_up(ti.h_l[c], kIndTile), sx_div_up(ti.h_l[c], kIndTile), 1,
+                                 MODE_S_FROM_L, c, -1, 0, 0, 0);
+                sx_launch(ctx, SX_KC_INDUCE_SCAN, 0, early_skip_kernel, dim3(1), dim3(8), st.cursor[st.par], st.early, c, stop);
+            } else if (ti.h_l[c] && !st.hoist) {
                 sx_launch(ctx, SX_KC_INDUCE_SCAN, 0, set_range_kernel, dim3(1), dim3(1), st.ranges, begin[c],
                           begin[c] + ti.h_l[c], (const uint32_t *)st.cursor[st.par], (int)c, 0, st.tickets, 1u,
                           (const uint32_t *)(st.unattended ? st.poison : nullptr));
@@ -677,15 +725,17 @@ int induce_typed(sx_ctx *ctx, const sx_text_info &ti, uint32_t sigma, const uint
         if (pass == 1 && tail[2]) return sx_fail_msg(ctx, SX_E_INTERNAL, "induce: a bucket's cursor is not where the text's bigram counts put it");
     }
 
+    ctx->stats.induce_early_s = (uint32_t)early_placed;
     if (ctx->prof_on) {
         // Algorithmic bytes of the two passes (the launches themselves were queued with bounds, not
         // sizes): the L pass scans every L-type entry and every LMS seed, the S pass every entry but
-        // the sentinel's; every suffix is written once.  The counting launches read the symbol bytes (windows for the seeds), the
+        // the sentinel's (early_s: of the L-type entries only those the L pass's placing rounds did not cover); every
+        // suffix is written once.  The counting launches read the symbol bytes (windows for the seeds), the
         // scatter launches the (position, window) pairs and write a symbol byte along; the few entries that went through the chained
         // rounds are booked here too.
         uint64_t n_l = 0;
         for (uint32_t c = 0; c < nk; ++c) n_l += ti.h_l[c];
-        const uint64_t scanned = n_l + ti.m + (N - 1);
+        const uint64_t scanned = n_l + ti.m + (N - 1) - (st.early ? n_l - early_rescan : 0u);
         // (with events around one class only -- bench.py's timed region -- that class alone is booked)
         if (ctx->prof_only < 0 || ctx->prof_only == SX_KC_INDUCE_GATHER)
             ctx->kstat[SX_KC_INDUCE_GATHER].alg_bytes += (scanned - ti.m) + ti.m * sizeof(WT); // symbol bytes; seeds: windows

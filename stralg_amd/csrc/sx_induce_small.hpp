@@ -19,7 +19,8 @@ namespace sx {
 __global__ __launch_bounds__(kBlock) void induce_count_bytes_kernel(const uint8_t *__restrict__ srcB,
                                                                     const uint32_t *__restrict__ range_in, int rev, int mode,
                                                                     uint32_t c, uint32_t *__restrict__ hist, uint32_t stride,
-                                                                    uint32_t nkeys, uint32_t chain_max, uint64_t src_len)
+                                                                    uint32_t nkeys, uint32_t chain_max, uint64_t src_len,
+                                                                    int keep_all /* the rows of the symbols the mode does not accept keep their counts too (early_s) */)
 {
     const uint32_t lo = range_in[0], len = range_in[1] - lo;
     if (len <= chain_max) return;
@@ -73,7 +74,7 @@ __global__ __launch_bounds__(kBlock) void induce_count_bytes_kernel(const uint8_
             odd = wave_total_packed(odd);
             if ((uint32_t)lane < nkeys && lane < 8) {
                 const uint32_t v = (uint32_t)(((lane & 1) ? odd : even) >> (16 * (lane >> 1))) & 0xFFFFu;
-                hist[(uint64_t)lane * stride + tile] = lane != 0 && induce_accept((uint32_t)lane, c, mode) ? v : 0u;
+                hist[(uint64_t)lane * stride + tile] = lane != 0 && (keep_all || induce_accept((uint32_t)lane, c, mode)) ? v : 0u;
             }
         }
     }
@@ -155,6 +156,24 @@ __global__ __launch_bounds__(kBlock) void induce_count_kernel(const WT *__restri
     }
 }
 
+// ---- S-type predecessors placed by the L pass (early_s) ------------------------------------------------------------
+// An L-type entry p of bucket c induces exactly one predecessor: L-type when text[p-1] >= c, S-type otherwise -- and the
+// S pass used to scan the whole L region again for the second kind.  The S-type ones induced from bucket c's L region
+// into bucket d < c fill the lower part of one block of d's S region, in the forward order of c's L region:
+//     base(c, d) = begin[d + 1] - sum over c' >= c of A[d][c'],   A[d][c'] = #{q : text[q] = d < text[q+1] = c'}
+// (the S pass fills d's S region from the top down, one block per source bucket c' = nk-1 ... d+1, the entries induced
+// from c''s S region on top of those induced from its L region; sa_is.c:245-263).  So a three-launch round of the L pass
+// that continues the scanned prefix of its bucket's L region places them there itself, while it holds the entries: the
+// counting launch keeps the rows of the symbols below c, the offsets launch hands out the round's first slot per symbol
+// and advances the block's fill, the scatter accepts every entry.  The first non-empty round another form takes (chained
+// launch, eight rounds at a time, tail kernel, run jump, a carry-on from the middle) ends the prefix for good; the S
+// pass scans the rest of the L region as before, writes downwards onto the slots above what was placed, and only then
+// lowers the cursors past them (early_skip_kernel).
+// The device words: [c * 8 + d]: next slot of block (c, d); its base; the L region's scanned prefix end as workgroup d of
+// the offsets launch saw it (one word per workgroup: they all take the same decision, none reads what another writes);
+// the round's flag and first slots for the scatter.
+constexpr uint32_t kEarlyCur = 0, kEarlyBase = 64, kEarlyUpto = 128, kEarlyFlag = 192, kEarlySlot = 193, kEarlyWords = 208;
+
 // one workgroup (1024 threads) per destination bucket: exclusive prefix over the tiles, cursor update
 __global__ __launch_bounds__(kRowThreads) void induce_offsets_kernel(uint32_t *__restrict__ hist, uint32_t stride,
                                                                 const uint32_t *__restrict__ range_in,
@@ -162,7 +181,8 @@ __global__ __launch_bounds__(kRowThreads) void induce_offsets_kernel(uint32_t *_
                                                                 const uint32_t *__restrict__ cursor_cur,
                                                                 uint32_t *__restrict__ cursor_nxt, int dir, uint32_t c,
                                                                 uint32_t chain_max,
-                                                                int only_form /* no chained launch follows (chain_max = 0): an empty range is carried on here */)
+                                                                int only_form /* no chained launch follows (chain_max = 0): an empty range is carried on here */,
+                                                                uint32_t *early /* L pass from the L region, early_s on: the words above; else null */)
 {
     __shared__ uint32_t lds[kRowPieces * kRowWaves];
     const uint32_t len = range_in[1] - range_in[0];
@@ -178,6 +198,22 @@ __global__ __launch_bounds__(kRowThreads) void induce_offsets_kernel(uint32_t *_
     const uint32_t total = wide_scan_row_inplace(hist + (uint64_t)key * stride, ntiles, lds);
     if (threadIdx.x == 0) {
         const uint32_t cur = cursor_cur[key];
+        if (early) {
+            // the round places S-type predecessors iff it continues the scanned prefix of bucket c's L region
+            uint32_t *upto = early + kEarlyUpto + c * 8u + key;
+            const bool placing = *upto == range_in[0];
+            if (placing) *upto = range_in[1];
+            if (key == c) early[kEarlyFlag] = placing ? 1u : 0u;
+            if (key < c) { // an S-type destination: bucket `key`'s own cursor stays
+                cursor_nxt[key] = cur;
+                if (placing) {
+                    const uint32_t slot = early[kEarlyCur + c * 8u + key];
+                    early[kEarlySlot + key] = slot;
+                    early[kEarlyCur + c * 8u + key] = slot + total;
+                }
+                return;
+            }
+        }
         cursor_nxt[key] = dir > 0 ? cur + total : cur - total;
         if (key == c && range_out) {
             range_out[0] = dir > 0 ? cur : cur - total;
@@ -199,7 +235,7 @@ __global__ __launch_bounds__(kBlock) void induce_scatter_small_kernel(
     const uint32_t *__restrict__ srcP, const WT *__restrict__ srcW, const uint32_t *__restrict__ range_in, uint32_t c,
     wnd_cfg cfg, const uint8_t *__restrict__ T, const uint32_t *__restrict__ offs, uint32_t stride,
     const uint32_t *__restrict__ cursor_cur, uint32_t *__restrict__ SA, WT *__restrict__ WN, uint8_t *__restrict__ BW,
-    uint32_t nkeys, uint32_t chain_max)
+    uint32_t nkeys, uint32_t chain_max, const uint32_t *__restrict__ early /* MODE_L_FROM_L, early_s on; else null */)
 {
     constexpr bool kRev = MODE == MODE_S_FROM_S || MODE == MODE_S_FROM_L; // the S pass scans right to left
     constexpr uint64_t kField16 = 0x00FF00FF00FF00FFull;
@@ -215,7 +251,10 @@ __global__ __launch_bounds__(kBlock) void induce_scatter_small_kernel(
     const uint32_t lo = range_in[0], len = range_in[1] - lo;
     if (len <= chain_max) return;
     const uint32_t ntiles = (len + kIndTile - 1) / kIndTile;
-    const uint32_t base_d = t < (int)nkeys ? cursor_cur[t] : 0u;
+    // (early_s: the offsets launch said that this round places the S-type predecessors too -- every entry has a destination,
+    //  a symbol below c goes to the round's first slot of its block, upwards like the others)
+    const bool place = MODE == MODE_L_FROM_L && early != nullptr && early[kEarlyFlag] != 0u; // uniform
+    const uint32_t base_d = t < (int)nkeys ? ((place && (uint32_t)t < c) ? early[kEarlySlot + t] : cursor_cur[t]) : 0u;
     for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) { // uniform per workgroup
         // this tile's first destination per bucket: asked for now, needed after the scan
         const uint32_t pre = t < (int)nkeys ? offs[(uint64_t)t * stride + tile] : 0u;
@@ -249,7 +288,7 @@ __global__ __launch_bounds__(kBlock) void induce_scatter_small_kernel(
 #pragma unroll
         for (int k = 0; k < kIndItems; ++k) {
             const uint32_t ch = wnd_first<WT>(W[k], cfg) & 7u;
-            ok[k] = P[k] != 0 && induce_accept(ch, c, MODE);
+            ok[k] = P[k] != 0 && (place || induce_accept(ch, c, MODE));
             dig[k] = ch;
             rnk[k] = (uint32_t)(cnt >> (8u * ch)) & 0xFFu;
             cnt += (uint64_t)(ok[k] ? 1u : 0u) << (8u * ch);
@@ -326,6 +365,31 @@ __global__ __launch_bounds__(kBlock) void induce_scatter_small_kernel(
         }
         __syncthreads(); // LDS is reused by the next tile
     }
+}
+
+// S pass, bucket c's L region with early_s on: the round's range begins where the L pass's placing rounds ended
+// (set_range_kernel otherwise: the tickets, the unattended pass's stop word)
+__global__ void early_range_kernel(uint32_t *range, const uint32_t *__restrict__ early, uint32_t c, uint32_t hi, uint32_t *tickets,
+                                   uint32_t ntickets, const uint32_t *poison)
+{
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        for (uint32_t i = 0; i < ntickets; ++i) tickets[i] = 0;
+        uint32_t lo = early[kEarlyUpto + c * 8u + c];
+        if (poison && poison[0]) lo = hi = 0;
+        range[0] = lo;
+        range[1] = hi;
+    }
+}
+
+// ... and behind that round the cursors of the buckets d < c skip what the L pass placed below the round's entries
+// (once: the block's base follows its fill; a stopped unattended pass leaves it to the host's carry-on)
+__global__ void early_skip_kernel(uint32_t *__restrict__ cursor, uint32_t *__restrict__ early, uint32_t c, const uint32_t *poison)
+{
+    const uint32_t d = threadIdx.x;
+    if (blockIdx.x != 0 || d == 0 || d >= c || (poison && poison[0])) return;
+    const uint32_t fill = early[kEarlyCur + c * 8u + d], base = early[kEarlyBase + c * 8u + d];
+    cursor[d] -= fill - base;
+    early[kEarlyBase + c * 8u + d] = fill;
 }
 
 // ---- the same for at most 8 buckets, without a ballot ---------------------------------------------------------

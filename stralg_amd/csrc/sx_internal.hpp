@@ -44,6 +44,8 @@ struct sx_text_info {
     uint32_t *d_hist;   // device: 3 * 256: all symbols, L-type symbols, LMS symbols
     uint32_t *d_scalar; // device: a few u32 results (totals)
     uint32_t h_all[256], h_l[256], h_lms[256];
+    uint32_t asc_syms;  // ascents were counted for symbols below this (0: not counted)
+    uint32_t h_asc[64]; // [d * 8 + c]: positions q with text[q] = d < text[q + 1] = c
     uint32_t open_tiles; // classification tiles made of one symbol whose run goes on: runs of 4096 symbols and more
     uint32_t maxc;      // largest symbol present
     uint64_t m;         // LMS positions incl. the sentinel
@@ -56,8 +58,9 @@ int sx_symbol_histogram(sx_ctx *ctx, const uint8_t *T, uint64_t n, uint32_t *d_s
 // carve the per-text scratch out of `arena`, run classification, read the histograms back.  src / src_tiles: the first
 // src_tiles classification tiles of T have not been copied from the caller's text `src` yet (16-byte aligned): the
 // classification reads them there and writes them into T as it goes (sx_classify.hip: cls_types_kernel)
+// asc_syms: the text's ascents are counted per symbol pair too, for symbols below it (at most 8; 0: not counted)
 int sx_classify(sx_ctx *ctx, uint8_t *T, uint64_t n, sx_arena &arena, sx_text_info &ti, const uint8_t *src = nullptr,
-                uint32_t src_tiles = 0);
+                uint32_t src_tiles = 0, uint32_t asc_syms = 0);
 // sample flags for piece width W (symbols between consecutive samples <= W); sets ti.M
 int sx_sample_flags(sx_ctx *ctx, sx_text_info &ti, uint32_t W);
 // compaction of the sample positions; pos[M], is_lms[M]
