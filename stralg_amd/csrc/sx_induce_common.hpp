@@ -22,6 +22,9 @@ constexpr uint32_t kTailEntries = (uint32_t)kTailTile;
 constexpr uint32_t kTailMulti = 4; // more than 8 buckets: tiles of a round the tail kernel takes one after the other
 
 enum { MODE_L_FROM_L = 0, MODE_L_FROM_LMS = 1, MODE_S_FROM_S = 2, MODE_S_FROM_L = 3 };
+// (host) mode fixes the scan direction (rev) and the side the buckets grow to (dir): what a launch hands its kernel
+static inline int induce_rev(int mode) { return mode == MODE_S_FROM_S || mode == MODE_S_FROM_L ? 1 : 0; }
+static inline int induce_dir(int mode) { return induce_rev(mode) ? -1 : +1; }
 __device__ __forceinline__ void tail_report(uint32_t lo, uint32_t hi, uint32_t c, uint32_t *poison, uint32_t *host_poison);
 
 __device__ __forceinline__ bool induce_accept(uint32_t ch, uint32_t c, int mode)
