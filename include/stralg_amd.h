@@ -298,6 +298,16 @@ int sx_sam_layout_dev(sx_ctx *ctx, const sx_sam_batch *batch, uint64_t *d_byte_o
  * from run to run. */
 int sx_sam_emit_dev(sx_ctx *ctx, const sx_sam_batch *batch, const uint64_t *d_byte_offsets, uint64_t total_bytes, uint64_t byte_lo,
                     uint64_t byte_hi, uint8_t *d_out);
+/* The same with a FLAG per read: d_read_flags[q] (device memory, n_reads entries, indexed like d_name_off) is printed in
+ * decimal as the second field of every line of read q; NULL: every line has FLAG 0, the calls are sx_sam_layout_dev and
+ * sx_sam_emit_dev and give their bytes. */
+typedef struct sx_sam_batch_ex {
+    sx_sam_batch batch;
+    const uint16_t *d_read_flags;
+} sx_sam_batch_ex;
+int sx_sam_layout_dev_ex(sx_ctx *ctx, const sx_sam_batch_ex *batch, uint64_t *d_byte_offsets, uint64_t *total_bytes_out);
+int sx_sam_emit_dev_ex(sx_ctx *ctx, const sx_sam_batch_ex *batch, const uint64_t *d_byte_offsets, uint64_t total_bytes, uint64_t byte_lo,
+                       uint64_t byte_hi, uint8_t *d_out);
 
 /* A FASTQ image indexed on the host (one pass of memchr over the file): read q's name is names[name_off[q] ..
  * name_off[q+1]), its sequence seqs[seq_off[q] ..), its quality quals[qual_off[q] ..): the raw bytes of the record's
@@ -338,6 +348,21 @@ typedef struct sx_map_record {
  * (pattern length + edits < 2^15), so that limit cannot be met here. */
 int sx_map_reads_stream(sx_ctx *ctx, const sx_map_record *records, uint32_t n_records, const uint8_t *fastq, size_t fastq_len,
                         int edits, sx_sink_fn sink, void *user);
+/* Both strands.  rc(read) has the read's name, its sequence reversed and complemented and its quality
+ * string reversed; the complement acts on the raw bytes, before any record's remap table, keeps the case and maps
+ * A<->T, C<->G, U->A, R<->Y, K<->M, B<->V, D<->H; N, S, W and every other byte (also '*', '-', 0x80 .. 0xFF) stay.  With
+ * SX_MAP_BOTH_STRANDS the text is, per read in file order, the lines of the read (FLAG 0) and then the lines that rc(read)
+ * would print as a read of its own, with FLAG 16 in place of 0: POS is the leftmost forward coordinate, CIGAR, SEQ and QUAL
+ * are in forward orientation, as SAM prescribes for a reverse-strand hit -- the reference mapper's stdout on the FASTQ file
+ * "read0, rc(read0), read1, rc(read1), ..." with the second field of the odd entries' lines rewritten.  The limit becomes
+ * 2 x reads x records < 2^32; the reads take twice the device memory.  flags == 0: sx_map_reads_stream, byte for byte and
+ * launch for launch; unknown bits: SX_E_ARG. */
+enum { SX_MAP_BOTH_STRANDS = 1 };
+int sx_map_reads_stream_ex(sx_ctx *ctx, const sx_map_record *records, uint32_t n_records, const uint8_t *fastq, size_t fastq_len,
+                           int edits, uint32_t flags, sx_sink_fn sink, void *user);
+/* the limit of a mapping call on its reads and records: 0, or SX_E_ARG when reads x records (twice that with
+ * SX_MAP_BOTH_STRANDS) does not stay below 2^32 or flags has unknown bits */
+int sx_map_reads_limit(uint64_t n_reads, uint64_t n_records, uint32_t flags);
 
 /* ---- a device-resident index: build from FASTA once, map many read sets ---------------- */
 /* sx_fastq_index on the device: the FASTQ image lies in device memory (len bytes), the six arrays of sx_fastq are
@@ -351,6 +376,14 @@ typedef struct sx_fastq_dev {
     uint64_t name_bytes, seq_bytes, qual_bytes;     /* = the offsets' last entries */
 } sx_fastq_dev;
 int sx_fastq_index_dev(sx_ctx *ctx, const uint8_t *d_image, uint64_t len, sx_fastq_dev *out);
+/* The read set of both strands: from the device arrays of sx_fastq_index_dev (`in`, left as it is) a set of 2 x count reads
+ * in device memory of its own (release with sx_fastq_dev_free; the contract of sx_fastq_dev holds: 16-byte aligned byte
+ * arrays followed by 16 readable bytes): read 2q is read q, read 2q + 1 is rc(read q) (sx_map_reads_stream_ex).
+ * d_flags_out (device memory of the caller, 2 x count entries): 0 for the even reads, 16 for the odd ones.  The same
+ * input gives the same bytes from run to run.  SX_E_ARG: 2 x count or a doubled offset does not fit 32 bits (answered
+ * before anything is launched), or the offsets' last entries are not in->name_bytes, seq_bytes, qual_bytes; after an
+ * error *out holds no memory. */
+int sx_fastq_strands_dev(sx_ctx *ctx, const sx_fastq_dev *in, sx_fastq_dev *out, uint16_t *d_flags_out);
 void sx_fastq_dev_free(sx_fastq_dev *fq);
 
 /* The index: for every record, in FASTA file order, its name, N (symbols + sentinel), sigma, remap table, the remapped
@@ -382,6 +415,9 @@ int sx_index_add_record(sx_ctx *ctx, sx_index *idx, const sx_index_source *sourc
  * sx_map_reads_stream. */
 int sx_index_map_reads(sx_ctx *ctx, const sx_index *idx, const uint8_t *fastq, size_t fastq_len, int edits, sx_sink_fn sink,
                        void *user);
+/* the same with the flags of sx_map_reads_stream_ex (SX_MAP_BOTH_STRANDS) */
+int sx_index_map_reads_ex(sx_ctx *ctx, const sx_index *idx, const uint8_t *fastq, size_t fastq_len, int edits, uint32_t flags,
+                          sx_sink_fn sink, void *user);
 typedef struct sx_index_record {
     const char *name; /* valid until the index changes or is destroyed */
     uint64_t N;

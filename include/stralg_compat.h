@@ -252,6 +252,10 @@ void stralg_amd_free_approx_result(struct stralg_amd_approx_result *result);
  * .bwttables file), matches in the iterator's order.  names[r] is the record name of tables[r].  Returns 0, or the code of
  * sx_map_reads_stream (SX_E_MALFORMED for a FASTQ stream outside the contract of sx_fastq_index) with a line on stderr. */
 int stralg_amd_map_reads(struct bwt_table *const *tables, const char *const *names, size_t n, FILE *fastq, int edits, FILE *sam);
+/* the same with the flags of sx_map_reads_stream_ex (stralg_amd.h): SX_MAP_BOTH_STRANDS maps every read and its reverse
+ * complement, the latter's lines with FLAG 16 */
+int stralg_amd_map_reads_ex(struct bwt_table *const *tables, const char *const *names, size_t n, FILE *fastq, int edits, uint32_t flags,
+                            FILE *sam);
 
 /* A device-resident index (stralg_amd.h sx_index) on the calling thread's context: index a genome once, map many read
  * sets.  _from_fasta_image builds every record's tables on the device from the bytes of a FASTA file; _read loads the
@@ -270,6 +274,8 @@ void stralg_amd_index_free(struct sx_index *idx);
  * the blocks, for records of at most 7 letters -- NULL where a record has more) */
 struct sx_index *stralg_amd_index_from_fasta_image_ex(const uint8_t *fasta, size_t len, bool include_reverse, uint32_t flags);
 struct sx_index *stralg_amd_index_read_ex(FILE *f, uint32_t flags);
+/* stralg_amd_index_map with the flags of sx_map_reads_stream_ex (SX_MAP_BOTH_STRANDS) */
+int stralg_amd_index_map_ex(const struct sx_index *idx, FILE *fastq, int edits, uint32_t flags, FILE *sam);
 
 #ifdef __cplusplus
 }

@@ -43,6 +43,7 @@ SX_SECTION_SAM = 3
 SX_FLAG_SAM_BATCH_READS, SX_FLAG_SAM_WINDOW_BYTES = 18, 19
 SX_FLAG_LOCATE_CHUNK_ROWS = 20
 SX_FLAG_INDUCE_EARLY_S_OFF = 21
+SX_MAP_BOTH_STRANDS = 1
 
 
 class SamBatch(C.Structure):
@@ -52,6 +53,11 @@ class SamBatch(C.Structure):
                 ("d_names", C.c_void_p), ("d_seqs", C.c_void_p), ("d_quals", C.c_void_p),
                 ("d_name_off", C.c_void_p), ("d_seq_off", C.c_void_p), ("d_qual_off", C.c_void_p), ("n_reads", C.c_uint32),
                 ("d_rnames", C.c_void_p), ("d_rname_off", C.c_void_p), ("n_records", C.c_uint32)]
+
+
+class SamBatchEx(C.Structure):
+    """include/stralg_amd.h sx_sam_batch_ex: a batch and a FLAG per read (device memory, uint16)"""
+    _fields_ = [("batch", SamBatch), ("d_read_flags", C.c_void_p)]
 
 
 class Fastq(C.Structure):
@@ -169,9 +175,15 @@ def load(path=None):
         "sx_build_tables_stream": (C.c_int, [vp, u8p, C.c_uint64, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]),
         "sx_sam_layout_dev": (C.c_int, [vp, C.POINTER(SamBatch), u64p, C.POINTER(C.c_uint64)]),
         "sx_sam_emit_dev": (C.c_int, [vp, C.POINTER(SamBatch), u64p, C.c_uint64, C.c_uint64, C.c_uint64, u8p]),
+        "sx_sam_layout_dev_ex": (C.c_int, [vp, C.POINTER(SamBatchEx), u64p, C.POINTER(C.c_uint64)]),
+        "sx_sam_emit_dev_ex": (C.c_int, [vp, C.POINTER(SamBatchEx), u64p, C.c_uint64, C.c_uint64, C.c_uint64, u8p]),
         "sx_fastq_index": (C.c_int, [u8p, C.c_size_t, C.POINTER(Fastq)]),
         "sx_fastq_free": (None, [C.POINTER(Fastq)]),
         "sx_map_reads_stream": (C.c_int, [vp, C.POINTER(MapRecord), C.c_uint32, u8p, C.c_size_t, C.c_int, SINK_FN, C.c_void_p]),
+        "sx_map_reads_stream_ex": (C.c_int, [vp, C.POINTER(MapRecord), C.c_uint32, u8p, C.c_size_t, C.c_int, C.c_uint32, SINK_FN,
+                                             C.c_void_p]),
+        "sx_map_reads_limit": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint32]),
+        "sx_fastq_strands_dev": (C.c_int, [vp, C.POINTER(FastqDev), C.POINTER(FastqDev), vp]),
         "sx_fastq_index_dev": (C.c_int, [vp, u8p, C.c_uint64, C.POINTER(FastqDev)]),
         "sx_fastq_dev_free": (None, [C.POINTER(FastqDev)]),
         "sx_index_build_fasta": (C.c_int, [vp, u8p, C.c_uint64, C.c_int, C.POINTER(vp)]),
@@ -179,6 +191,7 @@ def load(path=None):
         "sx_index_from_sources": (C.c_int, [vp, C.POINTER(IndexSource), C.c_uint32, C.POINTER(vp)]),
         "sx_index_add_record": (C.c_int, [vp, vp, C.POINTER(IndexSource), C.c_int]),
         "sx_index_map_reads": (C.c_int, [vp, vp, u8p, C.c_size_t, C.c_int, SINK_FN, C.c_void_p]),
+        "sx_index_map_reads_ex": (C.c_int, [vp, vp, u8p, C.c_size_t, C.c_int, C.c_uint32, SINK_FN, C.c_void_p]),
         "sx_index_info": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
         "sx_index_record_info": (C.c_int, [vp, C.c_uint32, C.POINTER(IndexRecord)]),
         "sx_index_destroy": (None, [vp]),
@@ -255,6 +268,8 @@ EXPORTS = ["sx_device_count", "sx_device_numa_node", "sx_ctx_create", "sx_ctx_de
            "sx_occ_packed_bytes", "sx_occ_packed_build_dev", "sx_occ_packed_expand_dev", "sx_bwt_exact_search_packed_dev",
            "sx_bwt_approx_search_packed_dev", "sx_index_is_packed",
            "sx_sa_sample_bytes", "sx_sa_sample_build_dev", "sx_sa_locate_rows_dev", "sx_index_record_samples", "sx_index_expand_sa",
+           "sx_sam_layout_dev_ex", "sx_sam_emit_dev_ex", "sx_map_reads_stream_ex", "sx_map_reads_limit", "sx_fastq_strands_dev",
+           "sx_index_map_reads_ex",
            "sx_synth_dev", "sx_membw_probe", "sx_prim_sort_pairs_dev", "sx_prim_exclusive_sum_dev", "sx_prim_classify_dev"]
 
 

@@ -227,24 +227,30 @@ class Context:
 
     # ---- SAM text of search hits (the read mapper's output) ---------------------------------
     def sam_batch(self, d_hits, n_hits, d_sa, sa_len, d_names, d_name_off, d_seqs, d_seq_off, d_quals, d_qual_off, n_reads,
-                  d_rnames, d_rname_off, n_records=1, d_sa_list=None, d_sa_len_list=None):
+                  d_rnames, d_rname_off, n_records=1, d_sa_list=None, d_sa_len_list=None, d_read_flags=None):
         """sx_sam_batch over device tensors (the caller keeps them alive): hits as sx_bwt_approx_search_dev leaves them,
         the suffix array, the reads' flat name / sequence / quality bytes with n_reads + 1 offsets each (uint32), the
-        record names likewise."""
-        return _lib.SamBatch(_ptr(d_hits), n_hits, _ptr(d_sa), sa_len, _ptr(d_sa_list), _ptr(d_sa_len_list), _ptr(d_names),
-                             _ptr(d_seqs), _ptr(d_quals), _ptr(d_name_off), _ptr(d_seq_off), _ptr(d_qual_off), n_reads,
-                             _ptr(d_rnames), _ptr(d_rname_off), n_records)
+        record names likewise.  d_read_flags (uint16, n_reads entries): a FLAG per read, and the batch is an
+        sx_sam_batch_ex that sam_layout_dev / sam_emit_dev send to the _ex calls."""
+        batch = _lib.SamBatch(_ptr(d_hits), n_hits, _ptr(d_sa), sa_len, _ptr(d_sa_list), _ptr(d_sa_len_list), _ptr(d_names),
+                              _ptr(d_seqs), _ptr(d_quals), _ptr(d_name_off), _ptr(d_seq_off), _ptr(d_qual_off), n_reads,
+                              _ptr(d_rnames), _ptr(d_rname_off), n_records)
+        return batch if d_read_flags is None else _lib.SamBatchEx(batch, _ptr(d_read_flags))
 
     def sam_layout_dev(self, batch, d_byte_offsets):
-        """sx_sam_layout_dev: d_byte_offsets (n_hits + 1 uint64) <- every hit's first output byte; returns the text's length"""
+        """sx_sam_layout_dev (sx_sam_layout_dev_ex for a batch with flags): d_byte_offsets (n_hits + 1 uint64) <- every
+        hit's first output byte; returns the text's length"""
         total = C.c_uint64(0)
-        self._check(self.lib.sx_sam_layout_dev(self.h, C.byref(batch), _ptr(d_byte_offsets), C.byref(total)), "sx_sam_layout_dev")
+        name = "sx_sam_layout_dev_ex" if isinstance(batch, _lib.SamBatchEx) else "sx_sam_layout_dev"
+        self._check(getattr(self.lib, name)(self.h, C.byref(batch), _ptr(d_byte_offsets), C.byref(total)), name)
         return int(total.value)
 
     def sam_emit_dev(self, batch, d_byte_offsets, total_bytes, byte_lo, byte_hi, d_out):
-        """sx_sam_emit_dev: bytes [byte_lo, byte_hi) of the text into d_out (uint8, 16-byte aligned)"""
-        self._check(self.lib.sx_sam_emit_dev(self.h, C.byref(batch), _ptr(d_byte_offsets), total_bytes, byte_lo, byte_hi,
-                                             _ptr(d_out)), "sx_sam_emit_dev")
+        """sx_sam_emit_dev (sx_sam_emit_dev_ex for a batch with flags): bytes [byte_lo, byte_hi) of the text into d_out
+        (uint8, 16-byte aligned)"""
+        name = "sx_sam_emit_dev_ex" if isinstance(batch, _lib.SamBatchEx) else "sx_sam_emit_dev"
+        self._check(getattr(self.lib, name)(self.h, C.byref(batch), _ptr(d_byte_offsets), total_bytes, byte_lo, byte_hi, _ptr(d_out)),
+                    name)
 
     def fastq_index(self, data):
         """sx_fastq_index of the bytes of a FASTQ file: (names, name_off, seqs, seq_off, quals, qual_off) as numpy arrays
@@ -284,13 +290,40 @@ class Context:
         self._check(self.lib.sx_fastq_index_dev(self.h, _ptr(d_image) if length else None, int(length), C.byref(fq)),
                     "sx_fastq_index_dev")
         try:
-            n = int(fq.count)
-            out = []
-            for data_p, off_p, nbytes in ((fq.d_names, fq.d_name_off, fq.name_bytes), (fq.d_seqs, fq.d_seq_off, fq.seq_bytes),
-                                          (fq.d_quals, fq.d_qual_off, fq.qual_bytes)):
-                out.append(self.download(data_p, nbytes, np.uint8))
-                out.append(self.download(off_p, n + 1, np.uint32))
-            return tuple(out), n
+            return self._fastq_dev_arrays(fq), int(fq.count)
+        finally:
+            self.lib.sx_fastq_dev_free(C.byref(fq))
+
+    def _fastq_dev_arrays(self, fq, spare=0):
+        """the six arrays of an sx_fastq_dev read back; spare: so many bytes behind each byte array come with it"""
+        n = int(fq.count)
+        out = []
+        for data_p, off_p, nbytes in ((fq.d_names, fq.d_name_off, fq.name_bytes), (fq.d_seqs, fq.d_seq_off, fq.seq_bytes),
+                                      (fq.d_quals, fq.d_qual_off, fq.qual_bytes)):
+            out.append(self.download(data_p, nbytes + spare, np.uint8))
+            out.append(self.download(off_p, n + 1, np.uint32))
+        return tuple(out)
+
+    def fastq_strands_dev(self, d_image, length, d_flags, spare=0):
+        """sx_fastq_index_dev of a FASTQ image in device memory, then sx_fastq_strands_dev of its arrays:
+        ((names, name_off, seqs, seq_off, quals, qual_off), flags, count) of the read set of both strands (read 2q is read q,
+        read 2q + 1 its reverse complement), read back as numpy arrays as fastq_index_dev returns them.  d_flags: device
+        memory of the caller for the flags, uint16, twice as many entries as the image has reads at least (length // 4
+        entries are enough for any image); flags: its first `count` entries read back, 0 and 16.  spare: so many of the readable bytes
+        behind each byte array are read back with it (the contract promises 16)."""
+        fq, both = _lib.FastqDev(), _lib.FastqDev()
+        self._check(self.lib.sx_fastq_index_dev(self.h, _ptr(d_image) if length else None, int(length), C.byref(fq)),
+                    "sx_fastq_index_dev")
+        try:
+            room = d_flags.numel() * d_flags.element_size() if hasattr(d_flags, "numel") else d_flags.nbytes
+            if room < 4 * int(fq.count):
+                raise ValueError(f"d_flags has {room} bytes, the image's {int(fq.count)} reads take four each")
+            self._check(self.lib.sx_fastq_strands_dev(self.h, C.byref(fq), C.byref(both), _ptr(d_flags)), "sx_fastq_strands_dev")
+            try:
+                flags = self.download(_ptr(d_flags), int(both.count), np.uint16)
+                return self._fastq_dev_arrays(both, spare), flags, int(both.count)
+            finally:
+                self.lib.sx_fastq_dev_free(C.byref(both))
         finally:
             self.lib.sx_fastq_dev_free(C.byref(fq))
 
@@ -322,10 +355,11 @@ class Context:
         self._check(self.lib.sx_sa_locate_rows_dev(self.h, _ptr(d_c), _ptr(d_occ), N, sigma, _ptr(d_marks), _ptr(d_values),
                                                    int(sa_sample).bit_length() - 1, row_lo, row_hi, _ptr(d_out)), "sx_sa_locate_rows_dev")
 
-    def map_reads_stream(self, records, fastq, edits, sink):
+    def map_reads_stream(self, records, fastq, edits, sink, both_strands=False):
         """sx_map_reads_stream: records = [(name bytes, BwtTable), ...] in the mapper's list order; sink(bytes) receives the
         SAM text window after window.  sink=None discards the text without touching it and returns [(time.perf_counter(),
-        bytes)] per window (measurement)."""
+        bytes)] per window (measurement).  both_strands (sx_map_reads_stream_ex, SX_MAP_BOTH_STRANDS): behind the lines of
+        every read come those of its reverse complement, with FLAG 16."""
         recs = (_lib.MapRecord * max(1, len(records)))()
         keep = []
         for r, (name, t) in enumerate(records):
@@ -347,10 +381,14 @@ class Context:
                 return 1
 
         cb = _lib.SINK_FN(_sink)
-        rc = self.lib.sx_map_reads_stream(self.h, recs, len(records), _ptr(buf) if buf.size else None, buf.size, edits, cb, None)
+        if both_strands:
+            rc = self.lib.sx_map_reads_stream_ex(self.h, recs, len(records), _ptr(buf) if buf.size else None, buf.size, edits,
+                                                 _lib.SX_MAP_BOTH_STRANDS, cb, None)
+        else:
+            rc = self.lib.sx_map_reads_stream(self.h, recs, len(records), _ptr(buf) if buf.size else None, buf.size, edits, cb, None)
         if failure:
             raise failure[0]
-        self._check(rc, "sx_map_reads_stream")
+        self._check(rc, "sx_map_reads_stream_ex" if both_strands else "sx_map_reads_stream")
         return seen if sink is None else None
 
     # ---- FASTA ingest and remap ------------------------------
@@ -632,10 +670,10 @@ class Index:
             raise StralgAmdError("the index is closed")
         return self.h
 
-    def map_reads(self, fastq, edits, sink=None, ctx=None):
+    def map_reads(self, fastq, edits, sink=None, ctx=None, both_strands=False):
         """sx_index_map_reads: the SAM text of every match of every read of a FASTQ image within `edits` edits, byte for
         byte stralg_amd.map_reads' (the reference mapper's stdout).  sink=None returns the text; sink(bytes) receives it
-        window after window and None is returned."""
+        window after window and None is returned.  both_strands: as in stralg_amd.map_reads (sx_index_map_reads_ex)."""
         ctx = ctx or self.ctx
         buf = np.frombuffer(bytes(fastq), dtype=np.uint8)
         chunks, failure = [], []
@@ -650,13 +688,20 @@ class Index:
                 return 1
 
         cb = _lib.SINK_FN(_sink)
-        rc = ctx.lib.sx_index_map_reads(ctx.h, self._handle(), _ptr(buf) if buf.size else None, buf.size, edits, cb, None)
+        rc = self._map(ctx, buf, edits, both_strands, cb)
         if failure:
             raise failure[0]
-        ctx._check(rc, "sx_index_map_reads")
+        ctx._check(rc, "sx_index_map_reads_ex" if both_strands else "sx_index_map_reads")
         return b"".join(chunks) if sink is None else None
 
-    def map_reads_discard(self, fastq, edits, ctx=None):
+    def _map(self, ctx, buf, edits, both_strands, cb):
+        """the return code of sx_index_map_reads, or of sx_index_map_reads_ex with SX_MAP_BOTH_STRANDS"""
+        image = _ptr(buf) if buf.size else None
+        if both_strands:
+            return ctx.lib.sx_index_map_reads_ex(ctx.h, self._handle(), image, buf.size, edits, _lib.SX_MAP_BOTH_STRANDS, cb, None)
+        return ctx.lib.sx_index_map_reads(ctx.h, self._handle(), image, buf.size, edits, cb, None)
+
+    def map_reads_discard(self, fastq, edits, ctx=None, both_strands=False):
         """the same with a sink that does not touch the text: [(time.perf_counter(), bytes)] per window (measurement)"""
         ctx = ctx or self.ctx
         buf = np.frombuffer(bytes(fastq), dtype=np.uint8)
@@ -667,8 +712,7 @@ class Index:
             return 0
 
         cb = _lib.SINK_FN(_sink)
-        ctx._check(ctx.lib.sx_index_map_reads(ctx.h, self._handle(), _ptr(buf) if buf.size else None, buf.size, edits, cb, None),
-                   "sx_index_map_reads")
+        ctx._check(self._map(ctx, buf, edits, both_strands, cb), "sx_index_map_reads_ex" if both_strands else "sx_index_map_reads")
         return seen
 
     def write(self, sink, ctx=None):
@@ -1017,13 +1061,16 @@ def bwt_approx_search(bwt_table, patterns, edits, ctx=None):
     return approx_matches(hits, hit_off, [p.size for p in pats], bwt_table.sa.array)
 
 
-def map_reads(fasta, fastq, edits, ctx=None):
+def map_reads(fasta, fastq, edits, ctx=None, both_strands=False):
     """The reference read mapper (tools/readmappers/bwt_readmapper: -p genome.fa, then -d edits genome.fa reads.fq) on the
     bytes of a FASTA and a FASTQ file: its stdout, the SAM lines of every match of every read in every record within
     `edits` edits, byte for byte.  Per read the records come in the mapper's list order, which is the FASTA file's order
-    (the iterator yields the records last first, -p writes them so, and -d prepends each to its list)."""
+    (the iterator yields the records last first, -p writes them so, and -d prepends each to its list).
+    both_strands: behind the lines of every read come the lines of its reverse complement (the name, the sequence reversed
+    and complemented, the quality string reversed) as the reference prints them for such a read, with FLAG 16 in place of 0;
+    the reference itself maps one strand only."""
     ctx = ctx or default_context()
     records = [(name, build_complete_table(seq, True, ctx)) for name, seq in ctx.fasta_records(fasta)]
     chunks = []
-    ctx.map_reads_stream(records, fastq, edits, chunks.append)
+    ctx.map_reads_stream(records, fastq, edits, chunks.append, both_strands=both_strands)
     return b"".join(chunks)

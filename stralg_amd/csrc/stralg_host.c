@@ -1744,6 +1744,12 @@ static int sam_to_file(void *user, int section, const void *data, size_t bytes)
 
 int stralg_amd_map_reads(struct bwt_table *const *tables, const char *const *names, size_t n, FILE *fastq, int edits, FILE *sam)
 {
+    return stralg_amd_map_reads_ex(tables, names, n, fastq, edits, 0, sam);
+}
+
+int stralg_amd_map_reads_ex(struct bwt_table *const *tables, const char *const *names, size_t n, FILE *fastq, int edits, uint32_t flags,
+                            FILE *sam)
+{
     if ((n && (!tables || !names)) || !fastq || !sam || n > 0xFFFFFFFFu) {
         fprintf(stderr, "stralg_amd_map_reads: malformed arguments\n");
         return SX_E_ARG;
@@ -1778,7 +1784,7 @@ int stralg_amd_map_reads(struct bwt_table *const *tables, const char *const *nam
         recs[r].remap = t->remap_table->table;
     }
     sx_ctx *ctx = thread_ctx();
-    rc = sx_map_reads_stream(ctx, recs, (uint32_t)n, image, len, edits, sam_to_file, sam);
+    rc = sx_map_reads_stream_ex(ctx, recs, (uint32_t)n, image, len, edits, flags, sam_to_file, sam);
     if (rc != 0) fprintf(stderr, "stralg_amd_map_reads: failed (code %d): %s\n", rc, sx_last_error(ctx));
 done:
     free(recs);
@@ -1869,7 +1875,9 @@ int stralg_amd_index_write(FILE *f, const sx_index *idx)
     return rc;
 }
 
-int stralg_amd_index_map(const sx_index *idx, FILE *fastq, int edits, FILE *sam)
+int stralg_amd_index_map(const sx_index *idx, FILE *fastq, int edits, FILE *sam) { return stralg_amd_index_map_ex(idx, fastq, edits, 0, sam); }
+
+int stralg_amd_index_map_ex(const sx_index *idx, FILE *fastq, int edits, uint32_t flags, FILE *sam)
 {
     if (!idx || !fastq || !sam) {
         fprintf(stderr, "stralg_amd_index_map: malformed arguments\n");
@@ -1879,7 +1887,7 @@ int stralg_amd_index_map(const sx_index *idx, FILE *fastq, int edits, FILE *sam)
     uint8_t *image = read_rest(fastq, &len);
     if (!image) return SX_E_NOMEM;
     sx_ctx *ctx = thread_ctx();
-    const int rc = sx_index_map_reads(ctx, idx, image, len, edits, sam_to_file, sam);
+    const int rc = sx_index_map_reads_ex(ctx, idx, image, len, edits, flags, sam_to_file, sam);
     if (rc != 0) fprintf(stderr, "stralg_amd_index_map: failed (code %d): %s\n", rc, sx_last_error(ctx));
     free(image);
     return rc;

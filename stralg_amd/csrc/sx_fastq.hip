@@ -10,12 +10,15 @@
 //   5. three exclusive scans turn the lengths into the offset arrays,
 //   6. a pass over the image in order sends every byte of a first, second or fourth line to its place: a workgroup
 //      holds its tile's line starts in LDS, a lane finds the line of its four bytes by a search in them.
+// sx_fastq_strands_dev makes the read set of both strands of these arrays (below).
 // Where a byte goes is a function of the scans alone (no atomics place anything): the same image gives the same bytes.
 #include "sx_common.hpp"
 #include "sx_device.hpp"
 #include "sx_bytes16.hpp"
 #include "sx_hostio.hpp"
 #include "sx_scan.hpp"
+
+#include <algorithm>
 
 namespace sx {
 
@@ -152,6 +155,122 @@ __global__ __launch_bounds__(kBlock) void fq_scatter_kernel(const uint8_t *__res
     }
 }
 
+// ---- the read set of both strands -------------------------------------------------------------
+// Read 2q of the output is read q, read 2q + 1 its reverse complement, so pair q takes the bytes [2 off[q], 2 off[q + 1]) of
+// an output array and nothing needs a scan.  The work is cut by output bytes, not by reads: a workgroup makes a tile of
+// 4096 bytes of one of the three arrays (blockIdx.y: names, sequences, qualities), a lane 16 of them in one store, whatever
+// the reads' lengths are (10 to 2046 bytes: a lane a read would leave a wave waiting for its longest read, a wave a read
+// would leave five lanes in six idle on a short one).  The workgroup finds the pairs at its tile's ends by a search in the
+// offsets, a lane the pair of its first byte by a search between them, and walks on from there.
+constexpr uint32_t kStrandPer = 16, kStrandTile = kBlock * kStrandPer;
+
+struct StrandArgs {
+    const uint8_t *names, *seqs, *quals;
+    const uint32_t *name_off, *seq_off, *qual_off;
+    uint8_t *names_out, *seqs_out, *quals_out;
+    uint32_t name_bytes, seq_bytes, qual_bytes; // of the input; the doubled ones fit 32 bits
+    uint32_t count;
+};
+
+// the complement of a FASTQ byte: letters keep their case, every byte outside the table stays
+__device__ __forceinline__ uint32_t strand_complement(uint32_t c)
+{
+    const uint32_t low = c | 0x20u;
+    if (low < 'a' || low > 'z') return c;
+    uint32_t v;
+    switch (c & 0xDFu) {
+    case 'A': v = 'T'; break;
+    case 'C': v = 'G'; break;
+    case 'G': v = 'C'; break;
+    case 'T': v = 'A'; break;
+    case 'U': v = 'A'; break;
+    case 'R': v = 'Y'; break;
+    case 'Y': v = 'R'; break;
+    case 'K': v = 'M'; break;
+    case 'M': v = 'K'; break;
+    case 'B': v = 'V'; break;
+    case 'V': v = 'B'; break;
+    case 'D': v = 'H'; break;
+    case 'H': v = 'D'; break;
+    default: v = c & 0xDFu; break;
+    }
+    return v | (c & 0x20u);
+}
+
+// the last q in [lo, hi] with 2 off[q] <= j (2 off[lo] <= j)
+__device__ __forceinline__ uint32_t strand_pair_of(const uint32_t *__restrict__ off, uint32_t lo, uint32_t hi, uint64_t j)
+{
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo + 1u) / 2u;
+        if (2ull * off[mid] <= j) lo = mid;
+        else hi = mid - 1u;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(kBlock) void fq_strand_bytes_kernel(StrandArgs A)
+{
+    __shared__ uint8_t tab[kBlock]; // the second read's byte of a source byte (kBlock == 256)
+    static_assert(kBlock == 256, "one lane a table entry");
+    const uint32_t which = blockIdx.y, t = threadIdx.x;
+    const uint8_t *__restrict__ in = which == 0 ? A.names : which == 1 ? A.seqs : A.quals;
+    const uint32_t *__restrict__ off = which == 0 ? A.name_off : which == 1 ? A.seq_off : A.qual_off;
+    uint8_t *__restrict__ out = which == 0 ? A.names_out : which == 1 ? A.seqs_out : A.quals_out;
+    const uint32_t in_bytes = which == 0 ? A.name_bytes : which == 1 ? A.seq_bytes : A.qual_bytes;
+    const bool reversed = which != 0; // (a name is repeated as it is)
+    const uint64_t total = 2ull * in_bytes, tile0 = (uint64_t)blockIdx.x * kStrandTile;
+    if (tile0 >= total) return; // (the whole workgroup: the grid is the longest array's)
+    tab[t] = (uint8_t)(which == 1 ? strand_complement(t) : t);
+    const uint64_t tile_last = total - tile0 < kStrandTile ? total - 1u : tile0 + kStrandTile - 1u;
+    const uint32_t p0 = strand_pair_of(off, 0u, A.count - 1u, tile0), p1 = strand_pair_of(off, p0, A.count - 1u, tile_last);
+    __syncthreads();
+    const uint64_t j0 = tile0 + (uint64_t)t * kStrandPer;
+    if (j0 >= total) return;
+    uint32_t q = strand_pair_of(off, p0, p1, j0);
+    uint32_t b = off[q], e = off[q + 1];
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (uint32_t k = 0; k < kStrandPer; ++k) {
+        const uint64_t j = j0 + k;
+        if (j >= total) break; // (the bytes behind the array's end are zeros: they lie in its 16 spare bytes)
+        while (j >= 2ull * e && q + 1u < A.count) { // (the next pair; more than one step only over reads without a byte)
+            ++q;
+            b = e;
+            e = off[q + 1];
+        }
+        const uint32_t len = e >= b ? e - b : 0u, r = (uint32_t)(j - 2ull * b);
+        uint32_t c = 0;
+        if (r < len) { // the read itself
+            if (b + r < in_bytes) c = in[b + r];
+        } else if (r - len < len) { // its second strand
+            const uint32_t at = reversed ? e - 1u - (r - len) : b + (r - len);
+            if (at < in_bytes) c = tab[in[at]];
+        }
+        w[k >> 2] |= c << (8u * (k & 3u));
+    }
+    const uint4 v = {w[0], w[1], w[2], w[3]};
+    *reinterpret_cast<uint4 *>(out + j0) = v;
+}
+
+// off_out[2q] = 2 off[q], off_out[2q + 1] = 2 off[q] + the read's length, off_out[2 count] = 2 off[count]; the flags
+__global__ __launch_bounds__(kBlock) void fq_strand_offsets_kernel(StrandArgs A, uint32_t *__restrict__ name_off_out,
+                                                                   uint32_t *__restrict__ seq_off_out, uint32_t *__restrict__ qual_off_out,
+                                                                   uint16_t *__restrict__ flags_out)
+{
+    const uint64_t q = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (q > A.count) return;
+    const uint32_t nb = A.name_off[q], sb = A.seq_off[q], qb = A.qual_off[q];
+    name_off_out[2 * q] = 2u * nb;
+    seq_off_out[2 * q] = 2u * sb;
+    qual_off_out[2 * q] = 2u * qb;
+    if (q == A.count) return;
+    name_off_out[2 * q + 1] = nb + A.name_off[q + 1];
+    seq_off_out[2 * q + 1] = sb + A.seq_off[q + 1];
+    qual_off_out[2 * q + 1] = qb + A.qual_off[q + 1];
+    flags_out[2 * q] = 0;
+    flags_out[2 * q + 1] = 16;
+}
+
 } // namespace sx
 
 using namespace sx;
@@ -230,6 +349,63 @@ static int fastq_index_dev(sx_ctx *ctx, const uint8_t *d_image, uint64_t len, sx
     out->name_bytes = h[4], out->seq_bytes = h[5], out->qual_bytes = h[6];
     S.keep();
     return 0;
+}
+
+static int fastq_strands_dev(sx_ctx *ctx, const sx_fastq_dev *in, sx_fastq_dev *out, uint16_t *d_flags_out)
+{
+    sx_dev_scope S;
+    const uint32_t count = in->count;
+    SX_TRY(S.take(ctx, &out->d_name_off, 2 * (size_t)count + 1));
+    SX_TRY(S.take(ctx, &out->d_seq_off, 2 * (size_t)count + 1));
+    SX_TRY(S.take(ctx, &out->d_qual_off, 2 * (size_t)count + 1));
+    SX_TRY(S.take(ctx, &out->d_names, 2 * (size_t)in->name_bytes + 16));
+    SX_TRY(S.take(ctx, &out->d_seqs, 2 * (size_t)in->seq_bytes + 16));
+    SX_TRY(S.take(ctx, &out->d_quals, 2 * (size_t)in->qual_bytes + 16));
+    if (count == 0) {
+        SX_CHECK(hipMemsetAsync(out->d_name_off, 0, 4, ctx->stream));
+        SX_CHECK(hipMemsetAsync(out->d_seq_off, 0, 4, ctx->stream));
+        SX_CHECK(hipMemsetAsync(out->d_qual_off, 0, 4, ctx->stream));
+        SX_TRY(sx_sync(ctx));
+        S.keep();
+        return 0;
+    }
+    // the totals the kernels' bounds rest on are the caller's: they must be the offsets' last entries
+    const uint32_t *last[3] = {in->d_name_off + count, in->d_seq_off + count, in->d_qual_off + count};
+    const uint32_t one[3] = {1, 1, 1};
+    uint32_t h[3] = {0, 0, 0};
+    SX_TRY(sx_readback_ranges(ctx, last, one, 3, h));
+    if (h[0] != in->name_bytes || h[1] != in->seq_bytes || h[2] != in->qual_bytes)
+        return sx_fail_msg(ctx, SX_E_ARG, "both strands: the byte counts of the read set are not its offsets' last entries");
+    const StrandArgs A = {in->d_names,    in->d_seqs,     in->d_quals,    in->d_name_off,          in->d_seq_off,          in->d_qual_off,
+                          out->d_names,   out->d_seqs,    out->d_quals,   (uint32_t)in->name_bytes, (uint32_t)in->seq_bytes, (uint32_t)in->qual_bytes,
+                          count};
+    sx_launch(ctx, SX_KC_REMAP, (uint64_t)count * 38, fq_strand_offsets_kernel, dim3(sx_div_up((uint64_t)count + 1, kBlock)), dim3(kBlock), A,
+              out->d_name_off, out->d_seq_off, out->d_qual_off, d_flags_out);
+    const uint64_t most = std::max(in->name_bytes, std::max(in->seq_bytes, in->qual_bytes));
+    // (every byte of the input is read twice and written twice)
+    if (most)
+        sx_launch(ctx, SX_KC_REMAP, 4 * (in->name_bytes + in->seq_bytes + in->qual_bytes), fq_strand_bytes_kernel,
+                  dim3(sx_div_up(2 * most, kStrandTile), 3), dim3(kBlock), A);
+    SX_TRY(sx_sync(ctx));
+    out->count = 2 * count;
+    out->name_bytes = 2 * in->name_bytes, out->seq_bytes = 2 * in->seq_bytes, out->qual_bytes = 2 * in->qual_bytes;
+    S.keep();
+    return 0;
+}
+
+int sx_fastq_strands_dev(sx_ctx *ctx, const sx_fastq_dev *in, sx_fastq_dev *out, uint16_t *d_flags_out)
+{
+    if (!ctx || !in || !out || in == out) return SX_E_ARG;
+    memset(out, 0, sizeof *out);
+    if (!in->d_name_off || !in->d_seq_off || !in->d_qual_off || (in->count && (!in->d_names || !in->d_seqs || !in->d_quals || !d_flags_out)) ||
+        ((uintptr_t)d_flags_out & 1))
+        return sx_fail_msg(ctx, SX_E_ARG, "both strands: the six arrays of a read set and room for the flags are needed");
+    if (in->count > 0x7FFFFFFFu || in->name_bytes > 0x7FFFFFFFull || in->seq_bytes > 0x7FFFFFFFull || in->qual_bytes > 0x7FFFFFFFull)
+        return sx_fail_msg(ctx, SX_E_ARG, "both strands: twice the reads' count and bytes must fit 32 bits");
+    SX_CHECK(hipSetDevice(ctx->device));
+    const int rc = fastq_strands_dev(ctx, in, out, d_flags_out);
+    if (rc != 0) memset(out, 0, sizeof *out); // (what was allocated has been released)
+    return sx_nomem_of(rc);
 }
 
 int sx_fastq_index_dev(sx_ctx *ctx, const uint8_t *d_image, uint64_t len, sx_fastq_dev *out)

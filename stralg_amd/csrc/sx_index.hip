@@ -469,9 +469,16 @@ int sx_index_expand_sa(sx_ctx *ctx, const sx_index *idx, uint32_t record, uint64
 
 int sx_index_map_reads(sx_ctx *ctx, const sx_index *idx, const uint8_t *fastq, size_t fastq_len, int edits, sx_sink_fn sink, void *user)
 {
+    return sx_index_map_reads_ex(ctx, idx, fastq, fastq_len, edits, 0, sink, user);
+}
+
+int sx_index_map_reads_ex(sx_ctx *ctx, const sx_index *idx, const uint8_t *fastq, size_t fastq_len, int edits, uint32_t flags, sx_sink_fn sink,
+                          void *user)
+{
     if (!ctx || !idx || !sink || (fastq_len && !fastq)) return SX_E_ARG;
     SX_TRY(device_check(ctx, idx));
     if (edits < 0 || edits > SX_APPROX_MAX_EDITS) return sx_fail_msg(ctx, SX_E_ARG, "read mapping: edits must be in [0, 8]");
+    if (flags & ~(uint32_t)SX_MAP_BOTH_STRANDS) return sx_fail_msg(ctx, SX_E_ARG, "read mapping: unknown flags");
     if (fastq_len > 0xFFFFFFFEull) return sx_fail_msg(ctx, SX_E_ARG, "read mapping: malformed FASTQ image (see sx_fastq_index)");
     SX_CHECK(hipSetDevice(ctx->device));
     sx_fastq_dev fq;
@@ -489,8 +496,8 @@ int sx_index_map_reads(sx_ctx *ctx, const sx_index *idx, const uint8_t *fastq, s
     reads.count = fq.count;
     reads.d_names = fq.d_names, reads.d_seqs = fq.d_seqs, reads.d_quals = fq.d_quals;
     reads.d_name_off = fq.d_name_off, reads.d_seq_off = fq.d_seq_off, reads.d_qual_off = fq.d_qual_off;
-    reads.seq_bytes = fq.seq_bytes;
-    const int rc = sx_map_reads_core(ctx, idx, reads, edits, sink, user);
+    reads.name_bytes = fq.name_bytes, reads.seq_bytes = fq.seq_bytes, reads.qual_bytes = fq.qual_bytes;
+    const int rc = sx_map_reads_core(ctx, idx, reads, edits, flags, sink, user);
     sx_fastq_dev_free(&fq);
     return rc;
 }

@@ -54,7 +54,7 @@ struct sx_reads_dev {
     const uint8_t *d_names = nullptr, *d_seqs = nullptr, *d_quals = nullptr;
     const uint32_t *d_name_off = nullptr, *d_seq_off = nullptr, *d_qual_off = nullptr;
     const uint32_t *h_seq_off = nullptr;
-    uint64_t seq_bytes = 0;
+    uint64_t name_bytes = 0, seq_bytes = 0, qual_bytes = 0; // the offsets' last entries
 };
 
 // A record's host tables as an index takes them (min_sigma 1: the record without symbols has N = 1, sigma = 1) or as the
@@ -69,7 +69,8 @@ static inline bool sx_map_record_check(const sx_map_record &R, uint32_t min_sigm
 }
 
 // sx_sam.hip: the mapper's loop over reads and an index that both lie on ctx's device
-int sx_map_reads_core(sx_ctx *ctx, const sx_index *idx, const sx_reads_dev &reads, int edits, sx_sink_fn sink, void *user);
+// (flags: those of sx_map_reads_stream_ex)
+int sx_map_reads_core(sx_ctx *ctx, const sx_index *idx, const sx_reads_dev &reads, int edits, uint32_t flags, sx_sink_fn sink, void *user);
 // sx_approx.hip: sx_bwt_approx_search_dev over the tables of a record, full, compact or packed
 int sx_approx_search_record(sx_ctx *ctx, const sx_index_rec &R, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, int max_edits,
                             uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t hit_capacity, uint64_t *total_hits_out);

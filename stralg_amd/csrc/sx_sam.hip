@@ -3,7 +3,9 @@
 //
 // One hit (sx_approx_hit) is an interval of a suffix array; it prints R - L lines
 //     <qname>\t0\t<rname>\t<sa[i]+1>\t0\t<cigar>\t*\t0\t0\t<seq>\t<qual>\n          i = L .. R-1
-// that differ in the position's digits only.  Two steps ("SAM text"):
+// that differ in the position's digits only.  The second field is 0, or, where the batch brings a FLAG per read (the
+// kernels' kFlags form: the reads of both strands), that FLAG in decimal.  Two steps (DESIGN.md
+// section 11, "SAM text"):
 //  * layout: a size pass gives every hit its byte count, (R - L) x (the fixed part for this read, record name and
 //    CIGAR) plus the digits of every sa[i] + 1 (hits of more than 32 matches are summed by their whole workgroup),
 //    and a 64-bit exclusive scan turns the counts into each hit's first output byte and the total.
@@ -59,11 +61,12 @@ struct SamArgs {
     const uint32_t *positions;
     const uint64_t *pos_off;
     uint64_t pos_base;
+    const uint16_t *flags; // a FLAG per read (the kernels' kFlags form), or null: every line has FLAG 0
 };
 
 struct HitInfo {
     const uint32_t *pos; // the hit's positions: pos[0 .. cnt)
-    uint32_t cnt, fixed, cig_len, m;
+    uint32_t cnt, fixed, cig_len, m, flag;
     uint32_t name_b, name_l, seq_b, seq_l, qual_b, qual_l, rn_b, rn_l;
     uint4 gaps;
     uint32_t n_gaps;
@@ -124,13 +127,14 @@ __device__ __forceinline__ uint32_t cigar_render(uint8_t *out, uint32_t cap, uin
 }
 
 // what the lines of hit h are made of; false: the hit does not fit the batch (its query, interval or offsets)
-template <bool kLocated> __device__ __forceinline__ bool hit_info(const SamArgs &A, uint64_t h, HitInfo &I)
+template <bool kLocated, bool kFlags> __device__ __forceinline__ bool hit_info(const SamArgs &A, uint64_t h, HitInfo &I)
 {
     const uint4 h0 = A.hits[2 * h];
     I.gaps = A.hits[2 * h + 1];
     I.cnt = 0;
     I.fixed = 0;
     I.cig_len = 0;
+    I.flag = 0;
     I.pos = nullptr;
     const uint32_t vq = h0.x, L = h0.y, R = h0.z;
     if ((uint64_t)vq >= (uint64_t)A.n_reads * A.n_records || L > R) return false;
@@ -154,17 +158,19 @@ template <bool kLocated> __device__ __forceinline__ bool hit_info(const SamArgs 
     if (I.n_gaps > SX_APPROX_MAX_EDITS) I.n_gaps = SX_APPROX_MAX_EDITS;
     I.pos = kLocated ? A.positions + (A.pos_off[h] - A.pos_base) : sa + L;
     I.cnt = R - L;
+    if (kFlags) I.flag = A.flags[read];
     return true;
 }
 
-// "\t0\t" + "\t" + "\t0\t" + "\t*\t0\t0\t" + "\t" + "\n": the 16 bytes of a line beside its fields and digits
+// "\t0\t" + "\t" + "\t0\t" + "\t*\t0\t0\t" + "\t" + "\n": the 16 bytes of a line beside its fields and digits; a FLAG
+// takes its digits in place of the first "0" (without kFlags I.flag is the constant 0: one digit, 16 bytes)
 __device__ __forceinline__ uint32_t fixed_bytes(const HitInfo &I)
 {
-    return I.name_l + I.rn_l + I.cig_len + I.seq_l + I.qual_l + 16u;
+    return I.name_l + I.rn_l + I.cig_len + I.seq_l + I.qual_l + 15u + dec_digits(I.flag);
 }
 
 // ---- layout: bytes per hit ---------------------------------------------------------------------
-template <bool kLocated> __global__ __launch_bounds__(kBlock) void sam_size_kernel(SamArgs A, uint64_t *len_out, uint32_t *err)
+template <bool kLocated, bool kFlags> __global__ __launch_bounds__(kBlock) void sam_size_kernel(SamArgs A, uint64_t *len_out, uint32_t *err)
 {
     __shared__ uint64_t red[kWavesPerBlock];
     __shared__ uint32_t long_cnt[kBlock];
@@ -175,7 +181,7 @@ template <bool kLocated> __global__ __launch_bounds__(kBlock) void sam_size_kern
     long_cnt[t] = 0;
     if (h < A.n_hits) {
         HitInfo I = {};
-        if (!hit_info<kLocated>(A, h, I)) {
+        if (!hit_info<kLocated, kFlags>(A, h, I)) {
             atomicOr(err, 1u);
         } else {
             I.cig_len = cigar_render(nullptr, kCigarMax, I.m, I.gaps, I.n_gaps);
@@ -218,7 +224,7 @@ __device__ __forceinline__ void put_bytes(uint8_t *obuf, int64_t &off, int64_t s
     off += n;
 }
 
-template <bool kLocated> __global__ __launch_bounds__(kBlock) void sam_emit_kernel(SamArgs A, const uint64_t *byte_off, uint64_t lo, uint64_t hi,
+template <bool kLocated, bool kFlags> __global__ __launch_bounds__(kBlock) void sam_emit_kernel(SamArgs A, const uint64_t *byte_off, uint64_t lo, uint64_t hi,
                                                           uint8_t *out)
 {
     __shared__ uint4 obuf4[kSlice / 16];
@@ -228,6 +234,7 @@ template <bool kLocated> __global__ __launch_bounds__(kBlock) void sam_emit_kern
     __shared__ uint64_t red[kWavesPerBlock];
     __shared__ uint32_t red32[kWavesPerBlock];
     __shared__ uint64_t nxt[2];
+    __shared__ uint16_t hflag[kFlags ? kBlock : 1]; // (kFlags) the FLAG of the step's hits
     uint8_t *obuf = (uint8_t *)obuf4;
     const uint32_t t = threadIdx.x;
     const uint64_t s_lo = lo + (uint64_t)blockIdx.x * kSlice;
@@ -249,7 +256,7 @@ template <bool kLocated> __global__ __launch_bounds__(kBlock) void sam_emit_kern
     uint32_t i = 0;
     {   // the walk inside the hit: whole steps of 1024 lines that end at or before the slice's first byte are skipped
         HitInfo I = {};
-        if (hit_info<kLocated>(A, h, I)) {
+        if (hit_info<kLocated, kFlags>(A, h, I)) {
             I.cig_len = cigar_render(nullptr, kCigarMax, I.m, I.gaps, I.n_gaps);
             const uint32_t fixed = fixed_bytes(I);
             while (I.cnt - i > kWalk * kBlock) {
@@ -269,7 +276,7 @@ template <bool kLocated> __global__ __launch_bounds__(kBlock) void sam_emit_kern
         // hits h .. h + 255: how many lines each has left, the first 256 lines' hits, their CIGARs
         HitInfo I = {};
         uint32_t c = 0;
-        if (h + t < A.n_hits && hit_info<kLocated>(A, h + t, I)) c = I.cnt - (t == 0 ? (i < I.cnt ? i : I.cnt) : 0u);
+        if (h + t < A.n_hits && hit_info<kLocated, kFlags>(A, h + t, I)) c = I.cnt - (t == 0 ? (i < I.cnt ? i : I.cnt) : 0u);
         const uint32_t cc = c < (uint32_t)kBlock ? c : (uint32_t)kBlock;
         uint32_t total;
         const uint32_t ex = block_exclusive_scan<OpAdd>(cc, red32, total);
@@ -284,6 +291,7 @@ template <bool kLocated> __global__ __launch_bounds__(kBlock) void sam_emit_kern
             H.fixed = fixed_bytes(I);
             H.name_b = I.name_b, H.name_l = I.name_l, H.seq_b = I.seq_b, H.seq_l = I.seq_l;
             H.qual_b = I.qual_b, H.qual_l = I.qual_l, H.rn_b = I.rn_b, H.rn_l = I.rn_l;
+            if (kFlags) hflag[t] = (uint16_t)I.flag;
         }
         __syncthreads();
         const uint32_t nlines = total < (uint32_t)kBlock ? total : (uint32_t)kBlock;
@@ -316,7 +324,15 @@ template <bool kLocated> __global__ __launch_bounds__(kBlock) void sam_emit_kern
             uint8_t dig[10];
             const uint32_t nd = put_dec(dig, 0, 10, p1);
             put_bytes(obuf, off, slice_len, A.names + H.name_b, H.name_l);
-            put_bytes(obuf, off, slice_len, (const uint8_t *)"\t0\t", 3);
+            if (kFlags) {
+                uint8_t fdig[5];
+                const uint32_t nf = put_dec(fdig, 0, 5, hflag[u]);
+                put_bytes(obuf, off, slice_len, (const uint8_t *)"\t", 1);
+                put_bytes(obuf, off, slice_len, fdig, nf);
+                put_bytes(obuf, off, slice_len, (const uint8_t *)"\t", 1);
+            } else {
+                put_bytes(obuf, off, slice_len, (const uint8_t *)"\t0\t", 3);
+            }
             put_bytes(obuf, off, slice_len, A.rnames + H.rn_b, H.rn_l);
             put_bytes(obuf, off, slice_len, (const uint8_t *)"\t", 1);
             put_bytes(obuf, off, slice_len, dig, nd);
@@ -404,7 +420,7 @@ static SamArgs sam_args_of(const sx_sam_batch &b)
 {
     return SamArgs{(const uint4 *)b.d_hits, b.n_hits,     b.d_sa,       b.sa_len,     b.d_sa_list, b.d_sa_len_list, b.d_names,   b.d_seqs,
                    b.d_quals,               b.d_name_off, b.d_seq_off,  b.d_qual_off, b.n_reads,   b.d_rnames,      b.d_rname_off, b.n_records,
-                   nullptr,                 nullptr,      0};
+                   nullptr,                 nullptr,      0,            nullptr};
 }
 
 static int sam_args(sx_ctx *ctx, const sx_sam_batch *b, SamArgs &A)
@@ -419,6 +435,20 @@ static int sam_args(sx_ctx *ctx, const sx_sam_batch *b, SamArgs &A)
     return 0;
 }
 
+// the same of a batch that may bring a FLAG per read
+static int sam_args_ex(sx_ctx *ctx, const sx_sam_batch_ex *b, SamArgs &A)
+{
+    if (!b) return SX_E_ARG;
+    SX_TRY(sam_args(ctx, &b->batch, A));
+    if ((uintptr_t)b->d_read_flags & 1) return sx_fail_msg(ctx, SX_E_ARG, "SAM text: the reads' flags are 16-bit entries");
+    A.flags = b->d_read_flags;
+    return 0;
+}
+
+// the four forms of the two kernels: positions located beforehand or read from a suffix array, a FLAG per read or none
+#define SX_SAM_KERNEL(kernel, A) \
+    ((A).positions ? ((A).flags ? kernel<true, true> : kernel<true, false>) : ((A).flags ? kernel<false, true> : kernel<false, false>))
+
 static int sam_layout(sx_ctx *ctx, const SamArgs &A, uint64_t *d_byte_off, uint64_t *total_out)
 {
     *total_out = 0;
@@ -426,7 +456,7 @@ static int sam_layout(sx_ctx *ctx, const SamArgs &A, uint64_t *d_byte_off, uint6
     uint32_t *d_err = (uint32_t *)ctx->slab[SX_SLAB_SORT].p;
     SX_CHECK(hipMemsetAsync(d_err, 0, 16, ctx->stream));
     if (A.n_hits)
-        sx_launch(ctx, SX_KC_SAM, A.n_hits * 40, A.positions ? sam_size_kernel<true> : sam_size_kernel<false>, dim3(sx_div_up(A.n_hits, kBlock)),
+        sx_launch(ctx, SX_KC_SAM, A.n_hits * 40, SX_SAM_KERNEL(sam_size_kernel, A), dim3(sx_div_up(A.n_hits, kBlock)),
                   dim3(kBlock), A, d_byte_off, d_err);
     SX_TRY(device_scan64_inplace(ctx, d_byte_off, A.n_hits, SX_KC_SAM));
     uint32_t h[2] = {0, 0}, e = 0;
@@ -444,7 +474,7 @@ static int sam_emit(sx_ctx *ctx, const SamArgs &A, const uint64_t *d_byte_off, u
     const uint64_t slices = (hi - lo + kSlice - 1) / kSlice;
     if (slices > 0x7FFFFFFFull) return sx_fail_msg(ctx, SX_E_ARG, "SAM text: window too long");
     // per line: its bytes out, 4 bytes of position in; the read's fields once a slice
-    sx_launch(ctx, SX_KC_SAM, hi - lo, A.positions ? sam_emit_kernel<true> : sam_emit_kernel<false>, dim3((uint32_t)slices), dim3(kBlock), A,
+    sx_launch(ctx, SX_KC_SAM, hi - lo, SX_SAM_KERNEL(sam_emit_kernel, A), dim3((uint32_t)slices), dim3(kBlock), A,
               d_byte_off, lo, hi, d_out);
     return 0;
 }
@@ -460,9 +490,11 @@ template <class T, class H> static int upload(sx_ctx *ctx, sx_dev_scope &B, cons
 
 // ---- the pieces of the mapper's loop (sx_map_reads_core) -----------------------------------------------------------
 // what a mapping call asks of its reads and records; records_ok: sx_map_dims_ok / sx_map_record_check with sigma >= 2
-static int map_check(sx_ctx *ctx, uint64_t n_reads, uint64_t n_records, bool records_ok)
+static int map_check(sx_ctx *ctx, uint64_t n_reads, uint64_t n_records, uint32_t flags, bool records_ok)
 {
-    if (n_reads * n_records > 0xFFFFFFFFull) return sx_fail_msg(ctx, SX_E_ARG, "read mapping: reads x records must stay below 2^32");
+    if (flags & ~(uint32_t)SX_MAP_BOTH_STRANDS) return sx_fail_msg(ctx, SX_E_ARG, "read mapping: unknown flags");
+    if (sx_map_reads_limit(n_reads, n_records, flags) != 0)
+        return sx_fail_msg(ctx, SX_E_ARG, "read mapping: reads x records (twice that for both strands) must stay below 2^32");
     if (!records_ok) return sx_fail_msg(ctx, SX_E_ARG, "read mapping: a record lacks its name, suffix array, tables or remap table");
     return 0;
 }
@@ -601,7 +633,8 @@ static int emit_windows(sx_ctx *ctx, const SamArgs &A, const MapBufs &M, const s
 // The text of a batch against an index with a sampled suffix array: its hits are taken in runs of consecutive hits whose
 // lines fit the cap (SX_FLAG_LOCATE_CHUNK_ROWS; a hit is never split: one with more lines gets a buffer of its own length);
 // a run is located, laid out and emitted through its windows before the next one starts
-static int emit_located(sx_ctx *ctx, const sx_index *idx, sx_sam_batch text, MapBufs &M, const sx_stage_events &E, sx_sink_fn sink, void *user)
+static int emit_located(sx_ctx *ctx, const sx_index *idx, sx_sam_batch text, const uint16_t *d_read_flags, MapBufs &M, const sx_stage_events &E,
+                        sx_sink_fn sink, void *user)
 {
     const LocRec *d_recs = (const LocRec *)idx->d_loc_list;
     const uint64_t n_hits = text.n_hits, cap = ctx->locate_chunk_rows > 0 ? (uint64_t)ctx->locate_chunk_rows : 1ull << 28;
@@ -628,6 +661,7 @@ static int emit_located(sx_ctx *ctx, const sx_index *idx, sx_sam_batch text, Map
         run.d_hits = text.d_hits + h_lo, run.n_hits = h_hi - h_lo;
         SamArgs A = sam_args_of(run);
         A.positions = M.d_positions, A.pos_off = M.d_pos_off + h_lo, A.pos_base = base;
+        A.flags = d_read_flags;
         SX_TRY(emit_windows(ctx, A, M, E, sink, user));
         base += rows;
         h_lo = h_hi;
@@ -641,33 +675,65 @@ using namespace sx;
 
 extern "C" {
 
-int sx_sam_layout_dev(sx_ctx *ctx, const sx_sam_batch *batch, uint64_t *d_byte_offsets, uint64_t *total_bytes_out)
+int sx_sam_layout_dev_ex(sx_ctx *ctx, const sx_sam_batch_ex *batch, uint64_t *d_byte_offsets, uint64_t *total_bytes_out)
 {
     SamArgs A;
-    SX_TRY(sam_args(ctx, batch, A));
+    SX_TRY(sam_args_ex(ctx, batch, A));
     if (!d_byte_offsets || !total_bytes_out) return SX_E_ARG;
     SX_CHECK(hipSetDevice(ctx->device));
     return sam_layout(ctx, A, d_byte_offsets, total_bytes_out);
 }
 
-int sx_sam_emit_dev(sx_ctx *ctx, const sx_sam_batch *batch, const uint64_t *d_byte_offsets, uint64_t total_bytes, uint64_t byte_lo,
-                    uint64_t byte_hi, uint8_t *d_out)
+int sx_sam_emit_dev_ex(sx_ctx *ctx, const sx_sam_batch_ex *batch, const uint64_t *d_byte_offsets, uint64_t total_bytes, uint64_t byte_lo,
+                       uint64_t byte_hi, uint8_t *d_out)
 {
     SamArgs A;
-    SX_TRY(sam_args(ctx, batch, A));
-    if (!d_byte_offsets || byte_lo > byte_hi || byte_hi > total_bytes || (batch->n_hits == 0 && byte_hi > byte_lo) || (byte_hi > byte_lo && (!d_out || ((uintptr_t)d_out & 15))))
+    SX_TRY(sam_args_ex(ctx, batch, A));
+    if (!d_byte_offsets || byte_lo > byte_hi || byte_hi > total_bytes || (A.n_hits == 0 && byte_hi > byte_lo) || (byte_hi > byte_lo && (!d_out || ((uintptr_t)d_out & 15))))
         return sx_fail_msg(ctx, SX_E_ARG, "SAM text: a window inside [0, total) and a 16-byte aligned buffer are needed");
     SX_CHECK(hipSetDevice(ctx->device));
     SX_TRY(sam_emit(ctx, A, d_byte_offsets, byte_lo, byte_hi, d_out));
     return sx_sync(ctx);
 }
 
+int sx_sam_layout_dev(sx_ctx *ctx, const sx_sam_batch *batch, uint64_t *d_byte_offsets, uint64_t *total_bytes_out)
+{
+    if (!batch) return SX_E_ARG;
+    const sx_sam_batch_ex ex = {*batch, nullptr};
+    return sx_sam_layout_dev_ex(ctx, &ex, d_byte_offsets, total_bytes_out);
+}
+
+int sx_sam_emit_dev(sx_ctx *ctx, const sx_sam_batch *batch, const uint64_t *d_byte_offsets, uint64_t total_bytes, uint64_t byte_lo,
+                    uint64_t byte_hi, uint8_t *d_out)
+{
+    if (!batch) return SX_E_ARG;
+    const sx_sam_batch_ex ex = {*batch, nullptr};
+    return sx_sam_emit_dev_ex(ctx, &ex, d_byte_offsets, total_bytes, byte_lo, byte_hi, d_out);
+}
+
+int sx_map_reads_limit(uint64_t n_reads, uint64_t n_records, uint32_t flags)
+{
+    if (flags & ~(uint32_t)SX_MAP_BOTH_STRANDS) return SX_E_ARG;
+    const uint64_t strands = (flags & SX_MAP_BOTH_STRANDS) ? 2 : 1;
+    // (no product is formed before it is known to fit)
+    if (n_reads > 0xFFFFFFFFull / strands) return SX_E_ARG;
+    if (n_records && n_reads * strands > 0xFFFFFFFFull / n_records) return SX_E_ARG;
+    return 0;
+}
+
 int sx_map_reads_stream(sx_ctx *ctx, const sx_map_record *records, uint32_t n_records, const uint8_t *fastq, size_t fastq_len,
                         int edits, sx_sink_fn sink, void *user)
+{
+    return sx_map_reads_stream_ex(ctx, records, n_records, fastq, fastq_len, edits, 0, sink, user);
+}
+
+int sx_map_reads_stream_ex(sx_ctx *ctx, const sx_map_record *records, uint32_t n_records, const uint8_t *fastq, size_t fastq_len,
+                           int edits, uint32_t flags, sx_sink_fn sink, void *user)
 {
     if (!ctx || !sink || (n_records && !records) || (fastq_len && !fastq)) return SX_E_ARG;
     if (edits < 0 || edits > SX_APPROX_MAX_EDITS)
         return sx_fail_msg(ctx, SX_E_ARG, "read mapping: edits must be in [0, 8]");
+    if (flags & ~(uint32_t)SX_MAP_BOTH_STRANDS) return sx_fail_msg(ctx, SX_E_ARG, "read mapping: unknown flags");
     sx_fastq fq;
     const int frc = sx_fastq_index(fastq, fastq_len, &fq);
     if (frc != 0) return sx_fail_msg(ctx, frc, "read mapping: malformed FASTQ image (see sx_fastq_index)");
@@ -678,7 +744,7 @@ int sx_map_reads_stream(sx_ctx *ctx, const sx_map_record *records, uint32_t n_re
     if (fq.count == 0 || n_records == 0) return 0;
     bool records_ok = true;
     for (uint32_t r = 0; r < n_records; ++r) records_ok = records_ok && sx_map_record_check(records[r], 2);
-    SX_TRY(map_check(ctx, fq.count, n_records, records_ok));
+    SX_TRY(map_check(ctx, fq.count, n_records, flags, records_ok));
     SX_CHECK(hipSetDevice(ctx->device));
     // the reads of this call, then a temporary index of the host tables (every record's suffix array and tables:
     // N x (4 + 8 sigma) bytes a record with its RO table), the loop, and the index goes again
@@ -693,10 +759,10 @@ int sx_map_reads_stream(sx_ctx *ctx, const sx_map_record *records, uint32_t n_re
     SX_TRY(upload(ctx, B, &reads.d_seq_off, fq.seq_off, (size_t)n_reads + 1));
     SX_TRY(upload(ctx, B, &reads.d_qual_off, fq.qual_off, (size_t)n_reads + 1));
     reads.h_seq_off = fq.seq_off;
-    reads.seq_bytes = fq.seq_off[n_reads];
+    reads.name_bytes = fq.name_off[n_reads], reads.seq_bytes = fq.seq_off[n_reads], reads.qual_bytes = fq.qual_off[n_reads];
     sx_index *idx = nullptr;
     SX_TRY(sx_index_from_tables(ctx, records, n_records, &idx));
-    const int rc = sx_map_reads_core(ctx, idx, reads, edits, sink, user);
+    const int rc = sx_map_reads_core(ctx, idx, reads, edits, flags, sink, user);
     sx_index_destroy(idx);
     return rc;
 }
@@ -705,13 +771,44 @@ int sx_map_reads_stream(sx_ctx *ctx, const sx_map_record *records, uint32_t n_re
 
 // The mapper's loop (bwt_readmapper.c:130-160, 257-266) over reads and tables that lie on the device: what
 // sx_map_reads_stream and sx_index_map_reads share.  A batch: search (on capacity: grow_or_halve, again), merge, emit.
-int sx_map_reads_core(sx_ctx *ctx, const sx_index *idx, const sx_reads_dev &reads, int edits, sx_sink_fn sink, void *user)
+// d_read_flags: a FLAG per read, or null.
+static int map_reads_loop(sx_ctx *ctx, const sx_index *idx, const sx_reads_dev &reads, const uint16_t *d_read_flags, int edits, sx_sink_fn sink,
+                          void *user);
+
+// Both strands: the read set of 2 x count reads, read 2q + strand, is made once and searched like any
+// read set, so its hits come in (read, strand, record, hit) order, which is the text's; the FLAGs go with the batches.
+int sx_map_reads_core(sx_ctx *ctx, const sx_index *idx, const sx_reads_dev &reads, int edits, uint32_t flags, sx_sink_fn sink, void *user)
 {
-    const uint32_t n_reads = reads.count, n_records = (uint32_t)idx->recs.size();
-    if (n_reads == 0 || n_records == 0) return 0;
+    const uint32_t n_records = (uint32_t)idx->recs.size();
+    if (reads.count == 0 || n_records == 0) return 0;
     bool records_ok = true;
     for (const sx_index_rec &R : idx->recs) records_ok = records_ok && sx_map_dims_ok(R.N, R.sigma, 2);
-    SX_TRY(map_check(ctx, n_reads, n_records, records_ok));
+    SX_TRY(map_check(ctx, reads.count, n_records, flags, records_ok));
+    if (!(flags & SX_MAP_BOTH_STRANDS)) return map_reads_loop(ctx, idx, reads, nullptr, edits, sink, user);
+    SX_CHECK(hipSetDevice(ctx->device));
+    sx_fastq_dev in = {}, both = {};
+    in.count = reads.count;
+    in.d_names = (uint8_t *)reads.d_names, in.d_seqs = (uint8_t *)reads.d_seqs, in.d_quals = (uint8_t *)reads.d_quals;
+    in.d_name_off = (uint32_t *)reads.d_name_off, in.d_seq_off = (uint32_t *)reads.d_seq_off, in.d_qual_off = (uint32_t *)reads.d_qual_off;
+    in.name_bytes = reads.name_bytes, in.seq_bytes = reads.seq_bytes, in.qual_bytes = reads.qual_bytes;
+    sx_dev_scope F;
+    uint16_t *d_flags;
+    SX_TRY(F.take(ctx, &d_flags, 2 * (size_t)reads.count));
+    SX_TRY(sx_fastq_strands_dev(ctx, &in, &both, d_flags)); // (syncs: the callers' uploads from pageable memory are done)
+    sx_reads_dev stranded;
+    stranded.count = both.count;
+    stranded.d_names = both.d_names, stranded.d_seqs = both.d_seqs, stranded.d_quals = both.d_quals;
+    stranded.d_name_off = both.d_name_off, stranded.d_seq_off = both.d_seq_off, stranded.d_qual_off = both.d_qual_off;
+    stranded.name_bytes = both.name_bytes, stranded.seq_bytes = both.seq_bytes, stranded.qual_bytes = both.qual_bytes;
+    const int rc = map_reads_loop(ctx, idx, stranded, d_flags, edits, sink, user);
+    sx_fastq_dev_free(&both);
+    return rc;
+}
+
+static int map_reads_loop(sx_ctx *ctx, const sx_index *idx, const sx_reads_dev &reads, const uint16_t *d_read_flags, int edits, sx_sink_fn sink,
+                          void *user)
+{
+    const uint32_t n_reads = reads.count, n_records = (uint32_t)idx->recs.size();
     SX_CHECK(hipSetDevice(ctx->device));
     MapBufs M;
     SX_TRY(M.own.take(ctx, &M.d_pat, (size_t)reads.seq_bytes));
@@ -756,8 +853,15 @@ int sx_map_reads_core(sx_ctx *ctx, const sx_index *idx, const sx_reads_dev &read
             text.d_hits = M.d_merged, text.n_hits = seg[n_records];
             text.d_name_off = reads.d_name_off + q0, text.d_seq_off = reads.d_seq_off + q0, text.d_qual_off = reads.d_qual_off + q0;
             text.n_reads = batch;
-            if (idx->sa_log2) SX_TRY(emit_located(ctx, idx, text, M, E, sink, user));
-            else SX_TRY(emit_windows(ctx, sam_args_of(text), M, E, sink, user));
+            // (the offsets are this batch's: so are the flags)
+            const uint16_t *d_batch_flags = d_read_flags ? d_read_flags + q0 : nullptr;
+            if (idx->sa_log2) {
+                SX_TRY(emit_located(ctx, idx, text, d_batch_flags, M, E, sink, user));
+            } else {
+                SamArgs A = sam_args_of(text);
+                A.flags = d_batch_flags;
+                SX_TRY(emit_windows(ctx, A, M, E, sink, user));
+            }
         }
         q0 += batch;
     }

@@ -4,9 +4,12 @@ lines and bytes of text, ms and GB/s of the layout pass and of the emit pass int
 SX_KC_SAM class; the emit pass fills one window buffer again and again) next to the bytes each moves, the search's kernel
 ms on the same batch, the box's fill rate (sx_membw_probe), the rate of a plain pinned device-to-host copy, and the
 streamed form (sx_map_reads_stream from host tables through a sink that discards) as wall time and as the rate of its
-windows, a fraction of that copy rate; the host's FASTQ index pass.
+windows, a fraction of that copy rate; the host's FASTQ index pass.  --repeats N times every figure N times (the runs stand
+next to their best as *_runs: the run-to-run spread that a comparison between two builds has to exceed).  --both-strands
+adds the strand kernel (sx_fastq_strands_dev: ms, bytes moved, against the probe's copy rate) and the streamed call with
+SX_MAP_BOTH_STRANDS (kept in profiles/strands_bench_2p28.json).
 
-    python tools/sam_bench.py [--log2n 28] [--reads 1000000] [--window-mib 1024]
+    python tools/sam_bench.py [--log2n 28] [--reads 1000000] [--window-mib 1024] [--repeats 5] [--both-strands]
 """
 import argparse
 import ctypes as C
@@ -30,6 +33,8 @@ def main():
     ap.add_argument("--ks", default="1,2")
     ap.add_argument("--reference-lines-per-s", type=float, default=0.0,
                     help="the reference mapper's rate measured elsewhere, recorded in the line as given")
+    ap.add_argument("--repeats", type=int, default=1, help="time layout, emit and the streamed call so many times")
+    ap.add_argument("--both-strands", action="store_true", help="also the strand kernel and the streamed call on both strands")
     args = ap.parse_args()
     import torch
 
@@ -122,7 +127,8 @@ def main():
         batch = ctx.sam_batch(d_hits, total, d_sa, N, d_names, d_name_off, d_seqs, d_off, d_quals, d_off, R, d_rname,
                               d_rname_off, 1)
         ctx.sam_layout_dev(batch, d_boff)  # warm-up
-        nbytes, _, layout_ms = profiled("sam", lambda: ctx.sam_layout_dev(batch, d_boff))
+        layout_runs = [profiled("sam", lambda: ctx.sam_layout_dev(batch, d_boff)) for _ in range(args.repeats)]
+        nbytes, layout_ms = layout_runs[0][0], min(r[2] for r in layout_runs)
         words = d_hits[:total * 32].view(torch.int32).reshape(-1, 8)  # (query, L, R, ...)
         lines = int(((words[:, 2].to(torch.int64) & 0xFFFFFFFF) - (words[:, 1].to(torch.int64) & 0xFFFFFFFF)).sum().item())
         del words
@@ -132,7 +138,8 @@ def main():
                 ctx.sam_emit_dev(batch, d_boff, nbytes, lo, min(nbytes, lo + window), d_win)
 
         ctx.sam_emit_dev(batch, d_boff, nbytes, 0, min(nbytes, window), d_win)  # warm-up
-        _, emit_wall, emit_ms = profiled("sam", emit_all)
+        emit_runs = [profiled("sam", emit_all) for _ in range(args.repeats)]
+        emit_wall, emit_ms = min(r[1] for r in emit_runs), min(r[2] for r in emit_runs)
         layout_bytes = total * (32 + 16) + lines * 4
         emit_bytes = nbytes + lines * 4 + total * 32
         out[f"k{k}"] = {"hits": int(total), "lines": lines, "text_bytes": int(nbytes),
@@ -143,6 +150,9 @@ def main():
                         "emit_GBps": round(emit_bytes / (emit_ms * 1e-3) / 1e9, 1),
                         "emit_fraction_of_fill": round(emit_bytes / (emit_ms * 1e-3) / 1e9 / probe["fill"], 3),
                         "lines_per_s": round(lines / ((layout_ms + emit_ms) * 1e-3), 1)}
+        if args.repeats > 1:
+            out[f"k{k}"]["layout_ms_runs"] = [round(r[2], 3) for r in layout_runs]
+            out[f"k{k}"]["emit_ms_runs"] = [round(r[2], 3) for r in emit_runs]
         del d_hits, d_boff
         torch.cuda.empty_cache()
     # ---- the streamed form: sx_map_reads_stream (host tables and FASTQ image in, SAM text out through a sink that discards)
@@ -166,10 +176,18 @@ def main():
                        d_ro.cpu().numpy().view(np.uint32))
     del d_sa, d_o, d_ro, d_win
     torch.cuda.empty_cache()
+    def streamed(k, **kw):
+        """(wall seconds, the windows) of the fastest of the repeated calls, and every call's wall time in ms"""
+        runs = []
+        for _ in range(args.repeats):
+            t0 = time.perf_counter()
+            seen = ctx.map_reads_stream([(b"chr1", rec)], fastq, k, None, **kw)
+            runs.append((time.perf_counter() - t0, seen))
+        best = min(runs, key=lambda r: r[0])
+        return best[0], best[1], [round(r[0] * 1e3, 1) for r in runs]
+
     for k in [int(x) for x in args.ks.split(",")]:
-        t0 = time.perf_counter()
-        seen = ctx.map_reads_stream([(b"chr1", rec)], fastq, k, None)
-        wall = time.perf_counter() - t0
+        wall, seen, walls = streamed(k)
         nbytes = sum(b for _, b in seen)
         assert nbytes == out[f"k{k}"]["text_bytes"], (nbytes, out[f"k{k}"]["text_bytes"])
         # the windows' own rate: from the first window's arrival at the sink to the last one's (the first window's
@@ -181,6 +199,33 @@ def main():
                                     "windows_GBps": None if rate is None else round(rate, 2),
                                     "fraction_of_pinned_copy": None if rate is None else round(rate / max(link), 3),
                                     "call_GBps": round(nbytes / wall / 1e9, 2)}
+        if args.repeats > 1:
+            out[f"k{k}"]["streamed"]["call_wall_ms_runs"] = walls
+        if args.both_strands:
+            both_wall, both_seen, both_walls = streamed(k, both_strands=True)
+            out[f"k{k}"]["streamed_both_strands"] = {"call_wall_ms": round(both_wall * 1e3, 1), "call_wall_ms_runs": both_walls,
+                                                    "text_bytes": int(sum(b for _, b in both_seen)), "windows": len(both_seen),
+                                                    "over_one_strand_call": round(both_wall / wall, 3)}
+    if args.both_strands:
+        # the strand kernel alone: the image indexed on the device, then sx_fastq_strands_dev (launches of the remap class)
+        d_img = torch.from_numpy(np.concatenate([img, pad])).cuda()
+        d_flags = torch.zeros(2 * R, dtype=torch.int16, device="cuda")
+        torch.cuda.synchronize()
+        one, both = _lib.FastqDev(), _lib.FastqDev()
+        assert ctx.lib.sx_fastq_index_dev(ctx.h, d_img.data_ptr(), img.size, C.byref(one)) == 0 and one.count == R
+
+        def strands():
+            assert ctx.lib.sx_fastq_strands_dev(ctx.h, C.byref(one), C.byref(both), d_flags.data_ptr()) == 0
+            ctx.lib.sx_fastq_dev_free(C.byref(both))
+
+        strands()  # warm-up
+        runs = [profiled("remap", strands) for _ in range(max(3, args.repeats))]
+        ms = min(r[2] for r in runs)
+        moved = 4 * (int(one.name_bytes) + int(one.seq_bytes) + int(one.qual_bytes)) + 3 * 12 * R + 4 * R
+        ctx.lib.sx_fastq_dev_free(C.byref(one))
+        out["strand_kernel"] = {"ms": round(ms, 3), "ms_runs": [round(r[2], 3) for r in runs], "call_wall_ms": round(min(r[1] for r in runs) * 1e3, 3),
+                                "bytes_moved": moved, "GBps": round(moved / (ms * 1e-3) / 1e9, 1),
+                                "fraction_of_copy": round(moved / (ms * 1e-3) / 1e9 / probe["copy"], 3)}
     if args.reference_lines_per_s:
         out["reference_mapper_one_core"] = {"lines_per_s": args.reference_lines_per_s,
                                             "what": "unmodified bwt_readmapper -d 2, hg38-10000.fa, reads-100-10-0.fq (408 980 lines, "

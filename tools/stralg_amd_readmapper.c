@@ -25,6 +25,10 @@
  *                                                   --compact alone takes 9, 3.4 at S = 32 where it takes 5.4; the
  *                                                   output is the same.  A record of more letters ends the run.  -p
  *                                                   writes the same file with or without it
+ *   --both-strands                                  with -d: behind the lines of every read come the lines of its reverse
+ *                                                   complement (sequence reversed and complemented, qualities reversed),
+ *                                                   with FLAG 16 in place of 0; goes with -i, --compact, --sa-sample,
+ *                                                   --packed and several FASTQ files
  *   (--preprocess, --edits and --in-memory are accepted for -p, -d and -i)
  *
  * Index file: u32 record count; per record, last FASTA record first, its name as u32 length + bytes + NUL, then the
@@ -114,7 +118,7 @@ static int build_index(const char *fasta)
 
 /* -d: the index is loaded once (from genome.fa.bwttables, or, with -i, built on the device from genome.fa itself) and
  * stays on the device; every FASTQ file is mapped against it, stdout is the files' texts one behind the other */
-static int map_reads(const char *fasta, char *const *reads, int n_reads, int k, int in_memory, uint32_t flags)
+static int map_reads(const char *fasta, char *const *reads, int n_reads, int k, int in_memory, uint32_t flags, uint32_t map_flags)
 {
     struct sx_index *idx = NULL;
     if (in_memory) {
@@ -136,7 +140,7 @@ static int map_reads(const char *fasta, char *const *reads, int n_reads, int k, 
     for (int f = 0; f < n_reads && rc == 0; ++f) {
         FILE *fq = fopen(reads[f], "rb");
         if (!fq) fail("cannot read", reads[f]);
-        rc = stralg_amd_index_map(idx, fq, k, stdout);
+        rc = stralg_amd_index_map_ex(idx, fq, k, map_flags, stdout);
         fclose(fq);
     }
     stralg_amd_index_free(idx);
@@ -154,6 +158,8 @@ static int usage(const char *self, int status)
     fprintf(stderr, "                                          two in 2 .. 1024) in place of the suffix array on the device\n");
     fprintf(stderr, "       --packed                           with --compact and -d: a nibble a row in the blocks (records of at\n");
     fprintf(stderr, "                                          most 7 letters)\n");
+    fprintf(stderr, "       --both-strands                     with -d: every read's reverse complement is mapped too, its lines\n");
+    fprintf(stderr, "                                          have FLAG 16\n");
     return status;
 }
 
@@ -162,7 +168,7 @@ int main(int argc, char **argv)
     const char *to_index = NULL;
     char **rest = calloc((size_t)argc + 1, sizeof *rest);
     int k = -1, n_rest = 0, in_memory = 0, indexing = 0;
-    uint32_t flags = 0, sa_log2 = 0;
+    uint32_t flags = 0, sa_log2 = 0, map_flags = 0;
     if (!rest) fail("out of memory", NULL);
     for (int a = 1; a < argc; ++a) {
         const char *s = argv[a];
@@ -174,6 +180,8 @@ int main(int argc, char **argv)
             flags |= SX_INDEX_COMPACT;
         } else if (!strcmp(s, "--packed")) {
             flags |= SX_INDEX_PACKED;
+        } else if (!strcmp(s, "--both-strands")) {
+            map_flags |= SX_MAP_BOTH_STRANDS;
         } else if (!strcmp(s, "--sa-sample")) {
             if (++a >= argc) return usage(argv[0], EXIT_FAILURE);
             const long dist = strtol(argv[a], NULL, 10);
@@ -199,5 +207,5 @@ int main(int argc, char **argv)
     if (indexing && !to_index && n_rest) to_index = rest[0];
     if (indexing) return to_index ? build_index(to_index) : usage(argv[0], EXIT_FAILURE);
     if (n_rest < 2 || k < 0) return usage(argv[0], EXIT_FAILURE);
-    return map_reads(rest[0], rest + 1, n_rest - 1, k, in_memory, flags);
+    return map_reads(rest[0], rest + 1, n_rest - 1, k, in_memory, flags, map_flags);
 }
