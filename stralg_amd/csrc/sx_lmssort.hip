@@ -29,6 +29,7 @@
 #include "sx_internal.hpp"
 #include "sx_window.hpp"
 #include "sx_lmskey.hpp"
+#include "sx_prefix_plan.hpp"
 
 namespace sx {
 
@@ -877,24 +878,11 @@ int sx_prefix_ties_sampled(sx_ctx *ctx, const sx_text_info &ti, sx_arena am, boo
     // positions hold the same symbol, times the symbols in use, is 1 for uniform symbols (1 GiB of random bytes: 1.000,
     // which then keeps the millisecond the look costs), 1.7 for English text, 1.3 for proteins
     if (ctx->sample_min < 0) {
-        double sum_p2 = 0.0;
-        uint32_t used = 0;
-        const double n_sym = (double)ti.N - 1.0;
-        for (int c = 1; c < 256 && n_sym > 0; ++c) {
-            if (!ti.h_all[c]) continue;
-            const double pc = (double)ti.h_all[c] / n_sym;
-            sum_p2 += pc * pc;
-            ++used;
-        }
-        if (sum_p2 * (double)used < 1.1) return 0;
+        const sx_symbol_stats st = sx_symbol_stats_of(ti.h_all, ti.N);
+        if (st.sum_p2 * (double)st.used < 1.1) return 0;
     }
-    const uint32_t base = ti.maxc + 1;
-    uint32_t Cmax = 0;
-    for (double cap63 = 9.2e18, v = 1.0; v * base <= cap63 && Cmax < 63; v *= base) ++Cmax;
-    if (Cmax < 1) Cmax = 1;
-    uint64_t top = 1;
-    for (uint32_t i = 0; i < Cmax; ++i) top *= base;
-    const int kbits = sx_bitlen(top - 1);
+    const uint32_t base = ti.maxc + 1, Cmax = sx_prefix_cmax(base);
+    const int kbits = sx_prefix_key_bits(base, Cmax);
     // one suffix a sampled word: LMS suffixes are thinned to about one in 19 (a word in four, its first LMS position),
     // positions 256-fold (short texts, which only tests send here: every word)
     const uint32_t step = m < (1ull << 22) ? 1 : all_suffixes ? 16 : 4;
@@ -936,6 +924,363 @@ size_t sx_lms_prefix_bytes(uint64_t m)
     return b + 4096;
 }
 
+// ---- the driver of the prefix-key sort: what an attempt does is decided by its plan (sx_prefix_plan.hpp); the stages below
+// launch it over one state
+namespace {
+
+struct prefix_sort {
+    sx_ctx *ctx;
+    const sx_text_info *ti;
+    bool all_suffixes;
+    uint64_t m;          // suffixes to sort
+    uint32_t base, Cmax; // the keys' base; longest prefix whose number fits 63 bits
+    uint32_t cap;        // slots of the refinement's arrays
+    // the arena's arrays (take_arrays)
+    uint64_t *ka, *kb; // keys
+    uint32_t *va, *vb; // values
+    uint64_t *key_keep, *rk_a, *rk_b; // refinement keys: kept copy + sort ping-pong
+    uint32_t *apos, *ap;   // the members of groups of equal keys are in (apos, ap, head), A of them
+    uint8_t *head;
+    uint32_t A;
+    uint32_t *apos2, *ap2; // their ping-pong partners (keep_tied)
+    uint8_t *head2;
+    uint32_t *ap_new;      // what a refinement step writes
+    uint8_t *head_new;
+    uint32_t *agid, *ord_a, *ord_b, *gsize, *sub_t, *sub_gid;
+    uint32_t *seedw, *d_scalar;
+    uint32_t *tile_cnt, *tile_pos; // tie counts and offsets per tile of the sorted keys
+    uint32_t ls_tiles;
+    uint32_t *tile_lsrt; // start, tied members, offset of every local-sort workgroup; null: no hybrid sort
+    uint32_t *long_list; // sub-buckets too long for a workgroup (repeat families, AT-rich prefixes): their starts, lengths, offsets (sx_long_subbuckets); null: not listed
+    uint32_t *tile_off;  // offset of every classification tile in the global order of the LMS positions
+    uint8_t *dig0;       // the key kernels leave the first pass's digits there (one byte each: 8-bit digits only)
+    uint32_t *vs;        // the positions in key order
+    // the refinement's settings (refine_ties)
+    wnd_cfg full_wcfg; // refined slots get their windows straight from the text
+    int kbits_r;       // ties are refined with the longest key that fits (Cmax symbols a round)
+    bool lds_tier, trace;
+    // the windows the keys carried, where they did
+    uint32_t *windows(const prefix_plan &p) const { return p.embed ? seedw : nullptr; }
+};
+
+// the arena's arrays, in this order; false: no room.  tile_lsrt and long_list may be absent and only switch features off.
+bool take_arrays(prefix_sort &s, sx_arena &am)
+{
+    const uint64_t m = s.m;
+    const uint32_t cap = s.cap;
+    s.ka = am.take<uint64_t>(m), s.kb = am.take<uint64_t>(m);
+    s.va = am.take<uint32_t>(m), s.vb = am.take<uint32_t>(m);
+    s.key_keep = am.take<uint64_t>(cap), s.rk_a = am.take<uint64_t>(cap), s.rk_b = am.take<uint64_t>(cap);
+    s.apos = am.take<uint32_t>(cap), s.apos2 = am.take<uint32_t>(cap);
+    s.ap = am.take<uint32_t>(cap), s.ap2 = am.take<uint32_t>(cap), s.ap_new = am.take<uint32_t>(cap);
+    s.agid = am.take<uint32_t>(cap), s.ord_a = am.take<uint32_t>(cap), s.ord_b = am.take<uint32_t>(cap);
+    s.gsize = am.take<uint32_t>(cap), s.sub_t = am.take<uint32_t>(cap), s.sub_gid = am.take<uint32_t>(cap);
+    s.head = am.take<uint8_t>(cap), s.head2 = am.take<uint8_t>(cap), s.head_new = am.take<uint8_t>(cap);
+    s.seedw = am.take<uint32_t>(m);
+    s.d_scalar = am.take<uint32_t>(16);
+    const uint32_t tied_tiles = sx_div_up(m, kTiedTile);
+    s.tile_cnt = am.take<uint32_t>(tied_tiles), s.tile_pos = am.take<uint32_t>(tied_tiles);
+    s.ls_tiles = sx_local_sort_tiles(m);
+    s.tile_lsrt = am.take<uint32_t>(3 * (size_t)s.ls_tiles);
+    s.long_list = s.ctx->long_subbuckets_off ? nullptr : am.take<uint32_t>(3 * (size_t)kLongCap);
+    return s.tile_cnt && s.tile_pos && s.seedw && s.ka && s.kb && s.va && s.vb && s.key_keep && s.rk_a && s.rk_b && s.apos && s.apos2 && s.ap &&
+           s.ap2 && s.ap_new && s.agid && s.ord_a && s.ord_b && s.gsize && s.sub_t && s.sub_gid && s.head && s.head2 && s.head_new && s.d_scalar;
+}
+
+// The (key, position) pairs of the attempt in (ka, va) and their first digits in dig0 -- by no kernel where the hybrid sort's
+// first pass computes the keys itself.
+int make_keys(prefix_sort &s, const prefix_plan &p)
+{
+    sx_ctx *ctx = s.ctx;
+    const sx_text_info &ti = *s.ti;
+    const uint64_t m = s.m;
+    const dim3 block(kBlock);
+    s.dig0 = (uint8_t *)sx_sort_digit_buffer(ctx, m, sx_sort_digit_bits(ctx));
+    if (!s.dig0) return sx_fail_msg(ctx, SX_E_NOMEM, "sort workspace");
+    if (p.text_keyed || p.lms_keyed) return 0;
+    if (s.all_suffixes && p.C <= 12) {
+        const pkey_cfg kc = pkey_make(s.base, p.C);
+        const dim3 grid16(sx_div_up(m, kBlock * 16));
+#define SX_KEYS16(G) sx_launch(ctx, SX_KC_KEYS, m * 10, all_keys16_kernel<G>, grid16, block, ti.T, m, kc, (uint32_t)p.kbits, p.wcfg, s.ka, s.dig0, p.dig_shift, p.dig_mask)
+        switch (kc.G) {
+        case 10: SX_KEYS16(10); break;
+        case 6: SX_KEYS16(6); break;
+        case 4: SX_KEYS16(4); break;
+        default: SX_KEYS16(3); break;
+        }
+#undef SX_KEYS16
+    } else if (s.all_suffixes) {
+        sx_launch(ctx, SX_KC_KEYS, m * 13, all_keys_kernel, dim3(sx_div_up(m, kBlock)), block, ti.T, m, pkey_make(s.base, p.C),
+                  (uint32_t)p.kbits, p.wcfg, s.ka, s.dig0, p.dig_shift, p.dig_mask);
+    } else {
+        const pkey_cfg kc = pkey_make(p.dense4 ? 4u : s.base, p.C);
+        // DNA-like texts: everything static for the usual prefix lengths (base 5: the window takes what
+        // 64 - kbits - 4 bits hold)
+        const bool dna = kc.dot && (p.wcfg.B == 2 || p.wcfg.B == 3) && p.kbits >= 8;
+#define SX_TILE_KEYS(CS, WS, BS)                                                                                       \
+    sx_launch(ctx, SX_KC_KEYS, m * 12 + ti.N + ti.N / 8, lms_tile_keys_kernel<CS, WS, BS>, dim3(ti.ntiles), block,     \
+              ti.T, (const uint16_t *)ti.lmsbits, (const uint32_t *)s.tile_off, kc, (uint32_t)p.kbits, p.wcfg, s.ka, s.va, s.dig0, p.dig_shift, p.dig_mask, \
+              (uint64_t)(p.dense4 ? ti.n + 1 : 0), p.lenbits)
+        const uint32_t shape = dna ? (p.C * 16 + p.wcfg.CW) * 4 + p.wcfg.B : 0u;
+        switch (shape) {
+        // base 5 (A C G T): 64 Mi ... 4 Gi symbols
+        case (14 * 16 + 13) * 4 + 2: SX_TILE_KEYS(14, 13, 2); break;
+        case (15 * 16 + 12) * 4 + 2: SX_TILE_KEYS(15, 12, 2); break;
+        case (16 * 16 + 11) * 4 + 2: SX_TILE_KEYS(16, 11, 2); break;
+        case (17 * 16 + 10) * 4 + 2: SX_TILE_KEYS(17, 10, 2); break;
+        case (18 * 16 + 9) * 4 + 2: SX_TILE_KEYS(18, 9, 2); break;
+        // base 6 (A C G N T)
+        case (13 * 16 + 8) * 4 + 3: SX_TILE_KEYS(13, 8, 3); break;
+        case (14 * 16 + 7) * 4 + 3: SX_TILE_KEYS(14, 7, 3); break;
+        case (15 * 16 + 7) * 4 + 3: SX_TILE_KEYS(15, 7, 3); break;
+        case (16 * 16 + 6) * 4 + 3: SX_TILE_KEYS(16, 6, 3); break;
+        default: SX_TILE_KEYS(0, 0, 0); break;
+        }
+#undef SX_TILE_KEYS
+    }
+    return 0;
+}
+
+// The hybrid sort: three stable passes on the top 24 bits, then the sub-buckets in LDS: positions, windows and ties in one go.
+// *listed: the positions are in s.vs and the tied members in (apos, ap, head), s.A of them.  Else a sub-bucket was too long for
+// a workgroup: either plain passes have ordered the pairs -- keys in *ks, positions in s.vs, *in_b -- or *general: the
+// general path's turn at once, s.A the tied members counted so far.
+int hybrid_sort(prefix_sort &s, const prefix_plan &p, bool last_attempt, const uint64_t **ks, int *in_b, bool *listed, bool *general)
+{
+    sx_ctx *ctx = s.ctx;
+    const sx_text_info &ti = *s.ti;
+    const uint64_t m = s.m;
+    const uint32_t cap = s.cap;
+    sx_textkey tkey = {ti.T, s.base, p.C, 1u, 1u, (uint32_t)p.kbits, p.wcfg.CW ? 1u : 0u};
+    for (uint32_t i = 0; i < 3; ++i) tkey.pow3 *= s.base;
+    for (uint32_t i = 0; i < p.C % 3; ++i) tkey.powR *= s.base;
+    const sx_lmskey lkey = {ti.T, (const uint16_t *)ti.lmsbits, (const uint32_t *)s.tile_off, ti.ntiles, (uint32_t)m,
+                            pkey_make(p.dense4 ? 4u : s.base, p.C), p.wcfg, (uint32_t)p.kbits, p.lenbits, (uint64_t)ti.n + 1, p.lms_shape};
+    SX_TRY(sx_sort_pairs(ctx, s.ka, s.va, s.kb, s.vb, m, p.kbits - p.top_bits, p.kbits, in_b, s.all_suffixes, true, 8,
+                         p.text_keyed ? &tkey : nullptr, p.lms_keyed ? &lkey : nullptr));
+    const uint64_t *kin = *in_b ? s.kb : s.ka;
+    const uint32_t *vin = *in_b ? s.vb : s.va;
+    uint32_t *vo = *in_b ? s.va : s.vb;
+    uint32_t res[3] = {0, 0, 0};
+    SX_TRY(sx_local_sort(ctx, kin, vin, m, p.kbits, p.top_bits, vo, s.windows(p), s.tile_lsrt, s.tile_lsrt + s.ls_tiles,
+                         s.tile_lsrt + 2 * (size_t)s.ls_tiles, (uint2 *)(*in_b ? s.ka : s.kb), s.dig0, s.apos, s.ap, s.head, cap, s.d_scalar,
+                         p.longest_expected, s.long_list, kLongCap, res));
+    bool fits = !(res[1] & 1u);
+    ctx->stats.long_subbuckets = 0;
+    if (fits && res[2] != 0) {
+        // sub-buckets that did not fit a workgroup were left out and listed: their members are ordered by HBM passes of
+        // their own (the refinement's arrays are free until the ties are refined: a quarter of the pairs at most)
+        uint32_t tied_all = res[0], pairs = 0;
+        int done = 0;
+        SX_TRY(sx_long_subbuckets(ctx, kin, vin, m, p.kbits, p.top_bits, res[2], s.long_list, kLongCap, s.rk_a, s.rk_b, s.ord_a, s.ord_b,
+                                  cap - 1024, vo, s.windows(p), s.apos, s.ap, s.head, cap, res[0], s.d_scalar + 4, &tied_all, &pairs, &done));
+        ctx->stats.long_subbuckets = res[2];
+        fits = done != 0;
+        res[0] = done ? tied_all : res[0] + pairs; // (not done: those pairs are as good as tied -- the decision below)
+    }
+    s.A = res[0];
+    if (fits) {
+        s.vs = vo; // (the sorted keys are not written by this path; nothing below reads them)
+        *listed = true;
+        ctx->stats.sort_local = 1u | (res[1] & 2u) | (p.top_bits == 32 ? 4u : 0u) | ((p.text_keyed || p.lms_keyed) ? 8u : 0u); // (bit 1: some workgroup ordered its pairs by stable passes)
+        return 0;
+    }
+    // a sub-bucket too long for a workgroup (a repeated prefix): plain LSD passes over all key bits from here
+    // -- unless the workgroups that did finish have listed more tied suffixes already than the refinement
+    // takes, and more than a longer key would be tried for: the general path's turn at once (a collection of
+    // near-identical sequences: five passes over all pairs and the pass that marks the ties, 11 of 210 ms)
+    if (res[0] > cap - 1024 && (last_attempt || (uint64_t)res[0] * 2 > m)) {
+        *general = true;
+        return 0;
+    }
+    uint64_t *k0 = *in_b ? s.kb : s.ka, *k1 = *in_b ? s.ka : s.kb;
+    uint32_t *v0 = *in_b ? s.vb : s.va, *v1 = *in_b ? s.va : s.vb;
+    int f = 0;
+    SX_TRY(sx_sort_pairs(ctx, k0, v0, k1, v1, m, 0, p.kbits, &f, false, false, 8));
+    *ks = f ? k1 : k0;
+    s.vs = f ? v1 : v0;
+    *in_b = (*ks == s.kb) ? 1 : 0;
+    return 0;
+}
+
+// The attempt's sort, by the hybrid sort or by plain passes, and the list of the members of groups with equal keys:
+// (apos, ap, head), s.A of them.  last_attempt: no longer key would be tried.  *general: the general path's turn at once.
+int sort_and_list_ties(prefix_sort &s, const prefix_plan &p, bool last_attempt, bool *general)
+{
+    sx_ctx *ctx = s.ctx;
+    const uint64_t m = s.m;
+    const uint64_t *ks = nullptr; // sorted keys (not kept by the hybrid sort)
+    int in_b = 0;
+    bool listed = false;
+    ctx->stats.sort_local = 0;
+    s.A = 0;
+    if (p.hybrid()) {
+        SX_TRY(hybrid_sort(s, p, last_attempt, &ks, &in_b, &listed, general));
+        if (listed || *general) return 0;
+    } else {
+        const int sort_db = sx_sort_digit_bits(ctx);
+        SX_TRY(sx_sort_pairs(ctx, s.ka, s.va, s.kb, s.vb, m, 0, p.kbits, &in_b, s.all_suffixes, sort_db == 8, sort_db)); // (all suffixes: value = index)
+        ks = in_b ? s.kb : s.ka;
+        s.vs = in_b ? s.vb : s.va;
+    }
+    const uint32_t tiles = sx_div_up(m, kTiedTile);
+    const dim3 block(kBlock);
+    // staging in the sort's spare buffers: 8 bytes per slot in the other key array, heads in the other value array
+    uint2 *stage = (uint2 *)(in_b ? s.ka : s.kb);
+    uint8_t *stage_head = (uint8_t *)(in_b ? s.va : s.vb);
+    sx_launch(ctx, SX_KC_NAMES, m * 13, tied_mark_kernel, dim3(tiles), block, ks, (const uint32_t *)s.vs, m, p.kmask,
+              (uint32_t)p.kbits, s.windows(p), s.tile_cnt, stage, stage_head);
+    SX_TRY((device_scan<OpAdd>(ctx, tiles, InU32{s.tile_cnt}, OutExclusive{s.tile_pos}, s.d_scalar, SX_KC_NAMES, 0)));
+    sx_launch(ctx, SX_KC_NAMES, 0, tied_gather_kernel, dim3(tiles), block, (const uint32_t *)s.tile_cnt,
+              (const uint32_t *)s.tile_pos, (const uint2 *)stage, (const uint8_t *)stage_head, s.apos, s.ap, s.head, s.cap);
+    return sx_readback(ctx, s.d_scalar, 1, &s.A);
+}
+
+// keep what is still tied after a refinement step: (apos, ap_new, head_new) -> (apos, ap, head), A
+int keep_tied(prefix_sort &s)
+{
+    sx_ctx *ctx = s.ctx;
+    SX_TRY((device_compact(ctx, s.A, InStillTied{s.head_new, s.A}, OutStillTied{s.apos, s.ap_new, s.head_new, s.apos2, s.ap2, s.head2},
+                           s.d_scalar, SX_KC_DOUBLING, (uint64_t)s.A * 20)));
+    uint32_t A2 = 0;
+    SX_TRY(sx_readback(ctx, s.d_scalar, 1, &A2));
+    uint32_t *tp = s.apos; s.apos = s.apos2; s.apos2 = tp;
+    tp = s.ap; s.ap = s.ap2; s.ap2 = tp;
+    uint8_t *th = s.head; s.head = s.head2; s.head2 = th;
+    s.A = A2;
+    return 0;
+}
+
+// One refinement step by the next Cmax symbols for the groups of more than kSmallGroup members (the smaller ones
+// are settled by their head's thread): group sizes, then groups of up to kMidGroup members inside a workgroup's
+// LDS, the members of longer ones compacted and ordered by two radix sorts of (group, next key).
+// SX_FLAG_SORT_MODE 1 (plain passes only): every group of more than kSmallGroup members takes the radix sorts.
+int refine_larger_groups(prefix_sort &s, const prefix_plan &p, uint64_t skip)
+{
+    sx_ctx *ctx = s.ctx;
+    const sx_text_info &ti = *s.ti;
+    const uint32_t A = s.A;
+    const dim3 block(kBlock);
+    const pkey_cfg kc_r = pkey_make(s.base, s.Cmax);
+    SX_TRY((device_scan<OpMax>(ctx, A, InActHead{s.head}, OutGroupIds{s.head, (uint64_t)A, s.agid, s.gsize}, nullptr,
+                               SX_KC_DOUBLING, (uint64_t)A * 9)));
+    if (s.lds_tier) {
+        ctx->stats.refine_tiers |= 1u;
+        sx_launch(ctx, SX_KC_DOUBLING, (uint64_t)A * 60, refine_mid_groups_kernel, dim3(sx_div_up(A, kRmSpan)),
+                  dim3(kRmThreads), ti.T, ti.n, (const uint32_t *)s.ap, (const uint32_t *)s.apos, (const uint32_t *)s.agid,
+                  (const uint32_t *)s.gsize, (uint64_t)A, skip, kc_r, s.vs, s.ap_new, s.head_new,
+                  s.windows(p), s.full_wcfg);
+    }
+    SX_TRY((device_compact(ctx, A, InLargeGroup{s.agid, s.gsize, (uint32_t)(s.lds_tier ? kMidGroup : kSmallGroup)},
+                           OutLargeMember{ti.T, s.ap, s.agid, ti.n, skip, kc_r, s.sub_t, s.sub_gid, s.key_keep, s.rk_a, s.ord_a}, s.d_scalar,
+                           SX_KC_DOUBLING, (uint64_t)A * 12)));
+    uint32_t A3 = 0;
+    SX_TRY(sx_readback(ctx, s.d_scalar, 1, &A3));
+    if (A3 == 0) return 0;
+    ctx->stats.refine_tiers |= 2u;
+    uint32_t *sub_num = s.gsize; // (the sizes are not needed any more)
+    SX_TRY((device_scan<OpAdd>(ctx, A3, InSubHead{s.sub_t, s.sub_gid}, OutGroupNumber{sub_num}, s.d_scalar + 3, SX_KC_DOUBLING,
+                               (uint64_t)A3 * 12)));
+    // (the groups' numbers are sort digits: how many there are is bounded by their least length -- no read-back of the count,
+    //  20 us of idle device a round; the bound is a bit too wide at most, and digits are taken eight bits at a time)
+    const uint32_t least = (uint32_t)(s.lds_tier ? kMidGroup : kSmallGroup) + 1u;
+    const uint32_t n_long_max = A3 / least > 1u ? A3 / least : 1u;
+    const uint32_t gbits = n_long_max > 1 ? (uint32_t)sx_bitlen(n_long_max - 1) : 1u;
+    if (s.trace) {
+        uint32_t n_long = 0;
+        SX_TRY(sx_readback(ctx, s.d_scalar + 3, 1, &n_long));
+        fprintf(stderr, "stralg_amd refine:   %u members of %u groups too long for the LDS tier\n", A3, n_long);
+    }
+    // order by (group, next key), LSD: stable sort by next key, then stable sort by group
+    int f = 0;
+    SX_TRY(sx_sort_pairs(ctx, s.rk_a, s.ord_a, s.rk_b, s.ord_b, A3, 0, s.kbits_r, &f));
+    uint32_t *ord1 = f ? s.ord_b : s.ord_a, *ord1_other = f ? s.ord_a : s.ord_b;
+    uint64_t *k1 = f ? s.rk_a : s.rk_b, *k1_other = f ? s.rk_b : s.rk_a; // k1: free to overwrite
+    sx_launch(ctx, SX_KC_DOUBLING, (uint64_t)A3 * 16, gid_keys_kernel, dim3(sx_div_up(A3, kBlock)), block,
+              (const uint32_t *)ord1, (const uint32_t *)sub_num, (uint64_t)A3, k1);
+    SX_TRY(sx_sort_pairs(ctx, k1, ord1, k1_other, ord1_other, A3, 0, (int)gbits, &f));
+    const uint32_t *order = f ? ord1_other : ord1;
+    sx_launch(ctx, SX_KC_DOUBLING, (uint64_t)A3 * 44, refine_write_kernel, dim3(sx_div_up(A3, kBlock)), block, order,
+              (const uint32_t *)s.sub_t, (const uint32_t *)s.ap, (const uint32_t *)s.apos, (const uint32_t *)sub_num,
+              (const uint64_t *)s.key_keep, (uint64_t)A3, s.vs, s.ap_new, s.head_new, s.windows(p), ti.T, s.full_wcfg);
+    return 0;
+}
+
+// One round of the refinement: the tied members by their next Cmax symbols.  *general: repetitive text, the general path.
+int refine_round(prefix_sort &s, const prefix_plan &p, int round, bool *general)
+{
+    sx_ctx *ctx = s.ctx;
+    const sx_text_info &ti = *s.ti;
+    const uint32_t A = s.A;
+    const dim3 block(kBlock);
+    // Few survivors are repeats proper: they get more rounds (each costs little) and, from the third round on,
+    // small groups are finished by comparing the suffixes themselves.  Many survivors after four rounds, or any
+    // after 32: repetitive text, general path.
+    const bool few = (uint64_t)A * 16 <= s.m;
+    if (round > (few ? 32 : 4)) {
+        *general = true;
+        return 0;
+    }
+    ctx->stats.doubling_rounds++;
+    const uint64_t skip = (uint64_t)p.C + (uint64_t)s.Cmax * (round - 1);
+    uint32_t counters[2] = {0, 0};
+    SX_CHECK(hipMemsetAsync(s.d_scalar + 1, 0, 2 * sizeof(uint32_t), ctx->stream));
+    if (few && round >= 3) {
+        SX_CHECK(hipMemcpyAsync(s.ap_new, s.ap, (size_t)A * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+        SX_CHECK(hipMemcpyAsync(s.head_new, s.head, (size_t)A, hipMemcpyDeviceToDevice, ctx->stream));
+        sx_launch(ctx, SX_KC_DOUBLING, (uint64_t)A * 60, refine_by_comparison_kernel, dim3(sx_div_up(A, kBlock)), block, ti.T,
+                  ti.n, (const uint32_t *)s.ap, (const uint32_t *)s.apos, (const uint8_t *)s.head, (uint64_t)A, skip, s.vs, s.ap_new, s.head_new,
+                  s.windows(p), s.full_wcfg, s.d_scalar + 1);
+        SX_TRY(sx_readback(ctx, s.d_scalar + 1, 2, counters));
+        if (counters[1]) { // a repeat beyond the comparison cap: general path
+            *general = true;
+            return 0;
+        }
+        SX_TRY(keep_tied(s));
+        if (s.A == 0) return 0;
+        SX_TRY(refine_larger_groups(s, p, skip)); // what is left sits in groups of more than eight: every member is rewritten
+        return keep_tied(s);
+    }
+    // groups of up to eight members: settled by their head's thread
+    if (ctx->sort_mode != 1)
+        sx_launch(ctx, SX_KC_DOUBLING, (uint64_t)A * 60, refine_small_groups_wave_kernel,
+                  dim3(sx_div_up(sx_div_up(A, kRsStride), kWavesPerBlock)), block, ti.T, ti.n, (const uint32_t *)s.ap,
+                  (const uint32_t *)s.apos, (const uint8_t *)s.head, (uint64_t)A, skip, pkey_make(s.base, s.Cmax), s.vs, s.ap_new, s.head_new,
+                  s.windows(p), s.full_wcfg, s.d_scalar + 1);
+    else
+        sx_launch(ctx, SX_KC_DOUBLING, (uint64_t)A * 60, refine_small_groups_kernel, dim3(sx_div_up(A, kBlock)), block, ti.T,
+                  ti.n, (const uint32_t *)s.ap, (const uint32_t *)s.apos, (const uint8_t *)s.head, (uint64_t)A, skip,
+                  pkey_make(s.base, s.Cmax), s.vs, s.ap_new, s.head_new, s.windows(p), s.full_wcfg, s.d_scalar + 1);
+    SX_TRY(sx_readback(ctx, s.d_scalar + 1, 1, counters));
+    if (counters[0]) SX_TRY(refine_larger_groups(s, p, skip)); // larger groups exist: they are refined in LDS or by sorting
+    return keep_tied(s);
+}
+
+// The tied members, round by round, until none is left (*resolved) or the text shows itself repetitive.
+int refine_ties(prefix_sort &s, const prefix_plan &p, int *resolved)
+{
+    const bool wide_windows = sx_window_cfg(s.ti->maxc, s.full_wcfg);
+    if (s.all_suffixes) s.full_wcfg.CW = 1; // (the seed windows are 32-bit words: one wide symbol fits, seven do not)
+    else if (wide_windows && p.embed) s.full_wcfg.CW = p.embed_chars; // (32-bit words here too: as many symbols as the keys carried)
+    s.kbits_r = sx_prefix_key_bits(s.base, s.Cmax);
+    s.lds_tier = s.ctx->sort_mode != 1;
+    s.trace = getenv("STRALG_AMD_TRACE_REFINE") != nullptr; // (diagnostic: members and time of every refinement round)
+    for (int round = 1; s.A > 0; ++round) {
+        const auto t0 = std::chrono::steady_clock::now();
+        const uint32_t a0 = s.A;
+        bool general = false;
+        const int rc = refine_round(s, p, round, &general);
+        if (s.trace)
+            fprintf(stderr, "stralg_amd refine: round %d  %u -> %u tied members  %.3f ms\n", round, a0, s.A,
+                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+        if (rc != 0 || general) return rc;
+    }
+    *resolved = 1;
+    return 0;
+}
+
+} // namespace
+
 // Returns 0 and *resolved = 1 with *out = device array of the m LMS suffix positions in
 // suffix order; *resolved = 0 when the caller must use the general path.
 int sx_sort_lms_by_prefix(sx_ctx *ctx, const sx_text_info &ti, sx_arena &am, const uint32_t **out,
@@ -943,501 +1288,50 @@ int sx_sort_lms_by_prefix(sx_ctx *ctx, const sx_text_info &ti, sx_arena &am, con
 {
     *resolved = 0;
     *seed_windows = nullptr;
+    prefix_sort s = {};
+    s.ctx = ctx, s.ti = &ti, s.all_suffixes = all_suffixes;
     // all_suffixes: the same machinery over every position of the text instead of the LMS positions; what comes
     // out is the suffix array itself (sx_build.hip decides when that is the cheaper way)
-    const uint64_t m = all_suffixes ? ti.N : ti.m;
-    const uint32_t base = ti.maxc + 1;
-    // longest prefix whose number fits 63 bits
-    uint32_t Cmax = 0;
-    for (double cap63 = 9.2e18, v = 1.0; v * base <= cap63 && Cmax < 63; v *= base) ++Cmax;
-    if (Cmax < 1) Cmax = 1;
-    // shortest prefix that tells ~97 % of m suffixes of a uniformly random text apart
-    uint32_t C = 1;
-    {
-        // (the direct sort of all suffixes accepts twice the ties to stay within 40 key bits at 32, 128, ... symbols)
-        const double eff = ti.maxc > 2 ? (double)ti.maxc : 2.0, target = (all_suffixes ? 16.0 : 32.0) * (double)m;
-        double v = eff;
-        while (v < target && C < Cmax) {
-            v *= eff;
-            ++C;
-        }
-        // Skewed symbol frequencies (a genome with 5 % N, a GC-poor one): two suffixes agree on a symbol with
-        // probability sum p^2, not 1 / maxc.  A prefix that is too short costs a whole second sort with the longest
-        // key; one symbol too many costs at most a pass.  So the prefix is also made long enough for <= ~6 % ties
-        // under the text's own collision rate (uniform text: never the larger of the two; symbols that only occur
-        // in long runs, like N, hardly enter the rate but do enter maxc: that case needs the margin).
-        double sum_p2 = 0.0;
-        const double n_sym = (double)ti.N - 1.0;
-        for (int c = 1; c < 256 && n_sym > 0; ++c) {
-            const double pc = (double)ti.h_all[c] / n_sym;
-            sum_p2 += pc * pc;
-        }
-        if (sum_p2 > 0.0 && sum_p2 < 1.0) {
-            const double eff_c = 1.0 / sum_p2, target_c = 16.0 * (double)m;
-            uint32_t Cc = 1;
-            for (double u = eff_c; u < target_c && Cc < Cmax; u *= eff_c) ++Cc;
-            if (Cc > C) C = Cc;
-        }
-    }
-    // Round 4: four-letter texts take one symbol more where the dense key still leaves at most 19 bits to the local sort
-    // (2 C + length field <= 41).  The prefix above leaves ~1.8 % of uniformly random suffixes tied, one symbol more a
-    // quarter of that, and the tied suffixes' refinement -- random reads of the text -- cost more than the symbol: same box,
-    // 1 GiB 22.13 -> 21.13 ms (refinement 1.00 -> 0.28 ms, every other class unchanged), 256 MiB 6.36 -> 6.19; a symbol
-    // less: 23.21.  Taken back below if the text turns out not to take the hybrid sort (plain passes would pay a pass for it).
-    bool one_more = false;
-    if (!all_suffixes && base == 5 && ctx->prefix_symbols <= 0 && ctx->sort_mode != 1 && C + 1 <= Cmax &&
-        2 * (C + 1) + (uint32_t)sx_bitlen(C + 1) <= 41) {
-        ++C;
-        one_more = true;
-    }
-    // (the direct sort of all suffixes likewise, while the key stays within 40 bits -- five 8-bit digits either way, at most
-    //  16 bits for the local sort: 1 GiB of 20 symbols 58.5 -> 56.3 ms, ties refined in 0.19 instead of 2.7 ms; bytes stay at
-    //  five symbols, six would be 48 bits)
-    if (all_suffixes && ctx->prefix_symbols <= 0 && C + 1 <= Cmax) {
-        double top = 1.0;
-        for (uint32_t i = 0; i <= C; ++i) top *= (double)base;
-        if (top <= 1099511627776.0) ++C; // base^(C+1) <= 2^40
-    }
-    if (ctx->prefix_symbols > 0) C = (uint32_t)ctx->prefix_symbols < Cmax ? (uint32_t)ctx->prefix_symbols : Cmax; // (tests)
-    const uint32_t cap = (uint32_t)(m / 4 + 1024);
-    uint64_t *ka = am.take<uint64_t>(m), *kb = am.take<uint64_t>(m);
-    uint32_t *va = am.take<uint32_t>(m), *vb = am.take<uint32_t>(m);
-    uint64_t *key_keep = am.take<uint64_t>(cap), *rk_a = am.take<uint64_t>(cap), *rk_b = am.take<uint64_t>(cap);
-    uint32_t *apos = am.take<uint32_t>(cap), *apos2 = am.take<uint32_t>(cap);
-    uint32_t *ap = am.take<uint32_t>(cap), *ap2 = am.take<uint32_t>(cap), *ap_new = am.take<uint32_t>(cap);
-    uint32_t *agid = am.take<uint32_t>(cap), *ord_a = am.take<uint32_t>(cap), *ord_b = am.take<uint32_t>(cap);
-    uint32_t *gsize = am.take<uint32_t>(cap), *sub_t = am.take<uint32_t>(cap), *sub_gid = am.take<uint32_t>(cap);
-    uint8_t *head = am.take<uint8_t>(cap), *head2 = am.take<uint8_t>(cap), *head_new = am.take<uint8_t>(cap);
-    uint32_t *seedw = am.take<uint32_t>(m);
-    uint32_t *d_scalar = am.take<uint32_t>(16);
-    const uint32_t tied_tiles = sx_div_up(m, kTiedTile);
-    uint32_t *tile_cnt = am.take<uint32_t>(tied_tiles), *tile_pos = am.take<uint32_t>(tied_tiles);
-    const uint32_t ls_tiles = sx_local_sort_tiles(m);
-    uint32_t *tile_lsrt = am.take<uint32_t>(3 * (size_t)ls_tiles); // start, tied members, offset of every local-sort workgroup
-    // sub-buckets too long for a workgroup (repeat families, AT-rich prefixes): their starts, lengths, offsets (sx_long_subbuckets)
-    uint32_t *long_list = ctx->long_subbuckets_off ? nullptr : am.take<uint32_t>(3 * (size_t)kLongCap);
-    if (!tile_cnt || !tile_pos || !seedw || !ka || !kb || !va || !vb || !key_keep || !rk_a || !rk_b || !apos || !apos2 || !ap || !ap2 || !ap_new ||
-        !agid || !ord_a || !ord_b || !gsize || !sub_t || !sub_gid || !head || !head2 || !head_new || !d_scalar)
-        return sx_fail_msg(ctx, SX_E_INTERNAL, "arena: LMS prefix sort");
-    const dim3 block(kBlock);
-
+    s.m = all_suffixes ? ti.N : ti.m;
+    s.base = ti.maxc + 1;
+    s.Cmax = sx_prefix_cmax(s.base);
+    s.cap = (uint32_t)(s.m / 4 + 1024);
+    if (!take_arrays(s, am)) return sx_fail_msg(ctx, SX_E_INTERNAL, "arena: LMS prefix sort");
     // offset of every classification tile in the global order of the LMS positions
-    uint32_t *tile_lms = ti.tile_u32, *tile_off = all_suffixes ? nullptr : ti.tile_u32 + 4 * (size_t)ti.ntiles;
-    if (!all_suffixes) SX_TRY((device_scan<OpAdd>(ctx, ti.ntiles, InU32{tile_lms}, OutExclusive{tile_off}, nullptr)));
+    uint32_t *tile_lms = ti.tile_u32;
+    s.tile_off = all_suffixes ? nullptr : ti.tile_u32 + 4 * (size_t)ti.ntiles;
+    if (!all_suffixes) SX_TRY((device_scan<OpAdd>(ctx, ti.ntiles, InU32{tile_lms}, OutExclusive{s.tile_off}, nullptr)));
 
-    const uint64_t *ks = nullptr; // sorted keys (not kept by the hybrid sort)
-    uint32_t *vs = nullptr;
-    uint32_t A = 0;
-    int kbits = 64;
-    bool embed = false;
-    uint32_t embed_chars = 0; // symbols of the windows the keys carry (embed)
-    uint64_t kmask = ~0ull;
-#ifndef SX_DENSE4
-#define SX_DENSE4 1
-#endif
+    prefix_inputs in = {};
+    in.N = ti.N, in.m = s.m, in.maxc = ti.maxc, in.ntiles = ti.ntiles, in.all_suffixes = all_suffixes;
+    in.st = sx_symbol_stats_of(ti.h_all, ti.N);
+    in.prefix_symbols = ctx->prefix_symbols, in.sort_mode = ctx->sort_mode, in.text_keys_off = ctx->text_keys_off != 0;
+    in.long_list = s.long_list != nullptr, in.ls_tiles = s.tile_lsrt != nullptr, in.digit_bits = sx_sort_digit_bits(ctx);
+    const prefix_first first = prefix_first_length(in);
+    prefix_plan p;
+    uint32_t C = first.C;
     for (int attempt = 0;; ++attempt) {
-        // four symbols and the sentinel: dense keys of two bits a symbol and a length field (dense4_finish); the plain-passes
-        // mode keeps the base-5 keys (tests run both)
-        const uint32_t lenbits = (uint32_t)sx_bitlen(C);
-        int kbits_wnd = 64, kbits_base = 64;
-        // (dense keys only with the hybrid sort: plain passes run faster on the base-5 keys' uneven digits -- the genome-like
-        //  text 41.9 against 40.5 ms --, so the decisions below are taken for the dense keys first and, if they end without
-        //  the hybrid sort, once more for the base-5 keys)
-        bool dense4 = SX_DENSE4 && !all_suffixes && base == 5 && ctx->sort_mode != 1 && 2 * C + lenbits <= 60;
-        wnd_cfg wcfg;
-        int sort_db = 8, top_bits = 0; // top_bits: of the hybrid sort; 0: plain passes over all key bits
-        bool ls_skewed = false;        // the hybrid sort was chosen by the mean sub-bucket of skewed symbol counts (a genome's: repeat
-                                       // families crowd the LDS step's bins, whose workgroups the kernel of rounds 3 and 4 takes at once)
-        uint8_t *dig0 = nullptr;
-        for (;;) {
-        {
-            uint64_t top = 1; // base^C - 1 is the largest key
-            for (uint32_t i = 0; i < C; ++i) top *= base;
-            kbits = dense4 ? (int)(2 * C + lenbits) : sx_bitlen(top - 1);
-            if (kbits < 1) kbits = 1;
-            kbits_base = sx_bitlen(top - 1) > 0 ? sx_bitlen(top - 1) : 1;
-            kbits_wnd = kbits > kbits_base ? kbits : kbits_base; // (dense keys: the windows of the base-5 keys, for which the static kernels are built)
-        }
-        // Symbol windows in the unsorted key bits, when at least four symbols fit.  Texts of more than 16 symbols, whose
-        // induction windows are 64-bit words, take part since round 4: the sort hands the windows on as 32-bit words (the
-        // same layout with fewer symbols: code fields of B bits above a 4-bit count), so up to 28 / B symbols, and from
-        // two on they are worth it -- an LMS seed's first symbol is its entry's bucket, its second the symbol byte of
-        // the entry it induces, and the text is read again where that entry is scanned.  (Without them every seed's
-        // window was gathered from the text in suffix order before the L pass: 3.6 * 10^8 random 16-byte reads, 8.3 of
-        // the 94 ms of 1 GiB of bytes through the induced-sort passes.)
-        const bool wide = sx_window_cfg(ti.maxc, wcfg);
-        uint32_t wchars = 0;
-        if (64 - kbits_wnd > kCntBits) wchars = (uint32_t)(64 - kbits_wnd - kCntBits) / wcfg.B;
-        if (wchars > wcfg.CW) wchars = wcfg.CW;
-        if (wide && wchars > (32u - (uint32_t)kCntBits) / wcfg.B) wchars = (32u - (uint32_t)kCntBits) / wcfg.B;
-        embed = wide ? wchars >= 2 : wchars >= 4;
-        embed_chars = embed ? wchars : 0;
-        if (all_suffixes) {
-            // no induction follows a direct sort; one symbol of window is the BWT symbol of the suffix, for free
-            wchars = 64 - kbits >= (int)(kCntBits + wcfg.B) ? 1u : 0u;
-            embed = wchars == 1;
-        }
-        wcfg.CW = embed ? wchars : 0;
-        kmask = kbits >= 64 ? ~0ull : ((1ull << kbits) - 1ull);
-        // the key kernels leave the first pass's digits there (one byte each: 8-bit digits only)
-        sort_db = sx_sort_digit_bits(ctx);
-        dig0 = (uint8_t *)sx_sort_digit_buffer(ctx, m, sort_db);
-        if (!dig0) return sx_fail_msg(ctx, SX_E_NOMEM, "sort workspace");
-        // Hybrid sort (sx_localsort.hip): only the top 24 key bits go through HBM passes, the sub-buckets they leave are
-        // ordered in LDS.  It needs sub-buckets that fit a workgroup: a prefix of 24 / log2(base) symbols must not be too
-        // frequent.  Judged here from the text's most frequent symbol (a run of it is the most frequent prefix of a text
-        // without repeats); repeats show when the kernel finds a sub-bucket that does not fit, and LSD passes finish the job.
-        top_bits = 0;
-        if (ctx->sort_mode != 1 && sort_db == 8 && tile_lsrt != nullptr) {
-            // Sub-buckets the top bits leave: the low L = kbits - top bits span base^(L / log2 base) key values, so the
-            // top bits tell apart prefixes of C - L / log2(base) symbols (A C G T in base 5, 17 symbols, L = 16: 10.1) -- and
-            // a text has about (effective alphabet)^(that many) of those, the effective alphabet being 1 / sum p^2 (4,
-            // not 5: a fifth of the key space per symbol is never used).  Also: the copies of the most frequent one.
-            // Three passes (24 bits).  Four passes (32 bits) leave short sub-buckets in texts of 2 Gi symbols and more and
-            // with skewed frequencies too (2 GiB of uniform DNA: 40.3 against 43.2 ms for six plain passes), but are only
-            // taken when asked for (SX_FLAG_SORT_MODE 3): texts that long are genomes, their repeat families overflow a
-            // workgroup whatever the symbol counts promise, and a failed attempt costs more than a good one saves
-            // (the genome-like 1 GiB text: 58 instead of 44 ms).  (Four-letter texts with dense keys: see cand0 below -- their
-            // sub-buckets' lengths are known, and 2 GiB ... 8 GiB of uniform DNA take the hybrid sort with 22 / 24 top bits.)
-            double pmax = 0.0, sum_p2 = 0.0;
-            const double n_sym = (double)ti.N - 1.0;
-            for (int c = 1; c < 256 && n_sym > 0; ++c) {
-                const double pc = (double)ti.h_all[c] / n_sym;
-                if (pc > pmax) pmax = pc;
-                sum_p2 += pc * pc;
-            }
-            const double eff = sum_p2 > 0.0 ? 1.0 / sum_p2 : 1.0;
-#ifndef SX_DENSE4_TOP
-#define SX_DENSE4_TOP 22 // (1 GiB of DNA, whole step: base-5 keys 23.30 ms; dense keys with 24 top bits 22.79, 22: 22.71, 21: 22.73, 20: 22.79)
-#endif
-            // Dense keys: a sub-bucket is a prefix of top_bits / 2 symbols, so its mean length (m / eff^symbols) and that of
-            // the most frequent symbol's run (m * pmax^symbols) are known better than for base-b keys; LMS suffixes favour
-            // some prefixes (the fullest sub-bucket of uniform text holds 3.6 times the mean, measured), so 4.5 times the
-            // larger of the two, with half as much again for safety, has to fit the 1024 pairs between a span's end and the
-            // reach.  Skewed symbol counts (a genome: 30 % A) give the run of the most frequent symbol many times the mean:
-            // such texts have repeat families too, and are left to plain passes as before.  22 top bits where they do
-            // (1 GiB ... 2 GiB of uniform DNA), else 24 (up to 8 GiB).
-            int cand0 = dense4 ? SX_DENSE4_TOP : 24;
-            bool dense_fits = false;
-            if (dense4 && ctx->sort_mode == 0) {
-                for (int tb = SX_DENSE4_TOP; tb <= 24 && !dense_fits; tb += 2) {
-                    const double sy = (double)tb / 2.0, mean_d = (double)m / pow(eff, sy), top_d = (double)m * pow(pmax, sy);
-                    if (top_d <= 1.5 * mean_d && 4.5 * top_d * 1.5 <= 1024.0 && sx_local_sort_applies(m, kbits, tb)) cand0 = tb, dense_fits = true;
-                }
-                // Round 4: skewed symbol counts and repeat families no longer rule the hybrid sort out -- the sub-buckets that
-                // do not fit a workgroup are listed and ordered by HBM passes of their own (sx_long_subbuckets) --, so what
-                // counts is the mean sub-bucket (the genome-like 1 GiB text: 115 pairs at 22 bits, 6 % of the pairs in long
-                // sub-buckets): three HBM passes and the LDS step instead of five passes, a key kernel and the pass that marks
-                // the ties.  (A text whose long sub-buckets hold a quarter of the pairs falls back as before.)
-                for (int tb = SX_DENSE4_TOP; tb <= 24 && !dense_fits && long_list != nullptr; tb += 2) {
-                    const double mean_d = (double)m / pow(eff, (double)tb / 2.0);
-                    if (mean_d <= 256.0 && sx_local_sort_applies(m, kbits, tb)) cand0 = tb, dense_fits = true, ls_skewed = true;
-                }
-            }
-            for (int ci = 0; ci < 2 && top_bits == 0; ++ci) {
-                const int cand = ci == 0 ? cand0 : 32;
-                if (!sx_local_sort_applies(m, kbits, cand)) continue;
-                if (ctx->sort_mode >= 2) { // forced (tests): 2 three passes, 3 four
-                    if ((ctx->sort_mode == 2) == (ci == 0)) top_bits = cand;
-                    continue;
-                }
-                const double syms = (double)C - (double)(kbits_base - (ci == 0 ? 24 : 32)) / log2((double)base);
-                const double mean_bucket = syms > 0.0 ? (double)m / pow(eff, syms) : (double)m;
-                const double top_bucket = syms > 0.0 ? (double)m * pow(pmax, syms) : (double)m;
-                if (ci == 0 && m >= (1u << 22) && (dense4 ? dense_fits : (mean_bucket <= 300.0 && top_bucket <= 400.0))) top_bits = cand; // (a workgroup owns the sub-buckets that start in its span and end within its reach: one that starts
-                                                                                                       //  at the span's last pair may hold kLsCap - kLsSpan = 1024 pairs, one that starts earlier more)
-            }
-        }
-        if (!dense4 || top_bits != 0) break;
-        dense4 = false;
-        if (one_more && attempt == 0) { // (no hybrid sort after all: the shorter key, as before)
-            --C;
-            one_more = false;
-        }
-        }
-        const bool hybrid = top_bits != 0;
-        const uint32_t dig_shift = hybrid ? (uint32_t)(kbits - top_bits) : 0u;
-        const uint32_t dig_mask = kbits - (int)dig_shift >= 8 ? 0xFFu : (1u << (kbits - (int)dig_shift)) - 1u;
-        // The direct sort's keys are a function of the text alone, so where the hybrid sort applies its first HBM pass computes
-        // them itself (sx_textkey, sx_radix.hip): no key kernel, and 8 bytes a suffix that are neither written nor read back
-        // (1 GiB of bytes: 2.4 ms of key kernel and 7.5 GB of the first scatter's reads).  Switch for the A/B and the
-        // tests: SX_FLAG_TEXT_KEYS_OFF keeps the key kernel.
-        const bool text_keyed = all_suffixes && C <= 12 && hybrid && sort_db == 8 && !ctx->text_keys_off;
-        sx_textkey tkey = {ti.T, base, C, 1u, 1u, (uint32_t)kbits, wcfg.CW ? 1u : 0u};
-        for (uint32_t i = 0; i < 3; ++i) tkey.pow3 *= base;
-        for (uint32_t i = 0; i < C % 3; ++i) tkey.powR *= base;
-        // The LMS sort of a four-letter text likewise (sx_lmskey, round 4): the hybrid sort's first pass lists the LMS
-        // suffixes of its piece of the text and computes their dense keys itself -- no key kernel, and 13 bytes an LMS suffix
-        // (key, position, first digit) that are neither written nor read back.  Same switch.
-        const pkey_cfg lms_kc = pkey_make(dense4 ? 4u : base, C);
-        const uint32_t lms_shape = (!all_suffixes && lms_kc.dot && wcfg.B == 2 && wcfg.CW) ? lms_key_shape(C, wcfg.CW, 2) : 0u;
-        const bool lms_keyed = !all_suffixes && hybrid && dense4 && sort_db == 8 && !ctx->text_keys_off && lms_shape != 0 &&
-                               sx_sort_lms_keys_applies(m, ti.ntiles, lms_shape);
-        const sx_lmskey lkey = {ti.T, (const uint16_t *)ti.lmsbits, (const uint32_t *)tile_off, ti.ntiles, (uint32_t)m, lms_kc, wcfg,
-                                (uint32_t)kbits, lenbits, (uint64_t)ti.n + 1, lms_shape};
-        if (text_keyed || lms_keyed) {
-        } else if (all_suffixes && C <= 12) {
-            const pkey_cfg kc = pkey_make(base, C);
-            const dim3 grid16(sx_div_up(m, kBlock * 16));
-#define SX_KEYS16(G) sx_launch(ctx, SX_KC_KEYS, m * 10, all_keys16_kernel<G>, grid16, block, ti.T, m, kc, (uint32_t)kbits, wcfg, ka, dig0, dig_shift, dig_mask)
-            switch (kc.G) {
-            case 10: SX_KEYS16(10); break;
-            case 6: SX_KEYS16(6); break;
-            case 4: SX_KEYS16(4); break;
-            default: SX_KEYS16(3); break;
-            }
-#undef SX_KEYS16
-        } else if (all_suffixes)
-            sx_launch(ctx, SX_KC_KEYS, m * 13, all_keys_kernel, dim3(sx_div_up(m, kBlock)), block, ti.T, m, pkey_make(base, C),
-                      (uint32_t)kbits, wcfg, ka, dig0, dig_shift, dig_mask);
-        else
-        {
-            const pkey_cfg kc = pkey_make(dense4 ? 4u : base, C);
-            // DNA-like texts: everything static for the usual prefix lengths (base 5: the window takes what
-            // 64 - kbits - 4 bits hold)
-            const bool dna = kc.dot && (wcfg.B == 2 || wcfg.B == 3) && kbits >= 8;
-#define SX_TILE_KEYS(CS, WS, BS)                                                                                       \
-    sx_launch(ctx, SX_KC_KEYS, m * 12 + ti.N + ti.N / 8, lms_tile_keys_kernel<CS, WS, BS>, dim3(ti.ntiles), block,     \
-              ti.T, (const uint16_t *)ti.lmsbits, (const uint32_t *)tile_off, kc, (uint32_t)kbits, wcfg, ka, va, dig0, dig_shift, dig_mask, \
-              (uint64_t)(dense4 ? ti.n + 1 : 0), lenbits)
-            const uint32_t shape = dna ? (C * 16 + wcfg.CW) * 4 + wcfg.B : 0u;
-            switch (shape) {
-            // base 5 (A C G T): 64 Mi ... 4 Gi symbols
-            case (14 * 16 + 13) * 4 + 2: SX_TILE_KEYS(14, 13, 2); break;
-            case (15 * 16 + 12) * 4 + 2: SX_TILE_KEYS(15, 12, 2); break;
-            case (16 * 16 + 11) * 4 + 2: SX_TILE_KEYS(16, 11, 2); break;
-            case (17 * 16 + 10) * 4 + 2: SX_TILE_KEYS(17, 10, 2); break;
-            case (18 * 16 + 9) * 4 + 2: SX_TILE_KEYS(18, 9, 2); break;
-            // base 6 (A C G N T)
-            case (13 * 16 + 8) * 4 + 3: SX_TILE_KEYS(13, 8, 3); break;
-            case (14 * 16 + 7) * 4 + 3: SX_TILE_KEYS(14, 7, 3); break;
-            case (15 * 16 + 7) * 4 + 3: SX_TILE_KEYS(15, 7, 3); break;
-            case (16 * 16 + 6) * 4 + 3: SX_TILE_KEYS(16, 6, 3); break;
-            default: SX_TILE_KEYS(0, 0, 0); break;
-            }
-#undef SX_TILE_KEYS
-        }
-        int in_b = 0;
-        ctx->stats.sort_local = 0;
-        bool listed = false; // the members of groups of equal keys are in (apos, ap, head), A of them
-        if (hybrid) {
-            // three stable passes on the top 24 bits, then the sub-buckets in LDS: positions, windows and ties in one go
-            SX_TRY(sx_sort_pairs(ctx, ka, va, kb, vb, m, kbits - top_bits, kbits, &in_b, all_suffixes, true, 8, text_keyed ? &tkey : nullptr,
-                                 lms_keyed ? &lkey : nullptr));
-            const uint64_t *kin = in_b ? kb : ka;
-            const uint32_t *vin = in_b ? vb : va;
-            uint32_t *vo = in_b ? va : vb;
-            // (dense keys: a sub-bucket is a prefix of top_bits / 2 symbols; LMS suffixes favour some prefixes -- two thirds of
-            //  them begin with the smallest symbol -- so the fullest sub-bucket of uniform text holds 3.6 times the mean: 4.5 times
-            //  the most frequent symbol's share to that power, for the local sort's choice of its span)
-            uint32_t longest = 0;
-            if ((dense4 || all_suffixes) && ctx->sort_mode == 0) {
-                double pm = 0.0;
-                for (int c = 1; c < 256; ++c) pm = (double)ti.h_all[c] > pm ? (double)ti.h_all[c] : pm;
-                pm /= (double)ti.N - 1.0;
-                // (all suffixes of a wide alphabet, the direct sort: no favoured prefixes, a sub-bucket is a prefix of
-                //  top_bits / log2(base) symbols -- three bytes at 256 symbols --: the most frequent symbol's run and what
-                //  chance adds to the fullest of 2^24 sub-buckets)
-                const double run = (double)m * pow(pm, dense4 ? (double)top_bits / 2.0 : (double)top_bits / log2((double)base));
-                const double est = dense4 ? 4.5 * run : 1.2 * run + 8.0 * sqrt(run) + 16.0;
-                longest = est < 1.0 ? 1u : (est > 1e9 ? 1000000000u : (uint32_t)est);
-            }
-            uint32_t res[3] = {0, 0, 0};
-            SX_TRY(sx_local_sort(ctx, kin, vin, m, kbits, top_bits, vo, embed ? seedw : nullptr, tile_lsrt, tile_lsrt + ls_tiles,
-                                 tile_lsrt + 2 * (size_t)ls_tiles, (uint2 *)(in_b ? ka : kb), dig0, apos, ap, head, cap, d_scalar, longest,
-                                 long_list, kLongCap, res, ls_skewed));
-            bool fits = !(res[1] & 1u);
-            ctx->stats.long_subbuckets = 0;
-            if (fits && res[2] != 0) {
-                // sub-buckets that did not fit a workgroup were left out and listed: their members are ordered by HBM passes of
-                // their own (the refinement's arrays are free until the ties are refined: a quarter of the pairs at most)
-                uint32_t tied_all = res[0], pairs = 0;
-                int done = 0;
-                SX_TRY(sx_long_subbuckets(ctx, kin, vin, m, kbits, top_bits, res[2], long_list, kLongCap, rk_a, rk_b, ord_a, ord_b, cap - 1024, vo,
-                                          embed ? seedw : nullptr, apos, ap, head, cap, res[0], d_scalar + 4, &tied_all, &pairs, &done));
-                ctx->stats.long_subbuckets = res[2];
-                fits = done != 0;
-                res[0] = done ? tied_all : res[0] + pairs; // (not done: those pairs are as good as tied -- the decision below)
-            }
-            if (fits) {
-                A = res[0];
-                vs = vo;
-                ks = nullptr; // (the sorted keys are not written by this path; nothing below reads them)
-                listed = true;
-                ctx->stats.sort_local = 1u | (res[1] & 2u) | (top_bits == 32 ? 4u : 0u) | ((text_keyed || lms_keyed) ? 8u : 0u); // (bit 1: some workgroup ordered its pairs by stable passes)
-            } else {
-                // a sub-bucket too long for a workgroup (a repeated prefix): plain LSD passes over all key bits from here
-                // -- unless the workgroups that did finish have listed more tied suffixes already than the refinement
-                // takes, and more than a longer key would be tried for: the general path's turn at once (a collection of
-                // near-identical sequences: five passes over all pairs and the pass that marks the ties, 11 of 210 ms)
-                if (res[0] > cap - 1024 && (attempt != 0 || C >= Cmax || (uint64_t)res[0] * 2 > m)) {
-                    ctx->stats.n_names = m - res[0];
-                    ctx->stats.key_slots = C;
-                    ctx->stats.key_bits = (uint32_t)kbits;
-                    return 0;
-                }
-                uint64_t *k0 = in_b ? kb : ka, *k1 = in_b ? ka : kb;
-                uint32_t *v0 = in_b ? vb : va, *v1 = in_b ? va : vb;
-                int f = 0;
-                SX_TRY(sx_sort_pairs(ctx, k0, v0, k1, v1, m, 0, kbits, &f, false, false, 8));
-                ks = f ? k1 : k0;
-                vs = f ? v1 : v0;
-                in_b = (ks == kb) ? 1 : 0;
-            }
-        } else {
-            SX_TRY(sx_sort_pairs(ctx, ka, va, kb, vb, m, 0, kbits, &in_b, all_suffixes, sort_db == 8, sort_db)); // (all suffixes: value = index)
-            ks = in_b ? kb : ka;
-            vs = in_b ? vb : va;
-        }
-        // members of groups with equal keys
-        if (!listed) {
-            const uint32_t tiles = sx_div_up(m, kTiedTile);
-            // staging in the sort's spare buffers: 8 bytes per slot in the other key array, heads in the other value array
-            uint2 *stage = (uint2 *)(in_b ? ka : kb);
-            uint8_t *stage_head = (uint8_t *)(in_b ? va : vb);
-            sx_launch(ctx, SX_KC_NAMES, m * 13, tied_mark_kernel, dim3(tiles), block, ks, (const uint32_t *)vs, m, kmask,
-                      (uint32_t)kbits, embed ? seedw : nullptr, tile_cnt, stage, stage_head);
-            SX_TRY((device_scan<OpAdd>(ctx, tiles, InU32{tile_cnt}, OutExclusive{tile_pos}, d_scalar, SX_KC_NAMES, 0)));
-            sx_launch(ctx, SX_KC_NAMES, 0, tied_gather_kernel, dim3(tiles), block, (const uint32_t *)tile_cnt,
-                      (const uint32_t *)tile_pos, (const uint2 *)stage, (const uint8_t *)stage_head, apos, ap, head, cap);
-            SX_TRY(sx_readback(ctx, d_scalar, 1, &A));
-        }
-        ctx->stats.n_names = m - A; // suffixes told apart by the first sort
-        ctx->stats.key_slots = C;
-        ctx->stats.key_bits = (uint32_t)kbits;
-        if (A <= cap - 1024) break;
+        p = prefix_plan_for(in, C, first.one_more && attempt == 0);
+        bool general = false;
+        SX_TRY(make_keys(s, p));
+        SX_TRY(sort_and_list_ties(s, p, attempt != 0 || p.C >= s.Cmax, &general));
+        ctx->stats.n_names = s.m - s.A; // suffixes told apart by the first sort
+        ctx->stats.key_slots = p.C;
+        ctx->stats.key_bits = (uint32_t)p.kbits;
+        if (general) return 0;
+        if (s.A <= s.cap - 1024) break;
         // skewed symbol frequencies leave a good quarter of the suffixes tied: once more with the longest key.  With
         // more than half of them tied the text repeats itself (words of a vocabulary, periods): a longer key would
         // tie them again, so the general path takes over without the second sort (8 passes over all pairs).
-        if (attempt == 0 && C < Cmax && (uint64_t)A * 2 <= m) {
-            C = Cmax;
+        if (attempt == 0 && p.C < s.Cmax && (uint64_t)s.A * 2 <= s.m) {
+            C = s.Cmax;
             continue;
         }
         return 0; // repetitive text: general path
     }
-
-    wnd_cfg full_wcfg; // refined slots get their windows straight from the text
-    const bool wide_windows = sx_window_cfg(ti.maxc, full_wcfg);
-    if (all_suffixes) full_wcfg.CW = 1; // (the seed windows are 32-bit words: one wide symbol fits, seven do not)
-    else if (wide_windows && embed) full_wcfg.CW = embed_chars; // (32-bit words here too: as many symbols as the keys carried)
-    // ties are refined with the longest key that fits (Cmax symbols a round)
-    uint64_t top_r = 1;
-    for (uint32_t i = 0; i < Cmax; ++i) top_r *= base;
-    const int kbits_r = sx_bitlen(top_r - 1) > 0 ? sx_bitlen(top_r - 1) : 1;
-    // keep what is still tied after a refinement step: (apos, ap_new, head_new) -> (apos, ap, head), A
-    auto keep_tied = [&]() -> int {
-        SX_TRY((device_compact(ctx, A, InStillTied{head_new, A}, OutStillTied{apos, ap_new, head_new, apos2, ap2, head2},
-                               d_scalar, SX_KC_DOUBLING, (uint64_t)A * 20)));
-        uint32_t A2 = 0;
-        SX_TRY(sx_readback(ctx, d_scalar, 1, &A2));
-        uint32_t *tp = apos; apos = apos2; apos2 = tp;
-        tp = ap; ap = ap2; ap2 = tp;
-        uint8_t *th = head; head = head2; head2 = th;
-        A = A2;
-        return 0;
-    };
-    // One refinement step by the next Cmax symbols for the groups of more than kSmallGroup members (the smaller ones
-    // are settled by their head's thread): group sizes, then groups of up to kMidGroup members inside a workgroup's
-    // LDS, the members of longer ones compacted and ordered by two radix sorts of (group, next key).
-    // SX_FLAG_SORT_MODE 1 (plain passes only): every group of more than kSmallGroup members takes the radix sorts.
-    const bool lds_tier = ctx->sort_mode != 1;
-    const bool trace_rounds = getenv("STRALG_AMD_TRACE_REFINE") != nullptr; // (diagnostic: members and time of every refinement round)
-    auto refine_larger_groups = [&](uint64_t skip) -> int {
-        const pkey_cfg kc_r = pkey_make(base, Cmax);
-        SX_TRY((device_scan<OpMax>(ctx, A, InActHead{head}, OutGroupIds{head, (uint64_t)A, agid, gsize}, nullptr,
-                                   SX_KC_DOUBLING, (uint64_t)A * 9)));
-        if (lds_tier) {
-            ctx->stats.refine_tiers |= 1u;
-            sx_launch(ctx, SX_KC_DOUBLING, (uint64_t)A * 60, refine_mid_groups_kernel, dim3(sx_div_up(A, kRmSpan)),
-                      dim3(kRmThreads), ti.T, ti.n, (const uint32_t *)ap, (const uint32_t *)apos, (const uint32_t *)agid,
-                      (const uint32_t *)gsize, (uint64_t)A, skip, kc_r, vs, ap_new, head_new,
-                      embed ? seedw : nullptr, full_wcfg);
-        }
-        SX_TRY((device_compact(ctx, A, InLargeGroup{agid, gsize, (uint32_t)(lds_tier ? kMidGroup : kSmallGroup)},
-                               OutLargeMember{ti.T, ap, agid, ti.n, skip, kc_r, sub_t, sub_gid, key_keep, rk_a, ord_a}, d_scalar,
-                               SX_KC_DOUBLING, (uint64_t)A * 12)));
-        uint32_t A3 = 0;
-        SX_TRY(sx_readback(ctx, d_scalar, 1, &A3));
-        if (A3 == 0) return 0;
-        ctx->stats.refine_tiers |= 2u;
-        uint32_t *sub_num = gsize; // (the sizes are not needed any more)
-        SX_TRY((device_scan<OpAdd>(ctx, A3, InSubHead{sub_t, sub_gid}, OutGroupNumber{sub_num}, d_scalar + 3, SX_KC_DOUBLING,
-                                   (uint64_t)A3 * 12)));
-        // (the groups' numbers are sort digits: how many there are is bounded by their least length -- no read-back of the count,
-        //  20 us of idle device a round; the bound is a bit too wide at most, and digits are taken eight bits at a time)
-        const uint32_t least = (uint32_t)(lds_tier ? kMidGroup : kSmallGroup) + 1u;
-        const uint32_t n_long_max = A3 / least > 1u ? A3 / least : 1u;
-        const uint32_t gbits = n_long_max > 1 ? (uint32_t)sx_bitlen(n_long_max - 1) : 1u;
-        if (trace_rounds) {
-            uint32_t n_long = 0;
-            SX_TRY(sx_readback(ctx, d_scalar + 3, 1, &n_long));
-            fprintf(stderr, "stralg_amd refine:   %u members of %u groups too long for the LDS tier\n", A3, n_long);
-        }
-        // order by (group, next key), LSD: stable sort by next key, then stable sort by group
-        int f = 0;
-        SX_TRY(sx_sort_pairs(ctx, rk_a, ord_a, rk_b, ord_b, A3, 0, kbits_r, &f));
-        uint32_t *ord1 = f ? ord_b : ord_a, *ord1_other = f ? ord_a : ord_b;
-        uint64_t *k1 = f ? rk_a : rk_b, *k1_other = f ? rk_b : rk_a; // k1: free to overwrite
-        sx_launch(ctx, SX_KC_DOUBLING, (uint64_t)A3 * 16, gid_keys_kernel, dim3(sx_div_up(A3, kBlock)), block,
-                  (const uint32_t *)ord1, (const uint32_t *)sub_num, (uint64_t)A3, k1);
-        SX_TRY(sx_sort_pairs(ctx, k1, ord1, k1_other, ord1_other, A3, 0, (int)gbits, &f));
-        const uint32_t *order = f ? ord1_other : ord1;
-        sx_launch(ctx, SX_KC_DOUBLING, (uint64_t)A3 * 44, refine_write_kernel, dim3(sx_div_up(A3, kBlock)), block, order,
-                  (const uint32_t *)sub_t, (const uint32_t *)ap, (const uint32_t *)apos, (const uint32_t *)sub_num,
-                  (const uint64_t *)key_keep, (uint64_t)A3, vs, ap_new, head_new, embed ? seedw : nullptr, ti.T, full_wcfg);
-        return 0;
-    };
-    const bool trace = trace_rounds;
-    for (int round = 1; A > 0; ++round) {
-        const auto trace_t0 = std::chrono::steady_clock::now();
-        const uint32_t trace_A = A;
-        struct trace_end {
-            bool on; int round; uint32_t a0; const uint32_t &a1; std::chrono::steady_clock::time_point t0;
-            ~trace_end() { if (on) fprintf(stderr, "stralg_amd refine: round %d  %u -> %u tied members  %.3f ms\n", round, a0, a1,
-                                           std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count()); }
-        } trace_guard{trace, round, trace_A, A, trace_t0};
-        // Few survivors are repeats proper: they get more rounds (each costs little) and, from the third round on,
-        // small groups are finished by comparing the suffixes themselves.  Many survivors after four rounds, or any
-        // after 32: repetitive text, general path.
-        const bool few = (uint64_t)A * 16 <= m;
-        if (round > (few ? 32 : 4)) return 0;
-        ctx->stats.doubling_rounds++;
-        const uint64_t skip = (uint64_t)C + (uint64_t)Cmax * (round - 1);
-        uint32_t counters[2] = {0, 0};
-        SX_CHECK(hipMemsetAsync(d_scalar + 1, 0, 2 * sizeof(uint32_t), ctx->stream));
-        if (few && round >= 3) {
-            SX_CHECK(hipMemcpyAsync(ap_new, ap, (size_t)A * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
-            SX_CHECK(hipMemcpyAsync(head_new, head, (size_t)A, hipMemcpyDeviceToDevice, ctx->stream));
-            sx_launch(ctx, SX_KC_DOUBLING, (uint64_t)A * 60, refine_by_comparison_kernel, dim3(sx_div_up(A, kBlock)), block, ti.T,
-                      ti.n, (const uint32_t *)ap, (const uint32_t *)apos, (const uint8_t *)head, (uint64_t)A, skip, vs, ap_new, head_new,
-                      embed ? seedw : nullptr, full_wcfg, d_scalar + 1);
-            SX_TRY(sx_readback(ctx, d_scalar + 1, 2, counters));
-            if (counters[1]) return 0; // a repeat beyond the comparison cap: general path
-            SX_TRY(keep_tied());
-            if (A == 0) break;
-            SX_TRY(refine_larger_groups(skip)); // what is left sits in groups of more than eight: every member is rewritten
-            SX_TRY(keep_tied());
-            continue;
-        }
-        // groups of up to eight members: settled by their head's thread
-#ifndef SX_RS_WAVES
-#define SX_RS_WAVES 1
-#endif
-        if (SX_RS_WAVES && ctx->sort_mode != 1)
-            sx_launch(ctx, SX_KC_DOUBLING, (uint64_t)A * 60, refine_small_groups_wave_kernel,
-                      dim3(sx_div_up(sx_div_up(A, kRsStride), kWavesPerBlock)), block, ti.T, ti.n, (const uint32_t *)ap,
-                      (const uint32_t *)apos, (const uint8_t *)head, (uint64_t)A, skip, pkey_make(base, Cmax), vs, ap_new, head_new,
-                      embed ? seedw : nullptr, full_wcfg, d_scalar + 1);
-        else
-        sx_launch(ctx, SX_KC_DOUBLING, (uint64_t)A * 60, refine_small_groups_kernel, dim3(sx_div_up(A, kBlock)), block, ti.T,
-                  ti.n, (const uint32_t *)ap, (const uint32_t *)apos, (const uint8_t *)head, (uint64_t)A, skip,
-                  pkey_make(base, Cmax), vs, ap_new, head_new, embed ? seedw : nullptr, full_wcfg, d_scalar + 1);
-        SX_TRY(sx_readback(ctx, d_scalar + 1, 1, counters));
-        if (counters[0]) SX_TRY(refine_larger_groups(skip)); // larger groups exist: they are refined in LDS or by sorting
-        SX_TRY(keep_tied());
-    }
-    *out = vs;
-    *seed_windows = embed ? seedw : nullptr;
-    *resolved = 1;
+    SX_TRY(refine_ties(s, p, resolved));
+    if (!*resolved) return 0;
+    *out = s.vs;
+    *seed_windows = s.windows(p);
     return 0;
 }

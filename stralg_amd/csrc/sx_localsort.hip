@@ -999,7 +999,7 @@ int sx_local_sort(sx_ctx *ctx, const uint64_t *kin, const uint32_t *vin, uint64_
                   uint8_t *stage_head, uint32_t *apos, uint32_t *ap, uint8_t *ahead, uint32_t cap,
                   uint32_t *d_total_and_fail /* [0] <- tied members, [1] <- bit 0: a sub-bucket did not fit, bit 1: stable passes were used,
                                                 [2] <- long sub-buckets listed */,
-                  uint32_t longest_expected, uint32_t *long_list, uint32_t long_cap, uint32_t res[3], bool crowded_expected)
+                  uint32_t longest_expected, uint32_t *long_list, uint32_t long_cap, uint32_t res[3])
 {
     // The span: a workgroup's costs that do not depend on its pairs (zeroing and scanning 8192 counters, the barriers) are
     // spread over more pairs the longer it is (1 GiB of DNA, dense keys: span 5120 2.79 ms, 5632 2.60, 5888 2.52), but a
@@ -1016,12 +1016,10 @@ int sx_local_sort(sx_ctx *ctx, const uint64_t *kin, const uint32_t *vin, uint64_
     uint32_t res_local[3];
     if (!res) res = res_local;
     SX_CHECK(hipMemsetAsync(d_total_and_fail + 1, 0, 2 * sizeof(uint32_t), ctx->stream));
-#ifndef SX_LS2_SKEWED
-#define SX_LS2_SKEWED 1 // texts with skewed symbol counts (repeat families crowd bins): 1 the lean kernel too, 0 the other one at once
-#endif
+    // Texts with skewed symbol counts (repeat families crowd bins) take the lean kernel too:
     // (1 GiB of uniform DNA 1.75 - 1.8 ms against the other kernel's 2.59; the genome-like 1 GiB text, whose repeat family crowds a bin
     //  in 42 % of the workgroups: 3.07 against 4.1 -- the lean kernel 2.2, the 2 % of the workgroups it leaves 0.2, the tied lists)
-    if (ctx->local_sort_lean_off || (crowded_expected && !SX_LS2_SKEWED)) { // SX_FLAG_LOCAL_SORT_LEAN_OFF (tests, A/B): rounds 3 and 4's kernel for every workgroup
+    if (ctx->local_sort_lean_off) { // SX_FLAG_LOCAL_SORT_LEAN_OFF (tests, A/B): rounds 3 and 4's kernel for every workgroup
         SX_CHECK(hipMemsetAsync(tile_start, 0xFF, (size_t)tiles * sizeof(uint32_t), ctx->stream));
         sx_launch(ctx, SX_KC_LOCAL_SORT, m * (12 + 4 + (seedw ? 4 : 0)), local_sort_redo_kernel, dim3(tiles), dim3(kLsThreads), kin, vin, m, L,
                   (uint32_t)kbits, vout, seedw, tile_start, tile_cnt, stage, stage_head, d_total_and_fail + 1, span, long_list,
