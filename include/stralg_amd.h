@@ -252,6 +252,26 @@ int sx_bwt_approx_search_dev(sx_ctx *ctx, const uint32_t *d_c_table, const uint3
 int sx_bwt_approx_search(sx_ctx *ctx, const uint32_t *c_table, const uint32_t *o_table, const uint32_t *ro_table,
                          uint64_t N, uint32_t sigma, const uint8_t *patterns, const uint32_t *offsets, uint32_t count,
                          int max_edits, uint64_t *hit_offsets, sx_approx_hit **hits_out, uint64_t *total_hits_out);
+/* Best stratum: sx_bwt_approx_search_dev by iterative deepening.  d_stratum[q] (count bytes) <-
+ * e*(q), the smallest d in 0 .. max_edits at which pattern q has a hit, or 0xFF where it has none; the hits of pattern q
+ * are exactly, and in the order of, those of sx_bwt_approx_search_dev at max_edits = d_stratum[q] (query = q), so every
+ * one of them uses exactly e*(q) edits.  Arguments, limits, the count-only form (d_hits == NULL) and the order of the
+ * output are those of sx_bwt_approx_search_dev; on SX_E_CAPACITY the offsets, the strata and the total are written all
+ * the same; max_edits < 0: no hits, every stratum 0xFF.  The same from run to run. */
+int sx_bwt_best_search_dev(sx_ctx *ctx, const uint32_t *d_c_table, const uint32_t *d_o_table, const uint32_t *d_ro_table,
+                           uint64_t N, uint32_t sigma, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count,
+                           int max_edits, uint8_t *d_stratum, uint64_t *d_hit_offsets, sx_approx_hit *d_hits,
+                           uint64_t hit_capacity, uint64_t *total_hits_out);
+/* The patterns q with d_keep[q] != 0 (count bytes), in order and flat: kept pattern j has its bytes at
+ * d_bytes_out[d_off_out[j] .. d_off_out[j+1]) with d_off_out[0] = 0, and d_ids_out[j] is its number in the input.
+ * d_off (count + 1 entries) need not start at 0; d_bytes is readable up to d_off[count].  d_bytes_out holds
+ * d_off[count] - d_off[0] + 16 bytes and is 16-byte aligned: the 16 bytes behind the kept ones are zeros.  d_off_out
+ * has count + 1, d_ids_out count entries.  *count_out, *bytes_out <- the kept patterns and their bytes.  Offsets that
+ * do not ascend give wrong bytes or SX_E_ARG, never an access outside the arrays.  No atomics: the same bytes from run
+ * to run. */
+int sx_patterns_select_dev(sx_ctx *ctx, const uint8_t *d_bytes, const uint32_t *d_off, uint32_t count, const uint8_t *d_keep,
+                           uint8_t *d_bytes_out, uint32_t *d_off_out, uint32_t *d_ids_out, uint32_t *count_out,
+                           uint64_t *bytes_out);
 
 /* ---- streaming download (serialisation without a host copy of the tables) ---- */
 /* sink(user, section, data, bytes): consecutive chunks of one section after the other; data is only valid
@@ -356,8 +376,15 @@ int sx_map_reads_stream(sx_ctx *ctx, const sx_map_record *records, uint32_t n_re
  * are in forward orientation, as SAM prescribes for a reverse-strand hit -- the reference mapper's stdout on the FASTQ file
  * "read0, rc(read0), read1, rc(read1), ..." with the second field of the odd entries' lines rewritten.  The limit becomes
  * 2 x reads x records < 2^32; the reads take twice the device memory.  flags == 0: sx_map_reads_stream, byte for byte and
- * launch for launch; unknown bits: SX_E_ARG. */
-enum { SX_MAP_BOTH_STRANDS = 1 };
+ * launch for launch; unknown bits: SX_E_ARG.
+ * Best stratum.  With SX_MAP_BEST_STRATUM and edits = k, e*(q) is the smallest d in 0 .. k for which
+ * the same call with edits = d and without this flag prints at least one line for read q, over all records (with
+ * SX_MAP_BOTH_STRANDS: over both strands of the read together); the text is, per read in file order, exactly the lines
+ * that call prints for q with edits = e*(q): the reference mapper's stdout for that read at -d e*(q).  A read without
+ * such a d prints nothing; k = 0 gives the text without the flag.  Every printed line uses exactly e*(q) edits.  The
+ * reads are searched at 0 edits, the rest at 1, ... (sx_bwt_best_search_dev over all records); batches hold whole
+ * reads (both strands of a read stay together).  Bits 2 and 4 stay unknown. */
+enum { SX_MAP_BOTH_STRANDS = 1, SX_MAP_BEST_STRATUM = 8 };
 int sx_map_reads_stream_ex(sx_ctx *ctx, const sx_map_record *records, uint32_t n_records, const uint8_t *fastq, size_t fastq_len,
                            int edits, uint32_t flags, sx_sink_fn sink, void *user);
 /* the limit of a mapping call on its reads and records: 0, or SX_E_ARG when reads x records (twice that with

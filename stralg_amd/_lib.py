@@ -44,6 +44,12 @@ SX_FLAG_SAM_BATCH_READS, SX_FLAG_SAM_WINDOW_BYTES = 18, 19
 SX_FLAG_LOCATE_CHUNK_ROWS = 20
 SX_FLAG_INDUCE_EARLY_S_OFF = 21
 SX_MAP_BOTH_STRANDS = 1
+SX_MAP_BEST_STRATUM = 8
+
+
+def map_flags(both_strands=False, best=False):
+    """the flags word of sx_map_reads_stream_ex / sx_index_map_reads_ex"""
+    return (SX_MAP_BOTH_STRANDS if both_strands else 0) | (SX_MAP_BEST_STRATUM if best else 0)
 
 
 class SamBatch(C.Structure):
@@ -170,6 +176,10 @@ def load(path=None):
         "sx_bwt_exact_search_dev": (C.c_int, [vp, u32p, u32p, C.c_uint64, C.c_uint32, u8p, u32p, C.c_uint32, u32p, u32p]),
         "sx_bwt_approx_search_dev": (C.c_int, [vp, u32p, u32p, u32p, C.c_uint64, C.c_uint32, u8p, u32p, C.c_uint32, C.c_int,
                                                u64p, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+        "sx_bwt_best_search_dev": (C.c_int, [vp, u32p, u32p, u32p, C.c_uint64, C.c_uint32, u8p, u32p, C.c_uint32, C.c_int, u8p,
+                                             u64p, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+        "sx_patterns_select_dev": (C.c_int, [vp, u8p, u32p, C.c_uint32, u8p, u8p, u32p, u32p, C.POINTER(C.c_uint32),
+                                             C.POINTER(C.c_uint64)]),
         "sx_bwt_approx_search": (C.c_int, [vp, u32p, u32p, u32p, C.c_uint64, C.c_uint32, u8p, u32p, C.c_uint32, C.c_int,
                                            u64p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
         "sx_build_tables_stream": (C.c_int, [vp, u8p, C.c_uint64, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]),
@@ -269,7 +279,7 @@ EXPORTS = ["sx_device_count", "sx_device_numa_node", "sx_ctx_create", "sx_ctx_de
            "sx_bwt_approx_search_packed_dev", "sx_index_is_packed",
            "sx_sa_sample_bytes", "sx_sa_sample_build_dev", "sx_sa_locate_rows_dev", "sx_index_record_samples", "sx_index_expand_sa",
            "sx_sam_layout_dev_ex", "sx_sam_emit_dev_ex", "sx_map_reads_stream_ex", "sx_map_reads_limit", "sx_fastq_strands_dev",
-           "sx_index_map_reads_ex",
+           "sx_index_map_reads_ex", "sx_bwt_best_search_dev", "sx_patterns_select_dev",
            "sx_synth_dev", "sx_membw_probe", "sx_prim_sort_pairs_dev", "sx_prim_exclusive_sum_dev", "sx_prim_classify_dev"]
 
 

@@ -150,6 +150,28 @@ class Context:
                                                       hit_capacity, C.byref(total)), "sx_bwt_approx_search_dev")
         return int(total.value)
 
+    def bwt_best_search_dev(self, d_c, d_o, d_ro, N, sigma, d_patterns, d_offsets, count, max_edits, d_stratum, d_hit_offsets,
+                            d_hits=None, hit_capacity=0):
+        """sx_bwt_best_search_dev: Context.bwt_approx_search_dev by iterative deepening.  d_stratum (count bytes) <- the
+        smallest edit count at which each pattern has a hit (0xFF: none within max_edits); a pattern's hits are those of
+        bwt_approx_search_dev at that edit count, in its order.  Returns the number of hits; on SX_E_CAPACITY (raised) the
+        offsets and strata are written all the same."""
+        total = C.c_uint64(0)
+        self._check(self.lib.sx_bwt_best_search_dev(self.h, _ptr(d_c), _ptr(d_o), _ptr(d_ro), N, sigma, _ptr(d_patterns),
+                                                    _ptr(d_offsets), count, max_edits, _ptr(d_stratum), _ptr(d_hit_offsets),
+                                                    _ptr(d_hits), hit_capacity, C.byref(total)), "sx_bwt_best_search_dev")
+        return int(total.value)
+
+    def patterns_select_dev(self, d_bytes, d_off, count, d_keep, d_bytes_out, d_off_out, d_ids_out):
+        """sx_patterns_select_dev: the patterns q with d_keep[q] != 0, in order and flat, into d_bytes_out (16-byte aligned,
+        the input's bytes + 16), d_off_out (count + 1, from 0) and d_ids_out (count: a kept pattern's number in the
+        input); returns (kept patterns, their bytes)"""
+        kept, nbytes = C.c_uint32(0), C.c_uint64(0)
+        self._check(self.lib.sx_patterns_select_dev(self.h, _ptr(d_bytes), _ptr(d_off), count, _ptr(d_keep), _ptr(d_bytes_out),
+                                                    _ptr(d_off_out), _ptr(d_ids_out), C.byref(kept), C.byref(nbytes)),
+                    "sx_patterns_select_dev")
+        return int(kept.value), int(nbytes.value)
+
     def bwt_approx_search(self, c, o, ro, sigma, patterns, offsets, max_edits):
         """sx_bwt_approx_search over host arrays (o, ro: (N+1, sigma); ro may be None): (hit offsets[count + 1], hits as a
         structured array of _lib.APPROX_HIT_DTYPE)."""
@@ -355,11 +377,12 @@ class Context:
         self._check(self.lib.sx_sa_locate_rows_dev(self.h, _ptr(d_c), _ptr(d_occ), N, sigma, _ptr(d_marks), _ptr(d_values),
                                                    int(sa_sample).bit_length() - 1, row_lo, row_hi, _ptr(d_out)), "sx_sa_locate_rows_dev")
 
-    def map_reads_stream(self, records, fastq, edits, sink, both_strands=False):
+    def map_reads_stream(self, records, fastq, edits, sink, both_strands=False, best=False):
         """sx_map_reads_stream: records = [(name bytes, BwtTable), ...] in the mapper's list order; sink(bytes) receives the
         SAM text window after window.  sink=None discards the text without touching it and returns [(time.perf_counter(),
         bytes)] per window (measurement).  both_strands (sx_map_reads_stream_ex, SX_MAP_BOTH_STRANDS): behind the lines of
-        every read come those of its reverse complement, with FLAG 16."""
+        every read come those of its reverse complement, with FLAG 16.  best (SX_MAP_BEST_STRATUM): per read only the
+        lines of the smallest edit count in 0 .. edits that has any (with both_strands: over both strands together)."""
         recs = (_lib.MapRecord * max(1, len(records)))()
         keep = []
         for r, (name, t) in enumerate(records):
@@ -381,14 +404,15 @@ class Context:
                 return 1
 
         cb = _lib.SINK_FN(_sink)
-        if both_strands:
+        flags = _lib.map_flags(both_strands, best)
+        if flags:
             rc = self.lib.sx_map_reads_stream_ex(self.h, recs, len(records), _ptr(buf) if buf.size else None, buf.size, edits,
-                                                 _lib.SX_MAP_BOTH_STRANDS, cb, None)
+                                                 flags, cb, None)
         else:
             rc = self.lib.sx_map_reads_stream(self.h, recs, len(records), _ptr(buf) if buf.size else None, buf.size, edits, cb, None)
         if failure:
             raise failure[0]
-        self._check(rc, "sx_map_reads_stream_ex" if both_strands else "sx_map_reads_stream")
+        self._check(rc, "sx_map_reads_stream_ex" if flags else "sx_map_reads_stream")
         return seen if sink is None else None
 
     # ---- FASTA ingest and remap ------------------------------
@@ -670,10 +694,10 @@ class Index:
             raise StralgAmdError("the index is closed")
         return self.h
 
-    def map_reads(self, fastq, edits, sink=None, ctx=None, both_strands=False):
+    def map_reads(self, fastq, edits, sink=None, ctx=None, both_strands=False, best=False):
         """sx_index_map_reads: the SAM text of every match of every read of a FASTQ image within `edits` edits, byte for
         byte stralg_amd.map_reads' (the reference mapper's stdout).  sink=None returns the text; sink(bytes) receives it
-        window after window and None is returned.  both_strands: as in stralg_amd.map_reads (sx_index_map_reads_ex)."""
+        window after window and None is returned.  both_strands, best: as in stralg_amd.map_reads (sx_index_map_reads_ex)."""
         ctx = ctx or self.ctx
         buf = np.frombuffer(bytes(fastq), dtype=np.uint8)
         chunks, failure = [], []
@@ -688,20 +712,21 @@ class Index:
                 return 1
 
         cb = _lib.SINK_FN(_sink)
-        rc = self._map(ctx, buf, edits, both_strands, cb)
+        flags = _lib.map_flags(both_strands, best)
+        rc = self._map(ctx, buf, edits, flags, cb)
         if failure:
             raise failure[0]
-        ctx._check(rc, "sx_index_map_reads_ex" if both_strands else "sx_index_map_reads")
+        ctx._check(rc, "sx_index_map_reads_ex" if flags else "sx_index_map_reads")
         return b"".join(chunks) if sink is None else None
 
-    def _map(self, ctx, buf, edits, both_strands, cb):
-        """the return code of sx_index_map_reads, or of sx_index_map_reads_ex with SX_MAP_BOTH_STRANDS"""
+    def _map(self, ctx, buf, edits, flags, cb):
+        """the return code of sx_index_map_reads, or of sx_index_map_reads_ex with a flags word that is not 0"""
         image = _ptr(buf) if buf.size else None
-        if both_strands:
-            return ctx.lib.sx_index_map_reads_ex(ctx.h, self._handle(), image, buf.size, edits, _lib.SX_MAP_BOTH_STRANDS, cb, None)
+        if flags:
+            return ctx.lib.sx_index_map_reads_ex(ctx.h, self._handle(), image, buf.size, edits, flags, cb, None)
         return ctx.lib.sx_index_map_reads(ctx.h, self._handle(), image, buf.size, edits, cb, None)
 
-    def map_reads_discard(self, fastq, edits, ctx=None, both_strands=False):
+    def map_reads_discard(self, fastq, edits, ctx=None, both_strands=False, best=False):
         """the same with a sink that does not touch the text: [(time.perf_counter(), bytes)] per window (measurement)"""
         ctx = ctx or self.ctx
         buf = np.frombuffer(bytes(fastq), dtype=np.uint8)
@@ -712,7 +737,8 @@ class Index:
             return 0
 
         cb = _lib.SINK_FN(_sink)
-        ctx._check(self._map(ctx, buf, edits, both_strands, cb), "sx_index_map_reads_ex" if both_strands else "sx_index_map_reads")
+        flags = _lib.map_flags(both_strands, best)
+        ctx._check(self._map(ctx, buf, edits, flags, cb), "sx_index_map_reads_ex" if flags else "sx_index_map_reads")
         return seen
 
     def write(self, sink, ctx=None):
@@ -1061,16 +1087,18 @@ def bwt_approx_search(bwt_table, patterns, edits, ctx=None):
     return approx_matches(hits, hit_off, [p.size for p in pats], bwt_table.sa.array)
 
 
-def map_reads(fasta, fastq, edits, ctx=None, both_strands=False):
+def map_reads(fasta, fastq, edits, ctx=None, both_strands=False, best=False):
     """The reference read mapper (tools/readmappers/bwt_readmapper: -p genome.fa, then -d edits genome.fa reads.fq) on the
     bytes of a FASTA and a FASTQ file: its stdout, the SAM lines of every match of every read in every record within
     `edits` edits, byte for byte.  Per read the records come in the mapper's list order, which is the FASTA file's order
     (the iterator yields the records last first, -p writes them so, and -d prepends each to its list).
     both_strands: behind the lines of every read come the lines of its reverse complement (the name, the sequence reversed
     and complemented, the quality string reversed) as the reference prints them for such a read, with FLAG 16 in place of 0;
-    the reference itself maps one strand only."""
+    the reference itself maps one strand only.
+    best: per read only the lines of its best stratum: those the mapper prints for it at -d e*, the smallest edit count in
+    0 .. edits at which it prints any for that read (with both_strands: over both strands of the read together)."""
     ctx = ctx or default_context()
     records = [(name, build_complete_table(seq, True, ctx)) for name, seq in ctx.fasta_records(fasta)]
     chunks = []
-    ctx.map_reads_stream(records, fastq, edits, chunks.append, both_strands=both_strands)
+    ctx.map_reads_stream(records, fastq, edits, chunks.append, both_strands=both_strands, best=best)
     return b"".join(chunks)

@@ -294,8 +294,8 @@ static uint32_t approx_lanes(uint32_t count)
     return want < SX_APPROX_LANES ? want : SX_APPROX_LANES;
 }
 
-// count pass + offsets; the workspace (stack, counts, counters) stays in the N slab for the emit pass
-template <class Occ> static int approx_count(sx_ctx *ctx, ApproxArgsT<Occ> &A, uint64_t *d_hit_off, uint64_t *total_out)
+// the workspace of a pass over A's patterns (stack, counts, counters: the BWT and N slabs)
+template <class Occ> static int approx_workspace(sx_ctx *ctx, ApproxArgsT<Occ> &A)
 {
     // the longest pattern (the stack's depth, the 2^15 limit)
     SX_TRY(sx_slab_ensure(ctx, SX_SLAB_BWT, 4096));
@@ -314,6 +314,14 @@ template <class Occ> static int approx_count(sx_ctx *ctx, ApproxArgsT<Occ> &A, u
     A.stack = (uint4 *)((char *)ctx->slab[SX_SLAB_N].p + cnt_b);
     A.total = (unsigned long long *)(scal + 2);
     A.next = scal + 4;
+    return 0;
+}
+
+// count pass + offsets; the workspace stays where it is for the emit pass
+template <class Occ> static int approx_count(sx_ctx *ctx, ApproxArgsT<Occ> &A, uint64_t *d_hit_off, uint64_t *total_out)
+{
+    SX_TRY(approx_workspace(ctx, A));
+    uint32_t *scal = (uint32_t *)ctx->slab[SX_SLAB_BWT].p;
     sx_launch(ctx, SX_KC_SEARCH, 0, bwt_approx_kernel<false, Occ>, dim3(A.lanes / kApproxBlock), dim3(kApproxBlock), A);
     SX_TRY((device_scan<OpAdd>(ctx, A.count, InU32{A.counts}, OutOffsets64{d_hit_off}, nullptr, SX_KC_SEARCH, (uint64_t)A.count * 12)));
     sx_launch(ctx, SX_KC_SEARCH, 0, approx_finish_offsets_kernel, dim3(1), dim3(64), (const unsigned long long *)A.total, d_hit_off, A.count);
@@ -402,6 +410,43 @@ int sx_approx_search_record(sx_ctx *ctx, const sx_index_rec &R, const uint8_t *d
                                                           d_hit_offsets, d_hits, hit_capacity, total_hits_out)
                        : sx_bwt_approx_search_dev(ctx, R.d_c, R.d_o, R.d_ro, R.N, R.sigma, d_patterns, d_offsets, count, max_edits, d_hit_offsets,
                                                   d_hits, hit_capacity, total_hits_out);
+}
+
+// f(o, ro): the accessors of a record's tables in whichever form they have
+template <class F> static int with_record_occ(const sx_index_rec &R, F f)
+{
+    if (R.compact() && (((uintptr_t)R.d_occ | (uintptr_t)R.d_rocc) & 15u)) return SX_E_ARG; // (the layout of sx_occ.hpp)
+    if (R.packed) return R.sigma > kOccPackedMaxSigma ? SX_E_ARG : f(OccPacked{R.d_occ}, OccPacked{R.d_rocc});
+    if (R.compact()) {
+        if (R.sigma > 128) return SX_E_ARG;
+        const uint32_t stride = occ_stride(R.sigma);
+        return f(OccCompact{R.d_occ, stride}, OccCompact{R.d_rocc, stride});
+    }
+    return f(OccFull{R.d_o}, OccFull{R.d_ro});
+}
+
+// the two passes on their own, for the rounds of sx_best.hip: they launch what the passes of approx_search_dev launch
+int sx_approx_count_record(sx_ctx *ctx, const sx_index_rec &R, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, int max_edits,
+                           uint64_t *d_hit_offsets, uint64_t *total_hits_out)
+{
+    if (!ctx || !d_hit_offsets || !total_hits_out || count == 0 || max_edits < 0) return SX_E_ARG;
+    return with_record_occ(R, [&](auto o, auto ro) -> int {
+        ApproxArgsT<decltype(o)> A;
+        SX_TRY(approx_args(ctx, A, R.d_c, o, ro, R.N, R.sigma, d_patterns, d_offsets, count, max_edits));
+        return approx_count(ctx, A, d_hit_offsets, total_hits_out);
+    });
+}
+
+int sx_approx_emit_record(sx_ctx *ctx, const sx_index_rec &R, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, int max_edits,
+                          const uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t total_hits)
+{
+    if (!ctx || !d_hit_offsets || !d_hits || ((uintptr_t)d_hits & 15) || count == 0 || max_edits < 0 || total_hits == 0) return SX_E_ARG;
+    return with_record_occ(R, [&](auto o, auto ro) -> int {
+        ApproxArgsT<decltype(o)> A;
+        SX_TRY(approx_args(ctx, A, R.d_c, o, ro, R.N, R.sigma, d_patterns, d_offsets, count, max_edits));
+        SX_TRY(approx_workspace(ctx, A));
+        return approx_emit(ctx, A, d_hit_offsets, d_hits, total_hits);
+    });
 }
 
 extern "C" {

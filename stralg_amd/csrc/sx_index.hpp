@@ -1,6 +1,7 @@
 // sx_index.hpp -- the device-resident index (sx_index.hip) and what the mapper's loop (sx_sam.hip) reads of it.
 #pragma once
 #include "sx_common.hpp"
+#include "sx_hostio.hpp"
 #include "sx_locate.hpp"
 
 #include <string>
@@ -68,9 +69,65 @@ static inline bool sx_map_record_check(const sx_map_record &R, uint32_t min_sigm
     return R.name && R.sa && R.c_table && R.o_table && R.remap && sx_map_dims_ok(R.N, R.sigma, min_sigma);
 }
 
+// the bits of a mapping call's flags word that mean something (sx_map_reads_stream_ex, sx_index_map_reads_ex, sx_map_reads_limit)
+constexpr uint32_t sx_map_known_flags = SX_MAP_BOTH_STRANDS | SX_MAP_BEST_STRATUM;
+
 // sx_sam.hip: the mapper's loop over reads and an index that both lie on ctx's device
 // (flags: those of sx_map_reads_stream_ex)
 int sx_map_reads_core(sx_ctx *ctx, const sx_index *idx, const sx_reads_dev &reads, int edits, uint32_t flags, sx_sink_fn sink, void *user);
 // sx_approx.hip: sx_bwt_approx_search_dev over the tables of a record, full, compact or packed
 int sx_approx_search_record(sx_ctx *ctx, const sx_index_rec &R, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, int max_edits,
                             uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t hit_capacity, uint64_t *total_hits_out);
+// the two passes of that search on their own (sx_best.hip runs them over different pattern sets).  Count: the hit offsets
+// (count + 1 entries) and the total of `count` >= 1 patterns.  Emit: the hits of patterns whose offsets are known (total of
+// them, total >= 1) to d_hits; hit.query is the pattern's number in this set
+int sx_approx_count_record(sx_ctx *ctx, const sx_index_rec &R, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, int max_edits,
+                           uint64_t *d_hit_offsets, uint64_t *total_hits_out);
+int sx_approx_emit_record(sx_ctx *ctx, const sx_index_rec &R, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, int max_edits,
+                          const uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t total_hits);
+// sx_sam.hip: out[i] = table[seqs[i]] for i in [lo, hi) (a record's 256-byte symbol table; sam_remap_kernel)
+void sx_sam_remap(sx_ctx *ctx, const uint8_t *d_seqs, const uint8_t *d_table, uint8_t *d_out, uint64_t lo, uint64_t hi);
+
+// ---- sx_best.hip: best-stratum search -----------------------------------------------------------
+// What a batch of the round loop holds on the device; sized once (init) for the largest batch, nothing is allocated in a round
+struct sx_best_state {
+    sx_dev_scope own;
+    uint32_t cap_count = 0, n_rec = 0, rounds = 0; // patterns a batch may have, records, rounds (max_edits + 1)
+    uint64_t cap_bytes = 0, fstride = 0;           // bytes a batch may have; entries of a record's found-set hit offsets
+    uint8_t *d_stratum = nullptr;                  // (unless the caller brings its own) a byte a group
+    uint8_t *d_keep_found = nullptr, *d_keep_open = nullptr;
+    uint8_t *d_open[2] = {nullptr, nullptr}, *d_found = nullptr; // compacted pattern sets: the open one of the next round, the found ones
+    uint32_t *d_open_off[2] = {nullptr, nullptr}, *d_open_ids[2] = {nullptr, nullptr}, *d_found_off = nullptr, *d_found_ids = nullptr;
+    uint32_t *d_rel_found = nullptr, *d_rel_open = nullptr; // a select's ids inside its input set
+    uint64_t *d_fho = nullptr, *d_seg = nullptr;   // hit offsets of the found sets (round, record); the segments' starts
+    uint32_t *d_err = nullptr;
+    // the batch in flight (host): round d's found set is entries [fbase[d], fbase[d + 1]) of d_found_ids
+    uint32_t fbase[SX_APPROX_MAX_EDITS + 2] = {0};
+    std::vector<uint64_t> seg; // rounds x records + 1: where (round, record)'s hits start in the room
+    int init(sx_ctx *ctx, uint32_t count_max, uint64_t bytes_max, uint32_t n_records, int max_edits, bool own_stratum);
+};
+// one batch of patterns against the records
+struct sx_best_batch {
+    const sx_index_rec *recs;
+    uint32_t n_rec;
+    const uint8_t *d_tabs; // a 256-byte symbol table a record, or null: the patterns hold symbols already
+    uint8_t *d_pat;        // (with d_tabs) room for the remapped bytes of any set of the batch, indexed like d_bytes
+    const uint8_t *d_bytes;
+    uint64_t bytes_total;  // d_bytes is readable in [0, bytes_total)
+    const uint32_t *d_off; // count + 1 offsets into d_bytes; [p_lo, p_hi): the batch's bytes
+    uint64_t p_lo, p_hi;
+    uint32_t count, gsize; // patterns; patterns a group (1, or 2: both strands of a read)
+    int k;
+    uint64_t *d_ho;        // n_rec x ho_stride entries of scratch (the count passes' hit offsets), ho_stride >= count + 1
+    uint64_t ho_stride;
+    uint8_t *d_stratum;    // a byte a group
+    sx_approx_hit *d_raw;  // the room: hits as segments (round, record); null: nothing is emitted
+    uint64_t raw_cap;
+    bool go_on_counting;   // more hits than raw_cap: the rounds go on without emitting (else they end there)
+};
+// The rounds d = 0 .. k.  *total_out <- the hits (with SX_E_CAPACITY and !go_on_counting: those known of so far).
+// SX_E_CAPACITY: the room is too small; the strata and (go_on_counting) the found sets' offsets are complete all the same
+int sx_best_rounds(sx_ctx *ctx, sx_best_state &S, const sx_best_batch &B, uint64_t *total_out);
+// d_vbase (count x n_rec + 1 entries) <- where the hits of (pattern, record) start in (pattern, record, hit) order and,
+// last, the total; with d_placed the room's hits go there in that order, query <- pattern x n_rec + record
+int sx_best_place(sx_ctx *ctx, sx_best_state &S, const sx_best_batch &B, uint64_t total, uint64_t *d_vbase, sx_approx_hit *d_placed);

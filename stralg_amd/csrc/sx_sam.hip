@@ -492,7 +492,7 @@ template <class T, class H> static int upload(sx_ctx *ctx, sx_dev_scope &B, cons
 // what a mapping call asks of its reads and records; records_ok: sx_map_dims_ok / sx_map_record_check with sigma >= 2
 static int map_check(sx_ctx *ctx, uint64_t n_reads, uint64_t n_records, uint32_t flags, bool records_ok)
 {
-    if (flags & ~(uint32_t)SX_MAP_BOTH_STRANDS) return sx_fail_msg(ctx, SX_E_ARG, "read mapping: unknown flags");
+    if (flags & ~sx_map_known_flags) return sx_fail_msg(ctx, SX_E_ARG, "read mapping: unknown flags");
     if (sx_map_reads_limit(n_reads, n_records, flags) != 0)
         return sx_fail_msg(ctx, SX_E_ARG, "read mapping: reads x records (twice that for both strands) must stay below 2^32");
     if (!records_ok) return sx_fail_msg(ctx, SX_E_ARG, "read mapping: a record lacks its name, suffix array, tables or remap table");
@@ -544,19 +544,26 @@ struct MapBufs { // what a mapping call holds on the device beside the hits' roo
 
 // The searches of reads q0 .. q0 + batch, record after record, into the room: seg[r] <- where record r's hits start,
 // seg[records] <- how many there are.  SX_E_CAPACITY: the room is too small for the *need_out hits known of so far.
-static int search_batch(sx_ctx *ctx, const sx_index *idx, const sx_reads_dev &reads, const MapBufs &M, const HitRoom &room, uint32_t q0,
-                        uint32_t batch, int edits, std::vector<uint64_t> &seg, uint64_t *need_out)
+// [*p_lo, *p_hi): the sequence bytes of reads q0 .. q0 + batch
+static int batch_bytes(sx_ctx *ctx, const sx_reads_dev &reads, uint32_t q0, uint32_t batch, uint64_t *p_lo, uint64_t *p_hi)
 {
-    uint64_t p_lo, p_hi;
     if (reads.h_seq_off) {
-        p_lo = reads.h_seq_off[q0], p_hi = reads.h_seq_off[q0 + batch];
+        *p_lo = reads.h_seq_off[q0], *p_hi = reads.h_seq_off[q0 + batch];
     } else { // (the offsets were made on the device: the two this batch needs come back)
         const uint32_t *src[2] = {reads.d_seq_off + q0, reads.d_seq_off + q0 + batch};
         const uint32_t one[2] = {1, 1};
         uint32_t got[2];
         SX_TRY(sx_readback_ranges(ctx, src, one, 2, got));
-        p_lo = got[0], p_hi = got[1];
+        *p_lo = got[0], *p_hi = got[1];
     }
+    return 0;
+}
+
+static int search_batch(sx_ctx *ctx, const sx_index *idx, const sx_reads_dev &reads, const MapBufs &M, const HitRoom &room, uint32_t q0,
+                        uint32_t batch, int edits, std::vector<uint64_t> &seg, uint64_t *need_out)
+{
+    uint64_t p_lo, p_hi;
+    SX_TRY(batch_bytes(ctx, reads, q0, batch, &p_lo, &p_hi));
     const uint32_t n_records = (uint32_t)idx->recs.size();
     uint64_t used = 0;
     for (uint32_t r = 0; r < n_records; ++r) {
@@ -578,10 +585,9 @@ static int search_batch(sx_ctx *ctx, const sx_index *idx, const sx_reads_dev &re
 }
 
 // The hits of the batch's searches in (read, record rank, hit) order: M.d_merged, query <- read x records + rank
-static int merge_batch(sx_ctx *ctx, MapBufs &M, const HitRoom &room, const std::vector<uint64_t> &seg, uint32_t batch)
+// room for `used` hits in (read, record, hit) order and for their byte offsets
+static int merged_room(sx_ctx *ctx, MapBufs &M, const HitRoom &room, uint64_t used)
 {
-    const uint32_t n_records = (uint32_t)seg.size() - 1;
-    const uint64_t used = seg[n_records];
     if (used > M.merged_cap) {
         if (M.d_merged) M.own.drop(M.d_merged), M.own.drop(M.d_byte_off), M.own.drop(M.d_pos_off);
         M.d_pos_off = nullptr;
@@ -589,6 +595,14 @@ static int merge_batch(sx_ctx *ctx, MapBufs &M, const HitRoom &room, const std::
         SX_TRY(M.own.take(ctx, &M.d_merged, (size_t)M.merged_cap));
         SX_TRY(M.own.take(ctx, &M.d_byte_off, (size_t)M.merged_cap + 1));
     }
+    return 0;
+}
+
+static int merge_batch(sx_ctx *ctx, MapBufs &M, const HitRoom &room, const std::vector<uint64_t> &seg, uint32_t batch)
+{
+    const uint32_t n_records = (uint32_t)seg.size() - 1;
+    const uint64_t used = seg[n_records];
+    SX_TRY(merged_room(ctx, M, room, used));
     SX_CHECK(hipMemcpyAsync(M.d_seg, seg.data(), seg.size() * 8, hipMemcpyHostToDevice, ctx->stream));
     SX_CHECK(hipStreamSynchronize(ctx->stream)); // (seg is reused by the next batch)
     const uint64_t nvq = (uint64_t)batch * n_records;
@@ -713,7 +727,7 @@ int sx_sam_emit_dev(sx_ctx *ctx, const sx_sam_batch *batch, const uint64_t *d_by
 
 int sx_map_reads_limit(uint64_t n_reads, uint64_t n_records, uint32_t flags)
 {
-    if (flags & ~(uint32_t)SX_MAP_BOTH_STRANDS) return SX_E_ARG;
+    if (flags & ~sx_map_known_flags) return SX_E_ARG;
     const uint64_t strands = (flags & SX_MAP_BOTH_STRANDS) ? 2 : 1;
     // (no product is formed before it is known to fit)
     if (n_reads > 0xFFFFFFFFull / strands) return SX_E_ARG;
@@ -733,7 +747,7 @@ int sx_map_reads_stream_ex(sx_ctx *ctx, const sx_map_record *records, uint32_t n
     if (!ctx || !sink || (n_records && !records) || (fastq_len && !fastq)) return SX_E_ARG;
     if (edits < 0 || edits > SX_APPROX_MAX_EDITS)
         return sx_fail_msg(ctx, SX_E_ARG, "read mapping: edits must be in [0, 8]");
-    if (flags & ~(uint32_t)SX_MAP_BOTH_STRANDS) return sx_fail_msg(ctx, SX_E_ARG, "read mapping: unknown flags");
+    if (flags & ~sx_map_known_flags) return sx_fail_msg(ctx, SX_E_ARG, "read mapping: unknown flags");
     sx_fastq fq;
     const int frc = sx_fastq_index(fastq, fastq_len, &fq);
     if (frc != 0) return sx_fail_msg(ctx, frc, "read mapping: malformed FASTQ image (see sx_fastq_index)");
@@ -772,8 +786,10 @@ int sx_map_reads_stream_ex(sx_ctx *ctx, const sx_map_record *records, uint32_t n
 // The mapper's loop (bwt_readmapper.c:130-160, 257-266) over reads and tables that lie on the device: what
 // sx_map_reads_stream and sx_index_map_reads share.  A batch: search (on capacity: grow_or_halve, again), merge, emit.
 // d_read_flags: a FLAG per read, or null.
-static int map_reads_loop(sx_ctx *ctx, const sx_index *idx, const sx_reads_dev &reads, const uint16_t *d_read_flags, int edits, sx_sink_fn sink,
-                          void *user);
+// group: 0, or (SX_MAP_BEST_STRATUM) the reads that share a stratum: 1, or 2 for the strands of a read;
+// the searches of a batch are then the rounds of sx_best.hip and its hits are put in order by their place step.
+static int map_reads_loop(sx_ctx *ctx, const sx_index *idx, const sx_reads_dev &reads, const uint16_t *d_read_flags, int edits, uint32_t group,
+                          sx_sink_fn sink, void *user);
 
 // Both strands: the read set of 2 x count reads, read 2q + strand, is made once and searched like any
 // read set, so its hits come in (read, strand, record, hit) order, which is the text's; the FLAGs go with the batches.
@@ -784,7 +800,8 @@ int sx_map_reads_core(sx_ctx *ctx, const sx_index *idx, const sx_reads_dev &read
     bool records_ok = true;
     for (const sx_index_rec &R : idx->recs) records_ok = records_ok && sx_map_dims_ok(R.N, R.sigma, 2);
     SX_TRY(map_check(ctx, reads.count, n_records, flags, records_ok));
-    if (!(flags & SX_MAP_BOTH_STRANDS)) return map_reads_loop(ctx, idx, reads, nullptr, edits, sink, user);
+    const bool best = (flags & SX_MAP_BEST_STRATUM) != 0;
+    if (!(flags & SX_MAP_BOTH_STRANDS)) return map_reads_loop(ctx, idx, reads, nullptr, edits, best ? 1u : 0u, sink, user);
     SX_CHECK(hipSetDevice(ctx->device));
     sx_fastq_dev in = {}, both = {};
     in.count = reads.count;
@@ -800,13 +817,36 @@ int sx_map_reads_core(sx_ctx *ctx, const sx_index *idx, const sx_reads_dev &read
     stranded.d_names = both.d_names, stranded.d_seqs = both.d_seqs, stranded.d_quals = both.d_quals;
     stranded.d_name_off = both.d_name_off, stranded.d_seq_off = both.d_seq_off, stranded.d_qual_off = both.d_qual_off;
     stranded.name_bytes = both.name_bytes, stranded.seq_bytes = both.seq_bytes, stranded.qual_bytes = both.qual_bytes;
-    const int rc = map_reads_loop(ctx, idx, stranded, d_flags, edits, sink, user);
+    const int rc = map_reads_loop(ctx, idx, stranded, d_flags, edits, best ? 2u : 0u, sink, user);
     sx_fastq_dev_free(&both);
     return rc;
 }
 
-static int map_reads_loop(sx_ctx *ctx, const sx_index *idx, const sx_reads_dev &reads, const uint16_t *d_read_flags, int edits, sx_sink_fn sink,
-                          void *user)
+void sx_sam_remap(sx_ctx *ctx, const uint8_t *d_seqs, const uint8_t *d_table, uint8_t *d_out, uint64_t lo, uint64_t hi)
+{
+    if (hi > lo) sx_launch(ctx, SX_KC_REMAP, 2 * (hi - lo), sam_remap_kernel, dim3(sx_div_up(hi - lo, kBlock)), dim3(kBlock), d_seqs, d_table, d_out, lo, hi);
+}
+
+// The best-stratum searches of reads q0 .. q0 + batch (whole groups): the rounds into the room, then the hits in (read, record,
+// hit) order in M.d_merged.  SX_E_CAPACITY: as search_batch
+static int best_batch(sx_ctx *ctx, const sx_index *idx, const sx_reads_dev &reads, MapBufs &M, const HitRoom &room, sx_best_state &S, uint32_t q0,
+                      uint32_t batch, int edits, uint32_t group, uint64_t *used_out)
+{
+    sx_best_batch B = {};
+    B.recs = idx->recs.data(), B.n_rec = (uint32_t)idx->recs.size(), B.d_tabs = idx->d_tabs, B.d_pat = M.d_pat;
+    B.d_bytes = reads.d_seqs, B.bytes_total = reads.seq_bytes, B.d_off = reads.d_seq_off + q0;
+    SX_TRY(batch_bytes(ctx, reads, q0, batch, &B.p_lo, &B.p_hi));
+    B.count = batch, B.gsize = group, B.k = edits;
+    B.d_ho = M.d_ho, B.ho_stride = M.stride, B.d_stratum = S.d_stratum;
+    B.d_raw = room.d_raw, B.raw_cap = room.cap, B.go_on_counting = false;
+    SX_TRY(sx_best_rounds(ctx, S, B, used_out));
+    if (*used_out == 0) return 0;
+    SX_TRY(merged_room(ctx, M, room, *used_out));
+    return sx_best_place(ctx, S, B, *used_out, M.d_vbase, M.d_merged);
+}
+
+static int map_reads_loop(sx_ctx *ctx, const sx_index *idx, const sx_reads_dev &reads, const uint16_t *d_read_flags, int edits, uint32_t group,
+                          sx_sink_fn sink, void *user)
 {
     const uint32_t n_reads = reads.count, n_records = (uint32_t)idx->recs.size();
     SX_CHECK(hipSetDevice(ctx->device));
@@ -815,6 +855,7 @@ static int map_reads_loop(sx_ctx *ctx, const sx_index *idx, const sx_reads_dev &
     SX_TRY(sx_sync(ctx)); // (the callers' uploads from pageable memory are done)
 
     uint32_t batch_max = ctx->sam_batch_reads > 0 ? (uint32_t)ctx->sam_batch_reads : (1u << 20);
+    if (group == 2) batch_max += batch_max & 1u; // (a batch holds whole groups: both strands of a read; n_reads is even)
     if (batch_max > n_reads) batch_max = n_reads;
     M.window = ctx->sam_window_bytes > 0 ? ((size_t)ctx->sam_window_bytes + 15) & ~(size_t)15 : (size_t)SX_SAM_WINDOW_BYTES;
     if (M.window > sx_stage_bytes) M.window = sx_stage_bytes;
@@ -831,6 +872,8 @@ static int map_reads_loop(sx_ctx *ctx, const sx_index *idx, const sx_reads_dev &
     HitRoom room;
     SX_TRY(room.init(ctx, (uint64_t)batch_max * n_records * 4));
     std::vector<uint64_t> seg(n_records + 1);
+    sx_best_state S;
+    if (group) SX_TRY(S.init(ctx, batch_max, reads.seq_bytes, n_records, edits, true));
     sx_sam_batch text = {}; // the batch whose text is emitted: what is the same for every batch here
     text.d_sa_list = idx->d_sa_list, text.d_sa_len_list = idx->d_sa_lens;
     text.d_names = reads.d_names, text.d_seqs = reads.d_seqs, text.d_quals = reads.d_quals;
@@ -839,18 +882,25 @@ static int map_reads_loop(sx_ctx *ctx, const sx_index *idx, const sx_reads_dev &
     uint32_t q0 = 0, batch = batch_max;
     while (q0 < n_reads) {
         if (batch > n_reads - q0) batch = n_reads - q0;
-        uint64_t need = 0;
-        const int rc = search_batch(ctx, idx, reads, M, room, q0, batch, edits, seg, &need);
+        uint64_t need = 0, used = 0;
+        const int rc = group ? best_batch(ctx, idx, reads, M, room, S, q0, batch, edits, group, &used)
+                             : search_batch(ctx, idx, reads, M, room, q0, batch, edits, seg, &need);
         if (rc == SX_E_CAPACITY) {
             bool halve;
+            if (group) { // (a group alone gets whatever it needs; a batch of groups is halved to whole groups)
+                SX_TRY(room.grow_or_halve(ctx, used, batch / group, &halve));
+                if (halve) batch_max = batch = (batch / group + 1) / 2 * group;
+                continue;
+            }
             SX_TRY(room.grow_or_halve(ctx, need, batch, &halve));
             if (halve) batch_max = batch = (batch + 1) / 2; // (it is not tried longer again)
             continue;
         }
         if (rc != 0) return rc;
-        if (seg[n_records]) {
-            SX_TRY(merge_batch(ctx, M, room, seg, batch));
-            text.d_hits = M.d_merged, text.n_hits = seg[n_records];
+        if (!group) used = seg[n_records];
+        if (used) {
+            if (!group) SX_TRY(merge_batch(ctx, M, room, seg, batch));
+            text.d_hits = M.d_merged, text.n_hits = used;
             text.d_name_off = reads.d_name_off + q0, text.d_seq_off = reads.d_seq_off + q0, text.d_qual_off = reads.d_qual_off + q0;
             text.n_reads = batch;
             // (the offsets are this batch's: so are the flags)

@@ -7,9 +7,13 @@ streamed form (sx_map_reads_stream from host tables through a sink that discards
 windows, a fraction of that copy rate; the host's FASTQ index pass.  --repeats N times every figure N times (the runs stand
 next to their best as *_runs: the run-to-run spread that a comparison between two builds has to exceed).  --both-strands
 adds the strand kernel (sx_fastq_strands_dev: ms, bytes moved, against the probe's copy rate) and the streamed call with
-SX_MAP_BOTH_STRANDS (kept in profiles/strands_bench_2p28.json).
+SX_MAP_BOTH_STRANDS (kept in profiles/strands_bench_2p28.json).  --best adds, per k, sx_bwt_best_search_dev on the same
+batch (wall, kernel ms of the search and of the select class, hits and lines), its rounds replayed through the public
+calls (per round: groups in and found; the count pass, the two selects with their bytes against the probe's copy rate, the
+emit pass as the difference of the search over the found set with and without its hits) and the streamed call with
+SX_MAP_BEST_STRATUM beside the plain one of the same run (kept in profiles/best_bench_2p28.json).
 
-    python tools/sam_bench.py [--log2n 28] [--reads 1000000] [--window-mib 1024] [--repeats 5] [--both-strands]
+    python tools/sam_bench.py [--log2n 28] [--reads 1000000] [--window-mib 1024] [--repeats 5] [--both-strands] [--best]
 """
 import argparse
 import ctypes as C
@@ -35,6 +39,7 @@ def main():
                     help="the reference mapper's rate measured elsewhere, recorded in the line as given")
     ap.add_argument("--repeats", type=int, default=1, help="time layout, emit and the streamed call so many times")
     ap.add_argument("--both-strands", action="store_true", help="also the strand kernel and the streamed call on both strands")
+    ap.add_argument("--best", action="store_true", help="also the best-stratum search, its rounds and the streamed call with best=True")
     args = ap.parse_args()
     import torch
 
@@ -155,6 +160,8 @@ def main():
             out[f"k{k}"]["emit_ms_runs"] = [round(r[2], 3) for r in emit_runs]
         del d_hits, d_boff
         torch.cuda.empty_cache()
+        if args.best:
+            out[f"k{k}"]["best"] = best_rounds(ctx, torch, profiled, probe, d_c, d_o, d_ro, N, sigma, d_pat, d_off, R, L, k, args.repeats)
     # ---- the streamed form: sx_map_reads_stream (host tables and FASTQ image in, SAM text out through a sink that discards)
     from stralg_amd import _lib, api
     fastq = b"".join(b"@%s\n%s\n+\n%s\n" % (names[q], row.tobytes(), b"~" * L)
@@ -201,6 +208,12 @@ def main():
                                     "call_GBps": round(nbytes / wall / 1e9, 2)}
         if args.repeats > 1:
             out[f"k{k}"]["streamed"]["call_wall_ms_runs"] = walls
+        if args.best:
+            for key, kw in [("streamed_best", dict(best=True))] + ([("streamed_best_both_strands", dict(best=True, both_strands=True))] if args.both_strands else []):
+                b_wall, b_seen, b_walls = streamed(k, **kw)
+                out[f"k{k}"][key] = {"call_wall_ms": round(b_wall * 1e3, 1), "call_wall_ms_runs": b_walls,
+                                     "text_bytes": int(sum(b for _, b in b_seen)), "windows": len(b_seen),
+                                     "plain_call_wall_ms": round(wall * 1e3, 1)}
         if args.both_strands:
             both_wall, both_seen, both_walls = streamed(k, both_strands=True)
             out[f"k{k}"]["streamed_both_strands"] = {"call_wall_ms": round(both_wall * 1e3, 1), "call_wall_ms_runs": both_walls,
@@ -232,6 +245,63 @@ def main():
                                                     "24.1 MB), whole program, page cache warm",
                                             "host": "the CPU-only build machine, not the GPU box"}
     print(json.dumps(out))
+
+
+def best_rounds(ctx, torch, profiled, probe, d_c, d_o, d_ro, N, sigma, d_pat, d_off, R, L, k, repeats):
+    """sx_bwt_best_search_dev on the batch, and its rounds replayed through the public calls"""
+    d_hoff = torch.zeros(R + 1, dtype=torch.int64, device="cuda")
+    d_stratum = torch.zeros(R, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    total = ctx.bwt_best_search_dev(d_c, d_o, d_ro, N, sigma, d_pat, d_off, R, k, d_stratum, d_hoff)
+    d_hits = torch.zeros(max(total, 1) * 32, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    call = lambda: ctx.bwt_best_search_dev(d_c, d_o, d_ro, N, sigma, d_pat, d_off, R, k, d_stratum, d_hoff, d_hits, total)
+    runs = [profiled("search", call) for _ in range(repeats)]
+    sel_runs = [profiled("remap", call) for _ in range(repeats)]
+    words = d_hits[:total * 32].view(torch.int32).reshape(-1, 8)
+    lines = int(((words[:, 2].to(torch.int64) & 0xFFFFFFFF) - (words[:, 1].to(torch.int64) & 0xFFFFFFFF)).sum().item())
+    strata = torch.bincount(d_stratum.to(torch.int64), minlength=256).cpu().tolist()
+    res = {"hits": int(total), "lines": lines, "call_wall_ms": round(min(r[1] for r in runs) * 1e3, 2),
+           "call_wall_ms_runs": [round(r[1] * 1e3, 2) for r in runs], "search_kernel_ms": round(min(r[2] for r in runs), 3),
+           "select_kernel_ms": round(min(r[2] for r in sel_runs), 3), "without_a_hit": strata[255], "rounds": []}
+    del words, d_hits
+    # the rounds again, one public call a step
+    cur_pat, cur_off, cur_n = d_pat, d_off, R
+    for d in range(k + 1):
+        if cur_n == 0:
+            break
+        d_ho = torch.zeros(cur_n + 1, dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        tot, count_wall, count_ms = profiled("search", lambda: ctx.bwt_approx_search_dev(d_c, d_o, d_ro, N, sigma, cur_pat, cur_off, cur_n, d, d_ho))
+        found = (d_ho[1:] > d_ho[:-1])
+        sets, sel = [], []
+        for keep in (found, ~found):
+            d_keep = keep.to(torch.uint8).contiguous()
+            d_out = torch.zeros(cur_n * L + 32, dtype=torch.uint8, device="cuda")
+            d_oo = torch.zeros(cur_n + 1, dtype=torch.int32, device="cuda")
+            d_ids = torch.zeros(max(cur_n, 1), dtype=torch.int32, device="cuda")
+            torch.cuda.synchronize()
+            (kept, nbytes), wall, ms = profiled("remap", lambda: ctx.patterns_select_dev(cur_pat, cur_off, cur_n, d_keep, d_out, d_oo, d_ids))
+            moved = 2 * nbytes + cur_n * 9 + kept * 16
+            sel.append({"kept": kept, "bytes": nbytes, "kernel_ms": round(ms, 3), "wall_ms": round(wall * 1e3, 3), "bytes_moved": moved,
+                        "fraction_of_copy": round(moved / (ms * 1e-3) / 1e9 / probe["copy"], 3) if ms > 0 else None})
+            sets.append((d_out, d_oo, kept))
+        emit_ms = None
+        f_pat, f_off, f_n = sets[0]
+        if f_n:
+            d_fho = torch.zeros(f_n + 1, dtype=torch.int64, device="cuda")
+            d_fh = torch.zeros(max(tot, 1) * 32, dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            _, _, both_ms = profiled("search", lambda: ctx.bwt_approx_search_dev(d_c, d_o, d_ro, N, sigma, f_pat, f_off, f_n, d, d_fho, d_fh, tot))
+            _, _, only_ms = profiled("search", lambda: ctx.bwt_approx_search_dev(d_c, d_o, d_ro, N, sigma, f_pat, f_off, f_n, d, d_fho))
+            emit_ms = round(both_ms - only_ms, 3)
+            del d_fho, d_fh
+        res["rounds"].append({"d": d, "groups_in": cur_n, "found": int(f_n), "hits": int(tot), "count_kernel_ms": round(count_ms, 3),
+                              "count_wall_ms": round(count_wall * 1e3, 2), "select_found": sel[0], "select_open": sel[1],
+                              "emit_kernel_ms_by_difference": emit_ms})
+        cur_pat, cur_off, cur_n = sets[1]
+        torch.cuda.empty_cache()
+    return res
 
 
 if __name__ == "__main__":

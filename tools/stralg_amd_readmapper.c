@@ -29,6 +29,10 @@
  *                                                   complement (sequence reversed and complemented, qualities reversed),
  *                                                   with FLAG 16 in place of 0; goes with -i, --compact, --sa-sample,
  *                                                   --packed and several FASTQ files
+ *   --best                                          with -d K: per read only the lines of its best stratum, those that
+ *                                                   -d e* prints for it, e* the smallest edit count in 0 .. K at which
+ *                                                   any are printed (with --both-strands: over both strands of the read
+ *                                                   together); a read without a match within K edits prints nothing
  *   (--preprocess, --edits and --in-memory are accepted for -p, -d and -i)
  *
  * Index file: u32 record count; per record, last FASTA record first, its name as u32 length + bytes + NUL, then the
@@ -160,6 +164,8 @@ static int usage(const char *self, int status)
     fprintf(stderr, "                                          most 7 letters)\n");
     fprintf(stderr, "       --both-strands                     with -d: every read's reverse complement is mapped too, its lines\n");
     fprintf(stderr, "                                          have FLAG 16\n");
+    fprintf(stderr, "       --best                             with -d K: per read only the matches of the smallest edit count\n");
+    fprintf(stderr, "                                          in 0 .. K that has any (with --both-strands: over both strands)\n");
     return status;
 }
 
@@ -182,6 +188,8 @@ int main(int argc, char **argv)
             flags |= SX_INDEX_PACKED;
         } else if (!strcmp(s, "--both-strands")) {
             map_flags |= SX_MAP_BOTH_STRANDS;
+        } else if (!strcmp(s, "--best")) {
+            map_flags |= SX_MAP_BEST_STRATUM;
         } else if (!strcmp(s, "--sa-sample")) {
             if (++a >= argc) return usage(argv[0], EXIT_FAILURE);
             const long dist = strtol(argv[a], NULL, 10);
