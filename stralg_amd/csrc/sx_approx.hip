@@ -399,7 +399,7 @@ static int approx_search_dev(sx_ctx *ctx, const uint32_t *d_c_table, Occ o, Occ 
     return sx_sync(ctx);
 }
 
-// the search over a record of an index in whichever form its tables have (the mapper's loop, sx_sam.hip)
+// the search over a record of an index in whichever form its tables have (the mapper's loop, sx_map.hip)
 int sx_approx_search_record(sx_ctx *ctx, const sx_index_rec &R, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, int max_edits,
                             uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t hit_capacity, uint64_t *total_hits_out)
 {

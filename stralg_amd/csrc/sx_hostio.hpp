@@ -1,4 +1,4 @@
-// sx_hostio.hpp -- what the streaming writer (sx_build.hip), the index (sx_index.hip) and the mapper (sx_sam.hip) share: the
+// sx_hostio.hpp -- what the streaming writer (sx_build.hip), the index (sx_index.hip) and the mapper (sx_map.hip) share: the
 // context's two pinned staging buffers, the chunked copies through them (sx_hostio.hip), the owner of a call's hipMallocs,
 // and the two window loops of the index's compact and sampled forms.
 #pragma once

@@ -492,12 +492,7 @@ int sx_index_map_reads_ex(sx_ctx *ctx, const sx_index *idx, const uint8_t *fastq
         if (frc == SX_E_MALFORMED || frc == SX_E_ARG) return sx_fail_msg(ctx, frc, "read mapping: malformed FASTQ image (see sx_fastq_index)");
         if (frc != 0) return frc;
     }
-    sx_reads_dev reads;
-    reads.count = fq.count;
-    reads.d_names = fq.d_names, reads.d_seqs = fq.d_seqs, reads.d_quals = fq.d_quals;
-    reads.d_name_off = fq.d_name_off, reads.d_seq_off = fq.d_seq_off, reads.d_qual_off = fq.d_qual_off;
-    reads.name_bytes = fq.name_bytes, reads.seq_bytes = fq.seq_bytes, reads.qual_bytes = fq.qual_bytes;
-    const int rc = sx_map_reads_core(ctx, idx, reads, edits, flags, sink, user);
+    const int rc = sx_map_reads_core(ctx, idx, fq, nullptr, edits, flags, sink, user);
     sx_fastq_dev_free(&fq);
     return rc;
 }

@@ -1,4 +1,4 @@
-// sx_index.hpp -- the device-resident index (sx_index.hip) and what the mapper's loop (sx_sam.hip) reads of it.
+// sx_index.hpp -- the device-resident index (sx_index.hip) and what the mapper's loop (sx_map.hip) reads of it.
 #pragma once
 #include "sx_common.hpp"
 #include "sx_hostio.hpp"
@@ -48,16 +48,6 @@ struct sx_index {
     size_t view_bytes = 0;
 };
 
-// the reads of one call on the device; h_seq_off: the host's copy of d_seq_off, or null (the loop then reads the two
-// entries a batch needs back)
-struct sx_reads_dev {
-    uint32_t count = 0;
-    const uint8_t *d_names = nullptr, *d_seqs = nullptr, *d_quals = nullptr;
-    const uint32_t *d_name_off = nullptr, *d_seq_off = nullptr, *d_qual_off = nullptr;
-    const uint32_t *h_seq_off = nullptr;
-    uint64_t name_bytes = 0, seq_bytes = 0, qual_bytes = 0; // the offsets' last entries
-};
-
 // A record's host tables as an index takes them (min_sigma 1: the record without symbols has N = 1, sigma = 1) or as the
 // mapper searches them (min_sigma 2): N and sigma in range, and every array there
 static inline bool sx_map_dims_ok(uint64_t N, uint32_t sigma, uint32_t min_sigma)
@@ -72,9 +62,11 @@ static inline bool sx_map_record_check(const sx_map_record &R, uint32_t min_sigm
 // the bits of a mapping call's flags word that mean something (sx_map_reads_stream_ex, sx_index_map_reads_ex, sx_map_reads_limit)
 constexpr uint32_t sx_map_known_flags = SX_MAP_BOTH_STRANDS | SX_MAP_BEST_STRATUM;
 
-// sx_sam.hip: the mapper's loop over reads and an index that both lie on ctx's device
-// (flags: those of sx_map_reads_stream_ex)
-int sx_map_reads_core(sx_ctx *ctx, const sx_index *idx, const sx_reads_dev &reads, int edits, uint32_t flags, sx_sink_fn sink, void *user);
+// sx_map.hip: the mapper's loop over reads and an index that both lie on ctx's device (flags: those of
+// sx_map_reads_stream_ex); h_seq_off: the host's copy of reads.d_seq_off, or null (the loop then reads the two entries a
+// batch needs back)
+int sx_map_reads_core(sx_ctx *ctx, const sx_index *idx, const sx_fastq_dev &reads, const uint32_t *h_seq_off, int edits, uint32_t flags,
+                      sx_sink_fn sink, void *user);
 // sx_approx.hip: sx_bwt_approx_search_dev over the tables of a record, full, compact or packed
 int sx_approx_search_record(sx_ctx *ctx, const sx_index_rec &R, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, int max_edits,
                             uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t hit_capacity, uint64_t *total_hits_out);
@@ -85,7 +77,7 @@ int sx_approx_count_record(sx_ctx *ctx, const sx_index_rec &R, const uint8_t *d_
                            uint64_t *d_hit_offsets, uint64_t *total_hits_out);
 int sx_approx_emit_record(sx_ctx *ctx, const sx_index_rec &R, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, int max_edits,
                           const uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t total_hits);
-// sx_sam.hip: out[i] = table[seqs[i]] for i in [lo, hi) (a record's 256-byte symbol table; sam_remap_kernel)
+// sx_map.hip: out[i] = table[seqs[i]] for i in [lo, hi) (a record's 256-byte symbol table; sam_remap_kernel)
 void sx_sam_remap(sx_ctx *ctx, const uint8_t *d_seqs, const uint8_t *d_table, uint8_t *d_out, uint64_t lo, uint64_t hi);
 
 // ---- sx_best.hip: best-stratum search -----------------------------------------------------------

@@ -1,0 +1,450 @@
+// sx_map.hip -- the read mapper's loop (tools/readmappers/bwt_readmapper/bwt_readmapper.c map_read, :130-160, 257-266) over
+// reads and an index that lie on the device: what sx_map_reads_stream and sx_index_map_reads share (DESIGN.md sections 11,
+// 12, 16, 17).  The reads go through in batches.  A batch: its searches, record after record, and its hits put in (read,
+// record, hit) order (on capacity: the hits' room grows or the batch is halved, and it runs again; sx_map_plan.hpp has
+// the arithmetic), then its SAM text (sx_sam.hip), window after window, to the sink.
+#include "sx_common.hpp"
+#include "sx_device.hpp"
+#include "sx_scan.hpp"
+#include "sx_hostio.hpp"
+#include "sx_index.hpp"
+#include "sx_locate.hpp"
+#include "sx_sam.hpp"
+#include "sx_map_plan.hpp"
+
+#include <vector>
+
+namespace sx {
+
+// ---- remap per record, hits of all records in (read, record rank, hit) order -------------------------------------------
+__global__ __launch_bounds__(kBlock) void sam_remap_kernel(const uint8_t *seqs, const uint8_t *table, uint8_t *out, uint64_t lo,
+                                                           uint64_t hi)
+{
+    const uint64_t i = lo + (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i < hi) out[i] = table[seqs[i]];
+}
+
+// cnt[q * n_rec + r] = hits of read q in record r (ho: n_rec arrays of stride entries, the searches' hit offsets)
+__global__ __launch_bounds__(kBlock) void sam_vq_count_kernel(const uint64_t *ho, uint64_t stride, uint32_t batch, uint32_t n_rec,
+                                                              uint64_t *cnt)
+{
+    const uint64_t idx = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (idx >= (uint64_t)batch * n_rec) return;
+    const uint32_t q = (uint32_t)(idx / n_rec), r = (uint32_t)(idx - (uint64_t)q * n_rec);
+    cnt[idx] = ho[r * stride + q + 1] - ho[r * stride + q];
+}
+
+// hit j of the searches' hit arrays (record r's at seg[r] .. seg[r + 1]) goes behind the hits of its read in the
+// records before r: query <- read * n_rec + r
+__global__ __launch_bounds__(kBlock) void sam_merge_kernel(const uint4 *src, uint64_t n_hits, const uint64_t *seg, uint32_t n_rec,
+                                                           const uint64_t *ho, uint64_t stride, uint32_t batch, const uint64_t *vbase,
+                                                           uint4 *dst, uint32_t *err)
+{
+    const uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (j >= n_hits) return;
+    uint32_t r = 0;
+    {
+        uint32_t b = n_rec; // seg[r] <= j < seg[b]
+        while (b - r > 1) {
+            const uint32_t mid = (r + b) / 2;
+            if (seg[mid] <= j) r = mid;
+            else b = mid;
+        }
+    }
+    uint4 h0 = src[2 * j];
+    const uint32_t q = h0.x;
+    if (q >= batch) {
+        atomicOr(err, 2u);
+        return;
+    }
+    const uint64_t at = vbase[(uint64_t)q * n_rec + r] + (j - seg[r] - ho[r * stride + q]);
+    if (at >= n_hits) {
+        atomicOr(err, 2u);
+        return;
+    }
+    h0.x = q * n_rec + r;
+    dst[2 * at] = h0;
+    dst[2 * at + 1] = src[2 * j + 1];
+}
+
+// ---- the pieces of the loop ---------------------------------------------------------------------------------------------
+template <class T> static int upload(sx_ctx *ctx, sx_dev_scope &B, T **d, const T *h, size_t count)
+{
+    SX_TRY(B.take(ctx, d, count));
+    if (count) SX_CHECK(hipMemcpyAsync(*d, h, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+    return 0;
+}
+
+// what a mapping call asks of its reads and records; records_ok: sx_map_dims_ok / sx_map_record_check with sigma >= 2
+static int map_check(sx_ctx *ctx, uint64_t n_reads, uint64_t n_records, uint32_t flags, bool records_ok)
+{
+    if (flags & ~sx_map_known_flags) return sx_fail_msg(ctx, SX_E_ARG, "read mapping: unknown flags");
+    if (sx_map_reads_limit(n_reads, n_records, flags) != 0)
+        return sx_fail_msg(ctx, SX_E_ARG, "read mapping: reads x records (twice that for both strands) must stay below 2^32");
+    if (!records_ok) return sx_fail_msg(ctx, SX_E_ARG, "read mapping: a record lacks its name, suffix array, tables or remap table");
+    return 0;
+}
+
+// Room for the hits of a batch's searches: a guess to start with; a batch that needs more makes it
+// grow, up to what map_room_largest allows, before the batch is halved
+struct HitRoom {
+    uint64_t cap = 0, cap_max = 0;
+    sx_approx_hit *d_raw = nullptr;
+    sx_dev_scope own;
+    int init(sx_ctx *ctx, uint32_t batch_max, uint32_t n_records)
+    {
+        size_t free_b = 0, total_b = 0;
+        const bool known = hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b;
+        if (!known) (void)hipGetLastError();
+        cap_max = map_room_largest(known, free_b);
+        cap = map_room_first(batch_max, n_records, cap_max);
+        return own.take(ctx, &d_raw, (size_t)cap);
+    }
+    // the searches of `groups` groups of reads need room for `need` hits: it grows, or *halve, and the caller goes on with
+    // half the groups
+    int grow_or_halve(sx_ctx *ctx, uint64_t need, uint32_t groups, bool *halve)
+    {
+        const map_room_step s = map_room_next(cap, cap_max, need, groups);
+        *halve = s.halve;
+        if (s.halve) return 0;
+        cap = s.cap;
+        own.drop(d_raw);
+        return own.take(ctx, &d_raw, (size_t)cap);
+    }
+};
+
+// the reads of a mapping call as the loop sees them
+struct MapReads {
+    const sx_fastq_dev *fq;
+    const uint32_t *h_seq_off; // the host's copy of fq->d_seq_off, or null (the two entries a batch needs are read back)
+    const uint16_t *d_flags;   // a FLAG per read, or null
+    uint32_t group; // 0, or (SX_MAP_BEST_STRATUM) the reads that share a stratum: 1, or 2 for the strands of a read
+};
+
+struct MapBufs { // what a mapping call holds on the device beside the hits' room
+    uint8_t *d_pat, *d_win[2];
+    uint64_t *d_ho, *d_vbase, *d_seg, *d_byte_off = nullptr;
+    uint32_t *d_err;
+    sx_approx_hit *d_merged = nullptr;
+    // an index with a sampled suffix array: the lines in front of every hit of the batch, the positions of a run of hits
+    uint64_t *d_pos_off = nullptr;
+    uint32_t *d_positions = nullptr;
+    uint64_t pos_cap = 0;
+    uint64_t merged_cap = 0, stride = 0; // stride: entries of a record's hit offsets in d_ho
+    size_t window = 0;
+    std::vector<uint64_t> seg; // (the plain batch) where record r's hits start in the room; last, how many there are
+    sx_dev_scope own;
+};
+
+// [*p_lo, *p_hi): the sequence bytes of reads q0 .. q0 + batch
+static int batch_bytes(sx_ctx *ctx, const MapReads &R, uint32_t q0, uint32_t batch, uint64_t *p_lo, uint64_t *p_hi)
+{
+    if (R.h_seq_off) {
+        *p_lo = R.h_seq_off[q0], *p_hi = R.h_seq_off[q0 + batch];
+    } else { // (the offsets were made on the device: the two this batch needs come back)
+        const uint32_t *src[2] = {R.fq->d_seq_off + q0, R.fq->d_seq_off + q0 + batch};
+        const uint32_t one[2] = {1, 1};
+        uint32_t got[2];
+        SX_TRY(sx_readback_ranges(ctx, src, one, 2, got));
+        *p_lo = got[0], *p_hi = got[1];
+    }
+    return 0;
+}
+
+// The searches of reads q0 .. q0 + batch, record after record, into the room: M.seg[r] <- where record r's hits start,
+// M.seg[records] and *hits_out <- how many there are.  SX_E_CAPACITY: the room is too small for the *hits_out hits known of
+// so far
+static int search_batch(sx_ctx *ctx, const sx_index *idx, const MapReads &R, MapBufs &M, const HitRoom &room, uint32_t q0, uint32_t batch,
+                        int edits, uint64_t *hits_out)
+{
+    uint64_t p_lo, p_hi;
+    SX_TRY(batch_bytes(ctx, R, q0, batch, &p_lo, &p_hi));
+    const uint32_t n_records = (uint32_t)idx->recs.size();
+    uint64_t used = 0;
+    for (uint32_t r = 0; r < n_records; ++r) {
+        if (p_hi > p_lo)
+            sx_launch(ctx, SX_KC_REMAP, 2 * (p_hi - p_lo), sam_remap_kernel, dim3(sx_div_up(p_hi - p_lo, kBlock)), dim3(kBlock),
+                      (const uint8_t *)R.fq->d_seqs, (const uint8_t *)(idx->d_tabs + (size_t)r * 256), M.d_pat, p_lo, p_hi);
+        uint64_t tot = 0;
+        // (whichever form the record has: the hits and their order are the same)
+        const int rc = sx_approx_search_record(ctx, idx->recs[r], M.d_pat, R.fq->d_seq_off + q0, batch, edits, M.d_ho + r * M.stride,
+                                               room.d_raw + used, room.cap - used, &tot);
+        if (rc == SX_E_CAPACITY) *hits_out = used + tot;
+        if (rc != 0) return rc;
+        M.seg[r] = used;
+        used += tot;
+    }
+    M.seg[n_records] = *hits_out = used;
+    return 0;
+}
+
+// room for `used` hits in (read, record, hit) order and for their byte offsets
+static int merged_room(sx_ctx *ctx, MapBufs &M, const HitRoom &room, uint64_t used)
+{
+    if (used > M.merged_cap) {
+        if (M.d_merged) M.own.drop(M.d_merged), M.own.drop(M.d_byte_off), M.own.drop(M.d_pos_off);
+        M.d_pos_off = nullptr;
+        M.merged_cap = used > room.cap ? used : room.cap;
+        SX_TRY(M.own.take(ctx, &M.d_merged, (size_t)M.merged_cap));
+        SX_TRY(M.own.take(ctx, &M.d_byte_off, (size_t)M.merged_cap + 1));
+    }
+    return 0;
+}
+
+// The hits of the batch's searches in (read, record rank, hit) order: M.d_merged, query <- read x records + rank
+static int merge_batch(sx_ctx *ctx, MapBufs &M, const HitRoom &room, uint32_t batch)
+{
+    const uint32_t n_records = (uint32_t)M.seg.size() - 1;
+    const uint64_t used = M.seg[n_records];
+    SX_TRY(merged_room(ctx, M, room, used));
+    SX_CHECK(hipMemcpyAsync(M.d_seg, M.seg.data(), M.seg.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    SX_CHECK(hipStreamSynchronize(ctx->stream)); // (seg is reused by the next batch)
+    const uint64_t nvq = (uint64_t)batch * n_records;
+    sx_launch(ctx, SX_KC_SAM, nvq * 24, sam_vq_count_kernel, dim3(sx_div_up(nvq, kBlock)), dim3(kBlock), (const uint64_t *)M.d_ho, M.stride,
+              batch, n_records, M.d_vbase);
+    SX_TRY(device_scan64_inplace(ctx, M.d_vbase, nvq, SX_KC_SAM));
+    sx_launch(ctx, SX_KC_SAM, used * 64, sam_merge_kernel, dim3(sx_div_up(used, kBlock)), dim3(kBlock), (const uint4 *)room.d_raw, used,
+              (const uint64_t *)M.d_seg, n_records, (const uint64_t *)M.d_ho, M.stride, batch, (const uint64_t *)M.d_vbase,
+              (uint4 *)M.d_merged, M.d_err);
+    uint32_t e = 0;
+    SX_TRY(sx_readback(ctx, M.d_err, 1, &e));
+    if (e) return sx_fail_msg(ctx, SX_E_INTERNAL, "read mapping: the hits of a batch do not add up");
+    return 0;
+}
+
+// A batch of either kind, reads q0 .. q0 + batch: on success its hits are in M.d_merged in (read, record, hit) order and
+// *hits_out is their count; SX_E_CAPACITY: the room is too small for the *hits_out hits known of so far.
+// The plain batch: every record's search, then the merge
+static int plain_batch(sx_ctx *ctx, const sx_index *idx, const MapReads &R, MapBufs &M, const HitRoom &room, int edits, uint32_t q0,
+                       uint32_t batch, uint64_t *hits_out)
+{
+    SX_TRY(search_batch(ctx, idx, R, M, room, q0, batch, edits, hits_out));
+    return *hits_out ? merge_batch(ctx, M, room, batch) : 0;
+}
+
+// The best-stratum batch (whole groups): the rounds of sx_best.hip into the room, then its place step
+static int best_batch(sx_ctx *ctx, const sx_index *idx, const MapReads &R, MapBufs &M, const HitRoom &room, sx_best_state &S, int edits,
+                      uint32_t q0, uint32_t batch, uint64_t *hits_out)
+{
+    sx_best_batch B = {};
+    B.recs = idx->recs.data(), B.n_rec = (uint32_t)idx->recs.size(), B.d_tabs = idx->d_tabs, B.d_pat = M.d_pat;
+    B.d_bytes = R.fq->d_seqs, B.bytes_total = R.fq->seq_bytes, B.d_off = R.fq->d_seq_off + q0;
+    SX_TRY(batch_bytes(ctx, R, q0, batch, &B.p_lo, &B.p_hi));
+    B.count = batch, B.gsize = R.group, B.k = edits;
+    B.d_ho = M.d_ho, B.ho_stride = M.stride, B.d_stratum = S.d_stratum;
+    B.d_raw = room.d_raw, B.raw_cap = room.cap, B.go_on_counting = false;
+    SX_TRY(sx_best_rounds(ctx, S, B, hits_out));
+    if (*hits_out == 0) return 0;
+    SX_TRY(merged_room(ctx, M, room, *hits_out));
+    return sx_best_place(ctx, S, B, *hits_out, M.d_vbase, M.d_merged);
+}
+
+// The text of A's hits: its layout, then window after window through the two device windows and the context's staging
+// buffers: emit and copy of window w are queued, then the sink works on window w - 1
+static int emit_windows(sx_ctx *ctx, const SamArgs &A, const MapBufs &M, const sx_stage_events &E, sx_sink_fn sink, void *user)
+{
+    uint64_t total = 0;
+    SX_TRY(sam_layout(ctx, A, M.d_byte_off, &total));
+    const uint64_t window = M.window, n_win = (total + window - 1) / window;
+    for (uint64_t w = 0; w <= n_win; ++w) {
+        if (w < n_win) {
+            const uint64_t lo = w * window, hi = total - lo < window ? total : lo + window;
+            SX_TRY(sam_emit(ctx, A, M.d_byte_off, lo, hi, M.d_win[w & 1]));
+            SX_CHECK(hipMemcpyAsync(ctx->h_stage[w & 1], M.d_win[w & 1], (size_t)(hi - lo), hipMemcpyDeviceToHost, ctx->stream));
+            SX_CHECK(hipEventRecord(E.ev[w & 1], ctx->stream));
+        }
+        if (w > 0) {
+            const uint64_t lo = (w - 1) * window, hi = total - lo < window ? total : lo + window;
+            SX_CHECK(hipEventSynchronize(E.ev[(w - 1) & 1]));
+            if (sink(user, SX_SECTION_SAM, ctx->h_stage[(w - 1) & 1], (size_t)(hi - lo)) != 0) {
+                (void)hipStreamSynchronize(ctx->stream);
+                return sx_fail_msg(ctx, SX_E_ARG, "the sink refused a chunk");
+            }
+        }
+    }
+    return sx_sync(ctx);
+}
+
+// The text of a batch (`text`: its hits, reads and records) against an index with a sampled suffix array: its hits are taken
+// in runs of consecutive hits whose lines fit the cap (SX_FLAG_LOCATE_CHUNK_ROWS; a hit is never split: one with more lines
+// gets a buffer of its own length); a run is located, laid out and emitted through its windows before the next one starts
+static int emit_located(sx_ctx *ctx, const sx_index *idx, const SamArgs &text, MapBufs &M, const sx_stage_events &E, sx_sink_fn sink, void *user)
+{
+    const LocRec *d_recs = (const LocRec *)idx->d_loc_list;
+    const uint64_t n_hits = text.n_hits, cap = map_located_rows(ctx->locate_chunk_rows);
+    if (!M.d_pos_off) SX_TRY(M.own.take(ctx, &M.d_pos_off, (size_t)M.merged_cap + 1));
+    uint64_t total = 0;
+    SX_TRY(sx_sa_hits_offsets(ctx, d_recs, text.n_records, (uint64_t)text.n_reads * text.n_records, text.hits, n_hits, M.d_pos_off, &total));
+    uint32_t *d_loc_err = M.d_err + 4, *d_run = M.d_err + 8;
+    for (uint64_t h_lo = 0, base = 0; h_lo < n_hits;) {
+        uint64_t h_hi = n_hits, rows = total - base;
+        if (rows > cap) SX_TRY(sx_sa_hits_run(ctx, M.d_pos_off, n_hits, h_lo, base, cap, d_run, &h_hi, &rows));
+        if (rows > M.pos_cap) {
+            if (M.d_positions) M.own.drop(M.d_positions);
+            M.d_positions = nullptr, M.pos_cap = 0;
+            SX_TRY(M.own.take(ctx, &M.d_positions, (size_t)rows));
+            M.pos_cap = rows;
+        }
+        if (!M.d_positions) SX_TRY(M.own.take(ctx, &M.d_positions, 1)); // (hits without a line: the kernels still want an address)
+        SX_TRY(sx_sa_locate_hits(ctx, d_recs, text.n_records, idx->packed, text.hits, M.d_pos_off, h_lo, h_hi, base, rows, M.d_positions, d_loc_err));
+        uint32_t e = 0;
+        SX_TRY(sx_readback(ctx, d_loc_err, 1, &e));
+        if (e) return sx_fail_msg(ctx, SX_E_INTERNAL, "read mapping: a walk over a sampled suffix array met its bound");
+        SamArgs A = text;
+        A.hits = text.hits + 2 * h_lo, A.n_hits = h_hi - h_lo;
+        A.positions = M.d_positions, A.pos_off = M.d_pos_off + h_lo, A.pos_base = base;
+        SX_TRY(emit_windows(ctx, A, M, E, sink, user));
+        base += rows;
+        h_lo = h_hi;
+    }
+    return 0;
+}
+
+// The loop.  A batch: its hits (on capacity: grow_or_halve, again), their text, on to the next reads
+static int map_reads_loop(sx_ctx *ctx, const sx_index *idx, const MapReads &R, int edits, sx_sink_fn sink, void *user)
+{
+    const sx_fastq_dev &fq = *R.fq;
+    const uint32_t n_reads = fq.count, n_records = (uint32_t)idx->recs.size(), g = R.group ? R.group : 1;
+    SX_CHECK(hipSetDevice(ctx->device));
+    MapBufs M;
+    SX_TRY(M.own.take(ctx, &M.d_pat, (size_t)fq.seq_bytes));
+    SX_TRY(sx_sync(ctx)); // (the callers' uploads from pageable memory are done)
+
+    const uint32_t batch_max = map_batch_max(ctx->sam_batch_reads, R.group, n_reads);
+    M.window = map_window_bytes(ctx->sam_window_bytes, sx_stage_bytes);
+    SX_TRY(sx_stage_ensure(ctx));
+    sx_stage_events E;
+    for (uint8_t *&w : M.d_win) SX_TRY(M.own.take(ctx, &w, M.window));
+    SX_TRY(E.create(ctx));
+    M.stride = (uint64_t)batch_max + 1;
+    SX_TRY(M.own.take(ctx, &M.d_ho, (size_t)M.stride * n_records));
+    SX_TRY(M.own.take(ctx, &M.d_vbase, (size_t)batch_max * n_records + 1));
+    SX_TRY(M.own.take(ctx, &M.d_seg, (size_t)n_records + 1));
+    SX_TRY(M.own.take(ctx, &M.d_err, 64));
+    SX_CHECK(hipMemsetAsync(M.d_err, 0, 256, ctx->stream));
+    M.seg.resize(n_records + 1);
+    HitRoom room;
+    SX_TRY(room.init(ctx, batch_max, n_records));
+    sx_best_state S;
+    if (R.group) SX_TRY(S.init(ctx, batch_max, fq.seq_bytes, n_records, edits, true));
+    SamArgs A = {}; // the batch whose text is emitted: what is the same for every batch here
+    A.sa_list = idx->d_sa_list, A.sa_len_list = idx->d_sa_lens;
+    A.names = fq.d_names, A.seqs = fq.d_seqs, A.quals = fq.d_quals;
+    A.rnames = idx->d_rnames, A.rname_off = idx->d_rname_off, A.n_records = n_records;
+
+    uint32_t q0 = 0, batch = batch_max;
+    while (q0 < n_reads) {
+        if (batch > n_reads - q0) batch = n_reads - q0;
+        uint64_t hits = 0;
+        const int rc = R.group ? best_batch(ctx, idx, R, M, room, S, edits, q0, batch, &hits) : plain_batch(ctx, idx, R, M, room, edits, q0, batch, &hits);
+        if (rc == SX_E_CAPACITY) { // (a group alone gets whatever it needs; a batch of groups is halved to whole groups)
+            bool halve;
+            SX_TRY(room.grow_or_halve(ctx, hits, batch / g, &halve));
+            if (halve) batch = map_batch_halved(batch, g); // (it is not tried longer again)
+            continue;
+        }
+        if (rc != 0) return rc;
+        if (hits) {
+            A.hits = (const uint4 *)M.d_merged, A.n_hits = hits;
+            A.name_off = fq.d_name_off + q0, A.seq_off = fq.d_seq_off + q0, A.qual_off = fq.d_qual_off + q0;
+            A.n_reads = batch;
+            A.flags = R.d_flags ? R.d_flags + q0 : nullptr; // (the offsets are this batch's: so are the flags)
+            SX_TRY(idx->sa_log2 ? emit_located(ctx, idx, A, M, E, sink, user) : emit_windows(ctx, A, M, E, sink, user));
+        }
+        q0 += batch;
+    }
+    return sx_sync(ctx);
+}
+
+} // namespace sx
+
+using namespace sx;
+
+// out[i] = table[seqs[i]] for i in [lo, hi) (sx_best.hip remaps its pattern sets with the loop's kernel)
+void sx_sam_remap(sx_ctx *ctx, const uint8_t *d_seqs, const uint8_t *d_table, uint8_t *d_out, uint64_t lo, uint64_t hi)
+{
+    if (hi > lo) sx_launch(ctx, SX_KC_REMAP, 2 * (hi - lo), sam_remap_kernel, dim3(sx_div_up(hi - lo, kBlock)), dim3(kBlock), d_seqs, d_table, d_out, lo, hi);
+}
+
+// A mapping call over reads and an index on ctx's device.  Both strands: the read set of 2 x count
+// reads, read 2q + strand, is made once and searched like any read set, so its hits come in (read, strand, record, hit)
+// order, which is the text's; the FLAGs go with the batches.
+int sx_map_reads_core(sx_ctx *ctx, const sx_index *idx, const sx_fastq_dev &reads, const uint32_t *h_seq_off, int edits, uint32_t flags,
+                      sx_sink_fn sink, void *user)
+{
+    const uint32_t n_records = (uint32_t)idx->recs.size();
+    if (reads.count == 0 || n_records == 0) return 0;
+    bool records_ok = true;
+    for (const sx_index_rec &R : idx->recs) records_ok = records_ok && sx_map_dims_ok(R.N, R.sigma, 2);
+    SX_TRY(map_check(ctx, reads.count, n_records, flags, records_ok));
+    const bool best = (flags & SX_MAP_BEST_STRATUM) != 0;
+    if (!(flags & SX_MAP_BOTH_STRANDS)) return map_reads_loop(ctx, idx, MapReads{&reads, h_seq_off, nullptr, best ? 1u : 0u}, edits, sink, user);
+    SX_CHECK(hipSetDevice(ctx->device));
+    sx_fastq_dev both = {};
+    sx_dev_scope F;
+    uint16_t *d_flags;
+    SX_TRY(F.take(ctx, &d_flags, 2 * (size_t)reads.count));
+    SX_TRY(sx_fastq_strands_dev(ctx, &reads, &both, d_flags)); // (syncs: the callers' uploads from pageable memory are done)
+    const int rc = map_reads_loop(ctx, idx, MapReads{&both, nullptr, d_flags, best ? 2u : 0u}, edits, sink, user);
+    sx_fastq_dev_free(&both);
+    return rc;
+}
+
+extern "C" {
+
+int sx_map_reads_limit(uint64_t n_reads, uint64_t n_records, uint32_t flags)
+{
+    if (flags & ~sx_map_known_flags) return SX_E_ARG;
+    const uint64_t strands = (flags & SX_MAP_BOTH_STRANDS) ? 2 : 1;
+    // (no product is formed before it is known to fit)
+    if (n_reads > 0xFFFFFFFFull / strands) return SX_E_ARG;
+    if (n_records && n_reads * strands > 0xFFFFFFFFull / n_records) return SX_E_ARG;
+    return 0;
+}
+
+int sx_map_reads_stream(sx_ctx *ctx, const sx_map_record *records, uint32_t n_records, const uint8_t *fastq, size_t fastq_len,
+                        int edits, sx_sink_fn sink, void *user)
+{
+    return sx_map_reads_stream_ex(ctx, records, n_records, fastq, fastq_len, edits, 0, sink, user);
+}
+
+int sx_map_reads_stream_ex(sx_ctx *ctx, const sx_map_record *records, uint32_t n_records, const uint8_t *fastq, size_t fastq_len,
+                           int edits, uint32_t flags, sx_sink_fn sink, void *user)
+{
+    if (!ctx || !sink || (n_records && !records) || (fastq_len && !fastq)) return SX_E_ARG;
+    if (edits < 0 || edits > SX_APPROX_MAX_EDITS)
+        return sx_fail_msg(ctx, SX_E_ARG, "read mapping: edits must be in [0, 8]");
+    if (flags & ~sx_map_known_flags) return sx_fail_msg(ctx, SX_E_ARG, "read mapping: unknown flags");
+    sx_fastq fq;
+    const int frc = sx_fastq_index(fastq, fastq_len, &fq);
+    if (frc != 0) return sx_fail_msg(ctx, frc, "read mapping: malformed FASTQ image (see sx_fastq_index)");
+    struct FqFree {
+        sx_fastq *f;
+        ~FqFree() { sx_fastq_free(f); }
+    } fq_free{&fq};
+    if (fq.count == 0 || n_records == 0) return 0;
+    bool records_ok = true;
+    for (uint32_t r = 0; r < n_records; ++r) records_ok = records_ok && sx_map_record_check(records[r], 2);
+    SX_TRY(map_check(ctx, fq.count, n_records, flags, records_ok));
+    SX_CHECK(hipSetDevice(ctx->device));
+    // the reads of this call, then a temporary index of the host tables (every record's suffix array and tables:
+    // N x (4 + 8 sigma) bytes a record with its RO table), the loop, and the index goes again
+    const uint32_t n_reads = fq.count;
+    sx_dev_scope B; // (it owns the reads' arrays: they are not released with sx_fastq_dev_free)
+    sx_fastq_dev reads = {};
+    reads.count = n_reads;
+    reads.name_bytes = fq.name_off[n_reads], reads.seq_bytes = fq.seq_off[n_reads], reads.qual_bytes = fq.qual_off[n_reads];
+    SX_TRY(upload(ctx, B, &reads.d_names, fq.names, (size_t)reads.name_bytes));
+    SX_TRY(upload(ctx, B, &reads.d_seqs, fq.seqs, (size_t)reads.seq_bytes));
+    SX_TRY(upload(ctx, B, &reads.d_quals, fq.quals, (size_t)reads.qual_bytes));
+    SX_TRY(upload(ctx, B, &reads.d_name_off, fq.name_off, (size_t)n_reads + 1));
+    SX_TRY(upload(ctx, B, &reads.d_seq_off, fq.seq_off, (size_t)n_reads + 1));
+    SX_TRY(upload(ctx, B, &reads.d_qual_off, fq.qual_off, (size_t)n_reads + 1));
+    sx_index *idx = nullptr;
+    SX_TRY(sx_index_from_tables(ctx, records, n_records, &idx));
+    const int rc = sx_map_reads_core(ctx, idx, reads, fq.seq_off, edits, flags, sink, user);
+    sx_index_destroy(idx);
+    return rc;
+}
+
+} // extern "C"

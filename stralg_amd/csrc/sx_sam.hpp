@@ -1,0 +1,35 @@
+// sx_sam.hpp -- what the read mapper's loop (sx_map.hip) uses of the SAM text (sx_sam.hip): the kernels' view of a batch of
+// hits, its layout and the emit of a window.
+#pragma once
+#include "sx_common.hpp"
+
+namespace sx {
+
+struct SamArgs {
+    const uint4 *hits; // sx_approx_hit as two 16-byte words
+    uint64_t n_hits;
+    const uint32_t *sa;
+    uint64_t sa_len;
+    const uint32_t *const *sa_list; // one suffix array per record rank (then sa is not used)
+    const uint64_t *sa_len_list;
+    const uint8_t *names, *seqs, *quals;
+    const uint32_t *name_off, *seq_off, *qual_off;
+    uint32_t n_reads;
+    const uint8_t *rnames;
+    const uint32_t *rname_off;
+    uint32_t n_records;
+    // an index with a sampled suffix array (the kernels' kLocated form): the positions of a run of hits, located before
+    // the layout; hit h's stand at positions[pos_off[h] - pos_base ..)
+    const uint32_t *positions;
+    const uint64_t *pos_off;
+    uint64_t pos_base;
+    const uint16_t *flags; // a FLAG per read (the kernels' kFlags form), or null: every line has FLAG 0
+};
+
+// d_byte_off[h] (n_hits + 1 entries) <- the first output byte of hit h's lines, the last entry and *total_out <- the
+// text's length
+int sam_layout(sx_ctx *ctx, const SamArgs &A, uint64_t *d_byte_off, uint64_t *total_out);
+// bytes [lo, hi) of the text to d_out (asynchronous: the caller syncs)
+int sam_emit(sx_ctx *ctx, const SamArgs &A, const uint64_t *d_byte_off, uint64_t lo, uint64_t hi, uint8_t *d_out);
+
+} // namespace sx
