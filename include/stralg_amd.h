@@ -163,6 +163,10 @@ enum {
     ,SX_FLAG_INDUCE_EARLY_S_OFF = 21 /* induced-sort passes over at most 8 buckets: 1 = the S pass scans every bucket's whole L
                                        region for the S-type predecessors (as before); 0 (default) = the L pass's large rounds
                                        place them while they hold the entries, the S pass scans what those rounds left */
+    ,SX_FLAG_SAM_ROOM_HITS = 22    /* read mapping, a test switch: > 0 = the largest room for the hits of a batch's searches, in
+                                       hits, in place of what the free memory gives, and the room a call starts with may be as
+                                       small as 1 hit (it is 2^16 at least otherwise); 0 (default) = by the free memory.  Tests
+                                       set small values so that the room grows and batches are halved (sx_map_last_stats) */
 };
 int sx_ctx_set_flag(sx_ctx *ctx, int flag, int value);
 
@@ -390,6 +394,19 @@ int sx_map_reads_stream_ex(sx_ctx *ctx, const sx_map_record *records, uint32_t n
 /* the limit of a mapping call on its reads and records: 0, or SX_E_ARG when reads x records (twice that with
  * SX_MAP_BOTH_STRANDS) does not stay below 2^32 or flags has unknown bits */
 int sx_map_reads_limit(uint64_t n_reads, uint64_t n_records, uint32_t flags);
+/* What the loop of the last mapping call on ctx did with its batches (zeroed when a call's loop starts; host counts only).
+ * A batch's searches answer SX_E_CAPACITY when their hits do not fit the room: the room grows, or the batch is halved,
+ * and the batch runs again (SX_FLAG_SAM_ROOM_HITS makes that happen on small inputs). */
+typedef struct sx_map_stats {
+    uint64_t batches;     /* batches whose text was emitted or that had no hits */
+    uint64_t retries;     /* capacity returns: room_grown + lone_grown + halved */
+    uint64_t room_grown;  /* the room grew for a batch of several groups (a group: a read, or both strands of a read) */
+    uint64_t lone_grown;  /* the room grew for one group alone, which gets whatever it needs */
+    uint64_t halved;      /* a batch was halved */
+    uint64_t room_first, room_final;   /* the room, in hits, at the start and at the end of the call */
+    uint64_t batch_first, batch_final; /* the reads of a batch at the start and at the end of the call */
+} sx_map_stats;
+int sx_map_last_stats(const sx_ctx *ctx, sx_map_stats *out);
 
 /* ---- a device-resident index: build from FASTA once, map many read sets ---------------- */
 /* sx_fastq_index on the device: the FASTQ image lies in device memory (len bytes), the six arrays of sx_fastq are

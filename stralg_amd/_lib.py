@@ -32,6 +32,15 @@ class BuildStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class MapStats(C.Structure):
+    """include/stralg_amd.h sx_map_stats: what the loop of the last mapping call did with its batches"""
+    _fields_ = [(k, C.c_uint64) for k in ("batches", "retries", "room_grown", "lone_grown", "halved", "room_first", "room_final",
+                                          "batch_first", "batch_final")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 # include/stralg_amd.h sx_approx_hit (32 bytes)
 APPROX_MAX_EDITS = 8
 APPROX_GAP_D = 0x8000
@@ -43,6 +52,7 @@ SX_SECTION_SAM = 3
 SX_FLAG_SAM_BATCH_READS, SX_FLAG_SAM_WINDOW_BYTES = 18, 19
 SX_FLAG_LOCATE_CHUNK_ROWS = 20
 SX_FLAG_INDUCE_EARLY_S_OFF = 21
+SX_FLAG_SAM_ROOM_HITS = 22
 SX_MAP_BOTH_STRANDS = 1
 SX_MAP_BEST_STRATUM = 8
 
@@ -193,6 +203,7 @@ def load(path=None):
         "sx_map_reads_stream_ex": (C.c_int, [vp, C.POINTER(MapRecord), C.c_uint32, u8p, C.c_size_t, C.c_int, C.c_uint32, SINK_FN,
                                              C.c_void_p]),
         "sx_map_reads_limit": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint32]),
+        "sx_map_last_stats": (C.c_int, [vp, C.POINTER(MapStats)]),
         "sx_fastq_strands_dev": (C.c_int, [vp, C.POINTER(FastqDev), C.POINTER(FastqDev), vp]),
         "sx_fastq_index_dev": (C.c_int, [vp, u8p, C.c_uint64, C.POINTER(FastqDev)]),
         "sx_fastq_dev_free": (None, [C.POINTER(FastqDev)]),
@@ -279,7 +290,7 @@ EXPORTS = ["sx_device_count", "sx_device_numa_node", "sx_ctx_create", "sx_ctx_de
            "sx_bwt_approx_search_packed_dev", "sx_index_is_packed",
            "sx_sa_sample_bytes", "sx_sa_sample_build_dev", "sx_sa_locate_rows_dev", "sx_index_record_samples", "sx_index_expand_sa",
            "sx_sam_layout_dev_ex", "sx_sam_emit_dev_ex", "sx_map_reads_stream_ex", "sx_map_reads_limit", "sx_fastq_strands_dev",
-           "sx_index_map_reads_ex", "sx_bwt_best_search_dev", "sx_patterns_select_dev",
+           "sx_index_map_reads_ex", "sx_bwt_best_search_dev", "sx_patterns_select_dev", "sx_map_last_stats",
            "sx_synth_dev", "sx_membw_probe", "sx_prim_sort_pairs_dev", "sx_prim_exclusive_sum_dev", "sx_prim_classify_dev"]
 
 

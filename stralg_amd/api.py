@@ -362,6 +362,19 @@ class Context:
         lines fit this many positions (0: the default, 2^28)"""
         self._check(self.lib.sx_ctx_set_flag(self.h, _lib.SX_FLAG_LOCATE_CHUNK_ROWS, int(rows)), "sx_ctx_set_flag")
 
+    def set_sam_room_hits(self, hits):
+        """read mapping, a test switch: the largest room for the hits of a batch's searches, in place of what the free memory
+        gives, and a first room as small as 1 hit (0: the default, by the free memory).  Small values make the room grow and
+        the batches halve on small inputs; map_stats() says what happened"""
+        self._check(self.lib.sx_ctx_set_flag(self.h, _lib.SX_FLAG_SAM_ROOM_HITS, int(hits)), "sx_ctx_set_flag")
+
+    def map_stats(self):
+        """sx_map_last_stats: what the loop of the last mapping call on this context did with its batches, as a dict (batches,
+        retries, room_grown, lone_grown, halved, room_first, room_final, batch_first, batch_final)"""
+        st = _lib.MapStats()
+        self._check(self.lib.sx_map_last_stats(self.h, C.byref(st)), "sx_map_last_stats")
+        return st.as_dict()
+
     # ---- the sampled suffix array (sx_locate.hpp) -----------------------------------------------
     def sa_sample_bytes(self, N, sa_sample):
         """sx_sa_sample_bytes: (bytes of the marks, bytes of the values) of a record of N rows sampled at this distance"""

@@ -96,6 +96,7 @@ struct sx_ctx {
     int64_t sam_batch_reads = 0;  // SX_FLAG_SAM_BATCH_READS; 0 = the default
     int64_t sam_window_bytes = 0; // SX_FLAG_SAM_WINDOW_BYTES; 0 = the default
     int64_t locate_chunk_rows = 0; // SX_FLAG_LOCATE_CHUNK_ROWS; 0 = the default
+    int64_t sam_room_hits = 0;    // SX_FLAG_SAM_ROOM_HITS; 0 = by the free memory
     int64_t sample_min = -1;  // SX_FLAG_SAMPLE_MIN; -1 = texts of 2^20 suffixes and more get the look at a sample
     int64_t recurse_min = -1; // SX_FLAG_RECURSE_MIN; -1 = the default length from which a reduced string of <= 255 names recurses
     sx_ctx *child = nullptr;  // the context a reduced string over a byte alphabet is sorted in (sx_build.hip), created on first use
@@ -110,6 +111,7 @@ struct sx_ctx {
     std::vector<sx_event_pair> ev_free;
     sx_kernel_stat kstat[SX_KC_COUNT];
     sx_build_stats stats;
+    sx_map_stats map_stats = {}; // the last mapping call's loop (sx_map.hip)
 };
 
 int sx_fail(sx_ctx *ctx, int code, const char *what, const char *file, int line);

@@ -398,6 +398,10 @@ int sx_ctx_set_flag(sx_ctx *ctx, int flag, int value)
         ctx->locate_chunk_rows = value > 0 ? value : 0;
         return 0;
     }
+    if (flag == SX_FLAG_SAM_ROOM_HITS) {
+        ctx->sam_room_hits = value > 0 ? value : 0;
+        return 0;
+    }
     if (flag == SX_FLAG_INDUCE_EARLY_S_OFF) {
         ctx->induce_early_s_off = value ? 1 : 0;
         return 0;
@@ -459,6 +463,13 @@ int sx_last_stats(const sx_ctx *ctx, sx_build_stats *out)
 {
     if (!ctx || !out) return SX_E_ARG;
     *out = ctx->stats;
+    return 0;
+}
+
+int sx_map_last_stats(const sx_ctx *ctx, sx_map_stats *out)
+{
+    if (!ctx || !out) return SX_E_ARG;
+    *out = ctx->map_stats;
     return 0;
 }
 

@@ -96,8 +96,8 @@ struct HitRoom {
         size_t free_b = 0, total_b = 0;
         const bool known = hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b;
         if (!known) (void)hipGetLastError();
-        cap_max = map_room_largest(known, free_b);
-        cap = map_room_first(batch_max, n_records, cap_max);
+        cap_max = map_room_largest(known, free_b, ctx->sam_room_hits);
+        cap = map_room_first(batch_max, n_records, cap_max, ctx->sam_room_hits);
         return own.take(ctx, &d_raw, (size_t)cap);
     }
     // the searches of `groups` groups of reads need room for `need` hits: it grows, or *halve, and the caller goes on with
@@ -306,6 +306,8 @@ static int map_reads_loop(sx_ctx *ctx, const sx_index *idx, const MapReads &R, i
     const sx_fastq_dev &fq = *R.fq;
     const uint32_t n_reads = fq.count, n_records = (uint32_t)idx->recs.size(), g = R.group ? R.group : 1;
     SX_CHECK(hipSetDevice(ctx->device));
+    sx_map_stats &T = ctx->map_stats; // (host counts: sx_map_last_stats)
+    T = {};
     MapBufs M;
     SX_TRY(M.own.take(ctx, &M.d_pat, (size_t)fq.seq_bytes));
     SX_TRY(sx_sync(ctx)); // (the callers' uploads from pageable memory are done)
@@ -325,6 +327,7 @@ static int map_reads_loop(sx_ctx *ctx, const sx_index *idx, const MapReads &R, i
     M.seg.resize(n_records + 1);
     HitRoom room;
     SX_TRY(room.init(ctx, batch_max, n_records));
+    T.room_first = T.room_final = room.cap, T.batch_first = T.batch_final = batch_max;
     sx_best_state S;
     if (R.group) SX_TRY(S.init(ctx, batch_max, fq.seq_bytes, n_records, edits, true));
     SamArgs A = {}; // the batch whose text is emitted: what is the same for every batch here
@@ -340,7 +343,9 @@ static int map_reads_loop(sx_ctx *ctx, const sx_index *idx, const MapReads &R, i
         if (rc == SX_E_CAPACITY) { // (a group alone gets whatever it needs; a batch of groups is halved to whole groups)
             bool halve;
             SX_TRY(room.grow_or_halve(ctx, hits, batch / g, &halve));
+            ++T.retries, ++(halve ? T.halved : batch / g == 1 ? T.lone_grown : T.room_grown);
             if (halve) batch = map_batch_halved(batch, g); // (it is not tried longer again)
+            T.room_final = room.cap, T.batch_final = batch;
             continue;
         }
         if (rc != 0) return rc;
@@ -351,6 +356,7 @@ static int map_reads_loop(sx_ctx *ctx, const sx_index *idx, const MapReads &R, i
             A.flags = R.d_flags ? R.d_flags + q0 : nullptr; // (the offsets are this batch's: so are the flags)
             SX_TRY(idx->sa_log2 ? emit_located(ctx, idx, A, M, E, sink, user) : emit_windows(ctx, A, M, E, sink, user));
         }
+        ++T.batches;
         q0 += batch;
     }
     return sx_sync(ctx);

@@ -1,6 +1,6 @@
 // sx_map_plan.hpp -- what the read mapper's loop (sx_map.hip) decides without looking at the device: how much room a batch's
 // hits get, when that room grows and when the batch is halved instead, how many reads a batch holds, the text's window,
-// the rows of a located run.  Plain arithmetic on the free memory, three of the context's switches and counts: host only,
+// the rows of a located run.  Plain arithmetic on the free memory, four of the context's switches and counts: host only,
 // no HIP, no context, so that tests/test_map_plan.py checks it without a GPU.
 #pragma once
 #include <stddef.h>
@@ -13,19 +13,21 @@
 namespace sx {
 
 // The largest room for the hits of a batch's searches: 2^27 hits or what a quarter of the free memory holds (72 bytes a hit:
-// the searches' array, the merged one, the byte offsets); 2^26 where the free memory is unknown or given as 0
-static inline uint64_t map_room_largest(bool free_known, uint64_t free_bytes)
+// the searches' array, the merged one, the byte offsets); 2^26 where the free memory is unknown or given as 0.
+// room_flag: SX_FLAG_SAM_ROOM_HITS, a test switch; > 0: that many hits, whatever the memory
+static inline uint64_t map_room_largest(bool free_known, uint64_t free_bytes, int64_t room_flag = 0)
 {
+    if (room_flag > 0) return (uint64_t)room_flag;
     uint64_t largest = 1ull << 26;
     if (free_known && free_bytes) largest = free_bytes / 4 / 72 < (1ull << 27) ? free_bytes / 4 / 72 : 1ull << 27;
     return largest < (1u << 16) ? 1u << 16 : largest;
 }
 
-// the room to start with: a guess of four hits a (read, record)
-static inline uint64_t map_room_first(uint32_t batch_max, uint32_t n_records, uint64_t largest)
+// the room to start with: a guess of four hits a (read, record), 2^16 hits at least (with the test switch set: 1)
+static inline uint64_t map_room_first(uint32_t batch_max, uint32_t n_records, uint64_t largest, int64_t room_flag = 0)
 {
-    const uint64_t guess = (uint64_t)batch_max * n_records * 4;
-    return guess < (1u << 16) ? 1u << 16 : guess > largest ? largest : guess;
+    const uint64_t guess = (uint64_t)batch_max * n_records * 4, least = room_flag > 0 ? 1u : 1u << 16;
+    return guess < least ? least : guess > largest ? largest : guess;
 }
 
 // A batch of `groups` groups needs room for `need` hits and has `cap`: the room grows where that is allowed (one group alone

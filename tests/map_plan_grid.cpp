@@ -24,11 +24,51 @@ static void step(uint64_t &cap, uint64_t largest, uint64_t need, uint32_t groups
     cap = s.cap;
 }
 
-static void next_row(uint64_t cap, uint64_t largest, uint64_t need, uint32_t groups)
+static void next_row(uint64_t cap, uint64_t largest, uint64_t need, uint32_t groups, const char *kind = "next")
 {
     const map_room_step s = map_room_next(cap, largest, need, groups);
-    printf("next cap=%" PRIu64 " largest=%" PRIu64 " need=%" PRIu64 " groups=%u : halve=%d cap=%" PRIu64 "\n", cap, largest, need, groups,
+    printf("%s cap=%" PRIu64 " largest=%" PRIu64 " need=%" PRIu64 " groups=%u : halve=%d cap=%" PRIu64 "\n", kind, cap, largest, need, groups,
            (int)s.halve, s.cap);
+}
+
+// The rows of the room switch (SX_FLAG_SAM_ROOM_HITS), behind everything else: the lines above are what they were without it
+static void room_switch_rows(const mem_kind *mems, const uint32_t *records, const uint32_t *reads, const uint32_t *groups,
+                             const int64_t *batch_flags)
+{
+    const int64_t room_flags[6] = {1, 4, 100, 400, (int64_t)1 << 20, (int64_t)1 << 40};
+    // the largest room is the switch, whatever the memory
+    for (int64_t s : room_flags) {
+        printf("switch_largest switch=%" PRId64 " :", s);
+        for (int m = 0; m < 5; ++m) printf(" free=%s->%" PRIu64, mems[m].name, map_room_largest(mems[m].known, mems[m].bytes, s));
+        printf("\n");
+    }
+    // the room to start with: a line a (switch, memory, records), reads x group x flag in the order of the lines above
+    for (int64_t s : room_flags)
+        for (int m = 0; m < 5; ++m)
+            for (int r = 0; r < 3; ++r) {
+                const uint64_t largest = map_room_largest(mems[m].known, mems[m].bytes, s);
+                printf("switch_first switch=%" PRId64 " free=%s n_records=%u :", s, mems[m].name, records[r]);
+                for (int n = 0; n < 4; ++n)
+                    for (int g = 0; g < 3; ++g)
+                        for (int f = 0; f < 4; ++f)
+                            printf(" %" PRIu64, map_room_first(map_batch_max(batch_flags[f], groups[g], reads[n]), records[r], largest, s));
+                printf("\n");
+            }
+    // A room's chain from those rooms: a need below twice the room, one above it, one above the largest for several groups
+    // (halve) and for one (it gets what it needs: the room is above the largest from here on), several groups where the need fits
+    for (int64_t s : room_flags)
+        for (int r = 0; r < 3; ++r)
+            for (int64_t f : {(int64_t)0, (int64_t)8}) {
+                const uint64_t largest = map_room_largest(true, 1ull << 30, s);
+                uint64_t cap = map_room_first(map_batch_max(f, 0, 240), records[r], largest, s);
+                printf("switch_chain switch=%" PRId64 " n_records=%u flag=%" PRId64 " largest=%" PRIu64 " cap=%" PRIu64 " :", s, records[r], f, largest, cap);
+                step(cap, largest, cap + cap / 2, 4);
+                step(cap, largest, 3 * cap, 4);
+                step(cap, largest, largest + 1000, 3);
+                step(cap, largest, largest + 1000, 1);
+                step(cap, largest, largest, 2);
+                printf("\n");
+            }
 }
 
 int main()
@@ -97,5 +137,19 @@ int main()
     next_row(1ull << 26, L, 120000000, 1);
     next_row(1ull << 26, L, 140000000, 1);
     next_row(1ull << 26, L, 140000000, 2);
+
+    room_switch_rows(mems, records, reads, groups, batch_flags);
+    // ... and its rows that the test asserts by value: batches of 8 and of 240 reads on two records
+    for (int64_t sw : {(int64_t)1, (int64_t)100, (int64_t)400, (int64_t)1 << 20})
+        for (uint32_t batch_max : {8u, 240u})
+            printf("room_first switch=%" PRId64 " batch_max=%u n_records=2 : %" PRIu64 "\n", sw, batch_max,
+                   map_room_first(batch_max, 2, map_room_largest(true, 80ull << 30, sw), sw));
+    next_row(1, 1, 5, 2, "room_next");
+    next_row(1, 1, 5, 1, "room_next");
+    next_row(6, 1, 7, 1, "room_next");
+    next_row(64, 100, 90, 4, "room_next");
+    next_row(100, 100, 332, 2, "room_next");
+    next_row(100, 100, 332, 1, "room_next");
+    next_row(64, 1ull << 20, 200, 4, "room_next");
     return 0;
 }

@@ -70,6 +70,26 @@ def test_struct_layouts_match_reference():
     assert [int(x) for x in out] == [40, 388, 56, 16, 260, 48]
 
 
+def test_map_stats_and_room_switch_match_the_header(tmp_path):
+    """sx_map_stats as the binding declares it (size, every field's offset) and the mapper's switches' numbers, against a C
+    program compiled with include/stralg_amd.h"""
+    from stralg_amd import _lib
+    fields = [k for k, _ in _lib.MapStats._fields_]
+    src = '#include "stralg_amd.h"\n#include <stdio.h>\n#include <stddef.h>\nint main(void) {\n'
+    src += '    printf("%zu", sizeof(sx_map_stats));\n'
+    src += "".join('    printf(" %%zu", offsetof(sx_map_stats, %s));\n' % k for k in fields)
+    src += '    printf(" %d %d %d %d\\n", SX_FLAG_SAM_BATCH_READS, SX_FLAG_SAM_WINDOW_BYTES, SX_FLAG_LOCATE_CHUNK_ROWS, SX_FLAG_SAM_ROOM_HITS);\n'
+    src += "    return 0;\n}\n"
+    (tmp_path / "t.c").write_text(src)
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(tmp_path / "t.c"), "-o", str(tmp_path / "t")])
+    out = [int(x) for x in subprocess.check_output([str(tmp_path / "t")]).split()]
+    assert fields == ["batches", "retries", "room_grown", "lone_grown", "halved", "room_first", "room_final", "batch_first", "batch_final"]
+    assert out[0] == C.sizeof(_lib.MapStats) == 72
+    assert out[1:10] == [getattr(_lib.MapStats, k).offset for k in fields]
+    assert out[10:] == [_lib.SX_FLAG_SAM_BATCH_READS, _lib.SX_FLAG_SAM_WINDOW_BYTES, _lib.SX_FLAG_LOCATE_CHUNK_ROWS, _lib.SX_FLAG_SAM_ROOM_HITS]
+    assert _lib.SX_FLAG_SAM_ROOM_HITS == 22
+
+
 def test_no_cpu_fallback_without_gpu():
     import torch
     if torch.cuda.is_available():

@@ -1,14 +1,19 @@
 """The read mapper's batch plan (stralg_amd/csrc/sx_map_plan.hpp): how much room the hits of a batch get, when the room grows
 and when the batch is halved instead, the reads of a batch, the text's window, the rows of a located run.  It is arithmetic
-on the free memory, three switches and counts, so tests/map_plan_grid.cpp computes it over a grid without a GPU and without
+on the free memory, four switches and counts, so tests/map_plan_grid.cpp computes it over a grid without a GPU and without
 the library; its output is compared with tests/golden/map_plans.txt, recorded from the expressions as they stood inside the
-mapper's loop before the plan was cut out of it.  No test reaches the halving branch end to end: it takes more hits than a
-quarter of the free memory holds.
+mapper's loop before the plan was cut out of it.  The loop's retries themselves -- the room growing, the batch halved, the
+batch run again -- are reached end to end by tests/test_room_cpu.py and tests/test_gpu_room.py through the room switch
+(SX_FLAG_SAM_ROOM_HITS).
 
 The grid: free memory unknown, 0, 2^20, 2^30, 80 x 2^30 bytes; 1, 2, 200 records; 1, 7, 2^20, 2^21 + 1 reads; groups of 0, 1, 2;
 the batch switch at 0, 1, 7, 8; the window switch at 0, 1, 4096, 2^40.  Every room of (memory, records, switch 0 or 7) takes a
 chain of needs: below twice the room, above it, between 4/5 of the largest room and the largest, above the largest with
-several groups and with one, and at the largest with several."""
+several groups and with one, and at the largest with several.
+
+The room switch's rows stand behind those (every line in front of them is what it was before the switch: with the switch at 0
+no expression changed): the switch at 1, 4, 100, 400, 2^20, 2^40 over the same memory, records, reads, groups and batch
+switches for the largest room and the first one, and chains from those rooms for batches of 240 and of 8 reads."""
 import os
 import subprocess
 
@@ -63,6 +68,33 @@ def test_rows_worked_out_by_hand(plans):
     assert nxt[1 << 26, 120000000, 1] == (False, 1 << 27)
     assert nxt[1 << 26, 140000000, 1] == (False, 175000000)
     assert nxt[1 << 26, 140000000, 2][0]
+
+    # the room switch: the largest room is the switch whatever the memory, and the first room may be as small as one hit
+    for case, v in _rows(plans, "switch_largest"):
+        assert {kv.split("->")[1] for kv in v.split()} == {case.split("=")[1]}
+    first = {}
+    for case, v in _rows(plans, "room_first"):
+        c = dict(kv.split("=") for kv in case.split())
+        first[int(c["switch"]), int(c["batch_max"])] = int(v)
+    assert first[1, 8] == 1 and first[1, 240] == 1
+    assert first[100, 8] == 64 and first[100, 240] == 100  # (the guess: 4 hits x 8 reads x 2 records; 1920 is cut to the switch)
+    assert first[400, 8] == 64 and first[400, 240] == 400
+    assert first[1 << 20, 8] == 64 and first[1 << 20, 240] == 1920
+    room = {}
+    for case, v in _rows(plans, "room_next"):
+        c, r = dict(kv.split("=") for kv in case.split()), dict(kv.split("=") for kv in v.split())
+        room[int(c["cap"]), int(c["largest"]), int(c["need"]), int(c["groups"])] = (r["halve"] == "1", int(r["cap"]))
+    assert room[1, 1, 5, 2] == (True, 1)
+    assert room[1, 1, 5, 1] == (False, 6)  # (one group alone: 5 + 5 / 4, above the largest)
+    assert room[6, 1, 7, 1] == (False, 12)  # (twice the room is more than 7 + 7 / 4)
+    assert room[64, 100, 90, 4] == (False, 100)  # (twice 64 is cut to the largest: the need fits it)
+    assert room[100, 100, 332, 2] == (True, 100)
+    assert room[100, 100, 332, 1] == (False, 415)
+    assert room[64, 1 << 20, 200, 4] == (False, 250)
+    chains = dict(_rows(plans, "switch_chain"))
+    assert chains["switch=100 n_records=2 flag=8 largest=100 cap=64"] == "96/4->100 300/4->halve 1100/3->halve 1100/1->1375 100/2->100"
+    assert chains["switch=1 n_records=2 flag=0 largest=1 cap=1"] == "1/4->1 3/4->halve 1001/3->halve 1001/1->1251 1/2->1"
+    assert len(_rows(plans, "switch_first")) == 6 * 5 * 3 and len(chains) == 6 * 3 * 2
 
     halved = {case: dict(kv.split("->") for kv in v.split()) for case, v in _rows(plans, "halved")}
     assert halved["g=1"]["7"] == "4"
