@@ -167,8 +167,37 @@ enum {
                                        hits, in place of what the free memory gives, and the room a call starts with may be as
                                        small as 1 hit (it is 2^16 at least otherwise); 0 (default) = by the free memory.  Tests
                                        set small values so that the room grows and batches are halved (sx_map_last_stats) */
+    ,SX_FLAG_CHAIN_EPOCH = 23      /* a test switch: the look-back epoch of the context, and of its child context if it has one,
+                                       becomes this value (0 .. 2^24 - 1; the next chained launch takes the one after it, and the
+                                       status words are retired where the 24 bits wrap) */
+    ,SX_FLAG_READBACK_SEQ = 24     /* a test switch: the value, taken as a 32-bit pattern, becomes the sequence number of the last
+                                       read-back, in the context and (after a wait for the stream) in the word of the pinned page
+                                       that holds it, so that the page still holds the last sequence number */
 };
 int sx_ctx_set_flag(sx_ctx *ctx, int flag, int value);
+
+/* Test hooks: what a context carries from one call to the next ("What a context carries from call to call").
+ *
+ * sx_ctx_scribble waits for the stream and then overwrites everything a later call must not rely on: the whole capacity
+ * of the workspace slabs 0 .. 5 and the pinned staging buffers (where they exist) with `byte`, words 0 .. 1023 of the
+ * read-back page likewise (the sequence word behind them is left alone).  The slab of look-back status words is filled
+ * within its invariant, which is stronger than arbitrary bytes: every header word becomes non-zero, every status word a
+ * ready inclusive prefix of the last launch's epoch with the value 0xEEEEEEEE -- the worst a past launch can have left, and
+ * never an epoch above the context's.  The child context, if there is one, gets the same.  `byte`: 0 .. 255.
+ *
+ * sx_ctx_counters reads the counters back; chain_slab_max_epoch is the largest epoch field among the status words, by a
+ * copy of the slab to the host (slow). */
+typedef struct sx_ctx_counts {
+    uint32_t chain_epoch;          /* the epoch of the last chained launch (24 bits) */
+    uint32_t readback_seq;         /* the sequence number of the last read-back */
+    uint32_t chain_slab_max_epoch; /* the largest epoch field in the status words (0: no slab, or nothing but zeros) */
+    uint32_t has_child;            /* whether a child context exists; its counters follow, zeros where there is none */
+    uint64_t slab_bytes[7];        /* the capacity of every workspace slab */
+    uint32_t child_chain_epoch, child_readback_seq, child_chain_slab_max_epoch, child_reserved;
+    uint64_t child_slab_bytes[7];
+} sx_ctx_counts;
+int sx_ctx_scribble(sx_ctx *ctx, int byte);
+int sx_ctx_counters(const sx_ctx *ctx, sx_ctx_counts *out);
 
 /* ---- suffix array -------------------------------------------------------- */
 /* Host buffers.  text[0..n) holds symbols in [1, alphabet_size), alphabet_size

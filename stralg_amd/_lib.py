@@ -41,6 +41,21 @@ class MapStats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class CtxCounts(C.Structure):
+    """include/stralg_amd.h sx_ctx_counts: what a context carries from call to call (test hook)"""
+    _fields_ = [("chain_epoch", C.c_uint32), ("readback_seq", C.c_uint32), ("chain_slab_max_epoch", C.c_uint32),
+                ("has_child", C.c_uint32), ("slab_bytes", C.c_uint64 * 7),
+                ("child_chain_epoch", C.c_uint32), ("child_readback_seq", C.c_uint32), ("child_chain_slab_max_epoch", C.c_uint32),
+                ("child_reserved", C.c_uint32), ("child_slab_bytes", C.c_uint64 * 7)]
+
+    def as_dict(self):
+        own = dict(chain_epoch=int(self.chain_epoch), readback_seq=int(self.readback_seq),
+                   chain_slab_max_epoch=int(self.chain_slab_max_epoch), slab_bytes=[int(b) for b in self.slab_bytes])
+        child = dict(chain_epoch=int(self.child_chain_epoch), readback_seq=int(self.child_readback_seq),
+                     chain_slab_max_epoch=int(self.child_chain_slab_max_epoch), slab_bytes=[int(b) for b in self.child_slab_bytes])
+        return dict(own, has_child=bool(self.has_child), child=child)
+
+
 # include/stralg_amd.h sx_approx_hit (32 bytes)
 APPROX_MAX_EDITS = 8
 APPROX_GAP_D = 0x8000
@@ -53,6 +68,10 @@ SX_FLAG_SAM_BATCH_READS, SX_FLAG_SAM_WINDOW_BYTES = 18, 19
 SX_FLAG_LOCATE_CHUNK_ROWS = 20
 SX_FLAG_INDUCE_EARLY_S_OFF = 21
 SX_FLAG_SAM_ROOM_HITS = 22
+SX_FLAG_CHAIN_EPOCH, SX_FLAG_READBACK_SEQ = 23, 24  # (test switches, as SX_FLAG_SAM_ROOM_HITS)
+N_SLABS = 7
+SLAB_CHAIN = 6
+CHAIN_EPOCH_LIMIT = 1 << 24  # the look-back epoch has 24 bits: the launch after 2^24 - 1 takes 1 again
 SX_MAP_BOTH_STRANDS = 1
 SX_MAP_BEST_STRATUM = 8
 
@@ -173,6 +192,8 @@ def load(path=None):
         "sx_last_error": (C.c_char_p, [vp]),
         "sx_ctx_trim": (None, [vp]),
         "sx_ctx_set_flag": (C.c_int, [vp, C.c_int, C.c_int]),
+        "sx_ctx_scribble": (C.c_int, [vp, C.c_int]),
+        "sx_ctx_counters": (C.c_int, [vp, C.POINTER(CtxCounts)]),
         "sx_sa_build": (C.c_int, [vp, u8p, C.c_uint64, C.c_uint32, u32p]),
         "sx_sa_build_dev": (C.c_int, [vp, u8p, C.c_uint64, C.c_uint32, u32p]),
         "sx_sa_bwt_build_dev": (C.c_int, [vp, u8p, C.c_uint64, C.c_uint32, u32p, u8p]),
@@ -276,6 +297,7 @@ def load(path=None):
 
 
 EXPORTS = ["sx_device_count", "sx_device_numa_node", "sx_ctx_create", "sx_ctx_destroy", "sx_ctx_live_count", "sx_last_error", "sx_ctx_trim", "sx_ctx_set_flag",
+           "sx_ctx_scribble", "sx_ctx_counters",
            "sx_sa_build", "sx_sa_build_dev", "sx_sa_bwt_build_dev", "sx_bwt_tables", "sx_bwt_tables_dev",
            "sx_bwt_tables_from_bwt_dev", "sx_build_tables", "sx_sa_inverse_dev", "sx_sa_lcp_dev", "sx_sa_inverse_lcp",
            "sx_bwt_exact_search_dev", "sx_bwt_approx_search_dev", "sx_bwt_approx_search", "sx_build_tables_stream", "sx_sam_layout_dev", "sx_sam_emit_dev", "sx_fastq_index", "sx_fastq_free", "sx_map_reads_stream",

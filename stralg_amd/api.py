@@ -586,6 +586,28 @@ class Context:
     def trim(self):
         self.lib.sx_ctx_trim(self.h)
 
+    # ---- test hooks: what the context carries from call to call ----------------------------
+    def scribble(self, byte):
+        """sx_ctx_scribble: every workspace slab, the staging buffers and the read-back page filled with `byte`, the look-back
+        status words with ready prefixes of the last epoch and a wrong value; the child context likewise"""
+        self._check(self.lib.sx_ctx_scribble(self.h, int(byte)), "sx_ctx_scribble")
+
+    def set_chain_epoch(self, epoch):
+        """SX_FLAG_CHAIN_EPOCH: the look-back epoch of the context and of its child (the next chained launch takes the next)"""
+        self._check(self.lib.sx_ctx_set_flag(self.h, _lib.SX_FLAG_CHAIN_EPOCH, int(epoch)), "sx_ctx_set_flag")
+
+    def set_readback_seq(self, seq):
+        """SX_FLAG_READBACK_SEQ: the sequence number of the last read-back, as a 32-bit pattern, in the context and on its page"""
+        seq = int(seq) & 0xFFFFFFFF
+        self._check(self.lib.sx_ctx_set_flag(self.h, _lib.SX_FLAG_READBACK_SEQ, seq - (1 << 32) if seq >> 31 else seq), "sx_ctx_set_flag")
+
+    def counters(self):
+        """sx_ctx_counters: dict(chain_epoch, readback_seq, chain_slab_max_epoch, slab_bytes[7], has_child, child=dict of the
+        same four); chain_slab_max_epoch copies the status words to the host: slow"""
+        st = _lib.CtxCounts()
+        self._check(self.lib.sx_ctx_counters(self.h, C.byref(st)), "sx_ctx_counters")
+        return st.as_dict()
+
     def bind_to_numa_node(self):
         """pin the calling thread (and the threads it starts later) to the CPUs next to this context's GPU
         (stralg_amd_bind_thread_to_device); returns the NUMA node, or -1 when the box does not tell"""

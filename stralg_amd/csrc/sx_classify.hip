@@ -48,8 +48,13 @@ __device__ __forceinline__ void decided_masks(const uint32_t (&c)[17], uint64_t 
     if (p0 + 16 <= n) { // everywhere but at the very end of the text: no position needs the 64-bit bound checks
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            dmask |= (c[i] != c[i + 1] ? 1u : 0u) << i;
-            vmask |= (c[i] < c[i + 1] ? 1u : 0u) << i;
+            // (the comparisons in words of their own: for `(c[i] != c[i + 1] ? 1u : 0u) << i` g++ 11 with -fsanitize=shift,bounds
+            //  -- the CPU harness under UndefinedBehaviorSanitizer -- warns that it reads an index before it is set, and the
+            //  masks it computes are wrong; the device code is the same either way)
+            const uint32_t differs = c[i] != c[i + 1] ? 1u : 0u;
+            dmask |= differs << i;
+            const uint32_t ascends = c[i] < c[i + 1] ? 1u : 0u;
+            vmask |= ascends << i;
         }
         return;
     }

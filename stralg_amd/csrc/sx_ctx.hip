@@ -2,6 +2,7 @@
 #include <atomic>
 #include <chrono>
 #include "sx_common.hpp"
+#include "sx_device.hpp"
 
 #include <new>
 
@@ -418,7 +419,84 @@ int sx_ctx_set_flag(sx_ctx *ctx, int flag, int value)
         ctx->chain_max_override = value < 0 ? -1 : (int64_t)value; // negative: back to the default
         return 0;
     }
+    if (flag == SX_FLAG_CHAIN_EPOCH) {
+        if (value < 0 || value >= (1 << 24)) return SX_E_ARG;
+        ctx->chain_epoch = (uint32_t)value;
+        if (ctx->child) ctx->child->chain_epoch = (uint32_t)value;
+        return 0;
+    }
+    if (flag == SX_FLAG_READBACK_SEQ) {
+        SX_CHECK(hipSetDevice(ctx->device));
+        SX_CHECK(hipStreamSynchronize(ctx->stream)); // (no read-back kernel is left to store an older number behind this one)
+        ctx->readback_seq = (uint32_t)value;
+        ctx->h_pin[1024] = (uint32_t)value;
+        return 0;
+    }
     return SX_E_ARG;
+}
+
+// ---- test hooks: what a context carries from call to call (include/stralg_amd.h) ----
+// chain_pack (sx_device.hpp) on the host: [63:40] epoch, [39:38] state, [31:0] value
+static uint64_t chain_word(uint32_t epoch, uint32_t state, uint32_t value)
+{
+    return ((uint64_t)epoch << 40) | ((uint64_t)state << 38) | (uint64_t)value;
+}
+
+int sx_ctx_scribble(sx_ctx *ctx, int byte)
+{
+    if (!ctx || byte < 0 || byte > 255) return SX_E_ARG;
+    SX_CHECK(hipSetDevice(ctx->device));
+    SX_CHECK(hipStreamSynchronize(ctx->stream));
+    for (int i = 0; i < SX_NSLABS; ++i)
+        if (i != SX_SLAB_CHAIN && ctx->slab[i].p) SX_CHECK(hipMemsetAsync(ctx->slab[i].p, byte, ctx->slab[i].cap, ctx->stream));
+    if (ctx->slab[SX_SLAB_CHAIN].p) {
+        // the worst a past launch can have left: every tile's inclusive prefix, ready, of the last epoch, with a wrong value;
+        // the header (word 0: the time-out flag of a launch) set
+        const size_t words = ctx->slab[SX_SLAB_CHAIN].cap / sizeof(uint64_t);
+        std::vector<uint64_t> fill(words, chain_word(ctx->chain_epoch, 2u, 0xEEEEEEEEu));
+        for (size_t w = 0; w < sx::kChainHeader && w < words; ++w) fill[w] = 0xEEEEEEEEEEEEEEEEull;
+        SX_CHECK(hipMemcpy(ctx->slab[SX_SLAB_CHAIN].p, fill.data(), words * sizeof(uint64_t), hipMemcpyHostToDevice));
+    }
+    SX_CHECK(hipStreamSynchronize(ctx->stream));
+    for (char *b : ctx->h_stage)
+        if (b) memset(b, byte, sx_stage_bytes);
+    memset(ctx->h_pin, byte, 1024 * sizeof(uint32_t)); // (word 1024 stays: the sequence number of the last read-back)
+    return ctx->child ? sx_ctx_scribble(ctx->child, byte) : 0;
+}
+
+// the largest epoch field among the status words of ctx's look-back slab
+static int chain_slab_max_epoch(sx_ctx *ctx, uint32_t *out)
+{
+    *out = 0;
+    const size_t words = ctx->slab[SX_SLAB_CHAIN].cap / sizeof(uint64_t);
+    if (!ctx->slab[SX_SLAB_CHAIN].p || words <= sx::kChainHeader) return 0;
+    SX_CHECK(hipSetDevice(ctx->device));
+    SX_CHECK(hipStreamSynchronize(ctx->stream));
+    std::vector<uint64_t> host(words);
+    SX_CHECK(hipMemcpy(host.data(), ctx->slab[SX_SLAB_CHAIN].p, words * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    for (size_t w = sx::kChainHeader; w < words; ++w) {
+        const uint32_t e = (uint32_t)(host[w] >> 40);
+        if (e > *out) *out = e;
+    }
+    return 0;
+}
+
+int sx_ctx_counters(const sx_ctx *ctx, sx_ctx_counts *out)
+{
+    if (!ctx || !out) return SX_E_ARG;
+    memset(out, 0, sizeof *out);
+    out->chain_epoch = ctx->chain_epoch;
+    out->readback_seq = ctx->readback_seq;
+    for (int i = 0; i < SX_NSLABS; ++i) out->slab_bytes[i] = ctx->slab[i].cap;
+    SX_TRY(chain_slab_max_epoch(const_cast<sx_ctx *>(ctx), &out->chain_slab_max_epoch)); // (it may leave an error text)
+    if (const sx_ctx *c = ctx->child) {
+        out->has_child = 1;
+        out->child_chain_epoch = c->chain_epoch;
+        out->child_readback_seq = c->readback_seq;
+        for (int i = 0; i < SX_NSLABS; ++i) out->child_slab_bytes[i] = c->slab[i].cap;
+        SX_TRY(chain_slab_max_epoch(ctx->child, &out->child_chain_slab_max_epoch));
+    }
+    return 0;
 }
 
 const char *sx_last_error(const sx_ctx *ctx) { return ctx ? ctx->err : "no context"; }

@@ -90,6 +90,27 @@ def test_map_stats_and_room_switch_match_the_header(tmp_path):
     assert _lib.SX_FLAG_SAM_ROOM_HITS == 22
 
 
+def test_ctx_counts_and_reuse_switches_match_the_header(tmp_path):
+    """sx_ctx_counts as the binding declares it (size, every field's offset) and the two test switches' numbers, against a C
+    program compiled with include/stralg_amd.h"""
+    from stralg_amd import _lib
+    fields = [k for k, _ in _lib.CtxCounts._fields_]
+    src = '#include "stralg_amd.h"\n#include <stdio.h>\n#include <stddef.h>\nint main(void) {\n'
+    src += '    printf("%zu", sizeof(sx_ctx_counts));\n'
+    src += "".join('    printf(" %%zu", offsetof(sx_ctx_counts, %s));\n' % k for k in fields)
+    src += '    printf(" %d %d\\n", SX_FLAG_CHAIN_EPOCH, SX_FLAG_READBACK_SEQ);\n'
+    src += "    return 0;\n}\n"
+    (tmp_path / "t.c").write_text(src)
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(tmp_path / "t.c"), "-o", str(tmp_path / "t")])
+    out = [int(x) for x in subprocess.check_output([str(tmp_path / "t")]).split()]
+    assert fields == ["chain_epoch", "readback_seq", "chain_slab_max_epoch", "has_child", "slab_bytes", "child_chain_epoch",
+                      "child_readback_seq", "child_chain_slab_max_epoch", "child_reserved", "child_slab_bytes"]
+    assert out[0] == C.sizeof(_lib.CtxCounts) == 144
+    assert out[1:11] == [getattr(_lib.CtxCounts, k).offset for k in fields]
+    assert out[11:] == [_lib.SX_FLAG_CHAIN_EPOCH, _lib.SX_FLAG_READBACK_SEQ] == [23, 24]
+    assert _lib.CtxCounts.slab_bytes.size == _lib.CtxCounts.child_slab_bytes.size == 8 * _lib.N_SLABS
+
+
 def test_no_cpu_fallback_without_gpu():
     import torch
     if torch.cuda.is_available():
