@@ -279,12 +279,28 @@ int sx_bwt_approx_search_dev(sx_ctx *ctx, const uint32_t *d_c_table, const uint3
                              const uint32_t *d_ro_table, uint64_t N, uint32_t sigma, const uint8_t *d_patterns,
                              const uint32_t *d_offsets, uint32_t count, int max_edits, uint64_t *d_hit_offsets,
                              sx_approx_hit *d_hits, uint64_t hit_capacity, uint64_t *total_hits_out);
+/* Search flags.  SX_SEARCH_NO_INDELS: mismatches only.  The hits of pattern q are those of the call
+ * without the flag at the same max_edits whose n_gaps is 0, in the same order: the intervals of the strings at Hamming
+ * distance <= max_edits from the pattern that occur in the text, each once, depth first from the last symbol with the
+ * children M over a = 1 .. sigma-1.  Every hit has match_length = the pattern's length, n_gaps = 0 and gap[] all zero.  The
+ * D table is the same one (NULL RO: zeros) and the result does not depend on it.  Limits, the count-only form,
+ * SX_E_CAPACITY, the patterns without hits and the identity from run to run are those of the plain call.  search_flags
+ * == 0: the plain call, launch for launch; unknown bits: SX_E_ARG.  The _ex forms below and of the compact, packed,
+ * best-stratum and host-buffer calls take the flags as their last argument; the calls without it pass 0. */
+enum { SX_SEARCH_NO_INDELS = 1 };
+int sx_bwt_approx_search_dev_ex(sx_ctx *ctx, const uint32_t *d_c_table, const uint32_t *d_o_table, const uint32_t *d_ro_table,
+                                uint64_t N, uint32_t sigma, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count,
+                                int max_edits, uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t hit_capacity,
+                                uint64_t *total_hits_out, uint32_t search_flags);
 /* The same over host buffers: the tables and patterns are uploaded (the whole O / RO tables, (N+1) x sigma words each,
  * once per call), hit_offsets (host, count + 1) is filled, *hits_out receives a malloc'd array of *total_hits_out hits
  * (NULL when there are none) that the caller releases with free(). */
 int sx_bwt_approx_search(sx_ctx *ctx, const uint32_t *c_table, const uint32_t *o_table, const uint32_t *ro_table,
                          uint64_t N, uint32_t sigma, const uint8_t *patterns, const uint32_t *offsets, uint32_t count,
                          int max_edits, uint64_t *hit_offsets, sx_approx_hit **hits_out, uint64_t *total_hits_out);
+int sx_bwt_approx_search_ex(sx_ctx *ctx, const uint32_t *c_table, const uint32_t *o_table, const uint32_t *ro_table, uint64_t N,
+                            uint32_t sigma, const uint8_t *patterns, const uint32_t *offsets, uint32_t count, int max_edits,
+                            uint64_t *hit_offsets, sx_approx_hit **hits_out, uint64_t *total_hits_out, uint32_t search_flags);
 /* Best stratum: sx_bwt_approx_search_dev by iterative deepening.  d_stratum[q] (count bytes) <-
  * e*(q), the smallest d in 0 .. max_edits at which pattern q has a hit, or 0xFF where it has none; the hits of pattern q
  * are exactly, and in the order of, those of sx_bwt_approx_search_dev at max_edits = d_stratum[q] (query = q), so every
@@ -295,6 +311,12 @@ int sx_bwt_best_search_dev(sx_ctx *ctx, const uint32_t *d_c_table, const uint32_
                            uint64_t N, uint32_t sigma, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count,
                            int max_edits, uint8_t *d_stratum, uint64_t *d_hit_offsets, sx_approx_hit *d_hits,
                            uint64_t hit_capacity, uint64_t *total_hits_out);
+/* the same over the search with search_flags: with SX_SEARCH_NO_INDELS e*(q) is the smallest Hamming distance in 0 ..
+ * max_edits at which pattern q occurs, and its hits are those of sx_bwt_approx_search_dev_ex with the flag at e*(q) */
+int sx_bwt_best_search_dev_ex(sx_ctx *ctx, const uint32_t *d_c_table, const uint32_t *d_o_table, const uint32_t *d_ro_table,
+                              uint64_t N, uint32_t sigma, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count,
+                              int max_edits, uint8_t *d_stratum, uint64_t *d_hit_offsets, sx_approx_hit *d_hits,
+                              uint64_t hit_capacity, uint64_t *total_hits_out, uint32_t search_flags);
 /* The patterns q with d_keep[q] != 0 (count bytes), in order and flat: kept pattern j has its bytes at
  * d_bytes_out[d_off_out[j] .. d_off_out[j+1]) with d_off_out[0] = 0, and d_ids_out[j] is its number in the input.
  * d_off (count + 1 entries) need not start at 0; d_bytes is readable up to d_off[count].  d_bytes_out holds
@@ -416,8 +438,13 @@ int sx_map_reads_stream(sx_ctx *ctx, const sx_map_record *records, uint32_t n_re
  * that call prints for q with edits = e*(q): the reference mapper's stdout for that read at -d e*(q).  A read without
  * such a d prints nothing; k = 0 gives the text without the flag.  Every printed line uses exactly e*(q) edits.  The
  * reads are searched at 0 edits, the rest at 1, ... (sx_bwt_best_search_dev over all records); batches hold whole
- * reads (both strands of a read stay together).  Bits 2 and 4 stay unknown. */
-enum { SX_MAP_BOTH_STRANDS = 1, SX_MAP_BEST_STRATUM = 8 };
+ * reads (both strands of a read stay together).
+ * No indels.  With SX_MAP_NO_INDELS every search of the call is the one of SX_SEARCH_NO_INDELS: the
+ * text is that of the same call without the flag with every line removed whose CIGAR is not "<length of SEQ>M", i.e. the
+ * placements of every read within `edits` substitutions, each once.  With SX_MAP_BEST_STRATUM the strata are taken under
+ * the flag (the smallest number of substitutions).  It composes with the other two flags in any combination and does not
+ * change the limit on reads x records; edits = 0 gives the text without the flag.  Bits 2 and 4 stay unknown. */
+enum { SX_MAP_BOTH_STRANDS = 1, SX_MAP_BEST_STRATUM = 8, SX_MAP_NO_INDELS = 16 };
 int sx_map_reads_stream_ex(sx_ctx *ctx, const sx_map_record *records, uint32_t n_records, const uint8_t *fastq, size_t fastq_len,
                            int edits, uint32_t flags, sx_sink_fn sink, void *user);
 /* the limit of a mapping call on its reads and records: 0, or SX_E_ARG when reads x records (twice that with
@@ -488,7 +515,7 @@ int sx_index_add_record(sx_ctx *ctx, sx_index *idx, const sx_index_source *sourc
  * sx_map_reads_stream. */
 int sx_index_map_reads(sx_ctx *ctx, const sx_index *idx, const uint8_t *fastq, size_t fastq_len, int edits, sx_sink_fn sink,
                        void *user);
-/* the same with the flags of sx_map_reads_stream_ex (SX_MAP_BOTH_STRANDS) */
+/* the same with the flags of sx_map_reads_stream_ex (SX_MAP_BOTH_STRANDS, SX_MAP_BEST_STRATUM, SX_MAP_NO_INDELS) */
 int sx_index_map_reads_ex(sx_ctx *ctx, const sx_index *idx, const uint8_t *fastq, size_t fastq_len, int edits, uint32_t flags,
                           sx_sink_fn sink, void *user);
 typedef struct sx_index_record {
@@ -536,6 +563,10 @@ int sx_bwt_exact_search_compact_dev(sx_ctx *ctx, const uint32_t *d_c_table, cons
 int sx_bwt_approx_search_compact_dev(sx_ctx *ctx, const uint32_t *d_c_table, const uint8_t *d_occ, const uint8_t *d_rocc, uint64_t N,
                                      uint32_t sigma, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, int max_edits,
                                      uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t hit_capacity, uint64_t *total_hits_out);
+int sx_bwt_approx_search_compact_dev_ex(sx_ctx *ctx, const uint32_t *d_c_table, const uint8_t *d_occ, const uint8_t *d_rocc, uint64_t N,
+                                        uint32_t sigma, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, int max_edits,
+                                        uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t hit_capacity, uint64_t *total_hits_out,
+                                        uint32_t search_flags); /* SX_SEARCH_* */
 /* An index in the compact form (flags: SX_INDEX_COMPACT): every record keeps blocks in place of O and RO, about
  * N x (5 + 2 (1 + sigma_pad / 16)) bytes with RO (9 N for DNA in place of 45 N); no buffer of (N + 1) x sigma words exists
  * during the build (the BWT goes into the block builder; tables that arrive as full tables come up in windows through
@@ -579,6 +610,10 @@ int sx_bwt_exact_search_packed_dev(sx_ctx *ctx, const uint32_t *d_c_table, const
 int sx_bwt_approx_search_packed_dev(sx_ctx *ctx, const uint32_t *d_c_table, const uint8_t *d_occ, const uint8_t *d_rocc, uint64_t N,
                                     uint32_t sigma, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, int max_edits,
                                     uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t hit_capacity, uint64_t *total_hits_out);
+int sx_bwt_approx_search_packed_dev_ex(sx_ctx *ctx, const uint32_t *d_c_table, const uint8_t *d_occ, const uint8_t *d_rocc, uint64_t N,
+                                       uint32_t sigma, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, int max_edits,
+                                       uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t hit_capacity, uint64_t *total_hits_out,
+                                       uint32_t search_flags); /* SX_SEARCH_* */
 /* An index in the packed form (flags: SX_INDEX_COMPACT | SX_INDEX_PACKED, with or without SX_INDEX_SA_SAMPLE_LOG2(q);
  * SX_INDEX_PACKED alone is SX_E_ARG): every record keeps packed blocks, about 7 N bytes with RO for DNA where the compact
  * index takes 9 N, 3.4 N with a suffix array sampled at 32 where it takes 5.4 N.  Mapping gives the same text and

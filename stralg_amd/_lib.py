@@ -74,11 +74,19 @@ SLAB_CHAIN = 6
 CHAIN_EPOCH_LIMIT = 1 << 24  # the look-back epoch has 24 bits: the launch after 2^24 - 1 takes 1 again
 SX_MAP_BOTH_STRANDS = 1
 SX_MAP_BEST_STRATUM = 8
+SX_MAP_NO_INDELS = 16
+SX_SEARCH_NO_INDELS = 1
 
 
-def map_flags(both_strands=False, best=False):
+def map_flags(both_strands=False, best=False, indels=True):
     """the flags word of sx_map_reads_stream_ex / sx_index_map_reads_ex"""
-    return (SX_MAP_BOTH_STRANDS if both_strands else 0) | (SX_MAP_BEST_STRATUM if best else 0)
+    return ((SX_MAP_BOTH_STRANDS if both_strands else 0) | (SX_MAP_BEST_STRATUM if best else 0)
+            | (0 if indels else SX_MAP_NO_INDELS))
+
+
+def search_flags(indels=True):
+    """the search_flags word of the _ex search calls"""
+    return 0 if indels else SX_SEARCH_NO_INDELS
 
 
 class SamBatch(C.Structure):
@@ -209,6 +217,16 @@ def load(path=None):
                                                u64p, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
         "sx_bwt_best_search_dev": (C.c_int, [vp, u32p, u32p, u32p, C.c_uint64, C.c_uint32, u8p, u32p, C.c_uint32, C.c_int, u8p,
                                              u64p, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+        "sx_bwt_approx_search_dev_ex": (C.c_int, [vp, u32p, u32p, u32p, C.c_uint64, C.c_uint32, u8p, u32p, C.c_uint32, C.c_int,
+                                                  u64p, vp, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32]),
+        "sx_bwt_best_search_dev_ex": (C.c_int, [vp, u32p, u32p, u32p, C.c_uint64, C.c_uint32, u8p, u32p, C.c_uint32, C.c_int, u8p,
+                                                u64p, vp, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32]),
+        "sx_bwt_approx_search_ex": (C.c_int, [vp, u32p, u32p, u32p, C.c_uint64, C.c_uint32, u8p, u32p, C.c_uint32, C.c_int,
+                                              u64p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.c_uint32]),
+        "sx_bwt_approx_search_compact_dev_ex": (C.c_int, [vp, u32p, u8p, u8p, C.c_uint64, C.c_uint32, u8p, u32p, C.c_uint32, C.c_int,
+                                                          u64p, vp, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32]),
+        "sx_bwt_approx_search_packed_dev_ex": (C.c_int, [vp, u32p, u8p, u8p, C.c_uint64, C.c_uint32, u8p, u32p, C.c_uint32, C.c_int,
+                                                         u64p, vp, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32]),
         "sx_patterns_select_dev": (C.c_int, [vp, u8p, u32p, C.c_uint32, u8p, u8p, u32p, u32p, C.POINTER(C.c_uint32),
                                              C.POINTER(C.c_uint64)]),
         "sx_bwt_approx_search": (C.c_int, [vp, u32p, u32p, u32p, C.c_uint64, C.c_uint32, u8p, u32p, C.c_uint32, C.c_int,
@@ -313,6 +331,8 @@ EXPORTS = ["sx_device_count", "sx_device_numa_node", "sx_ctx_create", "sx_ctx_de
            "sx_sa_sample_bytes", "sx_sa_sample_build_dev", "sx_sa_locate_rows_dev", "sx_index_record_samples", "sx_index_expand_sa",
            "sx_sam_layout_dev_ex", "sx_sam_emit_dev_ex", "sx_map_reads_stream_ex", "sx_map_reads_limit", "sx_fastq_strands_dev",
            "sx_index_map_reads_ex", "sx_bwt_best_search_dev", "sx_patterns_select_dev", "sx_map_last_stats",
+           "sx_bwt_approx_search_dev_ex", "sx_bwt_approx_search_compact_dev_ex", "sx_bwt_approx_search_packed_dev_ex",
+           "sx_bwt_best_search_dev_ex", "sx_bwt_approx_search_ex",
            "sx_synth_dev", "sx_membw_probe", "sx_prim_sort_pairs_dev", "sx_prim_exclusive_sum_dev", "sx_prim_classify_dev"]
 
 

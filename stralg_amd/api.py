@@ -140,26 +140,41 @@ class Context:
                     "sx_bwt_exact_search_dev")
 
     def bwt_approx_search_dev(self, d_c, d_o, d_ro, N, sigma, d_patterns, d_offsets, count, max_edits, d_hit_offsets,
-                              d_hits=None, hit_capacity=0):
+                              d_hits=None, hit_capacity=0, indels=True):
         """sx_bwt_approx_search_dev: fills d_hit_offsets (count + 1 uint64) and, when d_hits is given and large enough,
         d_hits (hit_capacity records of _lib.APPROX_HIT_DTYPE); returns the number of hits.  More hits than
-        hit_capacity raise StralgAmdError with code SX_E_CAPACITY (-5); the offsets are written all the same."""
+        hit_capacity raise StralgAmdError with code SX_E_CAPACITY (-5); the offsets are written all the same.
+        indels=False (sx_bwt_approx_search_dev_ex, SX_SEARCH_NO_INDELS): mismatches only -- the hits of the call whose
+        n_gaps is 0, in its order."""
         total = C.c_uint64(0)
-        self._check(self.lib.sx_bwt_approx_search_dev(self.h, _ptr(d_c), _ptr(d_o), _ptr(d_ro), N, sigma, _ptr(d_patterns),
+        if indels:
+            rc = self.lib.sx_bwt_approx_search_dev(self.h, _ptr(d_c), _ptr(d_o), _ptr(d_ro), N, sigma, _ptr(d_patterns),
+                                                   _ptr(d_offsets), count, max_edits, _ptr(d_hit_offsets), _ptr(d_hits),
+                                                   hit_capacity, C.byref(total))
+        else:
+            rc = self.lib.sx_bwt_approx_search_dev_ex(self.h, _ptr(d_c), _ptr(d_o), _ptr(d_ro), N, sigma, _ptr(d_patterns),
                                                       _ptr(d_offsets), count, max_edits, _ptr(d_hit_offsets), _ptr(d_hits),
-                                                      hit_capacity, C.byref(total)), "sx_bwt_approx_search_dev")
+                                                      hit_capacity, C.byref(total), _lib.search_flags(indels))
+        self._check(rc, "sx_bwt_approx_search_dev" if indels else "sx_bwt_approx_search_dev_ex")
         return int(total.value)
 
     def bwt_best_search_dev(self, d_c, d_o, d_ro, N, sigma, d_patterns, d_offsets, count, max_edits, d_stratum, d_hit_offsets,
-                            d_hits=None, hit_capacity=0):
+                            d_hits=None, hit_capacity=0, indels=True):
         """sx_bwt_best_search_dev: Context.bwt_approx_search_dev by iterative deepening.  d_stratum (count bytes) <- the
         smallest edit count at which each pattern has a hit (0xFF: none within max_edits); a pattern's hits are those of
         bwt_approx_search_dev at that edit count, in its order.  Returns the number of hits; on SX_E_CAPACITY (raised) the
-        offsets and strata are written all the same."""
+        offsets and strata are written all the same.  indels=False (sx_bwt_best_search_dev_ex): strata and hits are
+        those of the search with indels=False, so a stratum is the smallest number of mismatches."""
         total = C.c_uint64(0)
-        self._check(self.lib.sx_bwt_best_search_dev(self.h, _ptr(d_c), _ptr(d_o), _ptr(d_ro), N, sigma, _ptr(d_patterns),
+        if indels:
+            rc = self.lib.sx_bwt_best_search_dev(self.h, _ptr(d_c), _ptr(d_o), _ptr(d_ro), N, sigma, _ptr(d_patterns),
+                                                 _ptr(d_offsets), count, max_edits, _ptr(d_stratum), _ptr(d_hit_offsets),
+                                                 _ptr(d_hits), hit_capacity, C.byref(total))
+        else:
+            rc = self.lib.sx_bwt_best_search_dev_ex(self.h, _ptr(d_c), _ptr(d_o), _ptr(d_ro), N, sigma, _ptr(d_patterns),
                                                     _ptr(d_offsets), count, max_edits, _ptr(d_stratum), _ptr(d_hit_offsets),
-                                                    _ptr(d_hits), hit_capacity, C.byref(total)), "sx_bwt_best_search_dev")
+                                                    _ptr(d_hits), hit_capacity, C.byref(total), _lib.search_flags(indels))
+        self._check(rc, "sx_bwt_best_search_dev" if indels else "sx_bwt_best_search_dev_ex")
         return int(total.value)
 
     def patterns_select_dev(self, d_bytes, d_off, count, d_keep, d_bytes_out, d_off_out, d_ids_out):
@@ -172,9 +187,9 @@ class Context:
                     "sx_patterns_select_dev")
         return int(kept.value), int(nbytes.value)
 
-    def bwt_approx_search(self, c, o, ro, sigma, patterns, offsets, max_edits):
+    def bwt_approx_search(self, c, o, ro, sigma, patterns, offsets, max_edits, indels=True):
         """sx_bwt_approx_search over host arrays (o, ro: (N+1, sigma); ro may be None): (hit offsets[count + 1], hits as a
-        structured array of _lib.APPROX_HIT_DTYPE)."""
+        structured array of _lib.APPROX_HIT_DTYPE).  indels=False: sx_bwt_approx_search_ex with SX_SEARCH_NO_INDELS."""
         c = np.ascontiguousarray(c, dtype=np.uint32)
         o = np.ascontiguousarray(o, dtype=np.uint32)
         ro = None if ro is None else np.ascontiguousarray(ro, dtype=np.uint32)
@@ -183,9 +198,12 @@ class Context:
         count = offsets.size - 1
         hit_off = np.zeros(count + 1, dtype=np.uint64)
         hp, total = C.c_void_p(), C.c_uint64(0)
-        self._check(self.lib.sx_bwt_approx_search(self.h, _ptr(c), _ptr(o), _ptr(ro), o.shape[0] - 1, sigma,
-                                                  _ptr(patterns) if patterns.size else None, _ptr(offsets), count, max_edits,
-                                                  _ptr(hit_off), C.byref(hp), C.byref(total)), "sx_bwt_approx_search")
+        args = (self.h, _ptr(c), _ptr(o), _ptr(ro), o.shape[0] - 1, sigma, _ptr(patterns) if patterns.size else None,
+                _ptr(offsets), count, max_edits, _ptr(hit_off), C.byref(hp), C.byref(total))
+        if indels:
+            self._check(self.lib.sx_bwt_approx_search(*args), "sx_bwt_approx_search")
+        else:
+            self._check(self.lib.sx_bwt_approx_search_ex(*args, _lib.search_flags(indels)), "sx_bwt_approx_search_ex")
         n = int(total.value)
         hits = np.zeros(n, dtype=_lib.APPROX_HIT_DTYPE)
         if hp.value:
@@ -211,13 +229,17 @@ class Context:
                     "sx_bwt_exact_search_compact_dev")
 
     def bwt_approx_search_compact_dev(self, d_c, d_occ, d_rocc, N, sigma, d_patterns, d_offsets, count, max_edits, d_hit_offsets,
-                                      d_hits=None, hit_capacity=0):
-        """sx_bwt_approx_search_compact_dev: Context.bwt_approx_search_dev over blocks in place of the full tables"""
+                                      d_hits=None, hit_capacity=0, indels=True):
+        """sx_bwt_approx_search_compact_dev: Context.bwt_approx_search_dev over blocks in place of the full tables
+        (indels=False: sx_bwt_approx_search_compact_dev_ex with SX_SEARCH_NO_INDELS)"""
         total = C.c_uint64(0)
-        self._check(self.lib.sx_bwt_approx_search_compact_dev(self.h, _ptr(d_c), _ptr(d_occ), _ptr(d_rocc), N, sigma,
-                                                              _ptr(d_patterns), _ptr(d_offsets), count, max_edits,
-                                                              _ptr(d_hit_offsets), _ptr(d_hits), hit_capacity, C.byref(total)),
-                    "sx_bwt_approx_search_compact_dev")
+        args = (self.h, _ptr(d_c), _ptr(d_occ), _ptr(d_rocc), N, sigma, _ptr(d_patterns), _ptr(d_offsets), count, max_edits,
+                _ptr(d_hit_offsets), _ptr(d_hits), hit_capacity, C.byref(total))
+        if indels:
+            self._check(self.lib.sx_bwt_approx_search_compact_dev(*args), "sx_bwt_approx_search_compact_dev")
+        else:
+            self._check(self.lib.sx_bwt_approx_search_compact_dev_ex(*args, _lib.search_flags(indels)),
+                        "sx_bwt_approx_search_compact_dev_ex")
         return int(total.value)
 
     # ---- the packed form of the compact table (sx_occ.hpp: a nibble a row, sigma <= 8) ---------
@@ -238,13 +260,17 @@ class Context:
                     "sx_bwt_exact_search_packed_dev")
 
     def bwt_approx_search_packed_dev(self, d_c, d_occ, d_rocc, N, sigma, d_patterns, d_offsets, count, max_edits, d_hit_offsets,
-                                     d_hits=None, hit_capacity=0):
-        """sx_bwt_approx_search_packed_dev: Context.bwt_approx_search_dev over packed blocks in place of the full tables"""
+                                     d_hits=None, hit_capacity=0, indels=True):
+        """sx_bwt_approx_search_packed_dev: Context.bwt_approx_search_dev over packed blocks in place of the full tables
+        (indels=False: sx_bwt_approx_search_packed_dev_ex with SX_SEARCH_NO_INDELS)"""
         total = C.c_uint64(0)
-        self._check(self.lib.sx_bwt_approx_search_packed_dev(self.h, _ptr(d_c), _ptr(d_occ), _ptr(d_rocc), N, sigma,
-                                                             _ptr(d_patterns), _ptr(d_offsets), count, max_edits,
-                                                             _ptr(d_hit_offsets), _ptr(d_hits), hit_capacity, C.byref(total)),
-                    "sx_bwt_approx_search_packed_dev")
+        args = (self.h, _ptr(d_c), _ptr(d_occ), _ptr(d_rocc), N, sigma, _ptr(d_patterns), _ptr(d_offsets), count, max_edits,
+                _ptr(d_hit_offsets), _ptr(d_hits), hit_capacity, C.byref(total))
+        if indels:
+            self._check(self.lib.sx_bwt_approx_search_packed_dev(*args), "sx_bwt_approx_search_packed_dev")
+        else:
+            self._check(self.lib.sx_bwt_approx_search_packed_dev_ex(*args, _lib.search_flags(indels)),
+                        "sx_bwt_approx_search_packed_dev_ex")
         return int(total.value)
 
     # ---- SAM text of search hits (the read mapper's output) ---------------------------------
@@ -390,12 +416,14 @@ class Context:
         self._check(self.lib.sx_sa_locate_rows_dev(self.h, _ptr(d_c), _ptr(d_occ), N, sigma, _ptr(d_marks), _ptr(d_values),
                                                    int(sa_sample).bit_length() - 1, row_lo, row_hi, _ptr(d_out)), "sx_sa_locate_rows_dev")
 
-    def map_reads_stream(self, records, fastq, edits, sink, both_strands=False, best=False):
+    def map_reads_stream(self, records, fastq, edits, sink, both_strands=False, best=False, indels=True):
         """sx_map_reads_stream: records = [(name bytes, BwtTable), ...] in the mapper's list order; sink(bytes) receives the
         SAM text window after window.  sink=None discards the text without touching it and returns [(time.perf_counter(),
         bytes)] per window (measurement).  both_strands (sx_map_reads_stream_ex, SX_MAP_BOTH_STRANDS): behind the lines of
         every read come those of its reverse complement, with FLAG 16.  best (SX_MAP_BEST_STRATUM): per read only the
-        lines of the smallest edit count in 0 .. edits that has any (with both_strands: over both strands together)."""
+        lines of the smallest edit count in 0 .. edits that has any (with both_strands: over both strands together).
+        indels=False (SX_MAP_NO_INDELS): mismatches only -- the lines whose CIGAR is "<length of SEQ>M", each placement
+        once; with best the strata are the smallest number of mismatches."""
         recs = (_lib.MapRecord * max(1, len(records)))()
         keep = []
         for r, (name, t) in enumerate(records):
@@ -417,7 +445,7 @@ class Context:
                 return 1
 
         cb = _lib.SINK_FN(_sink)
-        flags = _lib.map_flags(both_strands, best)
+        flags = _lib.map_flags(both_strands, best, indels)
         if flags:
             rc = self.lib.sx_map_reads_stream_ex(self.h, recs, len(records), _ptr(buf) if buf.size else None, buf.size, edits,
                                                  flags, cb, None)
@@ -729,10 +757,11 @@ class Index:
             raise StralgAmdError("the index is closed")
         return self.h
 
-    def map_reads(self, fastq, edits, sink=None, ctx=None, both_strands=False, best=False):
+    def map_reads(self, fastq, edits, sink=None, ctx=None, both_strands=False, best=False, indels=True):
         """sx_index_map_reads: the SAM text of every match of every read of a FASTQ image within `edits` edits, byte for
         byte stralg_amd.map_reads' (the reference mapper's stdout).  sink=None returns the text; sink(bytes) receives it
-        window after window and None is returned.  both_strands, best: as in stralg_amd.map_reads (sx_index_map_reads_ex)."""
+        window after window and None is returned.  both_strands, best, indels: as in stralg_amd.map_reads
+        (sx_index_map_reads_ex)."""
         ctx = ctx or self.ctx
         buf = np.frombuffer(bytes(fastq), dtype=np.uint8)
         chunks, failure = [], []
@@ -747,7 +776,7 @@ class Index:
                 return 1
 
         cb = _lib.SINK_FN(_sink)
-        flags = _lib.map_flags(both_strands, best)
+        flags = _lib.map_flags(both_strands, best, indels)
         rc = self._map(ctx, buf, edits, flags, cb)
         if failure:
             raise failure[0]
@@ -761,7 +790,7 @@ class Index:
             return ctx.lib.sx_index_map_reads_ex(ctx.h, self._handle(), image, buf.size, edits, flags, cb, None)
         return ctx.lib.sx_index_map_reads(ctx.h, self._handle(), image, buf.size, edits, cb, None)
 
-    def map_reads_discard(self, fastq, edits, ctx=None, both_strands=False, best=False):
+    def map_reads_discard(self, fastq, edits, ctx=None, both_strands=False, best=False, indels=True):
         """the same with a sink that does not touch the text: [(time.perf_counter(), bytes)] per window (measurement)"""
         ctx = ctx or self.ctx
         buf = np.frombuffer(bytes(fastq), dtype=np.uint8)
@@ -772,7 +801,7 @@ class Index:
             return 0
 
         cb = _lib.SINK_FN(_sink)
-        flags = _lib.map_flags(both_strands, best)
+        flags = _lib.map_flags(both_strands, best, indels)
         ctx._check(self._map(ctx, buf, edits, flags, cb), "sx_index_map_reads_ex" if flags else "sx_index_map_reads")
         return seen
 
@@ -1106,11 +1135,13 @@ def approx_matches(hits, hit_offsets, pattern_lengths, sa):
     return out
 
 
-def bwt_approx_search(bwt_table, patterns, edits, ctx=None):
+def bwt_approx_search(bwt_table, patterns, edits, ctx=None, indels=True):
     """stralg/bwt.c:226-422 (init_bwt_approx_iter / next_bwt_approx_match) for a batch of remapped patterns at once:
     per pattern the list of (position, match_length, cigar) the reference iterator yields, in its order.  The RO table
     (when the table has one) feeds the search's D table.  A pattern that is empty or holds a symbol 0 or >=
-    alphabet_size has no matches."""
+    alphabet_size has no matches.
+    indels=False: mismatches only -- of that list the entries whose CIGAR is "<pattern length>M", in its order: every
+    occurrence of a string at Hamming distance <= edits from the pattern, once."""
     ctx = ctx or default_context()
     pats = [np.asarray(p, dtype=np.uint8) if not isinstance(p, (bytes, bytearray)) else np.frombuffer(bytes(p), np.uint8)
             for p in patterns]
@@ -1118,11 +1149,11 @@ def bwt_approx_search(bwt_table, patterns, edits, ctx=None):
     offsets[1:] = np.cumsum([p.size for p in pats])
     flat = np.concatenate(pats).astype(np.uint8) if offsets[-1] else np.zeros(0, np.uint8)
     hit_off, hits = ctx.bwt_approx_search(bwt_table.c_table, bwt_table.o_table, bwt_table.ro_table,
-                                          bwt_table.remap_table.alphabet_size, flat, offsets, edits)
+                                          bwt_table.remap_table.alphabet_size, flat, offsets, edits, indels=indels)
     return approx_matches(hits, hit_off, [p.size for p in pats], bwt_table.sa.array)
 
 
-def map_reads(fasta, fastq, edits, ctx=None, both_strands=False, best=False):
+def map_reads(fasta, fastq, edits, ctx=None, both_strands=False, best=False, indels=True):
     """The reference read mapper (tools/readmappers/bwt_readmapper: -p genome.fa, then -d edits genome.fa reads.fq) on the
     bytes of a FASTA and a FASTQ file: its stdout, the SAM lines of every match of every read in every record within
     `edits` edits, byte for byte.  Per read the records come in the mapper's list order, which is the FASTA file's order
@@ -1131,9 +1162,11 @@ def map_reads(fasta, fastq, edits, ctx=None, both_strands=False, best=False):
     and complemented, the quality string reversed) as the reference prints them for such a read, with FLAG 16 in place of 0;
     the reference itself maps one strand only.
     best: per read only the lines of its best stratum: those the mapper prints for it at -d e*, the smallest edit count in
-    0 .. edits at which it prints any for that read (with both_strands: over both strands of the read together)."""
+    0 .. edits at which it prints any for that read (with both_strands: over both strands of the read together).
+    indels=False: mismatches only -- of the mapper's lines those whose CIGAR is "<length of SEQ>M" (every placement of a read
+    within `edits` substitutions, once); with best the strata are taken over these lines."""
     ctx = ctx or default_context()
     records = [(name, build_complete_table(seq, True, ctx)) for name, seq in ctx.fasta_records(fasta)]
     chunks = []
-    ctx.map_reads_stream(records, fastq, edits, chunks.append, both_strands=both_strands, best=best)
+    ctx.map_reads_stream(records, fastq, edits, chunks.append, both_strands=both_strands, best=best, indels=indels)
     return b"".join(chunks)

@@ -271,6 +271,182 @@ __global__ __launch_bounds__(kApproxBlock) void bwt_approx_kernel(ApproxArgsT<Oc
     }
 }
 
+// The search without I and D (SX_SEARCH_NO_INDELS): the same walk with the M children only, so its
+// hits are those of bwt_approx_kernel whose path took no I or D child, in that kernel's order.  A node at search depth
+// d stands at pattern index m - 1 - d with match length d, so neither is kept; a frame is {L, R} and {next child |
+// edits_left | the node's pattern symbol}, 12 bytes in two planes of the same workspace (frame d of lane t at
+// lr[d * lanes + t], ce[d * lanes + t]); there is no list of operations, and a hit's match length is m and its gap[]
+// zeros.  The D table cuts as it does there: a bound on the edits of any kind that the rest of the pattern needs is one
+// on its substitutions too.
+// A step of the loop has one place where it reads the table: a step of the chain and a child of a node both come down
+// to "the interval of a in front of [lo, hi)", so the step first says what it looks up, then every lane of the wave that
+// looks anything up does so together (with the pattern symbol the next step will need), then the step's state moves on.
+// The loop has one back edge; the kernel above, whose steps each read on their own, is laid out by the compiler as
+// nested loops in which the lanes of a wave wait for each other's chains.
+template <bool kEmit, class Occ>
+__global__ __launch_bounds__(kApproxBlock) void bwt_hamming_kernel(ApproxArgsT<Occ> A)
+{
+    const uint32_t t = blockIdx.x * kApproxBlock + threadIdx.x;
+    if (t >= A.lanes) return;
+    const uint32_t sigma = A.sigma;
+    const uint32_t nM = sigma - 1; // children of a node: M(a) is a - 1
+    const uint32_t *__restrict__ C = A.c;
+    const Occ O = A.o;
+    uint2 *lr = reinterpret_cast<uint2 *>(A.stack) + t;
+    uint32_t *ce_plane = reinterpret_cast<uint32_t *>(reinterpret_cast<uint2 *>(A.stack) + (uint64_t)A.frames * A.lanes) + t;
+
+    uint32_t mode = kFetch, q = 0, m = 0, cnt = 0;
+    const uint8_t *p = nullptr;
+    uint64_t out_base = 0;
+    uint32_t brk[kMaxEdits + 1];
+    // current node: its interval, next child, search depth, edits left, and the pattern symbol it stands at
+    uint32_t L = 0, R = 0, c = 0, depth = 0, pa = 0;
+    int32_t e = 0;
+    // chain (the exact search below a child with no edit left, or a hit right away): interval, next index and its symbol
+    uint32_t L2 = 0, R2 = 0, pj = 0;
+    int32_t j = 0;
+
+    for (bool live = true; live;) {
+        // what this step looks up: a of [lo, hi), and the pattern index whose symbol the step behind it stands at
+        uint32_t a = 0, lo = 0, hi = 0;
+        int32_t ni = -1, ce = 0;
+        bool look = false;
+        if (mode == kChain) {
+            look = j >= 0 && L2 < R2;
+            a = pj, lo = L2, hi = R2, ni = j - 1;
+        } else if (mode == kScan && c < nM) {
+            a = c + 1, lo = L, hi = R, ni = (int32_t)(m - 1u - depth) - 1;
+            ce = e - (a == pa ? 0 : 1);
+            look = ce >= 0;
+        }
+        uint32_t nL = lo, nR = hi, nx = 0;
+        if (look) {
+            const uint32_t base = C[a];
+            nL = base + O.rank(a, lo, sigma);
+            nR = base + O.rank(a, hi, sigma);
+            if (ni >= 0) nx = p[ni];
+        }
+        if (mode == kChain) {
+            if (look) {
+                L2 = nL, R2 = nR, j = ni, pj = nx;
+            } else {
+                if (L2 < R2) { // a hit: the interval; the pattern is aligned to m symbols, with no I/D operation
+                    if (kEmit) {
+                        const uint64_t idx = out_base + cnt;
+                        if (idx < A.cap) {
+                            A.hits[2 * idx] = u4(q, L2, R2, m & 0xFFFFu);
+                            A.hits[2 * idx + 1] = u4(0u, 0u, 0u, 0u);
+                        }
+                    }
+                    ++cnt;
+                }
+                ++c;
+                mode = kScan;
+            }
+        } else if (mode == kScan) {
+            if (c < nM) {
+                bool take = look && nL < nR;
+                if (take && ni >= 0) { // the reference's cut at the child: edits_left < D[i]
+                    uint32_t b = brk[0];
+#pragma unroll
+                    for (int s = 1; s <= kMaxEdits; ++s)
+                        if (s == ce) b = brk[s];
+                    take = (uint32_t)ni < b;
+                }
+                if (!take) {
+                    ++c;
+                } else if (ni < 0 || ce == 0) { // a hit, or the exact search of the rest: no frame
+                    L2 = nL, R2 = nR, j = ni, pj = nx;
+                    mode = kChain;
+                } else if (depth >= A.frames) { // (cannot happen: frames >= longest pattern)
+                    atomicOr(A.next + 1, 1u);
+                    mode = kFetch;
+                    if (!kEmit) A.counts[q] = cnt;
+                } else {
+                    uint2 f;
+                    f.x = L;
+                    f.y = R;
+                    lr[(uint64_t)depth * A.lanes] = f;
+                    ce_plane[(uint64_t)depth * A.lanes] = c | ((uint32_t)e << 16) | (pa << 24);
+                    L = nL, R = nR, e = ce, pa = nx;
+                    c = 0;
+                    ++depth;
+                }
+            } else if (depth > 0) { // the node is done: back to its parent, on to the parent's next child
+                --depth;
+                const uint2 f = lr[(uint64_t)depth * A.lanes];
+                const uint32_t w = ce_plane[(uint64_t)depth * A.lanes];
+                L = f.x, R = f.y;
+                c = (w & 0xFFFFu) + 1u;
+                e = (int32_t)((w >> 16) & 0xFFu);
+                pa = w >> 24;
+            } else { // the root is done
+                if (!kEmit) {
+                    A.counts[q] = cnt;
+                    if (cnt) atomicAdd(A.total, (unsigned long long)cnt);
+                }
+                mode = kFetch;
+            }
+        } else { // kFetch: the next pattern
+            q = atomicAdd(A.next, 1u);
+            if (q >= A.count) {
+                live = false;
+            } else {
+                const uint32_t begin = A.off[q];
+                m = A.off[q + 1] - begin;
+                p = A.pat + begin;
+                cnt = 0;
+                if (kEmit) out_base = A.hit_off[q];
+                // symbols in [1, sigma) and the D table's break points, as in bwt_approx_kernel
+                bool ok = m > 0;
+#pragma unroll
+                for (int s = 0; s <= kMaxEdits; ++s) brk[s] = m;
+                uint32_t rL = 0, rR = (uint32_t)A.N;
+                int32_t me = 0;
+                for (uint32_t s = 0; s < m; ++s) {
+                    const uint32_t x = p[s];
+                    if (x == 0 || x >= sigma) {
+                        ok = false;
+                        break;
+                    }
+                    if (A.ro.present() && me <= A.k) {
+                        rL = C[x] + A.ro.rank(x, rL, sigma);
+                        rR = C[x] + A.ro.rank(x, rR, sigma);
+                        if (rL >= rR) {
+                            ++me;
+#pragma unroll
+                            for (int b = 0; b <= kMaxEdits; ++b)
+                                if (b == me - 1) brk[b] = s;
+                            rL = 0;
+                            rR = (uint32_t)A.N;
+                        }
+                    }
+                }
+                if (!ok) {
+                    if (!kEmit) A.counts[q] = 0;
+                } else {
+                    L = 0;
+                    R = (uint32_t)A.N;
+                    e = A.k;
+                    c = 0;
+                    depth = 0;
+                    pa = p[m - 1u];
+                    mode = kScan;
+                }
+            }
+        }
+    }
+}
+
+// the pass over A's patterns, with or without I and D
+template <bool kEmit, class Occ> static void approx_launch(sx_ctx *ctx, const ApproxArgsT<Occ> &A, uint32_t search_flags, uint64_t bytes)
+{
+    if (search_flags & SX_SEARCH_NO_INDELS)
+        sx_launch(ctx, SX_KC_SEARCH, bytes, bwt_hamming_kernel<kEmit, Occ>, dim3(A.lanes / kApproxBlock), dim3(kApproxBlock), A);
+    else
+        sx_launch(ctx, SX_KC_SEARCH, bytes, bwt_approx_kernel<kEmit, Occ>, dim3(A.lanes / kApproxBlock), dim3(kApproxBlock), A);
+}
+
 struct InLen {
     const uint32_t *off;
     __device__ __forceinline__ uint32_t operator()(uint64_t q) const { return off[q + 1] - off[q]; }
@@ -318,11 +494,11 @@ template <class Occ> static int approx_workspace(sx_ctx *ctx, ApproxArgsT<Occ> &
 }
 
 // count pass + offsets; the workspace stays where it is for the emit pass
-template <class Occ> static int approx_count(sx_ctx *ctx, ApproxArgsT<Occ> &A, uint64_t *d_hit_off, uint64_t *total_out)
+template <class Occ> static int approx_count(sx_ctx *ctx, ApproxArgsT<Occ> &A, uint32_t search_flags, uint64_t *d_hit_off, uint64_t *total_out)
 {
     SX_TRY(approx_workspace(ctx, A));
     uint32_t *scal = (uint32_t *)ctx->slab[SX_SLAB_BWT].p;
-    sx_launch(ctx, SX_KC_SEARCH, 0, bwt_approx_kernel<false, Occ>, dim3(A.lanes / kApproxBlock), dim3(kApproxBlock), A);
+    approx_launch<false>(ctx, A, search_flags, 0);
     SX_TRY((device_scan<OpAdd>(ctx, A.count, InU32{A.counts}, OutOffsets64{d_hit_off}, nullptr, SX_KC_SEARCH, (uint64_t)A.count * 12)));
     sx_launch(ctx, SX_KC_SEARCH, 0, approx_finish_offsets_kernel, dim3(1), dim3(64), (const unsigned long long *)A.total, d_hit_off, A.count);
     uint32_t h[4] = {0, 0, 0, 0};
@@ -334,14 +510,14 @@ template <class Occ> static int approx_count(sx_ctx *ctx, ApproxArgsT<Occ> &A, u
     return 0;
 }
 
-template <class Occ> static int approx_emit(sx_ctx *ctx, ApproxArgsT<Occ> &A, const uint64_t *d_hit_off, sx_approx_hit *d_hits, uint64_t total)
+template <class Occ>
+static int approx_emit(sx_ctx *ctx, ApproxArgsT<Occ> &A, uint32_t search_flags, const uint64_t *d_hit_off, sx_approx_hit *d_hits, uint64_t total)
 {
     A.hit_off = d_hit_off;
     A.hits = (uint4 *)d_hits;
     A.cap = total;
     SX_CHECK(hipMemsetAsync(A.next, 0, 8, ctx->stream));
-    sx_launch(ctx, SX_KC_SEARCH, total * sizeof(sx_approx_hit), bwt_approx_kernel<true, Occ>, dim3(A.lanes / kApproxBlock),
-              dim3(kApproxBlock), A);
+    approx_launch<true>(ctx, A, search_flags, total * sizeof(sx_approx_hit));
     uint32_t h[2] = {0, 0};
     SX_TRY(sx_readback(ctx, A.next, 2, h));
     if (h[1]) return sx_fail_msg(ctx, SX_E_INTERNAL, "approximate search: a search stack overflowed");
@@ -350,9 +526,10 @@ template <class Occ> static int approx_emit(sx_ctx *ctx, ApproxArgsT<Occ> &A, co
 
 template <class Occ>
 static int approx_args(sx_ctx *ctx, ApproxArgsT<Occ> &A, const uint32_t *c, Occ o, Occ ro, uint64_t N, uint32_t sigma, const uint8_t *pat,
-                       const uint32_t *off, uint32_t count, int k)
+                       const uint32_t *off, uint32_t count, int k, uint32_t search_flags)
 {
     (void)ctx;
+    if (search_flags & ~(uint32_t)SX_SEARCH_NO_INDELS) return SX_E_ARG;
     if (!c || !o.p || !off || N == 0 || N > 0xFFFFFFFFull || sigma < 2 || sigma > 256 || k > kMaxEdits) return SX_E_ARG;
     A = ApproxArgsT<Occ>{};
     A.c = c;
@@ -375,11 +552,11 @@ using namespace sx;
 template <class Occ>
 static int approx_search_dev(sx_ctx *ctx, const uint32_t *d_c_table, Occ o, Occ ro, uint64_t N, uint32_t sigma, const uint8_t *d_patterns,
                              const uint32_t *d_offsets, uint32_t count, int max_edits, uint64_t *d_hit_offsets, sx_approx_hit *d_hits,
-                             uint64_t hit_capacity, uint64_t *total_hits_out)
+                             uint64_t hit_capacity, uint64_t *total_hits_out, uint32_t search_flags)
 {
     if (!ctx || !d_hit_offsets || !total_hits_out || ((uintptr_t)d_hits & 15)) return SX_E_ARG;
     ApproxArgsT<Occ> A;
-    SX_TRY(approx_args(ctx, A, d_c_table, o, ro, N, sigma, d_patterns, d_offsets, count, max_edits));
+    SX_TRY(approx_args(ctx, A, d_c_table, o, ro, N, sigma, d_patterns, d_offsets, count, max_edits, search_flags));
     SX_CHECK(hipSetDevice(ctx->device));
     *total_hits_out = 0;
     if (max_edits < 0 || count == 0) { // no search: every offset 0
@@ -387,7 +564,7 @@ static int approx_search_dev(sx_ctx *ctx, const uint32_t *d_c_table, Occ o, Occ 
         return sx_sync(ctx);
     }
     uint64_t total = 0;
-    SX_TRY(approx_count(ctx, A, d_hit_offsets, &total));
+    SX_TRY(approx_count(ctx, A, search_flags, d_hit_offsets, &total));
     *total_hits_out = total;
     if (!d_hits) return sx_sync(ctx);
     if (total > hit_capacity) {
@@ -395,21 +572,21 @@ static int approx_search_dev(sx_ctx *ctx, const uint32_t *d_c_table, Occ o, Occ 
         sx_fail_msg(ctx, SX_E_CAPACITY, "approximate search: more hits than hit_capacity");
         return SX_E_CAPACITY;
     }
-    if (total) SX_TRY(approx_emit(ctx, A, d_hit_offsets, d_hits, total));
+    if (total) SX_TRY(approx_emit(ctx, A, search_flags, d_hit_offsets, d_hits, total));
     return sx_sync(ctx);
 }
 
 // the search over a record of an index in whichever form its tables have (the mapper's loop, sx_map.hip)
 int sx_approx_search_record(sx_ctx *ctx, const sx_index_rec &R, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, int max_edits,
-                            uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t hit_capacity, uint64_t *total_hits_out)
+                            uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t hit_capacity, uint64_t *total_hits_out, uint32_t search_flags)
 {
     if (R.packed)
-        return sx_bwt_approx_search_packed_dev(ctx, R.d_c, R.d_occ, R.d_rocc, R.N, R.sigma, d_patterns, d_offsets, count, max_edits, d_hit_offsets,
-                                               d_hits, hit_capacity, total_hits_out);
-    return R.compact() ? sx_bwt_approx_search_compact_dev(ctx, R.d_c, R.d_occ, R.d_rocc, R.N, R.sigma, d_patterns, d_offsets, count, max_edits,
-                                                          d_hit_offsets, d_hits, hit_capacity, total_hits_out)
-                       : sx_bwt_approx_search_dev(ctx, R.d_c, R.d_o, R.d_ro, R.N, R.sigma, d_patterns, d_offsets, count, max_edits, d_hit_offsets,
-                                                  d_hits, hit_capacity, total_hits_out);
+        return sx_bwt_approx_search_packed_dev_ex(ctx, R.d_c, R.d_occ, R.d_rocc, R.N, R.sigma, d_patterns, d_offsets, count, max_edits, d_hit_offsets,
+                                                  d_hits, hit_capacity, total_hits_out, search_flags);
+    return R.compact() ? sx_bwt_approx_search_compact_dev_ex(ctx, R.d_c, R.d_occ, R.d_rocc, R.N, R.sigma, d_patterns, d_offsets, count, max_edits,
+                                                             d_hit_offsets, d_hits, hit_capacity, total_hits_out, search_flags)
+                       : sx_bwt_approx_search_dev_ex(ctx, R.d_c, R.d_o, R.d_ro, R.N, R.sigma, d_patterns, d_offsets, count, max_edits, d_hit_offsets,
+                                                     d_hits, hit_capacity, total_hits_out, search_flags);
 }
 
 // f(o, ro): the accessors of a record's tables in whichever form they have
@@ -427,67 +604,102 @@ template <class F> static int with_record_occ(const sx_index_rec &R, F f)
 
 // the two passes on their own, for the rounds of sx_best.hip: they launch what the passes of approx_search_dev launch
 int sx_approx_count_record(sx_ctx *ctx, const sx_index_rec &R, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, int max_edits,
-                           uint64_t *d_hit_offsets, uint64_t *total_hits_out)
+                           uint64_t *d_hit_offsets, uint64_t *total_hits_out, uint32_t search_flags)
 {
     if (!ctx || !d_hit_offsets || !total_hits_out || count == 0 || max_edits < 0) return SX_E_ARG;
     return with_record_occ(R, [&](auto o, auto ro) -> int {
         ApproxArgsT<decltype(o)> A;
-        SX_TRY(approx_args(ctx, A, R.d_c, o, ro, R.N, R.sigma, d_patterns, d_offsets, count, max_edits));
-        return approx_count(ctx, A, d_hit_offsets, total_hits_out);
+        SX_TRY(approx_args(ctx, A, R.d_c, o, ro, R.N, R.sigma, d_patterns, d_offsets, count, max_edits, search_flags));
+        return approx_count(ctx, A, search_flags, d_hit_offsets, total_hits_out);
     });
 }
 
 int sx_approx_emit_record(sx_ctx *ctx, const sx_index_rec &R, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, int max_edits,
-                          const uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t total_hits)
+                          const uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t total_hits, uint32_t search_flags)
 {
     if (!ctx || !d_hit_offsets || !d_hits || ((uintptr_t)d_hits & 15) || count == 0 || max_edits < 0 || total_hits == 0) return SX_E_ARG;
     return with_record_occ(R, [&](auto o, auto ro) -> int {
         ApproxArgsT<decltype(o)> A;
-        SX_TRY(approx_args(ctx, A, R.d_c, o, ro, R.N, R.sigma, d_patterns, d_offsets, count, max_edits));
+        SX_TRY(approx_args(ctx, A, R.d_c, o, ro, R.N, R.sigma, d_patterns, d_offsets, count, max_edits, search_flags));
         SX_TRY(approx_workspace(ctx, A));
-        return approx_emit(ctx, A, d_hit_offsets, d_hits, total_hits);
+        return approx_emit(ctx, A, search_flags, d_hit_offsets, d_hits, total_hits);
     });
 }
 
 extern "C" {
+
+int sx_bwt_approx_search_dev_ex(sx_ctx *ctx, const uint32_t *d_c_table, const uint32_t *d_o_table, const uint32_t *d_ro_table, uint64_t N,
+                                uint32_t sigma, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, int max_edits,
+                                uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t hit_capacity, uint64_t *total_hits_out,
+                                uint32_t search_flags)
+{
+    return approx_search_dev(ctx, d_c_table, OccFull{d_o_table}, OccFull{d_ro_table}, N, sigma, d_patterns, d_offsets, count, max_edits,
+                             d_hit_offsets, d_hits, hit_capacity, total_hits_out, search_flags);
+}
 
 int sx_bwt_approx_search_dev(sx_ctx *ctx, const uint32_t *d_c_table, const uint32_t *d_o_table,
                              const uint32_t *d_ro_table, uint64_t N, uint32_t sigma, const uint8_t *d_patterns,
                              const uint32_t *d_offsets, uint32_t count, int max_edits, uint64_t *d_hit_offsets,
                              sx_approx_hit *d_hits, uint64_t hit_capacity, uint64_t *total_hits_out)
 {
-    return approx_search_dev(ctx, d_c_table, OccFull{d_o_table}, OccFull{d_ro_table}, N, sigma, d_patterns, d_offsets, count, max_edits,
-                             d_hit_offsets, d_hits, hit_capacity, total_hits_out);
+    return sx_bwt_approx_search_dev_ex(ctx, d_c_table, d_o_table, d_ro_table, N, sigma, d_patterns, d_offsets, count, max_edits, d_hit_offsets,
+                                       d_hits, hit_capacity, total_hits_out, 0);
+}
+
+int sx_bwt_approx_search_compact_dev_ex(sx_ctx *ctx, const uint32_t *d_c_table, const uint8_t *d_occ, const uint8_t *d_rocc, uint64_t N,
+                                        uint32_t sigma, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, int max_edits,
+                                        uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t hit_capacity, uint64_t *total_hits_out,
+                                        uint32_t search_flags)
+{
+    if (sigma > 128 || (((uintptr_t)d_occ | (uintptr_t)d_rocc) & 15u)) return SX_E_ARG; // (the layout of sx_occ.hpp)
+    const uint32_t stride = occ_stride(sigma);
+    return approx_search_dev(ctx, d_c_table, OccCompact{d_occ, stride}, OccCompact{d_rocc, stride}, N, sigma, d_patterns, d_offsets, count,
+                             max_edits, d_hit_offsets, d_hits, hit_capacity, total_hits_out, search_flags);
 }
 
 int sx_bwt_approx_search_compact_dev(sx_ctx *ctx, const uint32_t *d_c_table, const uint8_t *d_occ, const uint8_t *d_rocc, uint64_t N,
                                      uint32_t sigma, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, int max_edits,
                                      uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t hit_capacity, uint64_t *total_hits_out)
 {
-    if (sigma > 128 || (((uintptr_t)d_occ | (uintptr_t)d_rocc) & 15u)) return SX_E_ARG; // (the layout of sx_occ.hpp)
-    const uint32_t stride = occ_stride(sigma);
-    return approx_search_dev(ctx, d_c_table, OccCompact{d_occ, stride}, OccCompact{d_rocc, stride}, N, sigma, d_patterns, d_offsets, count,
-                             max_edits, d_hit_offsets, d_hits, hit_capacity, total_hits_out);
+    return sx_bwt_approx_search_compact_dev_ex(ctx, d_c_table, d_occ, d_rocc, N, sigma, d_patterns, d_offsets, count, max_edits, d_hit_offsets,
+                                               d_hits, hit_capacity, total_hits_out, 0);
+}
+
+int sx_bwt_approx_search_packed_dev_ex(sx_ctx *ctx, const uint32_t *d_c_table, const uint8_t *d_occ, const uint8_t *d_rocc, uint64_t N,
+                                       uint32_t sigma, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, int max_edits,
+                                       uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t hit_capacity, uint64_t *total_hits_out,
+                                       uint32_t search_flags)
+{
+    if (sigma > kOccPackedMaxSigma || (((uintptr_t)d_occ | (uintptr_t)d_rocc) & 15u)) return SX_E_ARG; // (the layout of sx_occ.hpp)
+    return approx_search_dev(ctx, d_c_table, OccPacked{d_occ}, OccPacked{d_rocc}, N, sigma, d_patterns, d_offsets, count, max_edits,
+                             d_hit_offsets, d_hits, hit_capacity, total_hits_out, search_flags);
 }
 
 int sx_bwt_approx_search_packed_dev(sx_ctx *ctx, const uint32_t *d_c_table, const uint8_t *d_occ, const uint8_t *d_rocc, uint64_t N,
                                     uint32_t sigma, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, int max_edits,
                                     uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t hit_capacity, uint64_t *total_hits_out)
 {
-    if (sigma > kOccPackedMaxSigma || (((uintptr_t)d_occ | (uintptr_t)d_rocc) & 15u)) return SX_E_ARG; // (the layout of sx_occ.hpp)
-    return approx_search_dev(ctx, d_c_table, OccPacked{d_occ}, OccPacked{d_rocc}, N, sigma, d_patterns, d_offsets, count, max_edits,
-                             d_hit_offsets, d_hits, hit_capacity, total_hits_out);
+    return sx_bwt_approx_search_packed_dev_ex(ctx, d_c_table, d_occ, d_rocc, N, sigma, d_patterns, d_offsets, count, max_edits, d_hit_offsets,
+                                              d_hits, hit_capacity, total_hits_out, 0);
 }
 
 int sx_bwt_approx_search(sx_ctx *ctx, const uint32_t *c_table, const uint32_t *o_table, const uint32_t *ro_table,
                          uint64_t N, uint32_t sigma, const uint8_t *patterns, const uint32_t *offsets, uint32_t count,
                          int max_edits, uint64_t *hit_offsets, sx_approx_hit **hits_out, uint64_t *total_hits_out)
 {
+    return sx_bwt_approx_search_ex(ctx, c_table, o_table, ro_table, N, sigma, patterns, offsets, count, max_edits, hit_offsets, hits_out,
+                                   total_hits_out, 0);
+}
+
+int sx_bwt_approx_search_ex(sx_ctx *ctx, const uint32_t *c_table, const uint32_t *o_table, const uint32_t *ro_table, uint64_t N,
+                            uint32_t sigma, const uint8_t *patterns, const uint32_t *offsets, uint32_t count, int max_edits,
+                            uint64_t *hit_offsets, sx_approx_hit **hits_out, uint64_t *total_hits_out, uint32_t search_flags)
+{
     if (!ctx || !hit_offsets || !hits_out || !total_hits_out) return SX_E_ARG;
     *hits_out = nullptr;
     *total_hits_out = 0;
     ApproxArgs A;
-    SX_TRY(approx_args(ctx, A, c_table, OccFull{o_table}, OccFull{ro_table}, N, sigma, patterns, offsets, count, max_edits));
+    SX_TRY(approx_args(ctx, A, c_table, OccFull{o_table}, OccFull{ro_table}, N, sigma, patterns, offsets, count, max_edits, search_flags));
     if (max_edits < 0 || count == 0) {
         memset(hit_offsets, 0, ((size_t)count + 1) * sizeof(uint64_t));
         return 0;
@@ -517,12 +729,12 @@ int sx_bwt_approx_search(sx_ctx *ctx, const uint32_t *c_table, const uint32_t *o
     A.pat = d_p;
     A.off = d_off;
     uint64_t total = 0;
-    SX_TRY(approx_count(ctx, A, d_ho, &total));
+    SX_TRY(approx_count(ctx, A, search_flags, d_ho, &total));
     SX_CHECK(hipMemcpyAsync(hit_offsets, d_ho, ((size_t)count + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (total) {
         SX_TRY(sx_slab_ensure(ctx, SX_SLAB_M, total * sizeof(sx_approx_hit)));
         sx_approx_hit *d_hits = (sx_approx_hit *)ctx->slab[SX_SLAB_M].p;
-        SX_TRY(approx_emit(ctx, A, d_ho, d_hits, total));
+        SX_TRY(approx_emit(ctx, A, search_flags, d_ho, d_hits, total));
         sx_approx_hit *h = (sx_approx_hit *)malloc(total * sizeof(sx_approx_hit));
         if (!h) return sx_fail_msg(ctx, SX_E_NOMEM, "approximate search: host hit array");
         const hipError_t e = hipMemcpyAsync(h, d_hits, total * sizeof(sx_approx_hit), hipMemcpyDeviceToHost, ctx->stream);

@@ -315,7 +315,7 @@ int sx_best_rounds(sx_ctx *ctx, sx_best_state &S, const sx_best_batch &B, uint64
                 sx_sam_remap(ctx, cur, B.d_tabs + (size_t)r * 256, B.d_pat, cur_lo, cur_hi);
                 pat = B.d_pat;
             }
-            SX_TRY(sx_approx_count_record(ctx, B.recs[r], pat, cur_off, cur_count, (int)d, B.d_ho + r * B.ho_stride, &rec_total[r]));
+            SX_TRY(sx_approx_count_record(ctx, B.recs[r], pat, cur_off, cur_count, (int)d, B.d_ho + r * B.ho_stride, &rec_total[r], B.search_flags));
             round_total += rec_total[r];
         }
         if (used + round_total >= (1ull << 32)) return sx_fail_msg(ctx, SX_E_ARG, "approximate search: 2^32 hits or more in one call");
@@ -354,7 +354,7 @@ int sx_best_rounds(sx_ctx *ctx, sx_best_state &S, const sx_best_batch &B, uint64
                     sx_sam_remap(ctx, f_bytes, B.d_tabs + (size_t)r * 256, B.d_pat, 0, found_bytes);
                     pat = B.d_pat;
                 }
-                SX_TRY(sx_approx_emit_record(ctx, B.recs[r], pat, f_off, n_found, (int)d, fho, B.d_raw + used, rec_total[r]));
+                SX_TRY(sx_approx_emit_record(ctx, B.recs[r], pat, f_off, n_found, (int)d, fho, B.d_raw + used, rec_total[r], B.search_flags));
             }
             used += rec_total[r];
         }
@@ -427,6 +427,16 @@ int sx_bwt_best_search_dev(sx_ctx *ctx, const uint32_t *d_c_table, const uint32_
                            const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, int max_edits, uint8_t *d_stratum,
                            uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t hit_capacity, uint64_t *total_hits_out)
 {
+    return sx_bwt_best_search_dev_ex(ctx, d_c_table, d_o_table, d_ro_table, N, sigma, d_patterns, d_offsets, count, max_edits, d_stratum, d_hit_offsets,
+                                     d_hits, hit_capacity, total_hits_out, 0);
+}
+
+int sx_bwt_best_search_dev_ex(sx_ctx *ctx, const uint32_t *d_c_table, const uint32_t *d_o_table, const uint32_t *d_ro_table, uint64_t N, uint32_t sigma,
+                              const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, int max_edits, uint8_t *d_stratum,
+                              uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t hit_capacity, uint64_t *total_hits_out,
+                              uint32_t search_flags)
+{
+    if (search_flags & ~(uint32_t)SX_SEARCH_NO_INDELS) return SX_E_ARG;
     if (!ctx || !d_hit_offsets || !total_hits_out || ((uintptr_t)d_hits & 15) || (count && !d_stratum)) return SX_E_ARG;
     if (!d_c_table || !d_o_table || !d_offsets || N == 0 || N > 0xFFFFFFFFull || sigma < 2 || sigma > 256 || max_edits > SX_APPROX_MAX_EDITS)
         return SX_E_ARG;
@@ -450,7 +460,7 @@ int sx_bwt_best_search_dev(sx_ctx *ctx, const uint32_t *d_c_table, const uint32_
     sx_dev_scope T;
     sx_best_batch B = {};
     B.recs = &R, B.n_rec = 1, B.d_bytes = d_patterns, B.bytes_total = h[1], B.d_off = d_offsets, B.p_lo = h[0], B.p_hi = h[1];
-    B.count = count, B.gsize = 1, B.k = max_edits;
+    B.count = count, B.gsize = 1, B.k = max_edits, B.search_flags = search_flags;
     SX_TRY(T.take(ctx, &B.d_ho, (size_t)count + 1));
     B.ho_stride = (uint64_t)count + 1, B.d_stratum = d_stratum;
     // the rounds leave their hits in the caller's array; the place step orders them through the M slab

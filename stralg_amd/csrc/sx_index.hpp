@@ -60,23 +60,25 @@ static inline bool sx_map_record_check(const sx_map_record &R, uint32_t min_sigm
 }
 
 // the bits of a mapping call's flags word that mean something (sx_map_reads_stream_ex, sx_index_map_reads_ex, sx_map_reads_limit)
-constexpr uint32_t sx_map_known_flags = SX_MAP_BOTH_STRANDS | SX_MAP_BEST_STRATUM;
+constexpr uint32_t sx_map_known_flags = SX_MAP_BOTH_STRANDS | SX_MAP_BEST_STRATUM | SX_MAP_NO_INDELS;
+// the search flags (SX_SEARCH_*) that a mapping call's flags word asks of its searches
+static inline uint32_t sx_map_search_flags(uint32_t flags) { return (flags & SX_MAP_NO_INDELS) ? (uint32_t)SX_SEARCH_NO_INDELS : 0u; }
 
 // sx_map.hip: the mapper's loop over reads and an index that both lie on ctx's device (flags: those of
 // sx_map_reads_stream_ex); h_seq_off: the host's copy of reads.d_seq_off, or null (the loop then reads the two entries a
 // batch needs back)
 int sx_map_reads_core(sx_ctx *ctx, const sx_index *idx, const sx_fastq_dev &reads, const uint32_t *h_seq_off, int edits, uint32_t flags,
                       sx_sink_fn sink, void *user);
-// sx_approx.hip: sx_bwt_approx_search_dev over the tables of a record, full, compact or packed
+// sx_approx.hip: sx_bwt_approx_search_dev_ex over the tables of a record, full, compact or packed (search_flags: SX_SEARCH_*)
 int sx_approx_search_record(sx_ctx *ctx, const sx_index_rec &R, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, int max_edits,
-                            uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t hit_capacity, uint64_t *total_hits_out);
+                            uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t hit_capacity, uint64_t *total_hits_out, uint32_t search_flags);
 // the two passes of that search on their own (sx_best.hip runs them over different pattern sets).  Count: the hit offsets
 // (count + 1 entries) and the total of `count` >= 1 patterns.  Emit: the hits of patterns whose offsets are known (total of
 // them, total >= 1) to d_hits; hit.query is the pattern's number in this set
 int sx_approx_count_record(sx_ctx *ctx, const sx_index_rec &R, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, int max_edits,
-                           uint64_t *d_hit_offsets, uint64_t *total_hits_out);
+                           uint64_t *d_hit_offsets, uint64_t *total_hits_out, uint32_t search_flags);
 int sx_approx_emit_record(sx_ctx *ctx, const sx_index_rec &R, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, int max_edits,
-                          const uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t total_hits);
+                          const uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t total_hits, uint32_t search_flags);
 // sx_map.hip: out[i] = table[seqs[i]] for i in [lo, hi) (a record's 256-byte symbol table; sam_remap_kernel)
 void sx_sam_remap(sx_ctx *ctx, const uint8_t *d_seqs, const uint8_t *d_table, uint8_t *d_out, uint64_t lo, uint64_t hi);
 
@@ -110,6 +112,7 @@ struct sx_best_batch {
     uint64_t p_lo, p_hi;
     uint32_t count, gsize; // patterns; patterns a group (1, or 2: both strands of a read)
     int k;
+    uint32_t search_flags; // SX_SEARCH_*: the strata and the hits are those of the search with these flags
     uint64_t *d_ho;        // n_rec x ho_stride entries of scratch (the count passes' hit offsets), ho_stride >= count + 1
     uint64_t ho_stride;
     uint8_t *d_stratum;    // a byte a group

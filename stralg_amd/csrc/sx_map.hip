@@ -119,6 +119,7 @@ struct MapReads {
     const uint32_t *h_seq_off; // the host's copy of fq->d_seq_off, or null (the two entries a batch needs are read back)
     const uint16_t *d_flags;   // a FLAG per read, or null
     uint32_t group; // 0, or (SX_MAP_BEST_STRATUM) the reads that share a stratum: 1, or 2 for the strands of a read
+    uint32_t search_flags; // SX_SEARCH_* of every search of the call (SX_MAP_NO_INDELS)
 };
 
 struct MapBufs { // what a mapping call holds on the device beside the hits' room
@@ -155,7 +156,7 @@ static int batch_bytes(sx_ctx *ctx, const MapReads &R, uint32_t q0, uint32_t bat
 // M.seg[records] and *hits_out <- how many there are.  SX_E_CAPACITY: the room is too small for the *hits_out hits known of
 // so far
 static int search_batch(sx_ctx *ctx, const sx_index *idx, const MapReads &R, MapBufs &M, const HitRoom &room, uint32_t q0, uint32_t batch,
-                        int edits, uint64_t *hits_out)
+                        int edits, uint32_t search_flags, uint64_t *hits_out)
 {
     uint64_t p_lo, p_hi;
     SX_TRY(batch_bytes(ctx, R, q0, batch, &p_lo, &p_hi));
@@ -168,7 +169,7 @@ static int search_batch(sx_ctx *ctx, const sx_index *idx, const MapReads &R, Map
         uint64_t tot = 0;
         // (whichever form the record has: the hits and their order are the same)
         const int rc = sx_approx_search_record(ctx, idx->recs[r], M.d_pat, R.fq->d_seq_off + q0, batch, edits, M.d_ho + r * M.stride,
-                                               room.d_raw + used, room.cap - used, &tot);
+                                               room.d_raw + used, room.cap - used, &tot, search_flags);
         if (rc == SX_E_CAPACITY) *hits_out = used + tot;
         if (rc != 0) return rc;
         M.seg[r] = used;
@@ -218,7 +219,7 @@ static int merge_batch(sx_ctx *ctx, MapBufs &M, const HitRoom &room, uint32_t ba
 static int plain_batch(sx_ctx *ctx, const sx_index *idx, const MapReads &R, MapBufs &M, const HitRoom &room, int edits, uint32_t q0,
                        uint32_t batch, uint64_t *hits_out)
 {
-    SX_TRY(search_batch(ctx, idx, R, M, room, q0, batch, edits, hits_out));
+    SX_TRY(search_batch(ctx, idx, R, M, room, q0, batch, edits, R.search_flags, hits_out));
     return *hits_out ? merge_batch(ctx, M, room, batch) : 0;
 }
 
@@ -230,7 +231,7 @@ static int best_batch(sx_ctx *ctx, const sx_index *idx, const MapReads &R, MapBu
     B.recs = idx->recs.data(), B.n_rec = (uint32_t)idx->recs.size(), B.d_tabs = idx->d_tabs, B.d_pat = M.d_pat;
     B.d_bytes = R.fq->d_seqs, B.bytes_total = R.fq->seq_bytes, B.d_off = R.fq->d_seq_off + q0;
     SX_TRY(batch_bytes(ctx, R, q0, batch, &B.p_lo, &B.p_hi));
-    B.count = batch, B.gsize = R.group, B.k = edits;
+    B.count = batch, B.gsize = R.group, B.k = edits, B.search_flags = R.search_flags;
     B.d_ho = M.d_ho, B.ho_stride = M.stride, B.d_stratum = S.d_stratum;
     B.d_raw = room.d_raw, B.raw_cap = room.cap, B.go_on_counting = false;
     SX_TRY(sx_best_rounds(ctx, S, B, hits_out));
@@ -384,14 +385,15 @@ int sx_map_reads_core(sx_ctx *ctx, const sx_index *idx, const sx_fastq_dev &read
     for (const sx_index_rec &R : idx->recs) records_ok = records_ok && sx_map_dims_ok(R.N, R.sigma, 2);
     SX_TRY(map_check(ctx, reads.count, n_records, flags, records_ok));
     const bool best = (flags & SX_MAP_BEST_STRATUM) != 0;
-    if (!(flags & SX_MAP_BOTH_STRANDS)) return map_reads_loop(ctx, idx, MapReads{&reads, h_seq_off, nullptr, best ? 1u : 0u}, edits, sink, user);
+    const uint32_t sflags = sx_map_search_flags(flags);
+    if (!(flags & SX_MAP_BOTH_STRANDS)) return map_reads_loop(ctx, idx, MapReads{&reads, h_seq_off, nullptr, best ? 1u : 0u, sflags}, edits, sink, user);
     SX_CHECK(hipSetDevice(ctx->device));
     sx_fastq_dev both = {};
     sx_dev_scope F;
     uint16_t *d_flags;
     SX_TRY(F.take(ctx, &d_flags, 2 * (size_t)reads.count));
     SX_TRY(sx_fastq_strands_dev(ctx, &reads, &both, d_flags)); // (syncs: the callers' uploads from pageable memory are done)
-    const int rc = map_reads_loop(ctx, idx, MapReads{&both, nullptr, d_flags, best ? 2u : 0u}, edits, sink, user);
+    const int rc = map_reads_loop(ctx, idx, MapReads{&both, nullptr, d_flags, best ? 2u : 0u, sflags}, edits, sink, user);
     sx_fastq_dev_free(&both);
     return rc;
 }

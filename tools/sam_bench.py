@@ -11,9 +11,12 @@ SX_MAP_BOTH_STRANDS (kept in profiles/strands_bench_2p28.json).  --best adds, pe
 batch (wall, kernel ms of the search and of the select class, hits and lines), its rounds replayed through the public
 calls (per round: groups in and found; the count pass, the two selects with their bytes against the probe's copy rate, the
 emit pass as the difference of the search over the found set with and without its hits) and the streamed call with
-SX_MAP_BEST_STRATUM beside the plain one of the same run (kept in profiles/best_bench_2p28.json).
+SX_MAP_BEST_STRATUM beside the plain one of the same run (kept in profiles/best_bench_2p28.json).  --no-indels adds, per k
+and on the same reads, the search with indels=False (SX_SEARCH_NO_INDELS): its hits, lines and text bytes, the search's
+kernel ms (every run: the spread), layout and emit over its hits, and the streamed call with SX_MAP_NO_INDELS (with --best:
+also with both flags) beside the plain one (kept in profiles/no_indels_bench_2p28.json).
 
-    python tools/sam_bench.py [--log2n 28] [--reads 1000000] [--window-mib 1024] [--repeats 5] [--both-strands] [--best]
+    python tools/sam_bench.py [--log2n 28] [--reads 1000000] [--window-mib 1024] [--repeats 5] [--both-strands] [--best] [--no-indels]
 """
 import argparse
 import ctypes as C
@@ -40,6 +43,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=1, help="time layout, emit and the streamed call so many times")
     ap.add_argument("--both-strands", action="store_true", help="also the strand kernel and the streamed call on both strands")
     ap.add_argument("--best", action="store_true", help="also the best-stratum search, its rounds and the streamed call with best=True")
+    ap.add_argument("--no-indels", action="store_true", help="also the search, the text and the streamed call without indels")
     args = ap.parse_args()
     import torch
 
@@ -122,13 +126,16 @@ def main():
            "membw_probe_GBps": {"read": round(probe["read"], 1), "fill": round(probe["fill"], 1), "copy": round(probe["copy"], 1)},
            "pinned_d2h_copy_GBps": round(max(link), 2)}
 
-    for k in [int(x) for x in args.ks.split(",")]:
-        total = ctx.bwt_approx_search_dev(d_c, d_o, d_ro, N, sigma, d_pat, d_off, R, k, d_hoff)
+    def text_of_search(k, indels):
+        """the figures of the search and of the text of its hits"""
+        total = ctx.bwt_approx_search_dev(d_c, d_o, d_ro, N, sigma, d_pat, d_off, R, k, d_hoff, indels=indels)
         d_hits = torch.zeros(max(total, 1) * 32, dtype=torch.uint8, device="cuda")
         d_boff = torch.zeros(total + 1, dtype=torch.int64, device="cuda")
         torch.cuda.synchronize()
-        _, _, search_ms = profiled("search", lambda: ctx.bwt_approx_search_dev(d_c, d_o, d_ro, N, sigma, d_pat, d_off, R, k,
-                                                                             d_hoff, d_hits, total))
+        search_runs = [profiled("search", lambda: ctx.bwt_approx_search_dev(d_c, d_o, d_ro, N, sigma, d_pat, d_off, R, k,
+                                                                           d_hoff, d_hits, total, indels=indels))
+                       for _ in range(args.repeats)]
+        search_ms = min(r[2] for r in search_runs)
         batch = ctx.sam_batch(d_hits, total, d_sa, N, d_names, d_name_off, d_seqs, d_off, d_quals, d_off, R, d_rname,
                               d_rname_off, 1)
         ctx.sam_layout_dev(batch, d_boff)  # warm-up
@@ -147,19 +154,26 @@ def main():
         emit_wall, emit_ms = min(r[1] for r in emit_runs), min(r[2] for r in emit_runs)
         layout_bytes = total * (32 + 16) + lines * 4
         emit_bytes = nbytes + lines * 4 + total * 32
-        out[f"k{k}"] = {"hits": int(total), "lines": lines, "text_bytes": int(nbytes),
-                        "search_kernel_ms": round(search_ms, 3),
-                        "layout_ms": round(layout_ms, 3), "layout_bytes": int(layout_bytes),
-                        "layout_GBps": round(layout_bytes / (layout_ms * 1e-3) / 1e9, 1),
-                        "emit_ms": round(emit_ms, 3), "emit_wall_ms": round(emit_wall * 1e3, 3), "emit_bytes": int(emit_bytes),
-                        "emit_GBps": round(emit_bytes / (emit_ms * 1e-3) / 1e9, 1),
-                        "emit_fraction_of_fill": round(emit_bytes / (emit_ms * 1e-3) / 1e9 / probe["fill"], 3),
-                        "lines_per_s": round(lines / ((layout_ms + emit_ms) * 1e-3), 1)}
+        entry = {"hits": int(total), "lines": lines, "text_bytes": int(nbytes),
+                 "search_kernel_ms": round(search_ms, 3),
+                 "layout_ms": round(layout_ms, 3), "layout_bytes": int(layout_bytes),
+                 "layout_GBps": round(layout_bytes / (layout_ms * 1e-3) / 1e9, 1),
+                 "emit_ms": round(emit_ms, 3), "emit_wall_ms": round(emit_wall * 1e3, 3), "emit_bytes": int(emit_bytes),
+                 "emit_GBps": round(emit_bytes / (emit_ms * 1e-3) / 1e9, 1),
+                 "emit_fraction_of_fill": round(emit_bytes / (emit_ms * 1e-3) / 1e9 / probe["fill"], 3),
+                 "lines_per_s": round(lines / ((layout_ms + emit_ms) * 1e-3), 1)}
         if args.repeats > 1:
-            out[f"k{k}"]["layout_ms_runs"] = [round(r[2], 3) for r in layout_runs]
-            out[f"k{k}"]["emit_ms_runs"] = [round(r[2], 3) for r in emit_runs]
+            entry["search_kernel_ms_runs"] = [round(r[2], 3) for r in search_runs]
+            entry["layout_ms_runs"] = [round(r[2], 3) for r in layout_runs]
+            entry["emit_ms_runs"] = [round(r[2], 3) for r in emit_runs]
         del d_hits, d_boff
         torch.cuda.empty_cache()
+        return entry
+
+    for k in [int(x) for x in args.ks.split(",")]:
+        out[f"k{k}"] = text_of_search(k, True)
+        if args.no_indels:
+            out[f"k{k}"]["no_indels"] = text_of_search(k, False)
         if args.best:
             out[f"k{k}"]["best"] = best_rounds(ctx, torch, profiled, probe, d_c, d_o, d_ro, N, sigma, d_pat, d_off, R, L, k, args.repeats)
     # ---- the streamed form: sx_map_reads_stream (host tables and FASTQ image in, SAM text out through a sink that discards)
@@ -208,6 +222,13 @@ def main():
                                     "call_GBps": round(nbytes / wall / 1e9, 2)}
         if args.repeats > 1:
             out[f"k{k}"]["streamed"]["call_wall_ms_runs"] = walls
+        if args.no_indels:
+            for key, kw in [("streamed", dict(indels=False))] + ([("streamed_best", dict(indels=False, best=True))] if args.best else []):
+                f_wall, f_seen, f_walls = streamed(k, **kw)
+                out[f"k{k}"]["no_indels"][key] = {"call_wall_ms": round(f_wall * 1e3, 1), "call_wall_ms_runs": f_walls,
+                                                  "text_bytes": int(sum(b for _, b in f_seen)), "windows": len(f_seen),
+                                                  "plain_call_wall_ms": round(wall * 1e3, 1)}
+            assert out[f"k{k}"]["no_indels"]["streamed"]["text_bytes"] == out[f"k{k}"]["no_indels"]["text_bytes"]
         if args.best:
             for key, kw in [("streamed_best", dict(best=True))] + ([("streamed_best_both_strands", dict(best=True, both_strands=True))] if args.both_strands else []):
                 b_wall, b_seen, b_walls = streamed(k, **kw)

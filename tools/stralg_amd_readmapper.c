@@ -33,6 +33,11 @@
  *                                                   -d e* prints for it, e* the smallest edit count in 0 .. K at which
  *                                                   any are printed (with --both-strands: over both strands of the read
  *                                                   together); a read without a match within K edits prints nothing
+ *   --no-indels                                     with -d K: mismatches only -- of the lines of -d K those whose CIGAR is
+ *                                                   "<read length>M", i.e. every placement of a read within K
+ *                                                   substitutions, once; with --best the strata are the smallest number
+ *                                                   of substitutions; goes with --both-strands, --compact, --packed,
+ *                                                   --sa-sample and -i
  *   (--preprocess, --edits and --in-memory are accepted for -p, -d and -i)
  *
  * Index file: u32 record count; per record, last FASTA record first, its name as u32 length + bytes + NUL, then the
@@ -166,6 +171,8 @@ static int usage(const char *self, int status)
     fprintf(stderr, "                                          have FLAG 16\n");
     fprintf(stderr, "       --best                             with -d K: per read only the matches of the smallest edit count\n");
     fprintf(stderr, "                                          in 0 .. K that has any (with --both-strands: over both strands)\n");
+    fprintf(stderr, "       --no-indels                        with -d K: mismatches only, every placement within K substitutions\n");
+    fprintf(stderr, "                                          once (with --best: the smallest number of substitutions)\n");
     return status;
 }
 
@@ -190,6 +197,8 @@ int main(int argc, char **argv)
             map_flags |= SX_MAP_BOTH_STRANDS;
         } else if (!strcmp(s, "--best")) {
             map_flags |= SX_MAP_BEST_STRATUM;
+        } else if (!strcmp(s, "--no-indels")) {
+            map_flags |= SX_MAP_NO_INDELS;
         } else if (!strcmp(s, "--sa-sample")) {
             if (++a >= argc) return usage(argv[0], EXIT_FAILURE);
             const long dist = strtol(argv[a], NULL, 10);
