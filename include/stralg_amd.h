@@ -383,6 +383,32 @@ typedef struct sx_sam_batch_ex {
 int sx_sam_layout_dev_ex(sx_ctx *ctx, const sx_sam_batch_ex *batch, uint64_t *d_byte_offsets, uint64_t *total_bytes_out);
 int sx_sam_emit_dev_ex(sx_ctx *ctx, const sx_sam_batch_ex *batch, const uint64_t *d_byte_offsets, uint64_t total_bytes, uint64_t byte_lo,
                        uint64_t byte_hi, uint8_t *d_out);
+/* The same with two optional fields between QUAL and the newline of every line:
+ *     ...<seq>\t<qual>\tNM:i:<nm>\tMD:Z:<md>\n
+ * d_text_list[r] (device memory, n_records addresses) is the remapped text of record rank r, as many bytes as its suffix
+ * array has entries with the sentinel last; d_letters (n_records x 256 bytes) has at [r * 256 + c] the letter behind code c
+ * of rank r.  NM and MD are those of the line's POS, CIGAR and SEQ over the record's letters: the CIGAR is walked from POS - 1;
+ * an M step with equal bytes extends the match run, one with unequal bytes prints "<run><letter of the text>", sets the run
+ * to 0 and adds 1 to NM; an I run adds its length to NM; a D run prints "<run>^<the deleted letters>", sets the run to 0 and
+ * adds its length to NM; the last run is printed at the end, so MD begins and ends with a number.  Bytes are compared as they
+ * are.  The fields are rendered once per hit, from the window at its first position (every row of a hit of the search is a
+ * suffix with the same first match_length symbols); a search of at most 8 operations gives one digit of NM and at most 61
+ * bytes of MD.  SX_E_ARG from the layout, as for a hit outside the batch: a hit with a line whose window does not lie in
+ * front of the record's sentinel, or whose walk finds more than SX_APPROX_MAX_EDITS differences.
+ * d_positions / d_pos_off (both or neither): the hits' positions located beforehand, as the mapper has them of a sampled
+ * suffix array -- hit h prints d_positions[d_pos_off[h] - pos_base + i] + 1, i = 0 .. R - L - 1, and no suffix array is
+ * read (the lengths of d_sa_len_list, or sa_len, still bound R and give the texts' lengths). */
+typedef struct sx_sam_batch_tags {
+    sx_sam_batch_ex ex;
+    const uint8_t *const *d_text_list;
+    const uint8_t *d_letters;
+    const uint32_t *d_positions;
+    const uint64_t *d_pos_off;
+    uint64_t pos_base;
+} sx_sam_batch_tags;
+int sx_sam_layout_dev_tags(sx_ctx *ctx, const sx_sam_batch_tags *batch, uint64_t *d_byte_offsets, uint64_t *total_bytes_out);
+int sx_sam_emit_dev_tags(sx_ctx *ctx, const sx_sam_batch_tags *batch, const uint64_t *d_byte_offsets, uint64_t total_bytes, uint64_t byte_lo,
+                         uint64_t byte_hi, uint8_t *d_out);
 
 /* A FASTQ image indexed on the host (one pass of memchr over the file): read q's name is names[name_off[q] ..
  * name_off[q+1]), its sequence seqs[seq_off[q] ..), its quality quals[qual_off[q] ..): the raw bytes of the record's
@@ -443,8 +469,16 @@ int sx_map_reads_stream(sx_ctx *ctx, const sx_map_record *records, uint32_t n_re
  * text is that of the same call without the flag with every line removed whose CIGAR is not "<length of SEQ>M", i.e. the
  * placements of every read within `edits` substitutions, each once.  With SX_MAP_BEST_STRATUM the strata are taken under
  * the flag (the smallest number of substitutions).  It composes with the other two flags in any combination and does not
- * change the limit on reads x records; edits = 0 gives the text without the flag.  Bits 2 and 4 stay unknown. */
-enum { SX_MAP_BOTH_STRANDS = 1, SX_MAP_BEST_STRATUM = 8, SX_MAP_NO_INDELS = 16 };
+ * change the limit on reads x records; edits = 0 gives the text without the flag.  Bits 2 and 4 stay unknown.
+ * Tags.  With SX_MAP_TAGS every line has "\tNM:i:<nm>\tMD:Z:<md>" between QUAL and its newline: the
+ * edit distance and the mismatch string of the line's own POS, CIGAR and SEQ over the record's letters as the FASTA gives
+ * them (the walk of sx_sam_batch_tags; FLAG 16 lines are in forward orientation already), rendered on the device once per
+ * hit.  The lines and their order are those of the same call without the flag.  It composes with the other three flags in
+ * any combination and with every form of the index, and does not change the limit on reads x records.  The records'
+ * remapped strings must be on the device: an index with a record that was given without its string (sx_index_from_tables),
+ * and sx_map_reads_stream_ex, whose records have none, answer SX_E_ARG before anything is launched or sunk.  Bit 32 stays
+ * unknown. */
+enum { SX_MAP_BOTH_STRANDS = 1, SX_MAP_BEST_STRATUM = 8, SX_MAP_NO_INDELS = 16, SX_MAP_TAGS = 64 };
 int sx_map_reads_stream_ex(sx_ctx *ctx, const sx_map_record *records, uint32_t n_records, const uint8_t *fastq, size_t fastq_len,
                            int edits, uint32_t flags, sx_sink_fn sink, void *user);
 /* the limit of a mapping call on its reads and records: 0, or SX_E_ARG when reads x records (twice that with
@@ -515,7 +549,8 @@ int sx_index_add_record(sx_ctx *ctx, sx_index *idx, const sx_index_source *sourc
  * sx_map_reads_stream. */
 int sx_index_map_reads(sx_ctx *ctx, const sx_index *idx, const uint8_t *fastq, size_t fastq_len, int edits, sx_sink_fn sink,
                        void *user);
-/* the same with the flags of sx_map_reads_stream_ex (SX_MAP_BOTH_STRANDS, SX_MAP_BEST_STRATUM, SX_MAP_NO_INDELS) */
+/* the same with the flags of sx_map_reads_stream_ex (SX_MAP_BOTH_STRANDS, SX_MAP_BEST_STRATUM, SX_MAP_NO_INDELS) and with
+ * SX_MAP_TAGS, which needs every record's string in the index */
 int sx_index_map_reads_ex(sx_ctx *ctx, const sx_index *idx, const uint8_t *fastq, size_t fastq_len, int edits, uint32_t flags,
                           sx_sink_fn sink, void *user);
 typedef struct sx_index_record {

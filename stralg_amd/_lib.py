@@ -75,13 +75,14 @@ CHAIN_EPOCH_LIMIT = 1 << 24  # the look-back epoch has 24 bits: the launch after
 SX_MAP_BOTH_STRANDS = 1
 SX_MAP_BEST_STRATUM = 8
 SX_MAP_NO_INDELS = 16
+SX_MAP_TAGS = 64
 SX_SEARCH_NO_INDELS = 1
 
 
-def map_flags(both_strands=False, best=False, indels=True):
+def map_flags(both_strands=False, best=False, indels=True, tags=False):
     """the flags word of sx_map_reads_stream_ex / sx_index_map_reads_ex"""
     return ((SX_MAP_BOTH_STRANDS if both_strands else 0) | (SX_MAP_BEST_STRATUM if best else 0)
-            | (0 if indels else SX_MAP_NO_INDELS))
+            | (0 if indels else SX_MAP_NO_INDELS) | (SX_MAP_TAGS if tags else 0))
 
 
 def search_flags(indels=True):
@@ -101,6 +102,13 @@ class SamBatch(C.Structure):
 class SamBatchEx(C.Structure):
     """include/stralg_amd.h sx_sam_batch_ex: a batch and a FLAG per read (device memory, uint16)"""
     _fields_ = [("batch", SamBatch), ("d_read_flags", C.c_void_p)]
+
+
+class SamBatchTags(C.Structure):
+    """include/stralg_amd.h sx_sam_batch_tags: a batch with flags (or none), every record's text and table of letters (NM
+    and MD behind QUAL) and, optionally, positions located beforehand"""
+    _fields_ = [("ex", SamBatchEx), ("d_text_list", C.c_void_p), ("d_letters", C.c_void_p), ("d_positions", C.c_void_p),
+                ("d_pos_off", C.c_void_p), ("pos_base", C.c_uint64)]
 
 
 class Fastq(C.Structure):
@@ -236,6 +244,8 @@ def load(path=None):
         "sx_sam_emit_dev": (C.c_int, [vp, C.POINTER(SamBatch), u64p, C.c_uint64, C.c_uint64, C.c_uint64, u8p]),
         "sx_sam_layout_dev_ex": (C.c_int, [vp, C.POINTER(SamBatchEx), u64p, C.POINTER(C.c_uint64)]),
         "sx_sam_emit_dev_ex": (C.c_int, [vp, C.POINTER(SamBatchEx), u64p, C.c_uint64, C.c_uint64, C.c_uint64, u8p]),
+        "sx_sam_layout_dev_tags": (C.c_int, [vp, C.POINTER(SamBatchTags), u64p, C.POINTER(C.c_uint64)]),
+        "sx_sam_emit_dev_tags": (C.c_int, [vp, C.POINTER(SamBatchTags), u64p, C.c_uint64, C.c_uint64, C.c_uint64, u8p]),
         "sx_fastq_index": (C.c_int, [u8p, C.c_size_t, C.POINTER(Fastq)]),
         "sx_fastq_free": (None, [C.POINTER(Fastq)]),
         "sx_map_reads_stream": (C.c_int, [vp, C.POINTER(MapRecord), C.c_uint32, u8p, C.c_size_t, C.c_int, SINK_FN, C.c_void_p]),
@@ -332,7 +342,7 @@ EXPORTS = ["sx_device_count", "sx_device_numa_node", "sx_ctx_create", "sx_ctx_de
            "sx_sam_layout_dev_ex", "sx_sam_emit_dev_ex", "sx_map_reads_stream_ex", "sx_map_reads_limit", "sx_fastq_strands_dev",
            "sx_index_map_reads_ex", "sx_bwt_best_search_dev", "sx_patterns_select_dev", "sx_map_last_stats",
            "sx_bwt_approx_search_dev_ex", "sx_bwt_approx_search_compact_dev_ex", "sx_bwt_approx_search_packed_dev_ex",
-           "sx_bwt_best_search_dev_ex", "sx_bwt_approx_search_ex",
+           "sx_bwt_best_search_dev_ex", "sx_bwt_approx_search_ex", "sx_sam_layout_dev_tags", "sx_sam_emit_dev_tags",
            "sx_synth_dev", "sx_membw_probe", "sx_prim_sort_pairs_dev", "sx_prim_exclusive_sum_dev", "sx_prim_classify_dev"]
 
 

@@ -285,18 +285,31 @@ class Context:
                               _ptr(d_rnames), _ptr(d_rname_off), n_records)
         return batch if d_read_flags is None else _lib.SamBatchEx(batch, _ptr(d_read_flags))
 
+    def sam_batch_tags(self, batch, d_text_list, d_letters, d_positions=None, d_pos_off=None, pos_base=0):
+        """sx_sam_batch_tags of a batch of sam_batch (with flags or without): every line gets NM:i and MD:Z behind QUAL.
+        d_text_list (uint64, one device address per record rank): the records' remapped texts, the sentinel last;
+        d_letters (uint8, 256 per record rank): the letter behind every code.  d_positions (uint32) with d_pos_off (uint64,
+        a first line per hit) and pos_base: positions located beforehand, in place of the suffix arrays' rows.
+        sam_layout_dev / sam_emit_dev send it to the _tags calls."""
+        ex = batch if isinstance(batch, _lib.SamBatchEx) else _lib.SamBatchEx(batch, None)
+        return _lib.SamBatchTags(ex, _ptr(d_text_list), _ptr(d_letters), _ptr(d_positions), _ptr(d_pos_off), pos_base)
+
+    @staticmethod
+    def _sam_call(batch, stem):
+        return stem + ("_tags" if isinstance(batch, _lib.SamBatchTags) else "_ex" if isinstance(batch, _lib.SamBatchEx) else "")
+
     def sam_layout_dev(self, batch, d_byte_offsets):
-        """sx_sam_layout_dev (sx_sam_layout_dev_ex for a batch with flags): d_byte_offsets (n_hits + 1 uint64) <- every
-        hit's first output byte; returns the text's length"""
+        """sx_sam_layout_dev (sx_sam_layout_dev_ex for a batch with flags, sx_sam_layout_dev_tags for one with tags):
+        d_byte_offsets (n_hits + 1 uint64) <- every hit's first output byte; returns the text's length"""
         total = C.c_uint64(0)
-        name = "sx_sam_layout_dev_ex" if isinstance(batch, _lib.SamBatchEx) else "sx_sam_layout_dev"
+        name = self._sam_call(batch, "sx_sam_layout_dev")
         self._check(getattr(self.lib, name)(self.h, C.byref(batch), _ptr(d_byte_offsets), C.byref(total)), name)
         return int(total.value)
 
     def sam_emit_dev(self, batch, d_byte_offsets, total_bytes, byte_lo, byte_hi, d_out):
-        """sx_sam_emit_dev (sx_sam_emit_dev_ex for a batch with flags): bytes [byte_lo, byte_hi) of the text into d_out
-        (uint8, 16-byte aligned)"""
-        name = "sx_sam_emit_dev_ex" if isinstance(batch, _lib.SamBatchEx) else "sx_sam_emit_dev"
+        """sx_sam_emit_dev (sx_sam_emit_dev_ex for a batch with flags, sx_sam_emit_dev_tags for one with tags): bytes
+        [byte_lo, byte_hi) of the text into d_out (uint8, 16-byte aligned)"""
+        name = self._sam_call(batch, "sx_sam_emit_dev")
         self._check(getattr(self.lib, name)(self.h, C.byref(batch), _ptr(d_byte_offsets), total_bytes, byte_lo, byte_hi, _ptr(d_out)),
                     name)
 
@@ -416,14 +429,16 @@ class Context:
         self._check(self.lib.sx_sa_locate_rows_dev(self.h, _ptr(d_c), _ptr(d_occ), N, sigma, _ptr(d_marks), _ptr(d_values),
                                                    int(sa_sample).bit_length() - 1, row_lo, row_hi, _ptr(d_out)), "sx_sa_locate_rows_dev")
 
-    def map_reads_stream(self, records, fastq, edits, sink, both_strands=False, best=False, indels=True):
+    def map_reads_stream(self, records, fastq, edits, sink, both_strands=False, best=False, indels=True, tags=False):
         """sx_map_reads_stream: records = [(name bytes, BwtTable), ...] in the mapper's list order; sink(bytes) receives the
         SAM text window after window.  sink=None discards the text without touching it and returns [(time.perf_counter(),
         bytes)] per window (measurement).  both_strands (sx_map_reads_stream_ex, SX_MAP_BOTH_STRANDS): behind the lines of
         every read come those of its reverse complement, with FLAG 16.  best (SX_MAP_BEST_STRATUM): per read only the
         lines of the smallest edit count in 0 .. edits that has any (with both_strands: over both strands together).
         indels=False (SX_MAP_NO_INDELS): mismatches only -- the lines whose CIGAR is "<length of SEQ>M", each placement
-        once; with best the strata are the smallest number of mismatches."""
+        once; with best the strata are the smallest number of mismatches.  tags (SX_MAP_TAGS) asks for NM:i and MD:Z, which
+        need the records' strings on the device: records of tables alone have none and the call raises StralgAmdError
+        (code SX_E_ARG = -1) before anything runs; map through an Index (Index.from_fasta) instead."""
         recs = (_lib.MapRecord * max(1, len(records)))()
         keep = []
         for r, (name, t) in enumerate(records):
@@ -445,7 +460,7 @@ class Context:
                 return 1
 
         cb = _lib.SINK_FN(_sink)
-        flags = _lib.map_flags(both_strands, best, indels)
+        flags = _lib.map_flags(both_strands, best, indels, tags)
         if flags:
             rc = self.lib.sx_map_reads_stream_ex(self.h, recs, len(records), _ptr(buf) if buf.size else None, buf.size, edits,
                                                  flags, cb, None)
@@ -757,11 +772,12 @@ class Index:
             raise StralgAmdError("the index is closed")
         return self.h
 
-    def map_reads(self, fastq, edits, sink=None, ctx=None, both_strands=False, best=False, indels=True):
+    def map_reads(self, fastq, edits, sink=None, ctx=None, both_strands=False, best=False, indels=True, tags=False):
         """sx_index_map_reads: the SAM text of every match of every read of a FASTQ image within `edits` edits, byte for
         byte stralg_amd.map_reads' (the reference mapper's stdout).  sink=None returns the text; sink(bytes) receives it
-        window after window and None is returned.  both_strands, best, indels: as in stralg_amd.map_reads
-        (sx_index_map_reads_ex)."""
+        window after window and None is returned.  both_strands, best, indels, tags: as in stralg_amd.map_reads
+        (sx_index_map_reads_ex); tags needs every record's string in the index (an index from_tables without strings
+        raises StralgAmdError, code SX_E_ARG = -1)."""
         ctx = ctx or self.ctx
         buf = np.frombuffer(bytes(fastq), dtype=np.uint8)
         chunks, failure = [], []
@@ -776,7 +792,7 @@ class Index:
                 return 1
 
         cb = _lib.SINK_FN(_sink)
-        flags = _lib.map_flags(both_strands, best, indels)
+        flags = _lib.map_flags(both_strands, best, indels, tags)
         rc = self._map(ctx, buf, edits, flags, cb)
         if failure:
             raise failure[0]
@@ -790,7 +806,7 @@ class Index:
             return ctx.lib.sx_index_map_reads_ex(ctx.h, self._handle(), image, buf.size, edits, flags, cb, None)
         return ctx.lib.sx_index_map_reads(ctx.h, self._handle(), image, buf.size, edits, cb, None)
 
-    def map_reads_discard(self, fastq, edits, ctx=None, both_strands=False, best=False, indels=True):
+    def map_reads_discard(self, fastq, edits, ctx=None, both_strands=False, best=False, indels=True, tags=False):
         """the same with a sink that does not touch the text: [(time.perf_counter(), bytes)] per window (measurement)"""
         ctx = ctx or self.ctx
         buf = np.frombuffer(bytes(fastq), dtype=np.uint8)
@@ -801,7 +817,7 @@ class Index:
             return 0
 
         cb = _lib.SINK_FN(_sink)
-        flags = _lib.map_flags(both_strands, best, indels)
+        flags = _lib.map_flags(both_strands, best, indels, tags)
         ctx._check(self._map(ctx, buf, edits, flags, cb), "sx_index_map_reads_ex" if flags else "sx_index_map_reads")
         return seen
 
@@ -1153,7 +1169,7 @@ def bwt_approx_search(bwt_table, patterns, edits, ctx=None, indels=True):
     return approx_matches(hits, hit_off, [p.size for p in pats], bwt_table.sa.array)
 
 
-def map_reads(fasta, fastq, edits, ctx=None, both_strands=False, best=False, indels=True):
+def map_reads(fasta, fastq, edits, ctx=None, both_strands=False, best=False, indels=True, tags=False):
     """The reference read mapper (tools/readmappers/bwt_readmapper: -p genome.fa, then -d edits genome.fa reads.fq) on the
     bytes of a FASTA and a FASTQ file: its stdout, the SAM lines of every match of every read in every record within
     `edits` edits, byte for byte.  Per read the records come in the mapper's list order, which is the FASTA file's order
@@ -1164,8 +1180,14 @@ def map_reads(fasta, fastq, edits, ctx=None, both_strands=False, best=False, ind
     best: per read only the lines of its best stratum: those the mapper prints for it at -d e*, the smallest edit count in
     0 .. edits at which it prints any for that read (with both_strands: over both strands of the read together).
     indels=False: mismatches only -- of the mapper's lines those whose CIGAR is "<length of SEQ>M" (every placement of a read
-    within `edits` substitutions, once); with best the strata are taken over these lines."""
+    within `edits` substitutions, once); with best the strata are taken over these lines.
+    tags: every line gets "\tNM:i:<nm>\tMD:Z:<md>" behind QUAL -- the edit distance and the mismatch string of the line's POS,
+    CIGAR and SEQ over the record's letters (no case folding), rendered on the device once per hit.  The tags read the
+    records' strings, so the call then maps through a temporary Index.from_fasta on ctx (the same lines)."""
     ctx = ctx or default_context()
+    if tags:
+        with Index.from_fasta(fasta, ctx=ctx) as idx:
+            return idx.map_reads(fastq, edits, both_strands=both_strands, best=best, indels=indels, tags=True)
     records = [(name, build_complete_table(seq, True, ctx)) for name, seq in ctx.fasta_records(fasta)]
     chunks = []
     ctx.map_reads_stream(records, fastq, edits, chunks.append, both_strands=both_strands, best=best, indels=indels)

@@ -23,9 +23,10 @@ static void free_rec(sx_index_rec &R)
 static void free_view(sx_index *idx)
 {
     (void)hipFree(idx->d_rnames), (void)hipFree(idx->d_tabs), (void)hipFree(idx->d_rname_off), (void)hipFree((void *)idx->d_sa_list),
-        (void)hipFree(idx->d_sa_lens), (void)hipFree(idx->d_loc_list);
+        (void)hipFree(idx->d_sa_lens), (void)hipFree(idx->d_loc_list), (void)hipFree(idx->d_letters), (void)hipFree((void *)idx->d_text_list);
     idx->d_loc_list = nullptr;
-    idx->d_rnames = idx->d_tabs = nullptr, idx->d_rname_off = nullptr, idx->d_sa_list = nullptr, idx->d_sa_lens = nullptr;
+    idx->d_text_list = nullptr;
+    idx->d_rnames = idx->d_tabs = idx->d_letters = nullptr, idx->d_rname_off = nullptr, idx->d_sa_list = nullptr, idx->d_sa_lens = nullptr;
     idx->device_bytes -= idx->view_bytes;
     idx->view_bytes = 0;
 }
@@ -35,7 +36,8 @@ static int make_view(sx_ctx *ctx, sx_index *idx)
 {
     free_view(idx);
     const size_t n = idx->recs.size();
-    std::vector<uint8_t> rnames, tabs(n * 256 + 1);
+    std::vector<uint8_t> rnames, tabs(n * 256 + 1), letters(n * 256 + 1);
+    std::vector<const uint8_t *> texts(n + 1);
     std::vector<uint32_t> rname_off(n + 1);
     std::vector<const uint32_t *> sa_ptrs(n + 1);
     std::vector<uint64_t> sa_lens(n + 1);
@@ -47,6 +49,8 @@ static int make_view(sx_ctx *ctx, sx_index *idx)
         // remap.c:102-114: a byte the table lacks makes remap() return NULL and the mapper skip the record for this
         // read; here it becomes symbol 0, for which the search has no hits
         for (int b = 0; b < 256; ++b) tabs[r * 256 + b] = R.remap[b] > 0 && (uint32_t)R.remap[b] < R.sigma ? (uint8_t)R.remap[b] : 0;
+        sx_map_letters_of(R.remap, R.sigma, &letters[r * 256]);
+        texts[r] = R.d_string;
         sa_ptrs[r] = R.d_sa;
         sa_lens[r] = R.N;
         if (idx->sa_log2) locs[r] = R.loc();
@@ -55,7 +59,8 @@ static int make_view(sx_ctx *ctx, sx_index *idx)
     rnames.push_back(0);
     sx_dev_scope S;
     size_t bytes = 0;
-    uint8_t *d_rnames, *d_tabs;
+    uint8_t *d_rnames, *d_tabs, *d_letters;
+    const uint8_t **d_text_list;
     uint32_t *d_rname_off;
     const uint32_t **d_sa_list;
     uint64_t *d_sa_lens;
@@ -64,6 +69,8 @@ static int make_view(sx_ctx *ctx, sx_index *idx)
     SX_TRY(S.take(ctx, &d_rname_off, rname_off.size(), &bytes));
     SX_TRY(S.take(ctx, &d_sa_list, sa_ptrs.size(), &bytes));
     SX_TRY(S.take(ctx, &d_sa_lens, sa_lens.size(), &bytes));
+    SX_TRY(S.take(ctx, &d_letters, letters.size(), &bytes));
+    SX_TRY(S.take(ctx, &d_text_list, texts.size(), &bytes));
     LocRec *d_locs = nullptr;
     if (!locs.empty()) {
         SX_TRY(S.take(ctx, &d_locs, locs.size(), &bytes));
@@ -74,10 +81,13 @@ static int make_view(sx_ctx *ctx, sx_index *idx)
     SX_CHECK(hipMemcpyAsync(d_rname_off, rname_off.data(), rname_off.size() * 4, hipMemcpyHostToDevice, ctx->stream));
     SX_CHECK(hipMemcpyAsync(d_sa_list, sa_ptrs.data(), sa_ptrs.size() * sizeof(void *), hipMemcpyHostToDevice, ctx->stream));
     SX_CHECK(hipMemcpyAsync(d_sa_lens, sa_lens.data(), sa_lens.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    SX_CHECK(hipMemcpyAsync(d_letters, letters.data(), letters.size(), hipMemcpyHostToDevice, ctx->stream));
+    SX_CHECK(hipMemcpyAsync(d_text_list, texts.data(), texts.size() * sizeof(void *), hipMemcpyHostToDevice, ctx->stream));
     SX_TRY(sx_sync(ctx)); // (the host vectors are pageable: their copies are done)
     S.keep();
     idx->d_rnames = d_rnames, idx->d_tabs = d_tabs, idx->d_rname_off = d_rname_off, idx->d_sa_list = d_sa_list, idx->d_sa_lens = d_sa_lens;
     idx->d_loc_list = d_locs;
+    idx->d_letters = d_letters, idx->d_text_list = d_text_list;
     idx->view_bytes = bytes;
     idx->device_bytes += bytes;
     return 0;
@@ -480,6 +490,7 @@ int sx_index_map_reads_ex(sx_ctx *ctx, const sx_index *idx, const uint8_t *fastq
     if (edits < 0 || edits > SX_APPROX_MAX_EDITS) return sx_fail_msg(ctx, SX_E_ARG, "read mapping: edits must be in [0, 8]");
     if (flags & ~sx_map_known_flags) return sx_fail_msg(ctx, SX_E_ARG, "read mapping: unknown flags");
     if (fastq_len > 0xFFFFFFFEull) return sx_fail_msg(ctx, SX_E_ARG, "read mapping: malformed FASTQ image (see sx_fastq_index)");
+    SX_TRY(sx_map_tags_check(ctx, idx, flags)); // (before the reads go up)
     SX_CHECK(hipSetDevice(ctx->device));
     sx_fastq_dev fq;
     memset(&fq, 0, sizeof fq);

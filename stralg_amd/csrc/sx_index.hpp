@@ -39,14 +39,25 @@ struct sx_index {
     size_t device_bytes = 0;
     // the mapper's view of the records (rebuilt whenever a record is added): names and their offsets, one 256-byte
     // symbol table a record, the suffix arrays' addresses and lengths and, in a sampled index, what a walk reads of every
-    // record (an array of sx::LocRec, sx_locate.hpp)
-    uint8_t *d_rnames = nullptr, *d_tabs = nullptr;
+    // record (an array of sx::LocRec, sx_locate.hpp); for NM and MD (SX_MAP_TAGS) the remapped strings' addresses (null
+    // where a record has none) and a 256-byte table a record, the letter behind every code: the inverse of its remap table
+    uint8_t *d_rnames = nullptr, *d_tabs = nullptr, *d_letters = nullptr;
+    const uint8_t **d_text_list = nullptr;
     void *d_loc_list = nullptr;
     uint32_t *d_rname_off = nullptr;
     const uint32_t **d_sa_list = nullptr;
     uint64_t *d_sa_lens = nullptr;
     size_t view_bytes = 0;
 };
+
+// the letter behind every code of a record: the inverse of its remap table (code 0, the sentinel, and the codes the table
+// does not give stay 0)
+static inline void sx_map_letters_of(const signed char *remap, uint32_t sigma, uint8_t *letters)
+{
+    for (int c = 0; c < 256; ++c) letters[c] = 0;
+    for (int b = 0; b < 256; ++b)
+        if (remap[b] > 0 && (uint32_t)remap[b] < sigma) letters[(int)remap[b]] = (uint8_t)b;
+}
 
 // A record's host tables as an index takes them (min_sigma 1: the record without symbols has N = 1, sigma = 1) or as the
 // mapper searches them (min_sigma 2): N and sigma in range, and every array there
@@ -60,7 +71,7 @@ static inline bool sx_map_record_check(const sx_map_record &R, uint32_t min_sigm
 }
 
 // the bits of a mapping call's flags word that mean something (sx_map_reads_stream_ex, sx_index_map_reads_ex, sx_map_reads_limit)
-constexpr uint32_t sx_map_known_flags = SX_MAP_BOTH_STRANDS | SX_MAP_BEST_STRATUM | SX_MAP_NO_INDELS;
+constexpr uint32_t sx_map_known_flags = SX_MAP_BOTH_STRANDS | SX_MAP_BEST_STRATUM | SX_MAP_NO_INDELS | SX_MAP_TAGS;
 // the search flags (SX_SEARCH_*) that a mapping call's flags word asks of its searches
 static inline uint32_t sx_map_search_flags(uint32_t flags) { return (flags & SX_MAP_NO_INDELS) ? (uint32_t)SX_SEARCH_NO_INDELS : 0u; }
 
@@ -69,6 +80,8 @@ static inline uint32_t sx_map_search_flags(uint32_t flags) { return (flags & SX_
 // batch needs back)
 int sx_map_reads_core(sx_ctx *ctx, const sx_index *idx, const sx_fastq_dev &reads, const uint32_t *h_seq_off, int edits, uint32_t flags,
                       sx_sink_fn sink, void *user);
+// sx_map.hip: SX_MAP_TAGS reads every record's string; SX_E_ARG with a message where the flag is set and a record has none
+int sx_map_tags_check(sx_ctx *ctx, const sx_index *idx, uint32_t flags);
 // sx_approx.hip: sx_bwt_approx_search_dev_ex over the tables of a record, full, compact or packed (search_flags: SX_SEARCH_*)
 int sx_approx_search_record(sx_ctx *ctx, const sx_index_rec &R, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, int max_edits,
                             uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t hit_capacity, uint64_t *total_hits_out, uint32_t search_flags);

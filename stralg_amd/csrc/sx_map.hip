@@ -120,6 +120,7 @@ struct MapReads {
     const uint16_t *d_flags;   // a FLAG per read, or null
     uint32_t group; // 0, or (SX_MAP_BEST_STRATUM) the reads that share a stratum: 1, or 2 for the strands of a read
     uint32_t search_flags; // SX_SEARCH_* of every search of the call (SX_MAP_NO_INDELS)
+    bool tags;             // NM and MD behind QUAL (SX_MAP_TAGS)
 };
 
 struct MapBufs { // what a mapping call holds on the device beside the hits' room
@@ -242,7 +243,7 @@ static int best_batch(sx_ctx *ctx, const sx_index *idx, const MapReads &R, MapBu
 
 // The text of A's hits: its layout, then window after window through the two device windows and the context's staging
 // buffers: emit and copy of window w are queued, then the sink works on window w - 1
-static int emit_windows(sx_ctx *ctx, const SamArgs &A, const MapBufs &M, const sx_stage_events &E, sx_sink_fn sink, void *user)
+static int emit_windows(sx_ctx *ctx, const SamTagArgs &A, const MapBufs &M, const sx_stage_events &E, sx_sink_fn sink, void *user)
 {
     uint64_t total = 0;
     SX_TRY(sam_layout(ctx, A, M.d_byte_off, &total));
@@ -269,7 +270,7 @@ static int emit_windows(sx_ctx *ctx, const SamArgs &A, const MapBufs &M, const s
 // The text of a batch (`text`: its hits, reads and records) against an index with a sampled suffix array: its hits are taken
 // in runs of consecutive hits whose lines fit the cap (SX_FLAG_LOCATE_CHUNK_ROWS; a hit is never split: one with more lines
 // gets a buffer of its own length); a run is located, laid out and emitted through its windows before the next one starts
-static int emit_located(sx_ctx *ctx, const sx_index *idx, const SamArgs &text, MapBufs &M, const sx_stage_events &E, sx_sink_fn sink, void *user)
+static int emit_located(sx_ctx *ctx, const sx_index *idx, const SamTagArgs &text, MapBufs &M, const sx_stage_events &E, sx_sink_fn sink, void *user)
 {
     const LocRec *d_recs = (const LocRec *)idx->d_loc_list;
     const uint64_t n_hits = text.n_hits, cap = map_located_rows(ctx->locate_chunk_rows);
@@ -291,7 +292,7 @@ static int emit_located(sx_ctx *ctx, const sx_index *idx, const SamArgs &text, M
         uint32_t e = 0;
         SX_TRY(sx_readback(ctx, d_loc_err, 1, &e));
         if (e) return sx_fail_msg(ctx, SX_E_INTERNAL, "read mapping: a walk over a sampled suffix array met its bound");
-        SamArgs A = text;
+        SamTagArgs A = text;
         A.hits = text.hits + 2 * h_lo, A.n_hits = h_hi - h_lo;
         A.positions = M.d_positions, A.pos_off = M.d_pos_off + h_lo, A.pos_base = base;
         SX_TRY(emit_windows(ctx, A, M, E, sink, user));
@@ -331,10 +332,11 @@ static int map_reads_loop(sx_ctx *ctx, const sx_index *idx, const MapReads &R, i
     T.room_first = T.room_final = room.cap, T.batch_first = T.batch_final = batch_max;
     sx_best_state S;
     if (R.group) SX_TRY(S.init(ctx, batch_max, fq.seq_bytes, n_records, edits, true));
-    SamArgs A = {}; // the batch whose text is emitted: what is the same for every batch here
+    SamTagArgs A = {}; // the batch whose text is emitted: what is the same for every batch here
     A.sa_list = idx->d_sa_list, A.sa_len_list = idx->d_sa_lens;
     A.names = fq.d_names, A.seqs = fq.d_seqs, A.quals = fq.d_quals;
     A.rnames = idx->d_rnames, A.rname_off = idx->d_rname_off, A.n_records = n_records;
+    if (R.tags) A.text_list = idx->d_text_list, A.letters = idx->d_letters; // (emit_windows and emit_located carry them in A)
 
     uint32_t q0 = 0, batch = batch_max;
     while (q0 < n_reads) {
@@ -373,6 +375,14 @@ void sx_sam_remap(sx_ctx *ctx, const uint8_t *d_seqs, const uint8_t *d_table, ui
     if (hi > lo) sx_launch(ctx, SX_KC_REMAP, 2 * (hi - lo), sam_remap_kernel, dim3(sx_div_up(hi - lo, kBlock)), dim3(kBlock), d_seqs, d_table, d_out, lo, hi);
 }
 
+int sx_map_tags_check(sx_ctx *ctx, const sx_index *idx, uint32_t flags)
+{
+    if (!(flags & SX_MAP_TAGS)) return 0;
+    for (const sx_index_rec &R : idx->recs)
+        if (!R.d_string) return sx_fail_msg(ctx, SX_E_ARG, "read mapping: NM and MD need every record's string, and a record was given without it");
+    return 0;
+}
+
 // A mapping call over reads and an index on ctx's device.  Both strands: the read set of 2 x count
 // reads, read 2q + strand, is made once and searched like any read set, so its hits come in (read, strand, record, hit)
 // order, which is the text's; the FLAGs go with the batches.
@@ -383,17 +393,17 @@ int sx_map_reads_core(sx_ctx *ctx, const sx_index *idx, const sx_fastq_dev &read
     if (reads.count == 0 || n_records == 0) return 0;
     bool records_ok = true;
     for (const sx_index_rec &R : idx->recs) records_ok = records_ok && sx_map_dims_ok(R.N, R.sigma, 2);
-    SX_TRY(map_check(ctx, reads.count, n_records, flags, records_ok));
-    const bool best = (flags & SX_MAP_BEST_STRATUM) != 0;
+    SX_TRY(map_check(ctx, reads.count, n_records, flags, records_ok)); // (SX_MAP_TAGS: the callers have seen to the strings)
+    const bool best = (flags & SX_MAP_BEST_STRATUM) != 0, tags = (flags & SX_MAP_TAGS) != 0;
     const uint32_t sflags = sx_map_search_flags(flags);
-    if (!(flags & SX_MAP_BOTH_STRANDS)) return map_reads_loop(ctx, idx, MapReads{&reads, h_seq_off, nullptr, best ? 1u : 0u, sflags}, edits, sink, user);
+    if (!(flags & SX_MAP_BOTH_STRANDS)) return map_reads_loop(ctx, idx, MapReads{&reads, h_seq_off, nullptr, best ? 1u : 0u, sflags, tags}, edits, sink, user);
     SX_CHECK(hipSetDevice(ctx->device));
     sx_fastq_dev both = {};
     sx_dev_scope F;
     uint16_t *d_flags;
     SX_TRY(F.take(ctx, &d_flags, 2 * (size_t)reads.count));
     SX_TRY(sx_fastq_strands_dev(ctx, &reads, &both, d_flags)); // (syncs: the callers' uploads from pageable memory are done)
-    const int rc = map_reads_loop(ctx, idx, MapReads{&both, nullptr, d_flags, best ? 2u : 0u, sflags}, edits, sink, user);
+    const int rc = map_reads_loop(ctx, idx, MapReads{&both, nullptr, d_flags, best ? 2u : 0u, sflags, tags}, edits, sink, user);
     sx_fastq_dev_free(&both);
     return rc;
 }
@@ -423,6 +433,8 @@ int sx_map_reads_stream_ex(sx_ctx *ctx, const sx_map_record *records, uint32_t n
     if (edits < 0 || edits > SX_APPROX_MAX_EDITS)
         return sx_fail_msg(ctx, SX_E_ARG, "read mapping: edits must be in [0, 8]");
     if (flags & ~sx_map_known_flags) return sx_fail_msg(ctx, SX_E_ARG, "read mapping: unknown flags");
+    if (flags & SX_MAP_TAGS) // (the rule of sx_index_write for a record without its string)
+        return sx_fail_msg(ctx, SX_E_ARG, "read mapping: NM and MD need every record's string, and these records are tables alone (map through an index)");
     sx_fastq fq;
     const int frc = sx_fastq_index(fastq, fastq_len, &fq);
     if (frc != 0) return sx_fail_msg(ctx, frc, "read mapping: malformed FASTQ image (see sx_fastq_index)");

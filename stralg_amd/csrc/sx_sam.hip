@@ -15,6 +15,9 @@
 //    is rendered once into LDS, not once per match), and stores the slice in 16-byte vector stores.  The last < 16
 //    bytes of a window whose length is not a multiple of 16 are the only bytes stored singly.  Where a byte goes is
 //    fixed by the scan alone (no atomics), so the text does not depend on scheduling.
+// With the texts of the records (the kernels' kTags form) every line has "\tNM:i:<nm>\tMD:Z:<md>" between
+// its quality string and its newline: one walk a hit over its edit string, the read and the text window at its first
+// position (md_render), in the size pass for the length and in the emit pass into LDS, beside the CIGAR.
 // The output does not fit the device in general: the caller fills a fixed buffer window after window; lines may start
 // in one window (or slice) and end in the next, the concatenation of the windows is the file.
 #include "sx_common.hpp"
@@ -31,6 +34,11 @@ static_assert(SX_SAM_SLICE_BYTES % 16 == 0 && SX_SAM_SLICE_BYTES >= 16 && SX_SAM
 
 constexpr uint32_t kSlice = SX_SAM_SLICE_BYTES;
 constexpr uint32_t kCigarMax = 80;  // 9 runs of M (5 digits) and 8 of I / D (1 digit) take 70 bytes; longer ones are cut
+// MD:Z of a hit: a search of at most SX_APPROX_MAX_EDITS = 8 operations gives at most 8 items (a mismatch: its letter; a
+// deletion: '^', or nothing behind another deletion, and its letter) between at most 9 numbers of at most 5 digits (the
+// edit string has fewer than 2^15 + 8 entries): 9 x 5 + 8 x 2 = 61 bytes.  NM is one digit.
+constexpr uint32_t kMdMax = 64;
+static_assert(SX_APPROX_MAX_EDITS == 8 && 9 * 5 + 8 * 2 <= kMdMax, "MD:Z of 8 edits fits its buffer");
 constexpr uint32_t kInlineMatches = 32;
 constexpr uint32_t kWalk = 4; // matches per lane in one step of the walk inside a long hit
 
@@ -40,6 +48,7 @@ struct HitInfo {
     uint32_t name_b, name_l, seq_b, seq_l, qual_b, qual_l, rn_b, rn_l;
     uint4 gaps;
     uint32_t n_gaps;
+    uint32_t rec, nm, md_len; // (kTags) the record's rank; NM and the bytes of MD once tags_render has run
 };
 
 __device__ __forceinline__ uint32_t dec_digits(uint32_t v)
@@ -96,6 +105,110 @@ __device__ __forceinline__ uint32_t cigar_render(uint8_t *out, uint32_t cap, uin
     return w;
 }
 
+// ---- NM:i and MD:Z ----------------------------------------------------------------------------------
+// entry g of a hit's gap[] (selects, not an indexed array: that would go to scratch or LDS)
+__device__ __forceinline__ uint32_t gap_at(uint4 gaps, uint32_t g)
+{
+    const uint32_t w = g < 4 ? (g < 2 ? gaps.x : gaps.y) : (g < 6 ? gaps.z : gaps.w);
+    return (w >> (16u * (g & 1u))) & 0xFFFFu;
+}
+__device__ __forceinline__ uint32_t gap_deletions(uint4 gaps, uint32_t ng)
+{
+    uint32_t n_d = 0;
+#pragma unroll
+    for (uint32_t g = 0; g < SX_APPROX_MAX_EDITS; ++g) n_d += (g < ng && (gap_at(gaps, g) & SX_APPROX_GAP_D)) ? 1u : 0u;
+    return n_d;
+}
+
+// The bytes of a text [lo, hi) one at a time, through the 16 aligned bytes around the last one asked for: a chunk that lies
+// inside the text is one 16-byte load, the chunks across its first and its last byte are read byte by byte
+// (at: the chunk's address, an odd number while there is none; b: its four words, kept apart so that they stay registers)
+__device__ __forceinline__ uint32_t text_symbol(const uint8_t *lo, const uint8_t *hi, const uint8_t *p, uintptr_t &at, uint32_t &b0, uint32_t &b1,
+                                                uint32_t &b2, uint32_t &b3)
+{
+    const uintptr_t a = (uintptr_t)p & ~(uintptr_t)15;
+    if (a != at) {
+        at = a;
+        if (a >= (uintptr_t)lo && a + 16 <= (uintptr_t)hi) {
+            const uint4 v = *(const uint4 *)a;
+            b0 = v.x, b1 = v.y, b2 = v.z, b3 = v.w;
+        } else {
+            b0 = b1 = b2 = b3 = 0;
+#pragma unroll
+            for (uint32_t k = 0; k < 16; ++k) {
+                const uint8_t *q = (const uint8_t *)a + k;
+                const uint32_t v = (q >= lo && q < hi) ? (uint32_t)*q << (8u * (k & 3u)) : 0u;
+                (k < 8 ? (k < 4 ? b0 : b1) : (k < 12 ? b2 : b3)) |= v;
+            }
+        }
+    }
+    const uint32_t k = (uint32_t)((uintptr_t)p & 15);
+    const uint32_t w = k < 8 ? (k < 4 ? b0 : b1) : (k < 12 ? b2 : b3);
+    return (w >> (8u * (k & 3u))) & 0xFFu;
+}
+
+// One walk over a hit's edit string (pattern order), the read's bytes and the text from the hit's first position on: an M
+// step compares the read's byte with the letter behind the text's code, an I step takes a read byte, a D step a text
+// symbol.  Returns the bytes of MD:Z (at most cap; out == nullptr: the length only, as cigar_render) and *nm <- the
+// mismatches, inserted and deleted symbols.  The window is win[0 .. tlen) inside the text [lo, hi); the walk stays inside
+// the read's m bytes and the window whatever the edit string holds.
+__device__ __forceinline__ uint32_t md_render(uint8_t *out, uint32_t cap, uint32_t m, uint4 gaps, uint32_t ng, const uint8_t *read,
+                                              const uint8_t *lo, const uint8_t *hi, const uint8_t *win, uint32_t tlen, const uint8_t *letters,
+                                              uint32_t *nm)
+{
+    const uint32_t len = m + gap_deletions(gaps, ng);
+    uintptr_t at = 1;
+    uint32_t b0 = 0, b1 = 0, b2 = 0, b3 = 0;
+    uint32_t w = 0, run = 0, edits = 0, ri = 0, ti = 0, g = 0;
+    bool in_del = false; // the step before was a D: this one's letter joins its '^' group
+    for (uint32_t pos = 0; pos < len; ++pos) {
+        const uint32_t e = g < ng ? gap_at(gaps, g) : 0u;
+        if (g < ng && (e & 0x7FFFu) == pos) {
+            ++g;
+            ++edits;
+            if (e & SX_APPROX_GAP_D) {
+                if (ti >= tlen) break;
+                if (!in_del) {
+                    w = put_dec(out, w, cap, run);
+                    if (w < cap) {
+                        if (out) out[w] = '^';
+                        ++w;
+                    }
+                    run = 0;
+                }
+                if (w < cap) {
+                    if (out) out[w] = letters[text_symbol(lo, hi, win + ti, at, b0, b1, b2, b3)];
+                    ++w;
+                }
+                ++ti;
+                in_del = true;
+            } else {
+                ++ri;
+                in_del = false;
+            }
+            continue;
+        }
+        if (ri >= m || ti >= tlen) break;
+        const uint8_t a = letters[text_symbol(lo, hi, win + ti, at, b0, b1, b2, b3)];
+        if (a == read[ri]) {
+            ++run;
+        } else {
+            w = put_dec(out, w, cap, run);
+            if (w < cap) {
+                if (out) out[w] = a;
+                ++w;
+            }
+            run = 0;
+            ++edits;
+        }
+        ++ri;
+        ++ti;
+        in_del = false;
+    }
+    *nm = edits;
+    return put_dec(out, w, cap, run);
+}
+
 // what the lines of hit h are made of; false: the hit does not fit the batch (its query, interval or offsets)
 template <bool kLocated, bool kFlags> __device__ __forceinline__ bool hit_info(const SamArgs &A, uint64_t h, HitInfo &I)
 {
@@ -124,6 +237,7 @@ template <bool kLocated, bool kFlags> __device__ __forceinline__ bool hit_info(c
     I.qual_l = qual_e - I.qual_b;
     I.rn_l = rn_e - I.rn_b;
     I.m = I.seq_l;
+    I.rec = rec;
     I.n_gaps = h0.w >> 16;
     if (I.n_gaps > SX_APPROX_MAX_EDITS) I.n_gaps = SX_APPROX_MAX_EDITS;
     I.pos = kLocated ? A.positions + (A.pos_off[h] - A.pos_base) : sa + L;
@@ -132,15 +246,38 @@ template <bool kLocated, bool kFlags> __device__ __forceinline__ bool hit_info(c
     return true;
 }
 
+// NM and MD of hit I, which has a line (I.cnt > 0): the text window starts at the hit's first position and has as many
+// symbols as the edit string takes of the text.  false: the window leaves the text in front of its sentinel, [0, N - 1),
+// or the walk finds more than SX_APPROX_MAX_EDITS differences -- such a hit is malformed, like one outside the batch
+__device__ __forceinline__ bool tags_render(const SamTagArgs &A, HitInfo &I, uint8_t *out)
+{
+    const uint32_t n_d = gap_deletions(I.gaps, I.n_gaps), n_i = I.n_gaps - n_d;
+    const uint64_t N = A.sa_list ? A.sa_len_list[I.rec] : A.sa_len;
+    I.nm = 0, I.md_len = 0;
+    if (I.m + n_d < n_i) return false;
+    const uint64_t tlen = I.m + n_d - n_i, p = I.pos[0];
+    const uint8_t *text = A.text_list[I.rec];
+    if (!text || N == 0 || p + tlen > N - 1) return false;
+    I.md_len = md_render(out, kMdMax, I.m, I.gaps, I.n_gaps, A.seqs + I.seq_b, text, text + N, text + p, (uint32_t)tlen, A.letters + (size_t)I.rec * 256, &I.nm);
+    return I.nm <= SX_APPROX_MAX_EDITS;
+}
+
 // "\t0\t" + "\t" + "\t0\t" + "\t*\t0\t0\t" + "\t" + "\n": the 16 bytes of a line beside its fields and digits; a FLAG
 // takes its digits in place of the first "0" (without kFlags I.flag is the constant 0: one digit, 16 bytes)
-__device__ __forceinline__ uint32_t fixed_bytes(const HitInfo &I)
+template <bool kTags = false> __device__ __forceinline__ uint32_t fixed_bytes(const HitInfo &I)
 {
-    return I.name_l + I.rn_l + I.cig_len + I.seq_l + I.qual_l + 15u + dec_digits(I.flag);
+    // (kTags) "\tNM:i:" + "\tMD:Z:" and the one digit of NM <= 8: 13 bytes beside the bytes of MD
+    return I.name_l + I.rn_l + I.cig_len + I.seq_l + I.qual_l + 15u + dec_digits(I.flag) + (kTags ? 13u + I.md_len : 0u);
 }
 
 // ---- layout: bytes per hit ---------------------------------------------------------------------
-template <bool kLocated, bool kFlags> __global__ __launch_bounds__(kBlock) void sam_size_kernel(SamArgs A, uint64_t *len_out, uint32_t *err)
+// what a kernel takes of a batch: the tagged forms alone carry the texts and the letters
+template <bool kTags> struct KernelArgs { typedef SamArgs type; };
+template <> struct KernelArgs<true> { typedef SamTagArgs type; };
+// (the forms without tags never get there)
+__device__ __forceinline__ bool tags_render(const SamArgs &, HitInfo &, uint8_t *) { return true; }
+
+template <bool kLocated, bool kFlags, bool kTags> __global__ __launch_bounds__(kBlock) void sam_size_kernel(typename KernelArgs<kTags>::type A, uint64_t *len_out, uint32_t *err)
 {
     __shared__ uint64_t red[kWavesPerBlock];
     __shared__ uint32_t long_cnt[kBlock];
@@ -155,7 +292,11 @@ template <bool kLocated, bool kFlags> __global__ __launch_bounds__(kBlock) void 
             atomicOr(err, 1u);
         } else {
             I.cig_len = cigar_render(nullptr, kCigarMax, I.m, I.gaps, I.n_gaps);
-            bytes = (uint64_t)I.cnt * fixed_bytes(I);
+            if (kTags && I.cnt && !tags_render(A, I, nullptr)) {
+                atomicOr(err, 1u);
+                I.cnt = 0;
+            }
+            bytes = (uint64_t)I.cnt * fixed_bytes<kTags>(I);
             if (I.cnt <= kInlineMatches) {
                 for (uint32_t i = 0; i < I.cnt; ++i) bytes += dec_digits(I.pos[i] + 1u);
             } else {
@@ -184,6 +325,7 @@ struct HitLds {
     const uint32_t *pos;
     uint32_t cnt, fixed, cig_len;
     uint32_t name_b, name_l, seq_b, seq_l, qual_b, qual_l, rn_b, rn_l;
+    uint32_t tags; // (kTags) the bytes of MD, and NM from bit 8 on (it fills the struct's 8-byte alignment)
 };
 
 // n bytes of a line that begins at slice offset `off` (may be negative), clipped to the slice
@@ -194,7 +336,7 @@ __device__ __forceinline__ void put_bytes(uint8_t *obuf, int64_t &off, int64_t s
     off += n;
 }
 
-template <bool kLocated, bool kFlags> __global__ __launch_bounds__(kBlock) void sam_emit_kernel(SamArgs A, const uint64_t *byte_off, uint64_t lo, uint64_t hi,
+template <bool kLocated, bool kFlags, bool kTags> __global__ __launch_bounds__(kBlock) void sam_emit_kernel(typename KernelArgs<kTags>::type A, const uint64_t *byte_off, uint64_t lo, uint64_t hi,
                                                           uint8_t *out)
 {
     __shared__ uint4 obuf4[kSlice / 16];
@@ -205,6 +347,7 @@ template <bool kLocated, bool kFlags> __global__ __launch_bounds__(kBlock) void 
     __shared__ uint32_t red32[kWavesPerBlock];
     __shared__ uint64_t nxt[2];
     __shared__ uint16_t hflag[kFlags ? kBlock : 1]; // (kFlags) the FLAG of the step's hits
+    __shared__ uint8_t md[kTags ? kBlock * kMdMax : 1]; // (kTags) MD:Z of the step's hits, rendered once a hit like the CIGAR
     uint8_t *obuf = (uint8_t *)obuf4;
     const uint32_t t = threadIdx.x;
     const uint64_t s_lo = lo + (uint64_t)blockIdx.x * kSlice;
@@ -228,7 +371,10 @@ template <bool kLocated, bool kFlags> __global__ __launch_bounds__(kBlock) void 
         HitInfo I = {};
         if (hit_info<kLocated, kFlags>(A, h, I)) {
             I.cig_len = cigar_render(nullptr, kCigarMax, I.m, I.gaps, I.n_gaps);
-            const uint32_t fixed = fixed_bytes(I);
+            // (the tags' length is needed by the steps below alone: a hit of up to 1024 lines, which is nearly every hit,
+            //  is not walked here, only by its lane in the loop further down)
+            if (kTags && I.cnt > kWalk * kBlock && !tags_render(A, I, nullptr)) I.cnt = 0;
+            const uint32_t fixed = fixed_bytes<kTags>(I);
             while (I.cnt - i > kWalk * kBlock) {
                 uint64_t b = 0;
 #pragma unroll
@@ -258,7 +404,11 @@ template <bool kLocated, bool kFlags> __global__ __launch_bounds__(kBlock) void 
             H.pos = I.pos;
             H.cnt = I.cnt;
             H.cig_len = I.cig_len;
-            H.fixed = fixed_bytes(I);
+            if (kTags) {
+                (void)tags_render(A, I, md + t * kMdMax); // (a hit that the layout refused never gets here)
+                H.tags = I.md_len | (I.nm << 8);
+            }
+            H.fixed = fixed_bytes<kTags>(I);
             H.name_b = I.name_b, H.name_l = I.name_l, H.seq_b = I.seq_b, H.seq_l = I.seq_l;
             H.qual_b = I.qual_b, H.qual_l = I.qual_l, H.rn_b = I.rn_b, H.rn_l = I.rn_l;
             if (kFlags) hflag[t] = (uint16_t)I.flag;
@@ -312,6 +462,13 @@ template <bool kLocated, bool kFlags> __global__ __launch_bounds__(kBlock) void 
             put_bytes(obuf, off, slice_len, A.seqs + H.seq_b, H.seq_l);
             put_bytes(obuf, off, slice_len, (const uint8_t *)"\t", 1);
             put_bytes(obuf, off, slice_len, A.quals + H.qual_b, H.qual_l);
+            if (kTags) {
+                const uint8_t nm = (uint8_t)('0' + (H.tags >> 8)); // (at most SX_APPROX_MAX_EDITS: the layout refuses the others)
+                put_bytes(obuf, off, slice_len, (const uint8_t *)"\tNM:i:", 6);
+                put_bytes(obuf, off, slice_len, &nm, 1);
+                put_bytes(obuf, off, slice_len, (const uint8_t *)"\tMD:Z:", 6);
+                put_bytes(obuf, off, slice_len, md + u * kMdMax, H.tags & 0xFFu);
+            }
             put_bytes(obuf, off, slice_len, (const uint8_t *)"\n", 1);
         }
         if (t == nlines - 1u) { // the line behind this step's last one
@@ -342,7 +499,7 @@ static SamArgs sam_args_of(const sx_sam_batch &b)
                    nullptr,                 nullptr,      0,            nullptr};
 }
 
-static int sam_args(sx_ctx *ctx, const sx_sam_batch *b, SamArgs &A)
+static int sam_args(sx_ctx *ctx, const sx_sam_batch *b, SamTagArgs &A)
 {
     if (!ctx || !b) return SX_E_ARG;
     if (b->n_hits && (!b->d_hits || ((uintptr_t)b->d_hits & 15) || !(b->d_sa || (b->d_sa_list && b->d_sa_len_list))))
@@ -350,12 +507,12 @@ static int sam_args(sx_ctx *ctx, const sx_sam_batch *b, SamArgs &A)
     if (!b->d_name_off || !b->d_seq_off || !b->d_qual_off || !b->d_rname_off || b->n_records == 0 ||
         (uint64_t)b->n_reads * b->n_records > 0xFFFFFFFFull)
         return sx_fail_msg(ctx, SX_E_ARG, "SAM text: offsets of the reads and record names; reads x records below 2^32");
-    A = sam_args_of(*b);
+    static_cast<SamArgs &>(A) = sam_args_of(*b);
     return 0;
 }
 
 // the same of a batch that may bring a FLAG per read
-static int sam_args_ex(sx_ctx *ctx, const sx_sam_batch_ex *b, SamArgs &A)
+static int sam_args_ex(sx_ctx *ctx, const sx_sam_batch_ex *b, SamTagArgs &A)
 {
     if (!b) return SX_E_ARG;
     SX_TRY(sam_args(ctx, &b->batch, A));
@@ -364,37 +521,61 @@ static int sam_args_ex(sx_ctx *ctx, const sx_sam_batch_ex *b, SamArgs &A)
     return 0;
 }
 
-// the four forms of the two kernels: positions located beforehand or read from a suffix array, a FLAG per read or none
-#define SX_SAM_KERNEL(kernel, A) \
-    ((A).positions ? ((A).flags ? kernel<true, true> : kernel<true, false>) : ((A).flags ? kernel<false, true> : kernel<false, false>))
+// the same of a batch whose lines carry NM and MD; its positions may have been located beforehand
+static int sam_args_tags(sx_ctx *ctx, const sx_sam_batch_tags *b, SamTagArgs &A)
+{
+    if (!b) return SX_E_ARG;
+    SX_TRY(sam_args_ex(ctx, &b->ex, A));
+    if (!b->d_text_list || !b->d_letters || ((uintptr_t)b->d_text_list & 7))
+        return sx_fail_msg(ctx, SX_E_ARG, "SAM text: NM and MD need every record's text and its table of letters");
+    if ((b->d_positions != nullptr) != (b->d_pos_off != nullptr) || ((uintptr_t)b->d_positions & 3) || ((uintptr_t)b->d_pos_off & 7))
+        return sx_fail_msg(ctx, SX_E_ARG, "SAM text: located positions come with their offsets");
+    A.text_list = b->d_text_list, A.letters = b->d_letters;
+    A.positions = b->d_positions, A.pos_off = b->d_pos_off, A.pos_base = b->pos_base;
+    return 0;
+}
 
-int sam_layout(sx_ctx *ctx, const SamArgs &A, uint64_t *d_byte_off, uint64_t *total_out)
+// the forms of the two kernels: positions located beforehand or read from a suffix array, a FLAG per read or none, and
+// each of the four with NM and MD behind QUAL
+#define SX_SAM_KERNEL_T(kernel, A, T) \
+    ((A).positions ? ((A).flags ? kernel<true, true, T> : kernel<true, false, T>) : ((A).flags ? kernel<false, true, T> : kernel<false, false, T>))
+
+int sam_layout(sx_ctx *ctx, const SamTagArgs &A, uint64_t *d_byte_off, uint64_t *total_out)
 {
     *total_out = 0;
     SX_TRY(sx_slab_ensure(ctx, SX_SLAB_SORT, 4096));
     uint32_t *d_err = (uint32_t *)ctx->slab[SX_SLAB_SORT].p;
     SX_CHECK(hipMemsetAsync(d_err, 0, 16, ctx->stream));
-    if (A.n_hits)
-        sx_launch(ctx, SX_KC_SAM, A.n_hits * 40, SX_SAM_KERNEL(sam_size_kernel, A), dim3(sx_div_up(A.n_hits, kBlock)),
+    if (A.n_hits && A.text_list) // (a text window of about a read's length a hit beside its 32 bytes)
+        sx_launch(ctx, SX_KC_SAM, A.n_hits * 40, SX_SAM_KERNEL_T(sam_size_kernel, A, true), dim3(sx_div_up(A.n_hits, kBlock)),
                   dim3(kBlock), A, d_byte_off, d_err);
+    else if (A.n_hits)
+        sx_launch(ctx, SX_KC_SAM, A.n_hits * 40, SX_SAM_KERNEL_T(sam_size_kernel, A, false), dim3(sx_div_up(A.n_hits, kBlock)),
+                  dim3(kBlock), static_cast<const SamArgs &>(A), d_byte_off, d_err);
     SX_TRY(device_scan64_inplace(ctx, d_byte_off, A.n_hits, SX_KC_SAM));
     uint32_t h[2] = {0, 0}, e = 0;
     SX_TRY(sx_readback(ctx, (const uint32_t *)(d_byte_off + A.n_hits), 2, h));
     SX_TRY(sx_readback(ctx, d_err, 1, &e));
+    if (e && A.text_list)
+        return sx_fail_msg(ctx, SX_E_ARG, "SAM text: a hit's query, interval, offsets or text window lie outside the batch, or it has more than 8 differences");
     if (e) return sx_fail_msg(ctx, SX_E_ARG, "SAM text: a hit's query, interval or offsets lie outside the batch");
     *total_out = (uint64_t)h[0] | ((uint64_t)h[1] << 32);
     return 0;
 }
 
 // (asynchronous: the caller syncs)
-int sam_emit(sx_ctx *ctx, const SamArgs &A, const uint64_t *d_byte_off, uint64_t lo, uint64_t hi, uint8_t *d_out)
+int sam_emit(sx_ctx *ctx, const SamTagArgs &A, const uint64_t *d_byte_off, uint64_t lo, uint64_t hi, uint8_t *d_out)
 {
     if (hi <= lo) return 0;
     const uint64_t slices = (hi - lo + kSlice - 1) / kSlice;
     if (slices > 0x7FFFFFFFull) return sx_fail_msg(ctx, SX_E_ARG, "SAM text: window too long");
     // per line: its bytes out, 4 bytes of position in; the read's fields once a slice
-    sx_launch(ctx, SX_KC_SAM, hi - lo, SX_SAM_KERNEL(sam_emit_kernel, A), dim3((uint32_t)slices), dim3(kBlock), A,
-              d_byte_off, lo, hi, d_out);
+    if (A.text_list)
+        sx_launch(ctx, SX_KC_SAM, hi - lo, SX_SAM_KERNEL_T(sam_emit_kernel, A, true), dim3((uint32_t)slices), dim3(kBlock), A,
+                  d_byte_off, lo, hi, d_out);
+    else
+        sx_launch(ctx, SX_KC_SAM, hi - lo, SX_SAM_KERNEL_T(sam_emit_kernel, A, false), dim3((uint32_t)slices), dim3(kBlock),
+                  static_cast<const SamArgs &>(A), d_byte_off, lo, hi, d_out);
     return 0;
 }
 
@@ -406,7 +587,7 @@ extern "C" {
 
 int sx_sam_layout_dev_ex(sx_ctx *ctx, const sx_sam_batch_ex *batch, uint64_t *d_byte_offsets, uint64_t *total_bytes_out)
 {
-    SamArgs A;
+    SamTagArgs A;
     SX_TRY(sam_args_ex(ctx, batch, A));
     if (!d_byte_offsets || !total_bytes_out) return SX_E_ARG;
     SX_CHECK(hipSetDevice(ctx->device));
@@ -416,8 +597,29 @@ int sx_sam_layout_dev_ex(sx_ctx *ctx, const sx_sam_batch_ex *batch, uint64_t *d_
 int sx_sam_emit_dev_ex(sx_ctx *ctx, const sx_sam_batch_ex *batch, const uint64_t *d_byte_offsets, uint64_t total_bytes, uint64_t byte_lo,
                        uint64_t byte_hi, uint8_t *d_out)
 {
-    SamArgs A;
+    SamTagArgs A;
     SX_TRY(sam_args_ex(ctx, batch, A));
+    if (!d_byte_offsets || byte_lo > byte_hi || byte_hi > total_bytes || (A.n_hits == 0 && byte_hi > byte_lo) || (byte_hi > byte_lo && (!d_out || ((uintptr_t)d_out & 15))))
+        return sx_fail_msg(ctx, SX_E_ARG, "SAM text: a window inside [0, total) and a 16-byte aligned buffer are needed");
+    SX_CHECK(hipSetDevice(ctx->device));
+    SX_TRY(sam_emit(ctx, A, d_byte_offsets, byte_lo, byte_hi, d_out));
+    return sx_sync(ctx);
+}
+
+int sx_sam_layout_dev_tags(sx_ctx *ctx, const sx_sam_batch_tags *batch, uint64_t *d_byte_offsets, uint64_t *total_bytes_out)
+{
+    SamTagArgs A;
+    SX_TRY(sam_args_tags(ctx, batch, A));
+    if (!d_byte_offsets || !total_bytes_out) return SX_E_ARG;
+    SX_CHECK(hipSetDevice(ctx->device));
+    return sam_layout(ctx, A, d_byte_offsets, total_bytes_out);
+}
+
+int sx_sam_emit_dev_tags(sx_ctx *ctx, const sx_sam_batch_tags *batch, const uint64_t *d_byte_offsets, uint64_t total_bytes, uint64_t byte_lo,
+                         uint64_t byte_hi, uint8_t *d_out)
+{
+    SamTagArgs A;
+    SX_TRY(sam_args_tags(ctx, batch, A));
     if (!d_byte_offsets || byte_lo > byte_hi || byte_hi > total_bytes || (A.n_hits == 0 && byte_hi > byte_lo) || (byte_hi > byte_lo && (!d_out || ((uintptr_t)d_out & 15))))
         return sx_fail_msg(ctx, SX_E_ARG, "SAM text: a window inside [0, total) and a 16-byte aligned buffer are needed");
     SX_CHECK(hipSetDevice(ctx->device));

@@ -26,10 +26,19 @@ struct SamArgs {
     const uint16_t *flags; // a FLAG per read (the kernels' kFlags form), or null: every line has FLAG 0
 };
 
+// The same with what NM:i and MD:Z behind QUAL are made of (the kernels' kTags form), or both null:
+// per record rank the address of its remapped text (as many bytes as its suffix array has entries, the sentinel last) and
+// a 256-byte table, the letter behind every code.  The kernels without tags take the SamArgs part alone, as they did
+// before there were tags.
+struct SamTagArgs : SamArgs {
+    const uint8_t *const *text_list = nullptr;
+    const uint8_t *letters = nullptr;
+};
+
 // d_byte_off[h] (n_hits + 1 entries) <- the first output byte of hit h's lines, the last entry and *total_out <- the
 // text's length
-int sam_layout(sx_ctx *ctx, const SamArgs &A, uint64_t *d_byte_off, uint64_t *total_out);
+int sam_layout(sx_ctx *ctx, const SamTagArgs &A, uint64_t *d_byte_off, uint64_t *total_out);
 // bytes [lo, hi) of the text to d_out (asynchronous: the caller syncs)
-int sam_emit(sx_ctx *ctx, const SamArgs &A, const uint64_t *d_byte_off, uint64_t lo, uint64_t hi, uint8_t *d_out);
+int sam_emit(sx_ctx *ctx, const SamTagArgs &A, const uint64_t *d_byte_off, uint64_t lo, uint64_t hi, uint8_t *d_out);
 
 } // namespace sx

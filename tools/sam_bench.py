@@ -14,9 +14,12 @@ emit pass as the difference of the search over the found set with and without it
 SX_MAP_BEST_STRATUM beside the plain one of the same run (kept in profiles/best_bench_2p28.json).  --no-indels adds, per k
 and on the same reads, the search with indels=False (SX_SEARCH_NO_INDELS): its hits, lines and text bytes, the search's
 kernel ms (every run: the spread), layout and emit over its hits, and the streamed call with SX_MAP_NO_INDELS (with --best:
-also with both flags) beside the plain one (kept in profiles/no_indels_bench_2p28.json).
+also with both flags) beside the plain one (kept in profiles/no_indels_bench_2p28.json).  --tags adds, per k (and per
+no-indels entry), layout and emit over the same hits with NM:i and MD:Z behind QUAL (sx_sam_layout_dev_tags /
+sx_sam_emit_dev_tags), and the call through a resident index with its strings (Index.map_reads_discard) with and without
+tags=True (kept in profiles/tags_bench_2p28.json).
 
-    python tools/sam_bench.py [--log2n 28] [--reads 1000000] [--window-mib 1024] [--repeats 5] [--both-strands] [--best] [--no-indels]
+    python tools/sam_bench.py [--log2n 28] [--reads 1000000] [--window-mib 1024] [--repeats 5] [--both-strands] [--best] [--no-indels] [--tags]
 """
 import argparse
 import ctypes as C
@@ -44,6 +47,7 @@ def main():
     ap.add_argument("--both-strands", action="store_true", help="also the strand kernel and the streamed call on both strands")
     ap.add_argument("--best", action="store_true", help="also the best-stratum search, its rounds and the streamed call with best=True")
     ap.add_argument("--no-indels", action="store_true", help="also the search, the text and the streamed call without indels")
+    ap.add_argument("--tags", action="store_true", help="also layout, emit and the index call with NM:i and MD:Z on every line")
     args = ap.parse_args()
     import torch
 
@@ -66,6 +70,10 @@ def main():
     d_ro = torch.zeros_like(d_o)
     ctx.sa_build_dev(d_rev, n, sigma, d_rsa)
     ctx.bwt_tables_dev(d_rev, d_rsa, N, sigma, d_c2, d_ro)
+    # (--tags: the remapped text, its sentinel behind it, stays; its letters are those of the reads below)
+    d_texts = torch.tensor([d_text.data_ptr()], dtype=torch.int64, device="cuda") if args.tags else None
+    d_letters = torch.from_numpy(np.frombuffer(b"\0ACGT" + bytes(251), np.uint8).copy()).cuda() if args.tags else None
+    d_text_kept = d_text if args.tags else None
     del d_rsa, d_c2, d_rev, d_text
     torch.cuda.empty_cache()
 
@@ -166,6 +174,26 @@ def main():
             entry["search_kernel_ms_runs"] = [round(r[2], 3) for r in search_runs]
             entry["layout_ms_runs"] = [round(r[2], 3) for r in layout_runs]
             entry["emit_ms_runs"] = [round(r[2], 3) for r in emit_runs]
+        if args.tags:  # the same hits with the two fields on every line
+            tb = ctx.sam_batch_tags(batch, d_texts, d_letters)
+            ctx.sam_layout_dev(tb, d_boff)  # warm-up
+            t_layout = [profiled("sam", lambda: ctx.sam_layout_dev(tb, d_boff)) for _ in range(args.repeats)]
+            t_bytes = t_layout[0][0]
+
+            def emit_tagged():
+                for lo in range(0, t_bytes, window):
+                    ctx.sam_emit_dev(tb, d_boff, t_bytes, lo, min(t_bytes, lo + window), d_win)
+
+            ctx.sam_emit_dev(tb, d_boff, t_bytes, 0, min(t_bytes, window), d_win)  # warm-up
+            t_emit = [profiled("sam", emit_tagged) for _ in range(args.repeats)]
+            tl, te = min(r[2] for r in t_layout), min(r[2] for r in t_emit)
+            # beside the untagged passes' bytes: a text window of the read's length a hit in either pass
+            t_emit_bytes = t_bytes + lines * 4 + total * (32 + L)
+            entry["tags"] = {"text_bytes": int(t_bytes), "layout_ms": round(tl, 3), "layout_ms_runs": [round(r[2], 3) for r in t_layout],
+                             "emit_ms": round(te, 3), "emit_ms_runs": [round(r[2], 3) for r in t_emit], "emit_bytes": int(t_emit_bytes),
+                             "emit_GBps": round(t_emit_bytes / (te * 1e-3) / 1e9, 1),
+                             "layout_plus_emit_over_untagged": round((tl + te) / (layout_ms + emit_ms), 3),
+                             "layout_plus_emit_over_search": round((tl + te) / search_ms, 4)}
         del d_hits, d_boff
         torch.cuda.empty_cache()
         return entry
@@ -192,7 +220,9 @@ def main():
     table[0] = 0
     table[np.frombuffer(b"ACGT", np.uint8)] = [1, 2, 3, 4]
     rev = np.full(128, -1, np.int16)
-    rec = api.BwtTable(api.RemapTable(sigma, table, rev), api.SuffixArray(None, d_sa.cpu().numpy().view(np.uint32)),
+    string = d_text_kept[:N].cpu().numpy() if args.tags else None  # (symbols and sentinel: the index then has its string)
+    del d_text_kept, d_texts
+    rec = api.BwtTable(api.RemapTable(sigma, table, rev), api.SuffixArray(string, d_sa.cpu().numpy().view(np.uint32)),
                        d_c.cpu().numpy().view(np.uint32), d_o.cpu().numpy().view(np.uint32),
                        d_ro.cpu().numpy().view(np.uint32))
     del d_sa, d_o, d_ro, d_win
@@ -240,6 +270,24 @@ def main():
             out[f"k{k}"]["streamed_both_strands"] = {"call_wall_ms": round(both_wall * 1e3, 1), "call_wall_ms_runs": both_walls,
                                                     "text_bytes": int(sum(b for _, b in both_seen)), "windows": len(both_seen),
                                                     "over_one_strand_call": round(both_wall / wall, 3)}
+    if args.tags:
+        # the call through a resident index that has its string (the tables go up once), with and without the fields
+        with api.Index.from_tables([(b"chr1", rec)], ctx=ctx) as idx:
+            for k in [int(x) for x in args.ks.split(",")]:
+                variants = [("", {})] + ([("no_indels", dict(indels=False))] if args.no_indels else []) + \
+                           ([("best", dict(best=True))] if args.best else [])
+                for key, kw in variants:
+                    res = {}
+                    for name, tags in (("plain", False), ("tags", True)):
+                        runs = []
+                        for _ in range(args.repeats):
+                            t0 = time.perf_counter()
+                            seen = idx.map_reads_discard(fastq, k, tags=tags, **kw)
+                            runs.append((time.perf_counter() - t0, sum(b for _, b in seen)))
+                        res[name] = {"call_wall_ms": round(min(r[0] for r in runs) * 1e3, 1), "call_wall_ms_runs": [round(r[0] * 1e3, 1) for r in runs],
+                                     "text_bytes": int(runs[0][1])}
+                    where = out[f"k{k}"] if not key else out[f"k{k}"].setdefault(key, {})
+                    where["index_call"] = res
     if args.both_strands:
         # the strand kernel alone: the image indexed on the device, then sx_fastq_strands_dev (launches of the remap class)
         d_img = torch.from_numpy(np.concatenate([img, pad])).cuda()

@@ -38,6 +38,10 @@
  *                                                   substitutions, once; with --best the strata are the smallest number
  *                                                   of substitutions; goes with --both-strands, --compact, --packed,
  *                                                   --sa-sample and -i
+ *   --tags                                          with -d: every line gets "\tNM:i:<nm>\tMD:Z:<md>" behind QUAL, the edit
+ *                                                   distance and the mismatch string of its POS, CIGAR and SEQ over the
+ *                                                   record's letters, rendered on the device; goes with every other
+ *                                                   switch
  *   (--preprocess, --edits and --in-memory are accepted for -p, -d and -i)
  *
  * Index file: u32 record count; per record, last FASTA record first, its name as u32 length + bytes + NUL, then the
@@ -173,6 +177,7 @@ static int usage(const char *self, int status)
     fprintf(stderr, "                                          in 0 .. K that has any (with --both-strands: over both strands)\n");
     fprintf(stderr, "       --no-indels                        with -d K: mismatches only, every placement within K substitutions\n");
     fprintf(stderr, "                                          once (with --best: the smallest number of substitutions)\n");
+    fprintf(stderr, "       --tags                             with -d: NM:i and MD:Z behind QUAL on every line\n");
     return status;
 }
 
@@ -199,6 +204,8 @@ int main(int argc, char **argv)
             map_flags |= SX_MAP_BEST_STRATUM;
         } else if (!strcmp(s, "--no-indels")) {
             map_flags |= SX_MAP_NO_INDELS;
+        } else if (!strcmp(s, "--tags")) {
+            map_flags |= SX_MAP_TAGS;
         } else if (!strcmp(s, "--sa-sample")) {
             if (++a >= argc) return usage(argv[0], EXIT_FAILURE);
             const long dist = strtol(argv[a], NULL, 10);
