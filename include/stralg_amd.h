@@ -59,6 +59,11 @@ enum {
     SX_KC_SEARCH,         /* batched exact and k-edit BWT search          bwt.c:164-199, 226-422 */
     SX_KC_LOCAL_SORT,     /* hybrid LMS sort: sub-buckets ordered in LDS, ties listed          */
     SX_KC_SAM,            /* SAM text of search hits: size pass, 64-bit scan, emit  bioinf/sam.c:4-10 */
+    SX_KC_PAIR_COUNT,     /* paired reads: the lines of a batch and the proper combinations of every line */
+    SX_KC_PAIR_SCAN,      /* paired reads: the 64-bit scans of the lines and of the combinations */
+    SX_KC_PAIR_FILL,      /* paired reads: two line descriptors a proper combination               */
+    SX_KC_PAIR_LAYOUT,    /* paired reads: bytes of every described line and their scan            */
+    SX_KC_PAIR_EMIT,      /* paired reads: the text of a window of described lines                 */
     SX_KC_COUNT
 };
 
@@ -173,6 +178,10 @@ enum {
     ,SX_FLAG_READBACK_SEQ = 24     /* a test switch: the value, taken as a 32-bit pattern, becomes the sequence number of the last
                                        read-back, in the context and (after a wait for the stream) in the word of the pinned page
                                        that holds it, so that the page still holds the last sequence number */
+    ,SX_FLAG_PAIRS_ROOM_LINES = 25 /* paired reads, a test switch: > 0 = the lines, and the line descriptors, that a batch of
+                                       several pairs may have before it is halved, in place of what the free memory gives (and
+                                       of SX_FLAG_SAM_ROOM_HITS, which sets it as well where this one is 0); the hits' room
+                                       is left as it is.  0 (default) = by the free memory */
 };
 int sx_ctx_set_flag(sx_ctx *ctx, int flag, int value);
 
@@ -410,6 +419,26 @@ int sx_sam_layout_dev_tags(sx_ctx *ctx, const sx_sam_batch_tags *batch, uint64_t
 int sx_sam_emit_dev_tags(sx_ctx *ctx, const sx_sam_batch_tags *batch, const uint64_t *d_byte_offsets, uint64_t total_bytes, uint64_t byte_lo,
                          uint64_t byte_hi, uint8_t *d_out);
 
+/* Lines with a mate.  A line descriptor names a hit of the batch (its read, record, CIGAR, SEQ and QUAL
+ * are the hit's) and carries what the hit does not say: line j prints
+ *     <qname>\t<flag>\t<rname>\t<pos>\t0\t<cigar>\t=\t<pnext>\t<tlen>\t<seq>\t<qual>\n
+ * with pos, pnext and flag in decimal as they stand in the descriptor (pos is the 1-based POS itself: no suffix array is
+ * read) and tlen as a signed decimal.  d_lines is device memory, 4-byte aligned, n_lines entries; batch.d_sa / d_sa_list
+ * may be NULL.  Layout: d_byte_offsets[j] (n_lines + 1 entries) <- the first output byte of line j, the last entry and
+ * *total_bytes_out <- the text's length; SX_E_ARG when a descriptor's hit lies outside the batch.  Emit: a window of the
+ * text, as sx_sam_emit_dev; the same bytes from run to run. */
+typedef struct sx_pair_line {
+    uint32_t hit;   /* index into batch.d_hits */
+    uint32_t pos;   /* POS */
+    uint32_t pnext; /* PNEXT */
+    int32_t tlen;   /* TLEN */
+    uint32_t flag;  /* FLAG (< 65536) */
+} sx_pair_line; /* 20 bytes */
+int sx_sam_layout_dev_pairs(sx_ctx *ctx, const sx_sam_batch *batch, const sx_pair_line *d_lines, uint64_t n_lines, uint64_t *d_byte_offsets,
+                            uint64_t *total_bytes_out);
+int sx_sam_emit_dev_pairs(sx_ctx *ctx, const sx_sam_batch *batch, const sx_pair_line *d_lines, uint64_t n_lines, const uint64_t *d_byte_offsets,
+                          uint64_t total_bytes, uint64_t byte_lo, uint64_t byte_hi, uint8_t *d_out);
+
 /* A FASTQ image indexed on the host (one pass of memchr over the file): read q's name is names[name_off[q] ..
  * name_off[q+1]), its sequence seqs[seq_off[q] ..), its quality quals[qual_off[q] ..): the raw bytes of the record's
  * first line behind '@' (blanks stay), of its second and of its fourth line; the third line is dropped
@@ -553,6 +582,32 @@ int sx_index_map_reads(sx_ctx *ctx, const sx_index *idx, const uint8_t *fastq, s
  * SX_MAP_TAGS, which needs every record's string in the index */
 int sx_index_map_reads_ex(sx_ctx *ctx, const sx_index *idx, const uint8_t *fastq, size_t fastq_len, int edits, uint32_t flags,
                           sx_sink_fn sink, void *user);
+/* Paired-end reads.  Read p of image 1 and read p of image 2 are the mates of pair p (different read
+ * counts: SX_E_ARG before anything runs; the names need not be equal).  Let lines(x) be what sx_index_map_reads_ex prints
+ * for read x with SX_MAP_BOTH_STRANDS and the same edits and flags.  (a, b), a in lines(mate 1), b in lines(mate 2), is a
+ * proper combination when both have the same record, one has FLAG 0 (f) and the other FLAG 16 (r), POS(f) <= POS(r),
+ * POS(f) + span(f) <= POS(r) + span(r) -- span: the hit's match_length, the M and D lengths of the CIGAR -- and
+ * min_insert <= t <= max_insert for t = POS(r) + span(r) - POS(f).  The text is, per pair in file order, for a over
+ * lines(mate 1) in order and b over lines(mate 2) in order, a's line and then b's line of every proper (a, b): the
+ * both-strands line with FLAG = 1 + 2 + (64 on mate 1's line, 128 on mate 2's) + (16 on the reverse line, else 32), RNEXT
+ * "=", PNEXT the other line's POS and TLEN t on f's line, -t on r's.  A pair without a proper combination prints nothing;
+ * there are no discordant, single-mate or unmapped lines.  Placements that the search reports twice (1I99M beside 100M)
+ * multiply: SX_MAP_BEST_STRATUM and SX_MAP_NO_INDELS are what a caller combines this with.  TLEN is a signed 32-bit
+ * field, [-2^31 + 1, 2^31 - 1] in SAM: a combination with t >= 2^31 (only on a record of more than 2^31 symbols) has no
+ * TLEN that can be written and is not printed, so a max_insert above 2^31 - 1 acts as 2^31 - 1.
+ * flags: SX_MAP_BOTH_STRANDS (implied: set or not, the same text), SX_MAP_BEST_STRATUM (each mate has its own stratum over
+ * its two strands) and SX_MAP_NO_INDELS; SX_MAP_TAGS and every other bit: SX_E_ARG, as min_insert > max_insert and a
+ * NULL opts.  The limit is 4 x pairs x records < 2^32 (sx_map_pairs_limit).  Batches hold whole pairs: here
+ * SX_FLAG_SAM_BATCH_READS counts pairs.  A batch whose lines or combinations do not fit the device is halved like one
+ * whose hits do not fit; a pair alone gets what it needs.  Windows, sink and the other error codes are those of
+ * sx_index_map_reads. */
+typedef struct sx_pair_opts {
+    uint32_t min_insert, max_insert;
+} sx_pair_opts;
+int sx_index_map_pairs(sx_ctx *ctx, const sx_index *idx, const uint8_t *fastq1, size_t len1, const uint8_t *fastq2, size_t len2, int edits,
+                       const sx_pair_opts *opts, uint32_t flags, sx_sink_fn sink, void *user);
+/* 0, or SX_E_ARG when 4 x pairs x records does not stay below 2^32 */
+int sx_map_pairs_limit(uint64_t n_pairs, uint64_t n_records);
 typedef struct sx_index_record {
     const char *name; /* valid until the index changes or is destroyed */
     uint64_t N;

@@ -276,6 +276,11 @@ struct sx_index *stralg_amd_index_from_fasta_image_ex(const uint8_t *fasta, size
 struct sx_index *stralg_amd_index_read_ex(FILE *f, uint32_t flags);
 /* stralg_amd_index_map with the flags of sx_map_reads_stream_ex (SX_MAP_BOTH_STRANDS, SX_MAP_BEST_STRATUM, SX_MAP_NO_INDELS) */
 int stralg_amd_index_map_ex(const struct sx_index *idx, FILE *fastq, int edits, uint32_t flags, FILE *sam);
+/* paired-end reads (stralg_amd.h sx_index_map_pairs): the rest of fastq1 and of fastq2 are the two mates' files, read p of
+ * either the mates of pair p; the SAM lines of the proper pairs go to `sam` */
+struct sx_pair_opts;
+int stralg_amd_index_map_pairs(const struct sx_index *idx, FILE *fastq1, FILE *fastq2, int edits, const struct sx_pair_opts *opts,
+                               uint32_t flags, FILE *sam);
 
 #ifdef __cplusplus
 }

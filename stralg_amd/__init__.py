@@ -9,6 +9,6 @@ from .api import (  # noqa: F401
     Context, Index, SuffixArray, BwtTable, RemapTable, StralgAmdError,
     sa_is_construction, sa_is_mem_construction, skew_sa_construction,
     remap_string, alloc_remap_table, remap, init_bwt_table, build_complete_table, bwt_approx_search, map_reads,
-    default_context,
+    map_pairs, default_context,
 )
 from .synth import synth  # noqa: F401

@@ -12,7 +12,8 @@ PRODUCT_LIB = os.path.join(_HERE, "libstralg_amd.so")
 
 KC_NAMES = ["classify", "samples", "keys", "radix_hist", "radix_scatter", "scan", "names", "doubling",
             "induce_gather", "induce_scan", "induce_scatter", "induce_chain", "bwt_gather", "otable", "misc",
-            "fasta", "remap", "lcp", "search", "local_sort", "sam"]
+            "fasta", "remap", "lcp", "search", "local_sort", "sam",
+            "pair_count", "pair_scan", "pair_fill", "pair_layout", "pair_emit"]
 
 
 class KernelStat(C.Structure):
@@ -69,6 +70,7 @@ SX_FLAG_LOCATE_CHUNK_ROWS = 20
 SX_FLAG_INDUCE_EARLY_S_OFF = 21
 SX_FLAG_SAM_ROOM_HITS = 22
 SX_FLAG_CHAIN_EPOCH, SX_FLAG_READBACK_SEQ = 23, 24  # (test switches, as SX_FLAG_SAM_ROOM_HITS)
+SX_FLAG_PAIRS_ROOM_LINES = 25  # (a test switch too)
 N_SLABS = 7
 SLAB_CHAIN = 6
 CHAIN_EPOCH_LIMIT = 1 << 24  # the look-back epoch has 24 bits: the launch after 2^24 - 1 takes 1 again
@@ -83,6 +85,11 @@ def map_flags(both_strands=False, best=False, indels=True, tags=False):
     """the flags word of sx_map_reads_stream_ex / sx_index_map_reads_ex"""
     return ((SX_MAP_BOTH_STRANDS if both_strands else 0) | (SX_MAP_BEST_STRATUM if best else 0)
             | (0 if indels else SX_MAP_NO_INDELS) | (SX_MAP_TAGS if tags else 0))
+
+
+def pair_flags(best=False, indels=True):
+    """the flags word of sx_index_map_pairs (both strands are implied)"""
+    return (SX_MAP_BEST_STRATUM if best else 0) | (0 if indels else SX_MAP_NO_INDELS)
 
 
 def search_flags(indels=True):
@@ -109,6 +116,15 @@ class SamBatchTags(C.Structure):
     and MD behind QUAL) and, optionally, positions located beforehand"""
     _fields_ = [("ex", SamBatchEx), ("d_text_list", C.c_void_p), ("d_letters", C.c_void_p), ("d_positions", C.c_void_p),
                 ("d_pos_off", C.c_void_p), ("pos_base", C.c_uint64)]
+
+
+# include/stralg_amd.h sx_pair_line (20 bytes)
+PAIR_LINE_DTYPE = [("hit", "<u4"), ("pos", "<u4"), ("pnext", "<u4"), ("tlen", "<i4"), ("flag", "<u4")]
+
+
+class PairOpts(C.Structure):
+    """include/stralg_amd.h sx_pair_opts"""
+    _fields_ = [("min_insert", C.c_uint32), ("max_insert", C.c_uint32)]
 
 
 class Fastq(C.Structure):
@@ -246,6 +262,11 @@ def load(path=None):
         "sx_sam_emit_dev_ex": (C.c_int, [vp, C.POINTER(SamBatchEx), u64p, C.c_uint64, C.c_uint64, C.c_uint64, u8p]),
         "sx_sam_layout_dev_tags": (C.c_int, [vp, C.POINTER(SamBatchTags), u64p, C.POINTER(C.c_uint64)]),
         "sx_sam_emit_dev_tags": (C.c_int, [vp, C.POINTER(SamBatchTags), u64p, C.c_uint64, C.c_uint64, C.c_uint64, u8p]),
+        "sx_sam_layout_dev_pairs": (C.c_int, [vp, C.POINTER(SamBatch), vp, C.c_uint64, u64p, C.POINTER(C.c_uint64)]),
+        "sx_sam_emit_dev_pairs": (C.c_int, [vp, C.POINTER(SamBatch), vp, C.c_uint64, u64p, C.c_uint64, C.c_uint64, C.c_uint64, u8p]),
+        "sx_index_map_pairs": (C.c_int, [vp, vp, u8p, C.c_size_t, u8p, C.c_size_t, C.c_int, C.POINTER(PairOpts), C.c_uint32, SINK_FN,
+                                         C.c_void_p]),
+        "sx_map_pairs_limit": (C.c_int, [C.c_uint64, C.c_uint64]),
         "sx_fastq_index": (C.c_int, [u8p, C.c_size_t, C.POINTER(Fastq)]),
         "sx_fastq_free": (None, [C.POINTER(Fastq)]),
         "sx_map_reads_stream": (C.c_int, [vp, C.POINTER(MapRecord), C.c_uint32, u8p, C.c_size_t, C.c_int, SINK_FN, C.c_void_p]),
@@ -343,6 +364,7 @@ EXPORTS = ["sx_device_count", "sx_device_numa_node", "sx_ctx_create", "sx_ctx_de
            "sx_index_map_reads_ex", "sx_bwt_best_search_dev", "sx_patterns_select_dev", "sx_map_last_stats",
            "sx_bwt_approx_search_dev_ex", "sx_bwt_approx_search_compact_dev_ex", "sx_bwt_approx_search_packed_dev_ex",
            "sx_bwt_best_search_dev_ex", "sx_bwt_approx_search_ex", "sx_sam_layout_dev_tags", "sx_sam_emit_dev_tags",
+           "sx_sam_layout_dev_pairs", "sx_sam_emit_dev_pairs", "sx_index_map_pairs", "sx_map_pairs_limit",
            "sx_synth_dev", "sx_membw_probe", "sx_prim_sort_pairs_dev", "sx_prim_exclusive_sum_dev", "sx_prim_classify_dev"]
 
 

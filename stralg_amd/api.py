@@ -313,6 +313,20 @@ class Context:
         self._check(getattr(self.lib, name)(self.h, C.byref(batch), _ptr(d_byte_offsets), total_bytes, byte_lo, byte_hi, _ptr(d_out)),
                     name)
 
+    def sam_layout_dev_pairs(self, batch, d_lines, n_lines, d_byte_offsets):
+        """sx_sam_layout_dev_pairs: d_lines (n_lines entries of _lib.PAIR_LINE_DTYPE in device memory) over the hits, reads
+        and records of a plain sam_batch; d_byte_offsets (n_lines + 1 uint64) <- every line's first byte; returns the
+        text's length"""
+        total = C.c_uint64(0)
+        self._check(self.lib.sx_sam_layout_dev_pairs(self.h, C.byref(batch), _ptr(d_lines), n_lines, _ptr(d_byte_offsets), C.byref(total)),
+                    "sx_sam_layout_dev_pairs")
+        return int(total.value)
+
+    def sam_emit_dev_pairs(self, batch, d_lines, n_lines, d_byte_offsets, total_bytes, byte_lo, byte_hi, d_out):
+        """sx_sam_emit_dev_pairs: bytes [byte_lo, byte_hi) of the described lines' text into d_out (uint8, 16-byte aligned)"""
+        self._check(self.lib.sx_sam_emit_dev_pairs(self.h, C.byref(batch), _ptr(d_lines), n_lines, _ptr(d_byte_offsets), total_bytes, byte_lo,
+                                                   byte_hi, _ptr(d_out)), "sx_sam_emit_dev_pairs")
+
     def fastq_index(self, data):
         """sx_fastq_index of the bytes of a FASTQ file: (names, name_off, seqs, seq_off, quals, qual_off) as numpy arrays
         (uint8 bytes, uint32 offsets of count + 1 entries); raises StralgAmdError (code SX_E_MALFORMED = -4) outside the
@@ -406,6 +420,12 @@ class Context:
         gives, and a first room as small as 1 hit (0: the default, by the free memory).  Small values make the room grow and
         the batches halve on small inputs; map_stats() says what happened"""
         self._check(self.lib.sx_ctx_set_flag(self.h, _lib.SX_FLAG_SAM_ROOM_HITS, int(hits)), "sx_ctx_set_flag")
+
+    def set_pairs_room_lines(self, lines):
+        """paired reads, a test switch: the lines, and the line descriptors, that a batch of several pairs may have before it
+        is halved, in place of what the free memory gives; the hits' room stays (0: the default; set_sam_room_hits sets it
+        too where this is 0)"""
+        self._check(self.lib.sx_ctx_set_flag(self.h, _lib.SX_FLAG_PAIRS_ROOM_LINES, int(lines)), "sx_ctx_set_flag")
 
     def map_stats(self):
         """sx_map_last_stats: what the loop of the last mapping call on this context did with its batches, as a dict (batches,
@@ -821,6 +841,53 @@ class Index:
         ctx._check(self._map(ctx, buf, edits, flags, cb), "sx_index_map_reads_ex" if flags else "sx_index_map_reads")
         return seen
 
+    def _map_pairs(self, ctx, fastq1, fastq2, edits, min_insert, max_insert, flags, cb):
+        """the return code of sx_index_map_pairs"""
+        b1, b2 = (np.frombuffer(bytes(f), dtype=np.uint8) for f in (fastq1, fastq2))
+        opts = _lib.PairOpts(min_insert, max_insert)
+        return ctx.lib.sx_index_map_pairs(ctx.h, self._handle(), _ptr(b1) if b1.size else None, b1.size, _ptr(b2) if b2.size else None,
+                                          b2.size, edits, C.byref(opts), flags, cb, None)
+
+    def map_pairs(self, fastq1, fastq2, edits, min_insert=0, max_insert=1000, sink=None, best=False, indels=True, ctx=None):
+        """sx_index_map_pairs: paired-end reads.  Read p of fastq1 and read p of fastq2 are the mates of pair p; the text
+        is, per pair in file order, the two lines of every proper combination of a line of mate 1 and a line of mate 2
+        (lines as map_reads(both_strands=True) prints them at the same edits, best and indels): same record, one on
+        either strand, the forward one not behind the reverse one at either end, and min_insert <= t <= max_insert for
+        t = the reverse line's end - the forward line's POS.  FLAG is 99 / 147 or 83 / 163, RNEXT "=", PNEXT the other
+        line's POS, TLEN t or -t.  A pair without a proper combination prints nothing.  The search reports some
+        placements more than once (1I99M beside 100M) and such lines multiply: best=True and indels=False are what
+        this is meant to be combined with.  sink=None returns the text; sink(bytes) receives it window after window."""
+        ctx = ctx or self.ctx
+        chunks, failure = [], []
+        put = chunks.append if sink is None else sink
+
+        def _sink(user, section, data, nbytes):
+            try:
+                put(C.string_at(data, nbytes))
+                return 0
+            except Exception as e:  # (an exception must not cross the C frames)
+                failure.append(e)
+                return 1
+
+        rc = self._map_pairs(ctx, fastq1, fastq2, edits, min_insert, max_insert, _lib.pair_flags(best, indels), _lib.SINK_FN(_sink))
+        if failure:
+            raise failure[0]
+        ctx._check(rc, "sx_index_map_pairs")
+        return b"".join(chunks) if sink is None else None
+
+    def map_pairs_discard(self, fastq1, fastq2, edits, min_insert=0, max_insert=1000, best=False, indels=True, ctx=None):
+        """the same with a sink that does not touch the text: [(time.perf_counter(), bytes)] per window (measurement)"""
+        ctx = ctx or self.ctx
+        seen = []
+
+        def _sink(user, section, data, nbytes):
+            seen.append((time.perf_counter(), nbytes))
+            return 0
+
+        ctx._check(self._map_pairs(ctx, fastq1, fastq2, edits, min_insert, max_insert, _lib.pair_flags(best, indels), _lib.SINK_FN(_sink)),
+                   "sx_index_map_pairs")
+        return seen
+
     def write(self, sink, ctx=None):
         """sx_index_write: the index file's bytes, chunk after chunk, to sink(bytes)"""
         ctx = ctx or self.ctx
@@ -1192,3 +1259,11 @@ def map_reads(fasta, fastq, edits, ctx=None, both_strands=False, best=False, ind
     chunks = []
     ctx.map_reads_stream(records, fastq, edits, chunks.append, both_strands=both_strands, best=best, indels=indels)
     return b"".join(chunks)
+
+
+def map_pairs(fasta, fastq1, fastq2, edits, min_insert=0, max_insert=1000, ctx=None, best=False, indels=True):
+    """Index.map_pairs through a temporary Index.from_fasta on ctx: the SAM text of the proper pairs of two FASTQ files
+    (mate 1 and mate 2 of pair p are read p of either file)."""
+    ctx = ctx or default_context()
+    with Index.from_fasta(fasta, ctx=ctx) as idx:
+        return idx.map_pairs(fastq1, fastq2, edits, min_insert=min_insert, max_insert=max_insert, best=best, indels=indels)

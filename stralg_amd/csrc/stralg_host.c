@@ -1893,4 +1893,24 @@ int stralg_amd_index_map_ex(const sx_index *idx, FILE *fastq, int edits, uint32_
     return rc;
 }
 
+int stralg_amd_index_map_pairs(const sx_index *idx, FILE *fastq1, FILE *fastq2, int edits, const sx_pair_opts *opts, uint32_t flags, FILE *sam)
+{
+    if (!idx || !fastq1 || !fastq2 || !opts || !sam) {
+        fprintf(stderr, "stralg_amd_index_map_pairs: malformed arguments\n");
+        return SX_E_ARG;
+    }
+    size_t len1 = 0, len2 = 0;
+    uint8_t *image1 = read_rest(fastq1, &len1), *image2 = image1 ? read_rest(fastq2, &len2) : NULL;
+    if (!image2) {
+        free(image1);
+        return SX_E_NOMEM;
+    }
+    sx_ctx *ctx = thread_ctx();
+    const int rc = sx_index_map_pairs(ctx, idx, image1, len1, image2, len2, edits, opts, flags, sam_to_file, sam);
+    if (rc != 0) fprintf(stderr, "stralg_amd_index_map_pairs: failed (code %d): %s\n", rc, sx_last_error(ctx));
+    free(image1);
+    free(image2);
+    return rc;
+}
+
 void stralg_amd_index_free(sx_index *idx) { sx_index_destroy(idx); }

@@ -112,6 +112,7 @@ struct sx_ctx {
     sx_kernel_stat kstat[SX_KC_COUNT];
     sx_build_stats stats;
     sx_map_stats map_stats = {}; // the last mapping call's loop (sx_map.hip)
+    int64_t pairs_room_lines = 0; // SX_FLAG_PAIRS_ROOM_LINES; 0 = SX_FLAG_SAM_ROOM_HITS, or by the free memory
 };
 
 int sx_fail(sx_ctx *ctx, int code, const char *what, const char *file, int line);

@@ -10,6 +10,7 @@ static const char *kClassNames[SX_KC_COUNT] = {
     "classify", "samples", "keys", "radix_hist", "radix_scatter", "scan", "names",
     "doubling", "induce_gather", "induce_scan", "induce_scatter", "induce_chain", "bwt_gather", "otable", "misc",
     "fasta", "remap", "lcp", "search", "local_sort", "sam",
+    "pair_count", "pair_scan", "pair_fill", "pair_layout", "pair_emit",
 };
 
 int sx_fail(sx_ctx *ctx, int code, const char *what, const char *file, int line)
@@ -401,6 +402,10 @@ int sx_ctx_set_flag(sx_ctx *ctx, int flag, int value)
     }
     if (flag == SX_FLAG_SAM_ROOM_HITS) {
         ctx->sam_room_hits = value > 0 ? value : 0;
+        return 0;
+    }
+    if (flag == SX_FLAG_PAIRS_ROOM_LINES) {
+        ctx->pairs_room_lines = value > 0 ? value : 0;
         return 0;
     }
     if (flag == SX_FLAG_INDUCE_EARLY_S_OFF) {

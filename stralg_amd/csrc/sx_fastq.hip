@@ -271,9 +271,111 @@ __global__ __launch_bounds__(kBlock) void fq_strand_offsets_kernel(StrandArgs A,
     flags_out[2 * q + 1] = 16;
 }
 
+// ---- the read set of the mates of two images ------------------------------------------------------
+// Read 2p of the output is read p of image 1, read 2p + 1 read p of image 2: pair p takes the bytes [off1[p] + off2[p],
+// off1[p + 1] + off2[p + 1]) of an output array, so the offsets need no scan here either.  The bytes are cut like those of the
+// strands: a lane makes 16 output bytes in one store; it finds the read of its first byte by a search in the new offsets and
+// walks on from there.  sx_fastq_strands_dev of this set is the set of 4 x pairs reads, read 4p + 2m + s, that the mapper searches.
+struct MateArgs {
+    const uint8_t *names1, *seqs1, *quals1, *names2, *seqs2, *quals2;
+    const uint32_t *name_off1, *seq_off1, *qual_off1, *name_off2, *seq_off2, *qual_off2;
+    uint8_t *names_out, *seqs_out, *quals_out;
+    uint32_t *name_off_out, *seq_off_out, *qual_off_out;
+    uint32_t count; // pairs
+};
+
+__global__ __launch_bounds__(kBlock) void fq_mate_offsets_kernel(MateArgs A)
+{
+    const uint64_t p = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (p > A.count) return;
+    const uint32_t n1 = A.name_off1[p], n2 = A.name_off2[p], s1 = A.seq_off1[p], s2 = A.seq_off2[p], q1 = A.qual_off1[p], q2 = A.qual_off2[p];
+    A.name_off_out[2 * p] = n1 + n2;
+    A.seq_off_out[2 * p] = s1 + s2;
+    A.qual_off_out[2 * p] = q1 + q2;
+    if (p == A.count) return;
+    A.name_off_out[2 * p + 1] = A.name_off1[p + 1] + n2;
+    A.seq_off_out[2 * p + 1] = A.seq_off1[p + 1] + s2;
+    A.qual_off_out[2 * p + 1] = A.qual_off1[p + 1] + q2;
+}
+
+__global__ __launch_bounds__(kBlock) void fq_mate_bytes_kernel(MateArgs A)
+{
+    const uint32_t which = blockIdx.y;
+    const uint8_t *__restrict__ in1 = which == 0 ? A.names1 : which == 1 ? A.seqs1 : A.quals1;
+    const uint8_t *__restrict__ in2 = which == 0 ? A.names2 : which == 1 ? A.seqs2 : A.quals2;
+    const uint32_t *__restrict__ off1 = which == 0 ? A.name_off1 : which == 1 ? A.seq_off1 : A.qual_off1;
+    const uint32_t *__restrict__ off2 = which == 0 ? A.name_off2 : which == 1 ? A.seq_off2 : A.qual_off2;
+    const uint32_t *__restrict__ off = which == 0 ? A.name_off_out : which == 1 ? A.seq_off_out : A.qual_off_out;
+    uint8_t *__restrict__ out = which == 0 ? A.names_out : which == 1 ? A.seqs_out : A.quals_out;
+    const uint32_t n = 2u * A.count;
+    const uint64_t total = off[n], j0 = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) * kStrandPer;
+    if (j0 >= total) return;
+    uint32_t i = 0;
+    { // the last read i in [0, n - 1] with off[i] <= j0
+        uint32_t hi = n - 1u;
+        while (i < hi) {
+            const uint32_t mid = i + (hi - i + 1u) / 2u;
+            if ((uint64_t)off[mid] <= j0) i = mid;
+            else hi = mid - 1u;
+        }
+    }
+    uint32_t b = off[i], e = off[i + 1];
+    uint32_t w0 = 0, w1 = 0, w2 = 0, w3 = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < kStrandPer; ++k) {
+        const uint64_t j = j0 + k;
+        if (j >= total) break; // (the bytes behind the array's end are zeros: they lie in its 16 spare bytes)
+        while (j >= e && i + 1u < n) {
+            ++i;
+            b = e;
+            e = off[i + 1];
+        }
+        const uint32_t r = (uint32_t)(j - b), p = i >> 1;
+        const uint32_t c = (i & 1u) ? in2[off2[p] + r] : in1[off1[p] + r];
+        (k < 8 ? (k < 4 ? w0 : w1) : (k < 12 ? w2 : w3)) |= c << (8u * (k & 3u));
+    }
+    const uint4 v = {w0, w1, w2, w3};
+    *reinterpret_cast<uint4 *>(out + j0) = v;
+}
+
 } // namespace sx
 
 using namespace sx;
+
+// the mates of two read sets of the same count as one: read 2p <- read p of in1, read 2p + 1 <- read p of in2 (the contract of
+// sx_fastq_dev holds for *out, which sx_fastq_dev_free releases; after an error it holds no memory)
+int sx_fastq_mates_dev(sx_ctx *ctx, const sx_fastq_dev *in1, const sx_fastq_dev *in2, sx_fastq_dev *out)
+{
+    memset(out, 0, sizeof *out);
+    const uint32_t count = in1->count;
+    if (in2->count != count) return sx_fail_msg(ctx, SX_E_ARG, "paired reads: the two read sets differ in their counts");
+    const uint64_t nb = in1->name_bytes + in2->name_bytes, sb = in1->seq_bytes + in2->seq_bytes, qb = in1->qual_bytes + in2->qual_bytes;
+    if (count > 0x3FFFFFFFu || nb > 0x7FFFFFFFull || sb > 0x7FFFFFFFull || qb > 0x7FFFFFFFull)
+        return sx_fail_msg(ctx, SX_E_ARG, "paired reads: four times the pairs and twice the bytes of both images must fit 32 bits");
+    sx_dev_scope S;
+    SX_TRY(S.take(ctx, &out->d_name_off, 2 * (size_t)count + 1));
+    SX_TRY(S.take(ctx, &out->d_seq_off, 2 * (size_t)count + 1));
+    SX_TRY(S.take(ctx, &out->d_qual_off, 2 * (size_t)count + 1));
+    SX_TRY(S.take(ctx, &out->d_names, (size_t)nb + 16));
+    SX_TRY(S.take(ctx, &out->d_seqs, (size_t)sb + 16));
+    SX_TRY(S.take(ctx, &out->d_quals, (size_t)qb + 16));
+    const MateArgs A = {in1->d_names,    in1->d_seqs,    in1->d_quals,    in2->d_names,    in2->d_seqs,    in2->d_quals,
+                        in1->d_name_off, in1->d_seq_off, in1->d_qual_off, in2->d_name_off, in2->d_seq_off, in2->d_qual_off,
+                        out->d_names,    out->d_seqs,    out->d_quals,    out->d_name_off, out->d_seq_off, out->d_qual_off, count};
+    sx_launch(ctx, SX_KC_REMAP, (uint64_t)count * 48, fq_mate_offsets_kernel, dim3(sx_div_up((uint64_t)count + 1, kBlock)), dim3(kBlock), A);
+    const uint64_t most = std::max(nb, std::max(sb, qb));
+    if (count && most) // (every byte is read once and written once)
+        sx_launch(ctx, SX_KC_REMAP, 2 * (nb + sb + qb), fq_mate_bytes_kernel, dim3(sx_div_up(most, kStrandTile), 3), dim3(kBlock), A);
+    const int rc = sx_sync(ctx);
+    if (rc != 0) {
+        memset(out, 0, sizeof *out); // (S releases what was taken)
+        return rc;
+    }
+    out->count = 2 * count;
+    out->name_bytes = nb, out->seq_bytes = sb, out->qual_bytes = qb;
+    S.keep();
+    return 0;
+}
 
 extern "C" {
 

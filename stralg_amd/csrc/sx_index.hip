@@ -508,6 +508,40 @@ int sx_index_map_reads_ex(sx_ctx *ctx, const sx_index *idx, const uint8_t *fastq
     return rc;
 }
 
+// a FASTQ image through the staging buffers to the device, indexed there (the image is released again)
+static int fastq_up(sx_ctx *ctx, const uint8_t *fastq, size_t fastq_len, sx_fastq_dev *fq)
+{
+    sx_dev_scope T;
+    uint8_t *d_image;
+    SX_TRY(T.take(ctx, &d_image, fastq_len + 16));
+    SX_TRY(sx_upload_staged(ctx, d_image, fastq, fastq_len));
+    const int frc = sx_fastq_index_dev(ctx, d_image, fastq_len, fq);
+    if (frc == SX_E_MALFORMED || frc == SX_E_ARG) return sx_fail_msg(ctx, frc, "read mapping: malformed FASTQ image (see sx_fastq_index)");
+    return frc;
+}
+
+int sx_index_map_pairs(sx_ctx *ctx, const sx_index *idx, const uint8_t *fastq1, size_t len1, const uint8_t *fastq2, size_t len2, int edits,
+                       const sx_pair_opts *opts, uint32_t flags, sx_sink_fn sink, void *user)
+{
+    if (!ctx || !idx || !sink || !opts || (len1 && !fastq1) || (len2 && !fastq2)) return SX_E_ARG;
+    SX_TRY(device_check(ctx, idx));
+    if (edits < 0 || edits > SX_APPROX_MAX_EDITS) return sx_fail_msg(ctx, SX_E_ARG, "read mapping: edits must be in [0, 8]");
+    if (flags & ~(uint32_t)(SX_MAP_BOTH_STRANDS | SX_MAP_BEST_STRATUM | SX_MAP_NO_INDELS))
+        return sx_fail_msg(ctx, SX_E_ARG, "paired reads: the flags are SX_MAP_BOTH_STRANDS (implied), SX_MAP_BEST_STRATUM and SX_MAP_NO_INDELS");
+    if (opts->min_insert > opts->max_insert) return sx_fail_msg(ctx, SX_E_ARG, "paired reads: min_insert must not exceed max_insert");
+    if (len1 > 0xFFFFFFFEull || len2 > 0xFFFFFFFEull) return sx_fail_msg(ctx, SX_E_ARG, "read mapping: malformed FASTQ image (see sx_fastq_index)");
+    SX_CHECK(hipSetDevice(ctx->device));
+    sx_fastq_dev fq1, fq2;
+    memset(&fq1, 0, sizeof fq1);
+    memset(&fq2, 0, sizeof fq2);
+    int rc = fastq_up(ctx, fastq1, len1, &fq1);
+    if (rc == 0) rc = fastq_up(ctx, fastq2, len2, &fq2);
+    if (rc == 0) rc = sx_map_pairs_core(ctx, idx, fq1, fq2, edits, *opts, flags, sink, user);
+    sx_fastq_dev_free(&fq1);
+    sx_fastq_dev_free(&fq2);
+    return rc;
+}
+
 int sx_index_write(sx_ctx *ctx, const sx_index *idx, sx_sink_fn sink, void *user)
 {
     if (!ctx || !idx || !sink) return SX_E_ARG;

@@ -80,6 +80,12 @@ static inline uint32_t sx_map_search_flags(uint32_t flags) { return (flags & SX_
 // batch needs back)
 int sx_map_reads_core(sx_ctx *ctx, const sx_index *idx, const sx_fastq_dev &reads, const uint32_t *h_seq_off, int edits, uint32_t flags,
                       sx_sink_fn sink, void *user);
+// sx_map.hip: the paired call over the two mates' read sets on ctx's device; flags: SX_MAP_BEST_STRATUM,
+// SX_MAP_NO_INDELS (the callers have refused the others)
+int sx_map_pairs_core(sx_ctx *ctx, const sx_index *idx, const sx_fastq_dev &reads1, const sx_fastq_dev &reads2, int edits, const sx_pair_opts &opts,
+                      uint32_t flags, sx_sink_fn sink, void *user);
+// sx_fastq.hip: the mates of two read sets of the same count as one set of twice as many reads, read 2p + m
+int sx_fastq_mates_dev(sx_ctx *ctx, const sx_fastq_dev *in1, const sx_fastq_dev *in2, sx_fastq_dev *out);
 // sx_map.hip: SX_MAP_TAGS reads every record's string; SX_E_ARG with a message where the flag is set and a record has none
 int sx_map_tags_check(sx_ctx *ctx, const sx_index *idx, uint32_t flags);
 // sx_approx.hip: sx_bwt_approx_search_dev_ex over the tables of a record, full, compact or packed (search_flags: SX_SEARCH_*)

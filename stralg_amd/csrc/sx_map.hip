@@ -2,7 +2,8 @@
 // reads and an index that lie on the device: what sx_map_reads_stream and sx_index_map_reads share (DESIGN.md sections 11,
 // 12, 16, 17).  The reads go through in batches.  A batch: its searches, record after record, and its hits put in (read,
 // record, hit) order (on capacity: the hits' room grows or the batch is halved, and it runs again; sx_map_plan.hpp has
-// the arithmetic), then its SAM text (sx_sam.hip), window after window, to the sink.
+// the arithmetic), then its SAM text (sx_sam.hip), window after window, to the sink.  Paired reads (sx_map_pairs_core, DESIGN.md
+// section 21) go through the same loop in batches of whole pairs; their text is that of the join's line descriptors (sx_pairs.hip).
 #include "sx_common.hpp"
 #include "sx_device.hpp"
 #include "sx_scan.hpp"
@@ -10,6 +11,7 @@
 #include "sx_index.hpp"
 #include "sx_locate.hpp"
 #include "sx_sam.hpp"
+#include "sx_pairs.hpp"
 #include "sx_map_plan.hpp"
 
 #include <vector>
@@ -121,6 +123,9 @@ struct MapReads {
     uint32_t group; // 0, or (SX_MAP_BEST_STRATUM) the reads that share a stratum: 1, or 2 for the strands of a read
     uint32_t search_flags; // SX_SEARCH_* of every search of the call (SX_MAP_NO_INDELS)
     bool tags;             // NM and MD behind QUAL (SX_MAP_TAGS)
+    // paired reads, or null: the reads are 4 x pairs, read 4p + 2m + s, a batch holds whole pairs and its
+    // text is that of the join's line descriptors
+    const sx_pair_opts *pairs = nullptr;
 };
 
 struct MapBufs { // what a mapping call holds on the device beside the hits' room
@@ -243,15 +248,14 @@ static int best_batch(sx_ctx *ctx, const sx_index *idx, const MapReads &R, MapBu
 
 // The text of A's hits: its layout, then window after window through the two device windows and the context's staging
 // buffers: emit and copy of window w are queued, then the sink works on window w - 1
-static int emit_windows(sx_ctx *ctx, const SamTagArgs &A, const MapBufs &M, const sx_stage_events &E, sx_sink_fn sink, void *user)
+// (emit(lo, hi, d_out): bytes [lo, hi) of a text of `total` bytes)
+template <class Emit> static int emit_windows_of(sx_ctx *ctx, uint64_t total, const MapBufs &M, const sx_stage_events &E, sx_sink_fn sink, void *user, Emit emit)
 {
-    uint64_t total = 0;
-    SX_TRY(sam_layout(ctx, A, M.d_byte_off, &total));
     const uint64_t window = M.window, n_win = (total + window - 1) / window;
     for (uint64_t w = 0; w <= n_win; ++w) {
         if (w < n_win) {
             const uint64_t lo = w * window, hi = total - lo < window ? total : lo + window;
-            SX_TRY(sam_emit(ctx, A, M.d_byte_off, lo, hi, M.d_win[w & 1]));
+            SX_TRY(emit(lo, hi, M.d_win[w & 1]));
             SX_CHECK(hipMemcpyAsync(ctx->h_stage[w & 1], M.d_win[w & 1], (size_t)(hi - lo), hipMemcpyDeviceToHost, ctx->stream));
             SX_CHECK(hipEventRecord(E.ev[w & 1], ctx->stream));
         }
@@ -265,6 +269,13 @@ static int emit_windows(sx_ctx *ctx, const SamTagArgs &A, const MapBufs &M, cons
         }
     }
     return sx_sync(ctx);
+}
+
+static int emit_windows(sx_ctx *ctx, const SamTagArgs &A, const MapBufs &M, const sx_stage_events &E, sx_sink_fn sink, void *user)
+{
+    uint64_t total = 0;
+    SX_TRY(sam_layout(ctx, A, M.d_byte_off, &total));
+    return emit_windows_of(ctx, total, M, E, sink, user, [&](uint64_t lo, uint64_t hi, uint8_t *d_out) { return sam_emit(ctx, A, M.d_byte_off, lo, hi, d_out); });
 }
 
 // The text of a batch (`text`: its hits, reads and records) against an index with a sampled suffix array: its hits are taken
@@ -302,11 +313,91 @@ static int emit_located(sx_ctx *ctx, const sx_index *idx, const SamTagArgs &text
     return 0;
 }
 
+// ---- paired reads -----------------------------------------------------------------------------------
+struct PairBufs { // what the join of a batch holds on the device; every array grows to what the largest batch so far needed
+    uint64_t largest = 0; // lines of the batch, and line descriptors, that a batch of several pairs may have
+    PairLines L = {nullptr, nullptr, nullptr, 0};
+    uint64_t *d_cnt = nullptr, *d_byte_off = nullptr;
+    sx_pair_line *d_desc = nullptr;
+    uint64_t hits_cap = 0, lines_cap = 0, desc_cap = 0;
+    sx_dev_scope own;
+    template <class T> int grow(sx_ctx *ctx, T **d, size_t count)
+    {
+        if (*d) own.drop(*d);
+        *d = nullptr;
+        return own.take(ctx, d, count);
+    }
+};
+
+// The text of a batch of whole pairs from its merged hits (A: the batch as the emitter sees it): the lines of the batch, their
+// positions, count, scan, fill, then the descriptors' text through the windows.  SX_E_CAPACITY (a batch of several pairs
+// only): its lines or its descriptors are more than P.largest; the caller halves the batch
+static int pairs_text(sx_ctx *ctx, const sx_index *idx, const SamTagArgs &A, MapBufs &M, PairBufs &P, const sx_pair_opts &opts, bool lone,
+                      const sx_stage_events &E, sx_sink_fn sink, void *user)
+{
+    PairJoin J = {A.hits, A.n_hits, M.d_vbase, A.n_reads, A.n_records, idx->d_sa_list, idx->d_sa_lens, nullptr, opts.min_insert,
+                  opts.max_insert > 0x7FFFFFFFu ? 0x7FFFFFFFu : opts.max_insert}; // (TLEN is a signed 32-bit number)
+    if (A.n_hits + 1 > P.hits_cap) {
+        SX_TRY(P.grow(ctx, &P.L.line_off, (size_t)M.merged_cap + 1));
+        P.hits_cap = M.merged_cap + 1;
+    }
+    SX_TRY(pair_lines_count(ctx, J, P.L));
+    const uint64_t n_lines = P.L.n_lines;
+    if (n_lines == 0) return 0;
+    if (n_lines > P.largest && !lone) return SX_E_CAPACITY;
+    if (n_lines + 1 > P.lines_cap) {
+        SX_TRY(P.grow(ctx, &P.L.ps, (size_t)n_lines));
+        SX_TRY(P.grow(ctx, &P.L.hit, (size_t)n_lines));
+        SX_TRY(P.grow(ctx, &P.d_cnt, (size_t)n_lines + 1));
+        P.lines_cap = n_lines + 1;
+    }
+    if (idx->sa_log2) { // the positions of every line of the batch, located in runs of hits whose lines fit the cap
+        const LocRec *d_recs = (const LocRec *)idx->d_loc_list;
+        const uint64_t cap = map_located_rows(ctx->locate_chunk_rows);
+        if (n_lines > M.pos_cap) {
+            if (M.d_positions) M.own.drop(M.d_positions);
+            M.d_positions = nullptr, M.pos_cap = 0;
+            SX_TRY(M.own.take(ctx, &M.d_positions, (size_t)n_lines));
+            M.pos_cap = n_lines;
+        }
+        uint32_t *d_loc_err = M.d_err + 4, *d_run = M.d_err + 8;
+        for (uint64_t h_lo = 0, base = 0; h_lo < A.n_hits;) {
+            uint64_t h_hi = A.n_hits, rows = n_lines - base;
+            if (rows > cap) SX_TRY(sx_sa_hits_run(ctx, P.L.line_off, A.n_hits, h_lo, base, cap, d_run, &h_hi, &rows));
+            SX_TRY(sx_sa_locate_hits(ctx, d_recs, A.n_records, idx->packed, A.hits, P.L.line_off, h_lo, h_hi, base, rows, M.d_positions + base, d_loc_err));
+            base += rows;
+            h_lo = h_hi;
+        }
+        uint32_t e = 0;
+        SX_TRY(sx_readback(ctx, d_loc_err, 1, &e));
+        if (e) return sx_fail_msg(ctx, SX_E_INTERNAL, "read mapping: a walk over a sampled suffix array met its bound");
+        J.positions = M.d_positions;
+    }
+    SX_TRY(pair_lines_expand(ctx, J, P.L));
+    uint64_t combos = 0;
+    SX_TRY(pair_count(ctx, J, P.L, P.d_cnt, &combos));
+    if (combos == 0) return 0;
+    const uint64_t n_desc = 2 * combos;
+    if (n_desc > P.largest && !lone) return SX_E_CAPACITY;
+    if (n_desc + 1 > P.desc_cap) {
+        SX_TRY(P.grow(ctx, &P.d_desc, (size_t)n_desc));
+        SX_TRY(P.grow(ctx, &P.d_byte_off, (size_t)n_desc + 1));
+        P.desc_cap = n_desc + 1;
+    }
+    SX_TRY(pair_fill(ctx, J, P.L, P.d_cnt, P.d_desc));
+    uint64_t total = 0;
+    const SamArgs &S = A;
+    SX_TRY(sam_layout_pairs(ctx, S, P.d_desc, n_desc, P.d_byte_off, &total));
+    return emit_windows_of(ctx, total, M, E, sink, user,
+                           [&](uint64_t lo, uint64_t hi, uint8_t *d_out) { return sam_emit_pairs(ctx, S, P.d_desc, n_desc, P.d_byte_off, lo, hi, d_out); });
+}
+
 // The loop.  A batch: its hits (on capacity: grow_or_halve, again), their text, on to the next reads
 static int map_reads_loop(sx_ctx *ctx, const sx_index *idx, const MapReads &R, int edits, sx_sink_fn sink, void *user)
 {
     const sx_fastq_dev &fq = *R.fq;
-    const uint32_t n_reads = fq.count, n_records = (uint32_t)idx->recs.size(), g = R.group ? R.group : 1;
+    const uint32_t n_reads = fq.count, n_records = (uint32_t)idx->recs.size();
+    const uint32_t g = R.pairs ? 4 : R.group ? R.group : 1; // the reads that a batch keeps together
     SX_CHECK(hipSetDevice(ctx->device));
     sx_map_stats &T = ctx->map_stats; // (host counts: sx_map_last_stats)
     T = {};
@@ -314,7 +405,7 @@ static int map_reads_loop(sx_ctx *ctx, const sx_index *idx, const MapReads &R, i
     SX_TRY(M.own.take(ctx, &M.d_pat, (size_t)fq.seq_bytes));
     SX_TRY(sx_sync(ctx)); // (the callers' uploads from pageable memory are done)
 
-    const uint32_t batch_max = map_batch_max(ctx->sam_batch_reads, R.group, n_reads);
+    const uint32_t batch_max = R.pairs ? map_pairs_batch_max(ctx->sam_batch_reads, n_reads) : map_batch_max(ctx->sam_batch_reads, R.group, n_reads);
     M.window = map_window_bytes(ctx->sam_window_bytes, sx_stage_bytes);
     SX_TRY(sx_stage_ensure(ctx));
     sx_stage_events E;
@@ -338,6 +429,14 @@ static int map_reads_loop(sx_ctx *ctx, const sx_index *idx, const MapReads &R, i
     A.rnames = idx->d_rnames, A.rname_off = idx->d_rname_off, A.n_records = n_records;
     if (R.tags) A.text_list = idx->d_text_list, A.letters = idx->d_letters; // (emit_windows and emit_located carry them in A)
 
+    PairBufs P;
+    if (R.pairs) {
+        size_t free_b = 0, total_b = 0;
+        const bool known = hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b;
+        if (!known) (void)hipGetLastError();
+        P.largest = map_pairs_largest(known, free_b, ctx->pairs_room_lines > 0 ? ctx->pairs_room_lines : ctx->sam_room_hits);
+    }
+
     uint32_t q0 = 0, batch = batch_max;
     while (q0 < n_reads) {
         if (batch > n_reads - q0) batch = n_reads - q0;
@@ -357,7 +456,17 @@ static int map_reads_loop(sx_ctx *ctx, const sx_index *idx, const MapReads &R, i
             A.name_off = fq.d_name_off + q0, A.seq_off = fq.d_seq_off + q0, A.qual_off = fq.d_qual_off + q0;
             A.n_reads = batch;
             A.flags = R.d_flags ? R.d_flags + q0 : nullptr; // (the offsets are this batch's: so are the flags)
-            SX_TRY(idx->sa_log2 ? emit_located(ctx, idx, A, M, E, sink, user) : emit_windows(ctx, A, M, E, sink, user));
+            if (R.pairs) {
+                const int prc = pairs_text(ctx, idx, A, M, P, *R.pairs, batch == g, E, sink, user);
+                if (prc == SX_E_CAPACITY) { // (the lines or the descriptors of several pairs do not fit: half of them are tried)
+                    ++T.retries, ++T.halved;
+                    T.batch_final = batch = map_batch_halved(batch, g);
+                    continue;
+                }
+                SX_TRY(prc);
+            } else {
+                SX_TRY(idx->sa_log2 ? emit_located(ctx, idx, A, M, E, sink, user) : emit_windows(ctx, A, M, E, sink, user));
+            }
         }
         ++T.batches;
         q0 += batch;
@@ -408,7 +517,43 @@ int sx_map_reads_core(sx_ctx *ctx, const sx_index *idx, const sx_fastq_dev &read
     return rc;
 }
 
+// A paired mapping call over the two mates' read sets and an index on ctx's device: the mates as one
+// set, read 2p + m, then its strands, read 4p + 2m + s, searched like any read set in batches of whole pairs
+int sx_map_pairs_core(sx_ctx *ctx, const sx_index *idx, const sx_fastq_dev &reads1, const sx_fastq_dev &reads2, int edits, const sx_pair_opts &opts,
+                      uint32_t flags, sx_sink_fn sink, void *user)
+{
+    const uint32_t n_records = (uint32_t)idx->recs.size();
+    if (reads1.count != reads2.count) return sx_fail_msg(ctx, SX_E_ARG, "paired reads: the two FASTQ images differ in their read counts");
+    if (reads1.count == 0 || n_records == 0) return 0;
+    if (sx_map_pairs_limit(reads1.count, n_records) != 0) return sx_fail_msg(ctx, SX_E_ARG, "paired reads: 4 x pairs x records must stay below 2^32");
+    for (const sx_index_rec &R : idx->recs)
+        if (!sx_map_dims_ok(R.N, R.sigma, 2)) return sx_fail_msg(ctx, SX_E_ARG, "read mapping: a record lacks its name, suffix array, tables or remap table");
+    SX_CHECK(hipSetDevice(ctx->device));
+    sx_fastq_dev mates = {}, both = {};
+    int rc = sx_fastq_mates_dev(ctx, &reads1, &reads2, &mates);
+    if (rc != 0) return sx_nomem_of(rc);
+    sx_dev_scope F;
+    uint16_t *d_flags = nullptr;
+    rc = F.take(ctx, &d_flags, 2 * (size_t)mates.count);
+    if (rc == 0) rc = sx_fastq_strands_dev(ctx, &mates, &both, d_flags);
+    sx_fastq_dev_free(&mates);
+    if (rc != 0) return rc;
+    MapReads R = {&both, nullptr, nullptr, (flags & SX_MAP_BEST_STRATUM) ? 2u : 0u, sx_map_search_flags(flags), false};
+    R.pairs = &opts;
+    rc = map_reads_loop(ctx, idx, R, edits, sink, user);
+    sx_fastq_dev_free(&both);
+    return rc;
+}
+
 extern "C" {
+
+int sx_map_pairs_limit(uint64_t n_pairs, uint64_t n_records)
+{
+    // (no product is formed before it is known to fit)
+    if (n_pairs > 0xFFFFFFFFull / 4) return SX_E_ARG;
+    if (n_records && n_pairs * 4 > 0xFFFFFFFFull / n_records) return SX_E_ARG;
+    return 0;
+}
 
 int sx_map_reads_limit(uint64_t n_reads, uint64_t n_records, uint32_t flags)
 {

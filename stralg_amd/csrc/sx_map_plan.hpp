@@ -63,6 +63,26 @@ static inline size_t map_window_bytes(int64_t flag, size_t stage_bytes)
     return window > stage_bytes ? stage_bytes : window;
 }
 
+// Paired reads.  Reads of a batch: whole pairs, four reads each (n_reads is a multiple of four); here
+// the flag, SX_FLAG_SAM_BATCH_READS, counts pairs; 2^18 pairs where it is not set
+static inline uint32_t map_pairs_batch_max(int64_t flag, uint32_t n_reads)
+{
+    const uint64_t pairs = flag > 0 ? (uint64_t)flag : 1u << 18;
+    return pairs * 4 > n_reads ? n_reads : (uint32_t)(pairs * 4);
+}
+
+// The lines of a batch, and the line descriptors of its proper combinations, that a batch of several pairs may have before
+// it is halved (a pair alone gets whatever it needs): 2^27, or what a quarter of the free memory holds at 28 bytes each (a
+// line: position, span, hit, count; a descriptor: 20 bytes and its byte offset), 2^16 at least.  room_flag:
+// SX_FLAG_PAIRS_ROOM_LINES, or where that is 0 SX_FLAG_SAM_ROOM_HITS, the test switch of the hits' room; > 0: that many
+static inline uint64_t map_pairs_largest(bool free_known, uint64_t free_bytes, int64_t room_flag = 0)
+{
+    if (room_flag > 0) return (uint64_t)room_flag;
+    uint64_t largest = 1ull << 26;
+    if (free_known && free_bytes) largest = free_bytes / 4 / 28 < (1ull << 27) ? free_bytes / 4 / 28 : 1ull << 27;
+    return largest < (1u << 16) ? 1u << 16 : largest;
+}
+
 // lines a located run may have; flag: SX_FLAG_LOCATE_CHUNK_ROWS
 static inline uint64_t map_located_rows(int64_t flag) { return flag > 0 ? (uint64_t)flag : 1ull << 28; }
 

@@ -491,6 +491,157 @@ template <bool kLocated, bool kFlags, bool kTags> __global__ __launch_bounds__(k
     if (t < tail) dst[full * 16u + t] = obuf[full * 16u + t];
 }
 
+// ---- lines with a mate ---------------------------------------------------------------------------
+// A line descriptor (sx_pair_line) names a hit and brings POS, FLAG, PNEXT and TLEN; the hit gives the read, the record and
+// the CIGAR.  One lane a line in both passes: a line's first byte is its entry of the scanned sizes, so the emit needs no walk
+// inside a hit and no step over 256 hits.  The kernels are separate from the ones above, which keep their registers and LDS.
+struct PairHit {
+    uint32_t name_b, name_l, seq_b, seq_l, qual_b, qual_l, rn_b, rn_l, n_gaps;
+    uint4 gaps;
+};
+
+// what line descriptors take of hit h (hit_info without the positions); false: the hit does not fit the batch
+__device__ __forceinline__ bool pair_hit(const SamArgs &A, uint64_t h, PairHit &P)
+{
+    if (h >= A.n_hits) return false;
+    const uint4 h0 = A.hits[2 * h];
+    P.gaps = A.hits[2 * h + 1];
+    const uint32_t vq = h0.x;
+    if ((uint64_t)vq >= (uint64_t)A.n_reads * A.n_records) return false;
+    const uint32_t read = vq / A.n_records, rec = vq - read * A.n_records;
+    P.name_b = A.name_off[read];
+    P.seq_b = A.seq_off[read];
+    P.qual_b = A.qual_off[read];
+    P.rn_b = A.rname_off[rec];
+    const uint32_t name_e = A.name_off[read + 1], seq_e = A.seq_off[read + 1], qual_e = A.qual_off[read + 1], rn_e = A.rname_off[rec + 1];
+    if (name_e < P.name_b || seq_e < P.seq_b || qual_e < P.qual_b || rn_e < P.rn_b) return false;
+    P.name_l = name_e - P.name_b;
+    P.seq_l = seq_e - P.seq_b;
+    P.qual_l = qual_e - P.qual_b;
+    P.rn_l = rn_e - P.rn_b;
+    P.n_gaps = h0.w >> 16;
+    if (P.n_gaps > SX_APPROX_MAX_EDITS) P.n_gaps = SX_APPROX_MAX_EDITS;
+    return true;
+}
+
+__device__ __forceinline__ uint32_t tlen_magnitude(int32_t t) { return t < 0 ? 0u - (uint32_t)t : (uint32_t)t; }
+
+// the digits of v at slice offset `off` (may be negative), clipped to the slice; no buffer of the lane's own
+__device__ __forceinline__ void put_dec_clipped(uint8_t *obuf, int64_t &off, int64_t slice_len, uint32_t v)
+{
+    const uint32_t nd = dec_digits(v);
+    for (uint32_t d = 0; d < nd; ++d) {
+        const int64_t where = off + (int64_t)(nd - 1u - d);
+        if (where >= 0 && where < slice_len) obuf[where] = (uint8_t)('0' + v % 10u);
+        v /= 10u;
+    }
+    off += nd;
+}
+
+// 10 tabs, the newline, MAPQ "0" and RNEXT "=": the 13 bytes of a line beside its fields and numbers
+__global__ __launch_bounds__(kBlock) void sam_pair_size_kernel(SamArgs A, const sx_pair_line *lines, uint64_t n_lines, uint64_t *len_out, uint32_t *err)
+{
+    const uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (j >= n_lines) return;
+    const sx_pair_line D = lines[j];
+    PairHit P;
+    uint64_t bytes = 0;
+    if (!pair_hit(A, D.hit, P)) {
+        atomicOr(err, 1u);
+    } else {
+        bytes = (uint64_t)P.name_l + P.rn_l + cigar_render(nullptr, kCigarMax, P.seq_l, P.gaps, P.n_gaps) + P.seq_l + P.qual_l + 13u +
+                dec_digits(D.flag) + dec_digits(D.pos) + dec_digits(D.pnext) + (D.tlen < 0 ? 1u : 0u) + dec_digits(tlen_magnitude(D.tlen));
+    }
+    len_out[j] = bytes;
+}
+
+__global__ __launch_bounds__(kBlock) void sam_pair_emit_kernel(SamArgs A, const sx_pair_line *lines, uint64_t n_lines, const uint64_t *byte_off,
+                                                               uint64_t lo, uint64_t hi, uint8_t *out)
+{
+    __shared__ uint4 obuf4[kSlice / 16];
+    __shared__ uint8_t cig[kBlock * kCigarMax]; // a lane's CIGAR: rendered once, then copied like a field
+    uint8_t *obuf = (uint8_t *)obuf4;
+    const uint32_t t = threadIdx.x;
+    const uint64_t s_lo = lo + (uint64_t)blockIdx.x * kSlice;
+    if (s_lo >= hi) return; // (the whole workgroup)
+    const uint64_t s_hi = hi - s_lo < kSlice ? hi : s_lo + kSlice;
+    const int64_t slice_len = (int64_t)(s_hi - s_lo);
+    // the line at the slice's first byte: the last j with byte_off[j] <= s_lo (byte_off[n_lines] = total > s_lo)
+    uint64_t j0 = 0;
+    {
+        uint64_t b = n_lines;
+        while (b - j0 > 1) {
+            const uint64_t mid = j0 + (b - j0) / 2;
+            if (byte_off[mid] <= s_lo) j0 = mid;
+            else b = mid;
+        }
+    }
+    // lines j0 + t, j0 + 256 + t, ... as far as they begin inside the slice (a line has 19 bytes at least)
+    for (uint64_t j = j0 + t; j < n_lines; j += kBlock) {
+        const uint64_t line_abs = byte_off[j];
+        if (line_abs >= s_hi) break;
+        const sx_pair_line D = lines[j];
+        PairHit P;
+        if (!pair_hit(A, D.hit, P)) continue; // (the layout refused it)
+        const uint32_t cig_len = cigar_render(cig + t * kCigarMax, kCigarMax, P.seq_l, P.gaps, P.n_gaps);
+        int64_t off = (int64_t)line_abs - (int64_t)s_lo;
+        put_bytes(obuf, off, slice_len, A.names + P.name_b, P.name_l);
+        put_bytes(obuf, off, slice_len, (const uint8_t *)"\t", 1);
+        put_dec_clipped(obuf, off, slice_len, D.flag);
+        put_bytes(obuf, off, slice_len, (const uint8_t *)"\t", 1);
+        put_bytes(obuf, off, slice_len, A.rnames + P.rn_b, P.rn_l);
+        put_bytes(obuf, off, slice_len, (const uint8_t *)"\t", 1);
+        put_dec_clipped(obuf, off, slice_len, D.pos);
+        put_bytes(obuf, off, slice_len, (const uint8_t *)"\t0\t", 3);
+        put_bytes(obuf, off, slice_len, cig + t * kCigarMax, cig_len);
+        put_bytes(obuf, off, slice_len, (const uint8_t *)"\t=\t", 3);
+        put_dec_clipped(obuf, off, slice_len, D.pnext);
+        put_bytes(obuf, off, slice_len, (const uint8_t *)"\t-", D.tlen < 0 ? 2 : 1);
+        put_dec_clipped(obuf, off, slice_len, tlen_magnitude(D.tlen));
+        put_bytes(obuf, off, slice_len, (const uint8_t *)"\t", 1);
+        put_bytes(obuf, off, slice_len, A.seqs + P.seq_b, P.seq_l);
+        put_bytes(obuf, off, slice_len, (const uint8_t *)"\t", 1);
+        put_bytes(obuf, off, slice_len, A.quals + P.qual_b, P.qual_l);
+        put_bytes(obuf, off, slice_len, (const uint8_t *)"\n", 1);
+    }
+    __syncthreads();
+    uint8_t *dst = out + (s_lo - lo);
+    const uint32_t full = (uint32_t)(slice_len / 16);
+    for (uint32_t k = t; k < full; k += kBlock) stream_store16((uint4 *)dst + k, obuf4[k]);
+    const uint32_t tail = (uint32_t)slice_len - full * 16u;
+    if (t < tail) dst[full * 16u + t] = obuf[full * 16u + t];
+}
+
+int sam_layout_pairs(sx_ctx *ctx, const SamArgs &A, const sx_pair_line *d_lines, uint64_t n_lines, uint64_t *d_byte_off, uint64_t *total_out)
+{
+    *total_out = 0;
+    SX_TRY(sx_slab_ensure(ctx, SX_SLAB_SORT, 4096));
+    uint32_t *d_err = (uint32_t *)ctx->slab[SX_SLAB_SORT].p;
+    SX_CHECK(hipMemsetAsync(d_err, 0, 16, ctx->stream));
+    if (n_lines) // (a descriptor in, a size out, 32 bytes of its hit and the offsets of its read)
+        sx_launch(ctx, SX_KC_PAIR_LAYOUT, n_lines * 76, sam_pair_size_kernel, dim3(sx_div_up(n_lines, kBlock)), dim3(kBlock), A, d_lines, n_lines,
+                  d_byte_off, d_err);
+    SX_TRY(device_scan64_inplace(ctx, d_byte_off, n_lines, SX_KC_PAIR_LAYOUT));
+    uint32_t h[2] = {0, 0}, e = 0;
+    SX_TRY(sx_readback(ctx, (const uint32_t *)(d_byte_off + n_lines), 2, h));
+    SX_TRY(sx_readback(ctx, d_err, 1, &e));
+    if (e) return sx_fail_msg(ctx, SX_E_ARG, "SAM text: a line descriptor's hit, or that hit's query or offsets, lie outside the batch");
+    *total_out = (uint64_t)h[0] | ((uint64_t)h[1] << 32);
+    return 0;
+}
+
+// (asynchronous: the caller syncs)
+int sam_emit_pairs(sx_ctx *ctx, const SamArgs &A, const sx_pair_line *d_lines, uint64_t n_lines, const uint64_t *d_byte_off, uint64_t lo,
+                   uint64_t hi, uint8_t *d_out)
+{
+    if (hi <= lo) return 0;
+    const uint64_t slices = (hi - lo + kSlice - 1) / kSlice;
+    if (slices > 0x7FFFFFFFull) return sx_fail_msg(ctx, SX_E_ARG, "SAM text: window too long");
+    sx_launch(ctx, SX_KC_PAIR_EMIT, hi - lo, sam_pair_emit_kernel, dim3((uint32_t)slices), dim3(kBlock), A, d_lines, n_lines, d_byte_off, lo, hi,
+              d_out);
+    return 0;
+}
+
 // what the kernels get of a batch (SamArgs has sx_sam_batch's fields in its order)
 static SamArgs sam_args_of(const sx_sam_batch &b)
 {
@@ -624,6 +775,41 @@ int sx_sam_emit_dev_tags(sx_ctx *ctx, const sx_sam_batch_tags *batch, const uint
         return sx_fail_msg(ctx, SX_E_ARG, "SAM text: a window inside [0, total) and a 16-byte aligned buffer are needed");
     SX_CHECK(hipSetDevice(ctx->device));
     SX_TRY(sam_emit(ctx, A, d_byte_offsets, byte_lo, byte_hi, d_out));
+    return sx_sync(ctx);
+}
+
+// a batch for line descriptors: hits, reads and records; no suffix array is asked for
+static int sam_args_pairs(sx_ctx *ctx, const sx_sam_batch *b, const sx_pair_line *d_lines, uint64_t n_lines, SamArgs &A)
+{
+    if (!ctx || !b) return SX_E_ARG;
+    if (n_lines && (!d_lines || ((uintptr_t)d_lines & 3) || !b->d_hits || ((uintptr_t)b->d_hits & 15)))
+        return sx_fail_msg(ctx, SX_E_ARG, "SAM text: line descriptors (4-byte aligned) and hits (16-byte aligned) are needed");
+    if (!b->d_name_off || !b->d_seq_off || !b->d_qual_off || !b->d_rname_off || b->n_records == 0 ||
+        (uint64_t)b->n_reads * b->n_records > 0xFFFFFFFFull)
+        return sx_fail_msg(ctx, SX_E_ARG, "SAM text: offsets of the reads and record names; reads x records below 2^32");
+    A = sam_args_of(*b);
+    return 0;
+}
+
+int sx_sam_layout_dev_pairs(sx_ctx *ctx, const sx_sam_batch *batch, const sx_pair_line *d_lines, uint64_t n_lines, uint64_t *d_byte_offsets,
+                            uint64_t *total_bytes_out)
+{
+    SamArgs A;
+    SX_TRY(sam_args_pairs(ctx, batch, d_lines, n_lines, A));
+    if (!d_byte_offsets || !total_bytes_out) return SX_E_ARG;
+    SX_CHECK(hipSetDevice(ctx->device));
+    return sam_layout_pairs(ctx, A, d_lines, n_lines, d_byte_offsets, total_bytes_out);
+}
+
+int sx_sam_emit_dev_pairs(sx_ctx *ctx, const sx_sam_batch *batch, const sx_pair_line *d_lines, uint64_t n_lines, const uint64_t *d_byte_offsets,
+                          uint64_t total_bytes, uint64_t byte_lo, uint64_t byte_hi, uint8_t *d_out)
+{
+    SamArgs A;
+    SX_TRY(sam_args_pairs(ctx, batch, d_lines, n_lines, A));
+    if (!d_byte_offsets || byte_lo > byte_hi || byte_hi > total_bytes || (n_lines == 0 && byte_hi > byte_lo) || (byte_hi > byte_lo && (!d_out || ((uintptr_t)d_out & 15))))
+        return sx_fail_msg(ctx, SX_E_ARG, "SAM text: a window inside [0, total) and a 16-byte aligned buffer are needed");
+    SX_CHECK(hipSetDevice(ctx->device));
+    SX_TRY(sam_emit_pairs(ctx, A, d_lines, n_lines, d_byte_offsets, byte_lo, byte_hi, d_out));
     return sx_sync(ctx);
 }
 

@@ -41,4 +41,12 @@ int sam_layout(sx_ctx *ctx, const SamTagArgs &A, uint64_t *d_byte_off, uint64_t 
 // bytes [lo, hi) of the text to d_out (asynchronous: the caller syncs)
 int sam_emit(sx_ctx *ctx, const SamTagArgs &A, const uint64_t *d_byte_off, uint64_t lo, uint64_t hi, uint8_t *d_out);
 
+// Lines with a mate: the text of n_lines line descriptors over A's hits, reads and records (A's suffix
+// arrays, positions and flags are not read: a descriptor has its POS and its FLAG).  d_byte_off[j] (n_lines + 1 entries) <-
+// the first output byte of line j, the last entry and *total_out <- the text's length
+int sam_layout_pairs(sx_ctx *ctx, const SamArgs &A, const sx_pair_line *d_lines, uint64_t n_lines, uint64_t *d_byte_off, uint64_t *total_out);
+// bytes [lo, hi) of that text to d_out (asynchronous: the caller syncs)
+int sam_emit_pairs(sx_ctx *ctx, const SamArgs &A, const sx_pair_line *d_lines, uint64_t n_lines, const uint64_t *d_byte_off, uint64_t lo,
+                   uint64_t hi, uint8_t *d_out);
+
 } // namespace sx

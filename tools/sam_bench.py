@@ -17,9 +17,14 @@ kernel ms (every run: the spread), layout and emit over its hits, and the stream
 also with both flags) beside the plain one (kept in profiles/no_indels_bench_2p28.json).  --tags adds, per k (and per
 no-indels entry), layout and emit over the same hits with NM:i and MD:Z behind QUAL (sx_sam_layout_dev_tags /
 sx_sam_emit_dev_tags), and the call through a resident index with its strings (Index.map_reads_discard) with and without
-tags=True (kept in profiles/tags_bench_2p28.json).
+tags=True (kept in profiles/tags_bench_2p28.json).  --pairs adds paired-end reads: every read gets a
+mate drawn 200 - 499 symbols downstream on the other strand, with the same substitution rates, and per k Index.map_pairs_discard
+with indels=False, and with best=True as well, on the two files: the call's wall time, the kernel ms of its five classes
+(pair_count, pair_scan, pair_fill, pair_layout, pair_emit; a run of their own with every launch timed), the emit's rate over
+its text against the plain emit's, and the wall time of the two both_strands calls on the two files with the same flags
+(kept in profiles/pairs_bench_2p28.json).
 
-    python tools/sam_bench.py [--log2n 28] [--reads 1000000] [--window-mib 1024] [--repeats 5] [--both-strands] [--best] [--no-indels] [--tags]
+    python tools/sam_bench.py [--log2n 28] [--reads 1000000] [--window-mib 1024] [--repeats 5] [--both-strands] [--best] [--no-indels] [--tags] [--pairs]
 """
 import argparse
 import ctypes as C
@@ -48,6 +53,7 @@ def main():
     ap.add_argument("--best", action="store_true", help="also the best-stratum search, its rounds and the streamed call with best=True")
     ap.add_argument("--no-indels", action="store_true", help="also the search, the text and the streamed call without indels")
     ap.add_argument("--tags", action="store_true", help="also layout, emit and the index call with NM:i and MD:Z on every line")
+    ap.add_argument("--pairs", action="store_true", help="also the paired call on the reads and their mates, indels=False without and with best=True")
     args = ap.parse_args()
     import torch
 
@@ -288,6 +294,53 @@ def main():
                                      "text_bytes": int(runs[0][1])}
                     where = out[f"k{k}"] if not key else out[f"k{k}"].setdefault(key, {})
                     where["index_call"] = res
+    if args.pairs:
+        # the mates: 200 - 499 symbols downstream of their reads, on the other strand, substitutions drawn like the reads'
+        prng = np.random.default_rng(101)
+        gap = prng.integers(200, 500, R)
+        m_starts = np.minimum(starts + gap, n - L)
+        mates = text[m_starts[:, None] + np.arange(L)[None, :]]
+        for e in range(2):
+            hit = prng.random(R) < (0.5 if e == 0 else 0.25)
+            at = prng.integers(0, L, R)
+            rows = np.flatnonzero(hit)
+            mates[rows, at[rows]] = 1 + (mates[rows, at[rows]] % 4)
+        rc_letters = np.frombuffer(b"\0TGCA", np.uint8)  # (the complement of the letter behind every code)
+        fastq2 = b"".join(b"@%s\n%s\n+\n%s\n" % (names[q], row.tobytes(), b"~" * L) for q, row in enumerate(rc_letters[mates[:, ::-1]]))
+        pair_classes = ["pair_count", "pair_scan", "pair_fill", "pair_layout", "pair_emit"]
+        with api.Index.from_tables([(b"chr1", rec)], ctx=ctx) as idx:
+            for k in [int(x) for x in args.ks.split(",")]:
+                res = {}
+                for key, kw in [("no_indels", dict(indels=False)), ("no_indels_best", dict(indels=False, best=True))]:
+                    runs = []
+                    for _ in range(args.repeats):
+                        t0 = time.perf_counter()
+                        seen = idx.map_pairs_discard(fastq, fastq2, k, 0, 1000, **kw)
+                        runs.append((time.perf_counter() - t0, sum(b for _, b in seen)))
+                    singles = []
+                    for _ in range(args.repeats):
+                        t0 = time.perf_counter()
+                        b1 = sum(b for _, b in idx.map_reads_discard(fastq, k, both_strands=True, **kw))
+                        b2 = sum(b for _, b in idx.map_reads_discard(fastq2, k, both_strands=True, **kw))
+                        singles.append((time.perf_counter() - t0, b1 + b2))
+                    # the five classes' kernel time: one more call with every launch between events
+                    ctx.profile_only(None)
+                    ctx.profile_enable(True)
+                    ctx.profile_reset()
+                    idx.map_pairs_discard(fastq, fastq2, k, 0, 1000, **kw)
+                    prof = ctx.profile_read()
+                    ctx.profile_enable(False)
+                    text_bytes, wall = int(runs[0][1]), min(r[0] for r in runs)
+                    emit_ms = prof["pair_emit"]["ms"]
+                    res[key] = {"text_bytes": text_bytes, "call_wall_ms": round(wall * 1e3, 1), "call_wall_ms_runs": [round(r[0] * 1e3, 1) for r in runs],
+                                "two_both_strands_calls_wall_ms": round(min(r[0] for r in singles) * 1e3, 1),
+                                "two_both_strands_calls_wall_ms_runs": [round(r[0] * 1e3, 1) for r in singles],
+                                "two_both_strands_calls_text_bytes": int(singles[0][1]),
+                                "over_two_both_strands_calls": round(wall / min(r[0] for r in singles), 3),
+                                "kernel_ms": {c: round(prof[c]["ms"], 3) for c in pair_classes + ["search", "sam", "remap"]},
+                                "launches": {c: int(prof[c]["launches"]) for c in pair_classes},
+                                "emit_GBps_of_text": round(text_bytes / (emit_ms * 1e-3) / 1e9, 1) if emit_ms > 0 else None}
+                out[f"k{k}"]["pairs"] = res
     if args.both_strands:
         # the strand kernel alone: the image indexed on the device, then sx_fastq_strands_dev (launches of the remap class)
         d_img = torch.from_numpy(np.concatenate([img, pad])).cuda()

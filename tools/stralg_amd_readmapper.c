@@ -42,6 +42,17 @@
  *                                                   distance and the mismatch string of its POS, CIGAR and SEQ over the
  *                                                   record's letters, rendered on the device; goes with every other
  *                                                   switch
+ *   -2 mates.fq (--mates)                           with -d and one reads.fq: paired-end reads.  Read p of reads.fq and read p of
+ *                                                   mates.fq are the mates of pair p; the output is the two lines of every
+ *                                                   proper pair of their placements -- same record, one mate on either
+ *                                                   strand, the forward one in front, the distance from its first base to
+ *                                                   the reverse one's last in the window -- with FLAG 99 / 147 or 83 / 163,
+ *                                                   RNEXT "=", PNEXT and TLEN; a pair without one prints nothing.  Both
+ *                                                   strands are implied.  Goes with -i, --compact, --sa-sample, --packed,
+ *                                                   --best and --no-indels (which is what it is meant to be used with: the
+ *                                                   search reports some placements with indels more than once); not with
+ *                                                   --tags or several read files
+ *   --min-insert N, --max-insert N                  with -2: the window of that distance (0 and 1000)
  *   (--preprocess, --edits and --in-memory are accepted for -p, -d and -i)
  *
  * Index file: u32 record count; per record, last FASTA record first, its name as u32 length + bytes + NUL, then the
@@ -131,7 +142,8 @@ static int build_index(const char *fasta)
 
 /* -d: the index is loaded once (from genome.fa.bwttables, or, with -i, built on the device from genome.fa itself) and
  * stays on the device; every FASTQ file is mapped against it, stdout is the files' texts one behind the other */
-static int map_reads(const char *fasta, char *const *reads, int n_reads, int k, int in_memory, uint32_t flags, uint32_t map_flags)
+static int map_reads(const char *fasta, char *const *reads, int n_reads, int k, int in_memory, uint32_t flags, uint32_t map_flags,
+                     const char *mates, const sx_pair_opts *window)
 {
     struct sx_index *idx = NULL;
     if (in_memory) {
@@ -150,6 +162,14 @@ static int map_reads(const char *fasta, char *const *reads, int n_reads, int k, 
         free(path);
     }
     int rc = 0;
+    if (mates) { /* -2: reads[0] and mates are the two files of the pairs */
+        FILE *fq1 = fopen(reads[0], "rb"), *fq2 = fopen(mates, "rb");
+        if (!fq1 || !fq2) fail("cannot read", fq1 ? mates : reads[0]);
+        rc = stralg_amd_index_map_pairs(idx, fq1, fq2, k, window, map_flags, stdout);
+        fclose(fq1);
+        fclose(fq2);
+        n_reads = 0;
+    }
     for (int f = 0; f < n_reads && rc == 0; ++f) {
         FILE *fq = fopen(reads[f], "rb");
         if (!fq) fail("cannot read", reads[f]);
@@ -178,12 +198,16 @@ static int usage(const char *self, int status)
     fprintf(stderr, "       --no-indels                        with -d K: mismatches only, every placement within K substitutions\n");
     fprintf(stderr, "                                          once (with --best: the smallest number of substitutions)\n");
     fprintf(stderr, "       --tags                             with -d: NM:i and MD:Z behind QUAL on every line\n");
+    fprintf(stderr, "       -2 mates.fq, --mates mates.fq      with -d and one reads.fq: paired-end reads, the lines of the proper\n");
+    fprintf(stderr, "                                          pairs (FLAG 99 / 147, 83 / 163); not with --tags\n");
+    fprintf(stderr, "       --min-insert N, --max-insert N     with -2: the window of a pair's length (0, 1000)\n");
     return status;
 }
 
 int main(int argc, char **argv)
 {
-    const char *to_index = NULL;
+    const char *to_index = NULL, *mates = NULL;
+    sx_pair_opts window = {0, 1000};
     char **rest = calloc((size_t)argc + 1, sizeof *rest);
     int k = -1, n_rest = 0, in_memory = 0, indexing = 0;
     uint32_t flags = 0, sa_log2 = 0, map_flags = 0;
@@ -206,6 +230,15 @@ int main(int argc, char **argv)
             map_flags |= SX_MAP_NO_INDELS;
         } else if (!strcmp(s, "--tags")) {
             map_flags |= SX_MAP_TAGS;
+        } else if (!strcmp(s, "-2") || !strcmp(s, "--mates")) {
+            if (++a >= argc) return usage(argv[0], EXIT_FAILURE);
+            mates = argv[a];
+        } else if (!strcmp(s, "--min-insert") || !strcmp(s, "--max-insert")) {
+            if (++a >= argc) return usage(argv[0], EXIT_FAILURE);
+            char *end = NULL;
+            const unsigned long long v = strtoull(argv[a], &end, 10);
+            if (argv[a][0] < '0' || argv[a][0] > '9' || *end || v > 0xFFFFFFFFull) fail("an insert size is a number below 2^32, not", argv[a]);
+            *(s[3] == 'i' ? &window.min_insert : &window.max_insert) = (uint32_t)v;
         } else if (!strcmp(s, "--sa-sample")) {
             if (++a >= argc) return usage(argv[0], EXIT_FAILURE);
             const long dist = strtol(argv[a], NULL, 10);
@@ -231,5 +264,8 @@ int main(int argc, char **argv)
     if (indexing && !to_index && n_rest) to_index = rest[0];
     if (indexing) return to_index ? build_index(to_index) : usage(argv[0], EXIT_FAILURE);
     if (n_rest < 2 || k < 0) return usage(argv[0], EXIT_FAILURE);
-    return map_reads(rest[0], rest + 1, n_rest - 1, k, in_memory, flags, map_flags);
+    if (mates && (map_flags & SX_MAP_TAGS)) fail("-2 does not go with --tags", NULL);
+    if (mates && n_rest != 2) fail("-2 takes one reads file beside the mates' file", NULL);
+    if (mates && window.min_insert > window.max_insert) fail("--min-insert must not exceed --max-insert", NULL);
+    return map_reads(rest[0], rest + 1, n_rest - 1, k, in_memory, flags, map_flags, mates, &window);
 }
