@@ -418,6 +418,14 @@ typedef struct sx_sam_batch_tags {
 int sx_sam_layout_dev_tags(sx_ctx *ctx, const sx_sam_batch_tags *batch, uint64_t *d_byte_offsets, uint64_t *total_bytes_out);
 int sx_sam_emit_dev_tags(sx_ctx *ctx, const sx_sam_batch_tags *batch, const uint64_t *d_byte_offsets, uint64_t total_bytes, uint64_t byte_lo,
                          uint64_t byte_hi, uint8_t *d_out);
+/* The emitter of SX_MAP_UNMAPPED: the batch of sx_sam_batch_tags, d_text_list and d_letters both or
+ * neither (neither: no tags), and a hit with R == L is the placeholder of a read that has no line: it prints
+ *     <qname>\t4\t*\t0\t0\t*\t*\t0\t0\t<seq>\t<qual>\n
+ * of the read of its query (no position, CIGAR, NM or MD; FLAG 4 whatever d_read_flags says).  Every other hit prints its
+ * lines as the calls above do. */
+int sx_sam_layout_dev_unmapped(sx_ctx *ctx, const sx_sam_batch_tags *batch, uint64_t *d_byte_offsets, uint64_t *total_bytes_out);
+int sx_sam_emit_dev_unmapped(sx_ctx *ctx, const sx_sam_batch_tags *batch, const uint64_t *d_byte_offsets, uint64_t total_bytes, uint64_t byte_lo,
+                             uint64_t byte_hi, uint8_t *d_out);
 
 /* Lines with a mate.  A line descriptor names a hit of the batch (its read, record, CIGAR, SEQ and QUAL
  * are the hit's) and carries what the hit does not say: line j prints
@@ -506,8 +514,19 @@ int sx_map_reads_stream(sx_ctx *ctx, const sx_map_record *records, uint32_t n_re
  * any combination and with every form of the index, and does not change the limit on reads x records.  The records'
  * remapped strings must be on the device: an index with a record that was given without its string (sx_index_from_tables),
  * and sx_map_reads_stream_ex, whose records have none, answer SX_E_ARG before anything is launched or sunk.  Bit 32 stays
- * unknown. */
-enum { SX_MAP_BOTH_STRANDS = 1, SX_MAP_BEST_STRATUM = 8, SX_MAP_NO_INDELS = 16, SX_MAP_TAGS = 64 };
+ * unknown.
+ * Unmapped reads.  With SX_MAP_UNMAPPED the lines of the same call without the flag stay as they
+ * are, and every read group for which that call prints no line (a group: a read, or with SX_MAP_BOTH_STRANDS the read and
+ * its reverse complement; no line in any record, on either strand, in any stratum) gets one, where its lines would stand:
+ *     <qname>\t4\t*\t0\t0\t*\t*\t0\t0\t<seq>\t<qual>\n
+ * with QNAME, SEQ and QUAL of the read as the FASTQ has them (forward orientation, FLAG 4 also with both strands) and no
+ * NM / MD under SX_MAP_TAGS.  It composes with the other flags and every index form and does not change the limit;
+ * sx_index_map_pairs answers it with SX_E_ARG.
+ * Header.  With SX_MAP_HEADER one sink call in front of the text writes "@HD\tVN:1.6\tSO:unsorted\n"
+ * and, per record in the mapper's list order, "@SQ\tSN:<name>\tLN:<N - 1>\n", <name> byte for byte the RNAME of the lines.
+ * Every argument check comes first (a refused call sinks nothing); an empty FASTQ gives the header alone.  It composes with
+ * everything, sx_index_map_pairs included.  Neither bit changes a byte or a launch of a call without it. */
+enum { SX_MAP_BOTH_STRANDS = 1, SX_MAP_BEST_STRATUM = 8, SX_MAP_NO_INDELS = 16, SX_MAP_TAGS = 64, SX_MAP_UNMAPPED = 128, SX_MAP_HEADER = 256 };
 int sx_map_reads_stream_ex(sx_ctx *ctx, const sx_map_record *records, uint32_t n_records, const uint8_t *fastq, size_t fastq_len,
                            int edits, uint32_t flags, sx_sink_fn sink, void *user);
 /* the limit of a mapping call on its reads and records: 0, or SX_E_ARG when reads x records (twice that with

@@ -78,18 +78,21 @@ SX_MAP_BOTH_STRANDS = 1
 SX_MAP_BEST_STRATUM = 8
 SX_MAP_NO_INDELS = 16
 SX_MAP_TAGS = 64
+SX_MAP_UNMAPPED = 128
+SX_MAP_HEADER = 256
 SX_SEARCH_NO_INDELS = 1
 
 
-def map_flags(both_strands=False, best=False, indels=True, tags=False):
+def map_flags(both_strands=False, best=False, indels=True, tags=False, unmapped=False, header=False):
     """the flags word of sx_map_reads_stream_ex / sx_index_map_reads_ex"""
     return ((SX_MAP_BOTH_STRANDS if both_strands else 0) | (SX_MAP_BEST_STRATUM if best else 0)
-            | (0 if indels else SX_MAP_NO_INDELS) | (SX_MAP_TAGS if tags else 0))
+            | (0 if indels else SX_MAP_NO_INDELS) | (SX_MAP_TAGS if tags else 0) | (SX_MAP_UNMAPPED if unmapped else 0)
+            | (SX_MAP_HEADER if header else 0))
 
 
-def pair_flags(best=False, indels=True):
+def pair_flags(best=False, indels=True, header=False):
     """the flags word of sx_index_map_pairs (both strands are implied)"""
-    return (SX_MAP_BEST_STRATUM if best else 0) | (0 if indels else SX_MAP_NO_INDELS)
+    return (SX_MAP_BEST_STRATUM if best else 0) | (0 if indels else SX_MAP_NO_INDELS) | (SX_MAP_HEADER if header else 0)
 
 
 def search_flags(indels=True):
@@ -262,6 +265,8 @@ def load(path=None):
         "sx_sam_emit_dev_ex": (C.c_int, [vp, C.POINTER(SamBatchEx), u64p, C.c_uint64, C.c_uint64, C.c_uint64, u8p]),
         "sx_sam_layout_dev_tags": (C.c_int, [vp, C.POINTER(SamBatchTags), u64p, C.POINTER(C.c_uint64)]),
         "sx_sam_emit_dev_tags": (C.c_int, [vp, C.POINTER(SamBatchTags), u64p, C.c_uint64, C.c_uint64, C.c_uint64, u8p]),
+        "sx_sam_layout_dev_unmapped": (C.c_int, [vp, C.POINTER(SamBatchTags), u64p, C.POINTER(C.c_uint64)]),
+        "sx_sam_emit_dev_unmapped": (C.c_int, [vp, C.POINTER(SamBatchTags), u64p, C.c_uint64, C.c_uint64, C.c_uint64, u8p]),
         "sx_sam_layout_dev_pairs": (C.c_int, [vp, C.POINTER(SamBatch), vp, C.c_uint64, u64p, C.POINTER(C.c_uint64)]),
         "sx_sam_emit_dev_pairs": (C.c_int, [vp, C.POINTER(SamBatch), vp, C.c_uint64, u64p, C.c_uint64, C.c_uint64, C.c_uint64, u8p]),
         "sx_index_map_pairs": (C.c_int, [vp, vp, u8p, C.c_size_t, u8p, C.c_size_t, C.c_int, C.POINTER(PairOpts), C.c_uint32, SINK_FN,
@@ -365,6 +370,7 @@ EXPORTS = ["sx_device_count", "sx_device_numa_node", "sx_ctx_create", "sx_ctx_de
            "sx_bwt_approx_search_dev_ex", "sx_bwt_approx_search_compact_dev_ex", "sx_bwt_approx_search_packed_dev_ex",
            "sx_bwt_best_search_dev_ex", "sx_bwt_approx_search_ex", "sx_sam_layout_dev_tags", "sx_sam_emit_dev_tags",
            "sx_sam_layout_dev_pairs", "sx_sam_emit_dev_pairs", "sx_index_map_pairs", "sx_map_pairs_limit",
+           "sx_sam_layout_dev_unmapped", "sx_sam_emit_dev_unmapped",
            "sx_synth_dev", "sx_membw_probe", "sx_prim_sort_pairs_dev", "sx_prim_exclusive_sum_dev", "sx_prim_classify_dev"]
 
 

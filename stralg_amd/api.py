@@ -313,6 +313,27 @@ class Context:
         self._check(getattr(self.lib, name)(self.h, C.byref(batch), _ptr(d_byte_offsets), total_bytes, byte_lo, byte_hi, _ptr(d_out)),
                     name)
 
+    @staticmethod
+    def _unmapped_batch(batch):
+        if isinstance(batch, _lib.SamBatchTags):
+            return batch
+        ex = batch if isinstance(batch, _lib.SamBatchEx) else _lib.SamBatchEx(batch, None)
+        return _lib.SamBatchTags(ex, None, None, None, None, 0)
+
+    def sam_layout_dev_unmapped(self, batch, d_byte_offsets):
+        """sx_sam_layout_dev_unmapped: sam_layout_dev of a batch (of sam_batch, with flags or not, or of sam_batch_tags)
+        whose hits with R == L are placeholders, one FLAG 4 line each; returns the text's length"""
+        total = C.c_uint64(0)
+        b = self._unmapped_batch(batch)
+        self._check(self.lib.sx_sam_layout_dev_unmapped(self.h, C.byref(b), _ptr(d_byte_offsets), C.byref(total)), "sx_sam_layout_dev_unmapped")
+        return int(total.value)
+
+    def sam_emit_dev_unmapped(self, batch, d_byte_offsets, total_bytes, byte_lo, byte_hi, d_out):
+        """sx_sam_emit_dev_unmapped: bytes [byte_lo, byte_hi) of that text into d_out (uint8, 16-byte aligned)"""
+        b = self._unmapped_batch(batch)
+        self._check(self.lib.sx_sam_emit_dev_unmapped(self.h, C.byref(b), _ptr(d_byte_offsets), total_bytes, byte_lo, byte_hi, _ptr(d_out)),
+                    "sx_sam_emit_dev_unmapped")
+
     def sam_layout_dev_pairs(self, batch, d_lines, n_lines, d_byte_offsets):
         """sx_sam_layout_dev_pairs: d_lines (n_lines entries of _lib.PAIR_LINE_DTYPE in device memory) over the hits, reads
         and records of a plain sam_batch; d_byte_offsets (n_lines + 1 uint64) <- every line's first byte; returns the
@@ -449,7 +470,8 @@ class Context:
         self._check(self.lib.sx_sa_locate_rows_dev(self.h, _ptr(d_c), _ptr(d_occ), N, sigma, _ptr(d_marks), _ptr(d_values),
                                                    int(sa_sample).bit_length() - 1, row_lo, row_hi, _ptr(d_out)), "sx_sa_locate_rows_dev")
 
-    def map_reads_stream(self, records, fastq, edits, sink, both_strands=False, best=False, indels=True, tags=False):
+    def map_reads_stream(self, records, fastq, edits, sink, both_strands=False, best=False, indels=True, tags=False, unmapped=False,
+                         header=False):
         """sx_map_reads_stream: records = [(name bytes, BwtTable), ...] in the mapper's list order; sink(bytes) receives the
         SAM text window after window.  sink=None discards the text without touching it and returns [(time.perf_counter(),
         bytes)] per window (measurement).  both_strands (sx_map_reads_stream_ex, SX_MAP_BOTH_STRANDS): behind the lines of
@@ -458,7 +480,10 @@ class Context:
         indels=False (SX_MAP_NO_INDELS): mismatches only -- the lines whose CIGAR is "<length of SEQ>M", each placement
         once; with best the strata are the smallest number of mismatches.  tags (SX_MAP_TAGS) asks for NM:i and MD:Z, which
         need the records' strings on the device: records of tables alone have none and the call raises StralgAmdError
-        (code SX_E_ARG = -1) before anything runs; map through an Index (Index.from_fasta) instead."""
+        (code SX_E_ARG = -1) before anything runs; map through an Index (Index.from_fasta) instead.  unmapped
+        (SX_MAP_UNMAPPED): every read (with both_strands: read and reverse complement) that prints no line gets one FLAG 4
+        line "<name>\t4\t*\t0\t0\t*\t*\t0\t0\t<seq>\t<qual>" where its lines would stand.  header (SX_MAP_HEADER): the @HD
+        line and an @SQ line per record in front of the text."""
         recs = (_lib.MapRecord * max(1, len(records)))()
         keep = []
         for r, (name, t) in enumerate(records):
@@ -480,7 +505,7 @@ class Context:
                 return 1
 
         cb = _lib.SINK_FN(_sink)
-        flags = _lib.map_flags(both_strands, best, indels, tags)
+        flags = _lib.map_flags(both_strands, best, indels, tags, unmapped, header)
         if flags:
             rc = self.lib.sx_map_reads_stream_ex(self.h, recs, len(records), _ptr(buf) if buf.size else None, buf.size, edits,
                                                  flags, cb, None)
@@ -792,12 +817,13 @@ class Index:
             raise StralgAmdError("the index is closed")
         return self.h
 
-    def map_reads(self, fastq, edits, sink=None, ctx=None, both_strands=False, best=False, indels=True, tags=False):
+    def map_reads(self, fastq, edits, sink=None, ctx=None, both_strands=False, best=False, indels=True, tags=False, unmapped=False,
+                  header=False):
         """sx_index_map_reads: the SAM text of every match of every read of a FASTQ image within `edits` edits, byte for
         byte stralg_amd.map_reads' (the reference mapper's stdout).  sink=None returns the text; sink(bytes) receives it
         window after window and None is returned.  both_strands, best, indels, tags: as in stralg_amd.map_reads
         (sx_index_map_reads_ex); tags needs every record's string in the index (an index from_tables without strings
-        raises StralgAmdError, code SX_E_ARG = -1)."""
+        raises StralgAmdError, code SX_E_ARG = -1).  unmapped, header: as in stralg_amd.map_reads."""
         ctx = ctx or self.ctx
         buf = np.frombuffer(bytes(fastq), dtype=np.uint8)
         chunks, failure = [], []
@@ -812,7 +838,7 @@ class Index:
                 return 1
 
         cb = _lib.SINK_FN(_sink)
-        flags = _lib.map_flags(both_strands, best, indels, tags)
+        flags = _lib.map_flags(both_strands, best, indels, tags, unmapped, header)
         rc = self._map(ctx, buf, edits, flags, cb)
         if failure:
             raise failure[0]
@@ -826,7 +852,8 @@ class Index:
             return ctx.lib.sx_index_map_reads_ex(ctx.h, self._handle(), image, buf.size, edits, flags, cb, None)
         return ctx.lib.sx_index_map_reads(ctx.h, self._handle(), image, buf.size, edits, cb, None)
 
-    def map_reads_discard(self, fastq, edits, ctx=None, both_strands=False, best=False, indels=True, tags=False):
+    def map_reads_discard(self, fastq, edits, ctx=None, both_strands=False, best=False, indels=True, tags=False, unmapped=False,
+                          header=False):
         """the same with a sink that does not touch the text: [(time.perf_counter(), bytes)] per window (measurement)"""
         ctx = ctx or self.ctx
         buf = np.frombuffer(bytes(fastq), dtype=np.uint8)
@@ -837,7 +864,7 @@ class Index:
             return 0
 
         cb = _lib.SINK_FN(_sink)
-        flags = _lib.map_flags(both_strands, best, indels, tags)
+        flags = _lib.map_flags(both_strands, best, indels, tags, unmapped, header)
         ctx._check(self._map(ctx, buf, edits, flags, cb), "sx_index_map_reads_ex" if flags else "sx_index_map_reads")
         return seen
 
@@ -848,7 +875,7 @@ class Index:
         return ctx.lib.sx_index_map_pairs(ctx.h, self._handle(), _ptr(b1) if b1.size else None, b1.size, _ptr(b2) if b2.size else None,
                                           b2.size, edits, C.byref(opts), flags, cb, None)
 
-    def map_pairs(self, fastq1, fastq2, edits, min_insert=0, max_insert=1000, sink=None, best=False, indels=True, ctx=None):
+    def map_pairs(self, fastq1, fastq2, edits, min_insert=0, max_insert=1000, sink=None, best=False, indels=True, ctx=None, header=False):
         """sx_index_map_pairs: paired-end reads.  Read p of fastq1 and read p of fastq2 are the mates of pair p; the text
         is, per pair in file order, the two lines of every proper combination of a line of mate 1 and a line of mate 2
         (lines as map_reads(both_strands=True) prints them at the same edits, best and indels): same record, one on
@@ -856,7 +883,8 @@ class Index:
         t = the reverse line's end - the forward line's POS.  FLAG is 99 / 147 or 83 / 163, RNEXT "=", PNEXT the other
         line's POS, TLEN t or -t.  A pair without a proper combination prints nothing.  The search reports some
         placements more than once (1I99M beside 100M) and such lines multiply: best=True and indels=False are what
-        this is meant to be combined with.  sink=None returns the text; sink(bytes) receives it window after window."""
+        this is meant to be combined with.  sink=None returns the text; sink(bytes) receives it window after window.
+        header (SX_MAP_HEADER): the @HD line and an @SQ line per record in front of the text."""
         ctx = ctx or self.ctx
         chunks, failure = [], []
         put = chunks.append if sink is None else sink
@@ -869,13 +897,13 @@ class Index:
                 failure.append(e)
                 return 1
 
-        rc = self._map_pairs(ctx, fastq1, fastq2, edits, min_insert, max_insert, _lib.pair_flags(best, indels), _lib.SINK_FN(_sink))
+        rc = self._map_pairs(ctx, fastq1, fastq2, edits, min_insert, max_insert, _lib.pair_flags(best, indels, header), _lib.SINK_FN(_sink))
         if failure:
             raise failure[0]
         ctx._check(rc, "sx_index_map_pairs")
         return b"".join(chunks) if sink is None else None
 
-    def map_pairs_discard(self, fastq1, fastq2, edits, min_insert=0, max_insert=1000, best=False, indels=True, ctx=None):
+    def map_pairs_discard(self, fastq1, fastq2, edits, min_insert=0, max_insert=1000, best=False, indels=True, ctx=None, header=False):
         """the same with a sink that does not touch the text: [(time.perf_counter(), bytes)] per window (measurement)"""
         ctx = ctx or self.ctx
         seen = []
@@ -884,7 +912,7 @@ class Index:
             seen.append((time.perf_counter(), nbytes))
             return 0
 
-        ctx._check(self._map_pairs(ctx, fastq1, fastq2, edits, min_insert, max_insert, _lib.pair_flags(best, indels), _lib.SINK_FN(_sink)),
+        ctx._check(self._map_pairs(ctx, fastq1, fastq2, edits, min_insert, max_insert, _lib.pair_flags(best, indels, header), _lib.SINK_FN(_sink)),
                    "sx_index_map_pairs")
         return seen
 
@@ -1236,7 +1264,7 @@ def bwt_approx_search(bwt_table, patterns, edits, ctx=None, indels=True):
     return approx_matches(hits, hit_off, [p.size for p in pats], bwt_table.sa.array)
 
 
-def map_reads(fasta, fastq, edits, ctx=None, both_strands=False, best=False, indels=True, tags=False):
+def map_reads(fasta, fastq, edits, ctx=None, both_strands=False, best=False, indels=True, tags=False, unmapped=False, header=False):
     """The reference read mapper (tools/readmappers/bwt_readmapper: -p genome.fa, then -d edits genome.fa reads.fq) on the
     bytes of a FASTA and a FASTQ file: its stdout, the SAM lines of every match of every read in every record within
     `edits` edits, byte for byte.  Per read the records come in the mapper's list order, which is the FASTA file's order
@@ -1250,20 +1278,25 @@ def map_reads(fasta, fastq, edits, ctx=None, both_strands=False, best=False, ind
     within `edits` substitutions, once); with best the strata are taken over these lines.
     tags: every line gets "\tNM:i:<nm>\tMD:Z:<md>" behind QUAL -- the edit distance and the mismatch string of the line's POS,
     CIGAR and SEQ over the record's letters (no case folding), rendered on the device once per hit.  The tags read the
-    records' strings, so the call then maps through a temporary Index.from_fasta on ctx (the same lines)."""
+    records' strings, so the call then maps through a temporary Index.from_fasta on ctx (the same lines).
+    unmapped: every read (with both_strands: the read and its reverse complement) that prints no line gets one,
+    "<name>\t4\t*\t0\t0\t*\t*\t0\t0\t<seq>\t<qual>", where its lines would stand (no tags on it).
+    header: "@HD\tVN:1.6\tSO:unsorted" and "@SQ\tSN:<name>\tLN:<length>" per record in front of the text."""
     ctx = ctx or default_context()
     if tags:
         with Index.from_fasta(fasta, ctx=ctx) as idx:
-            return idx.map_reads(fastq, edits, both_strands=both_strands, best=best, indels=indels, tags=True)
+            return idx.map_reads(fastq, edits, both_strands=both_strands, best=best, indels=indels, tags=True, unmapped=unmapped,
+                                 header=header)
     records = [(name, build_complete_table(seq, True, ctx)) for name, seq in ctx.fasta_records(fasta)]
     chunks = []
-    ctx.map_reads_stream(records, fastq, edits, chunks.append, both_strands=both_strands, best=best, indels=indels)
+    ctx.map_reads_stream(records, fastq, edits, chunks.append, both_strands=both_strands, best=best, indels=indels, unmapped=unmapped,
+                         header=header)
     return b"".join(chunks)
 
 
-def map_pairs(fasta, fastq1, fastq2, edits, min_insert=0, max_insert=1000, ctx=None, best=False, indels=True):
+def map_pairs(fasta, fastq1, fastq2, edits, min_insert=0, max_insert=1000, ctx=None, best=False, indels=True, header=False):
     """Index.map_pairs through a temporary Index.from_fasta on ctx: the SAM text of the proper pairs of two FASTQ files
     (mate 1 and mate 2 of pair p are read p of either file)."""
     ctx = ctx or default_context()
     with Index.from_fasta(fasta, ctx=ctx) as idx:
-        return idx.map_pairs(fastq1, fastq2, edits, min_insert=min_insert, max_insert=max_insert, best=best, indels=indels)
+        return idx.map_pairs(fastq1, fastq2, edits, min_insert=min_insert, max_insert=max_insert, best=best, indels=indels, header=header)

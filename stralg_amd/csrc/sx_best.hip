@@ -187,9 +187,10 @@ __global__ __launch_bounds__(kBlock) void best_vq_count_kernel(PlaceArgs A, uint
 }
 
 // Hit h of the room (segment (d, r) at seg[d * n_rec + r] .. seg[d * n_rec + r + 1]) goes behind the hits of its pattern in
-// the records before r: query <- pattern * n_rec + r (sam_merge_kernel, with the rounds as one more level of segments)
+// the records before r: query <- pattern * n_rec + r (sam_merge_kernel, with the rounds as one more level of segments;
+// n_dst: dst's entries, the hits and SX_MAP_UNMAPPED's placeholders)
 __global__ __launch_bounds__(kBlock) void best_place_kernel(PlaceArgs A, const uint4 *src, uint64_t n_hits, const uint64_t *seg, const uint64_t *vbase,
-                                                            uint4 *dst, uint32_t *err)
+                                                            uint4 *dst, uint64_t n_dst, uint32_t *err)
 {
     const uint64_t h = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     if (h >= n_hits) return;
@@ -216,7 +217,7 @@ __global__ __launch_bounds__(kBlock) void best_place_kernel(PlaceArgs A, const u
     }
     const uint64_t *f = A.fho + r * A.fstride + A.fbase[d] + d;
     const uint64_t at = vbase[(uint64_t)q * A.n_rec + r] + (h - seg[s] - f[j]);
-    if (at >= n_hits) {
+    if (at >= n_dst) {
         atomicOr(err, 2u);
         return;
     }
@@ -378,7 +379,8 @@ int sx_best_rounds(sx_ctx *ctx, sx_best_state &S, const sx_best_batch &B, uint64
     return 0;
 }
 
-int sx_best_place(sx_ctx *ctx, sx_best_state &S, const sx_best_batch &B, uint64_t total, uint64_t *d_vbase, sx_approx_hit *d_placed)
+int sx_best_place(sx_ctx *ctx, sx_best_state &S, const sx_best_batch &B, uint64_t total, uint64_t *d_vbase, sx_approx_hit *d_placed, bool unmapped,
+                  uint64_t *placed_out)
 {
     const uint32_t n_rec = B.n_rec, rounds = (uint32_t)B.k + 1u;
     PlaceArgs A = {};
@@ -386,17 +388,28 @@ int sx_best_place(sx_ctx *ctx, sx_best_state &S, const sx_best_batch &B, uint64_
     A.rounds = rounds, A.n_rec = n_rec, A.count = B.count;
     A.ids = S.d_found_ids, A.fho = S.d_fho, A.fstride = S.fstride;
     const uint64_t nvq = (uint64_t)B.count * n_rec, nf = (uint64_t)S.fbase[rounds] * n_rec;
+    const uint32_t groups = unmapped && d_placed ? B.count / B.gsize : 0; // (SX_MAP_UNMAPPED: a placeholder a group without a hit)
     SX_CHECK(hipMemsetAsync(d_vbase, 0, (size_t)(nvq + 1) * 8, ctx->stream));
     if (nf) sx_launch(ctx, SX_KC_SAM, nf * 28, best_vq_count_kernel, dim3(sx_div_up(nf, kBlock)), dim3(kBlock), A, d_vbase, S.d_err);
+    if (groups) sx_map_unmapped_count(ctx, d_vbase, groups, B.gsize, n_rec);
     SX_TRY(device_scan64_inplace(ctx, d_vbase, nvq, SX_KC_SAM));
+    uint64_t placed = total;
+    if (groups) {
+        uint32_t w[2] = {0, 0};
+        SX_TRY(sx_readback(ctx, (const uint32_t *)(d_vbase + nvq), 2, w));
+        placed = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
+        if (placed < total || placed > total + groups) return sx_fail_msg(ctx, SX_E_INTERNAL, "best stratum: the hits of a batch do not add up");
+        sx_map_unmapped_place(ctx, d_vbase, groups, B.gsize, n_rec, d_placed, placed, S.d_err);
+    }
     if (d_placed && total) {
         SX_CHECK(hipMemcpyAsync(S.d_seg, S.seg.data(), ((size_t)rounds * n_rec + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
         sx_launch(ctx, SX_KC_SAM, total * 64, best_place_kernel, dim3(sx_div_up(total, kBlock)), dim3(kBlock), A, (const uint4 *)B.d_raw, total,
-                  (const uint64_t *)S.d_seg, (const uint64_t *)d_vbase, (uint4 *)d_placed, S.d_err);
+                  (const uint64_t *)S.d_seg, (const uint64_t *)d_vbase, (uint4 *)d_placed, placed, S.d_err);
     }
     uint32_t e = 0;
     SX_TRY(sx_readback(ctx, S.d_err, 1, &e)); // (syncs: seg is the next batch's again)
     if (e) return sx_fail_msg(ctx, SX_E_INTERNAL, "best stratum: the hits of a batch do not add up");
+    if (placed_out) *placed_out = placed;
     return 0;
 }
 

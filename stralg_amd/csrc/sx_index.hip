@@ -526,8 +526,8 @@ int sx_index_map_pairs(sx_ctx *ctx, const sx_index *idx, const uint8_t *fastq1, 
     if (!ctx || !idx || !sink || !opts || (len1 && !fastq1) || (len2 && !fastq2)) return SX_E_ARG;
     SX_TRY(device_check(ctx, idx));
     if (edits < 0 || edits > SX_APPROX_MAX_EDITS) return sx_fail_msg(ctx, SX_E_ARG, "read mapping: edits must be in [0, 8]");
-    if (flags & ~(uint32_t)(SX_MAP_BOTH_STRANDS | SX_MAP_BEST_STRATUM | SX_MAP_NO_INDELS))
-        return sx_fail_msg(ctx, SX_E_ARG, "paired reads: the flags are SX_MAP_BOTH_STRANDS (implied), SX_MAP_BEST_STRATUM and SX_MAP_NO_INDELS");
+    if (flags & ~(uint32_t)(SX_MAP_BOTH_STRANDS | SX_MAP_BEST_STRATUM | SX_MAP_NO_INDELS | SX_MAP_HEADER))
+        return sx_fail_msg(ctx, SX_E_ARG, "paired reads: the flags are SX_MAP_BOTH_STRANDS (implied), SX_MAP_BEST_STRATUM, SX_MAP_NO_INDELS and SX_MAP_HEADER");
     if (opts->min_insert > opts->max_insert) return sx_fail_msg(ctx, SX_E_ARG, "paired reads: min_insert must not exceed max_insert");
     if (len1 > 0xFFFFFFFEull || len2 > 0xFFFFFFFEull) return sx_fail_msg(ctx, SX_E_ARG, "read mapping: malformed FASTQ image (see sx_fastq_index)");
     SX_CHECK(hipSetDevice(ctx->device));

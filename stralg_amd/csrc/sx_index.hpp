@@ -71,7 +71,7 @@ static inline bool sx_map_record_check(const sx_map_record &R, uint32_t min_sigm
 }
 
 // the bits of a mapping call's flags word that mean something (sx_map_reads_stream_ex, sx_index_map_reads_ex, sx_map_reads_limit)
-constexpr uint32_t sx_map_known_flags = SX_MAP_BOTH_STRANDS | SX_MAP_BEST_STRATUM | SX_MAP_NO_INDELS | SX_MAP_TAGS;
+constexpr uint32_t sx_map_known_flags = SX_MAP_BOTH_STRANDS | SX_MAP_BEST_STRATUM | SX_MAP_NO_INDELS | SX_MAP_TAGS | SX_MAP_UNMAPPED | SX_MAP_HEADER;
 // the search flags (SX_SEARCH_*) that a mapping call's flags word asks of its searches
 static inline uint32_t sx_map_search_flags(uint32_t flags) { return (flags & SX_MAP_NO_INDELS) ? (uint32_t)SX_SEARCH_NO_INDELS : 0u; }
 
@@ -100,6 +100,14 @@ int sx_approx_emit_record(sx_ctx *ctx, const sx_index_rec &R, const uint8_t *d_p
                           const uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t total_hits, uint32_t search_flags);
 // sx_map.hip: out[i] = table[seqs[i]] for i in [lo, hi) (a record's 256-byte symbol table; sam_remap_kernel)
 void sx_sam_remap(sx_ctx *ctx, const uint8_t *d_seqs, const uint8_t *d_table, uint8_t *d_out, uint64_t lo, uint64_t hi);
+// sx_map.hip, SX_MAP_UNMAPPED.  Count: d_cnt (groups x gsize x n_rec counts of (read, record), not yet
+// scanned) gives every group of gsize reads whose counts are all 0 one slot, its first read's with record 0.  Place: over
+// those counts scanned (d_vbase), the placeholder (query: that slot, L = R = 0, no gaps) of every group with exactly one
+// slot into d_dst (n_dst entries; error bit 2 in *d_err beyond them) -- before the hits are merged, which overwrite it
+// where that one slot is a hit's
+void sx_map_unmapped_count(sx_ctx *ctx, uint64_t *d_cnt, uint32_t groups, uint32_t gsize, uint32_t n_rec);
+void sx_map_unmapped_place(sx_ctx *ctx, const uint64_t *d_vbase, uint32_t groups, uint32_t gsize, uint32_t n_rec, sx_approx_hit *d_dst, uint64_t n_dst,
+                           uint32_t *d_err);
 
 // ---- sx_best.hip: best-stratum search -----------------------------------------------------------
 // What a batch of the round loop holds on the device; sized once (init) for the largest batch, nothing is allocated in a round
@@ -143,5 +151,8 @@ struct sx_best_batch {
 // SX_E_CAPACITY: the room is too small; the strata and (go_on_counting) the found sets' offsets are complete all the same
 int sx_best_rounds(sx_ctx *ctx, sx_best_state &S, const sx_best_batch &B, uint64_t *total_out);
 // d_vbase (count x n_rec + 1 entries) <- where the hits of (pattern, record) start in (pattern, record, hit) order and,
-// last, the total; with d_placed the room's hits go there in that order, query <- pattern x n_rec + record
-int sx_best_place(sx_ctx *ctx, sx_best_state &S, const sx_best_batch &B, uint64_t total, uint64_t *d_vbase, sx_approx_hit *d_placed);
+// last, the total; with d_placed the room's hits go there in that order, query <- pattern x n_rec + record.
+// unmapped (SX_MAP_UNMAPPED, with d_placed): every group without a hit gets its placeholder in that order too (d_placed
+// has room for total + count / gsize entries) and *placed_out <- the entries placed
+int sx_best_place(sx_ctx *ctx, sx_best_state &S, const sx_best_batch &B, uint64_t total, uint64_t *d_vbase, sx_approx_hit *d_placed, bool unmapped = false,
+                  uint64_t *placed_out = nullptr);

@@ -36,11 +36,43 @@ __global__ __launch_bounds__(kBlock) void sam_vq_count_kernel(const uint64_t *ho
     cnt[idx] = ho[r * stride + q + 1] - ho[r * stride + q];
 }
 
+// ---- unmapped read groups (SX_MAP_UNMAPPED) ------------------------------------------------------
+// cnt as sam_vq_count_kernel leaves it (or best_vq_count_kernel): a group of gsize reads whose counts are all 0 gets one
+// slot, the one of its first read and record 0, for its placeholder
+__global__ __launch_bounds__(kBlock) void sam_unmapped_count_kernel(uint64_t *cnt, uint32_t groups, uint32_t gsize, uint32_t n_rec)
+{
+    const uint64_t g = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (g >= groups) return;
+    const uint64_t first = g * gsize * n_rec;
+    uint64_t sum = 0;
+    for (uint64_t k = 0; k < (uint64_t)gsize * n_rec; ++k) sum += cnt[first + k];
+    if (sum == 0) cnt[first] = 1;
+}
+
+// vbase: those counts scanned.  A group with exactly one slot gets the placeholder there, an empty interval of its first
+// read and record 0 -- before the merge, which overwrites it where that slot is a real hit's (the group's one hit lands on
+// the group's first slot as well)
+__global__ __launch_bounds__(kBlock) void sam_unmapped_place_kernel(const uint64_t *vbase, uint32_t groups, uint32_t gsize, uint32_t n_rec, uint4 *dst,
+                                                                    uint64_t n_dst, uint32_t *err)
+{
+    const uint64_t g = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (g >= groups) return;
+    const uint64_t first = g * gsize * n_rec, at = vbase[first];
+    if (vbase[first + (uint64_t)gsize * n_rec] - at != 1) return;
+    if (at >= n_dst) {
+        atomicOr(err, 2u);
+        return;
+    }
+    const uint4 h0 = {(uint32_t)first, 0u, 0u, 0u}, h1 = {0u, 0u, 0u, 0u};
+    dst[2 * at] = h0;
+    dst[2 * at + 1] = h1;
+}
+
 // hit j of the searches' hit arrays (record r's at seg[r] .. seg[r + 1]) goes behind the hits of its read in the
-// records before r: query <- read * n_rec + r
+// records before r: query <- read * n_rec + r (n_dst: the merged array's entries, the hits and the placeholders)
 __global__ __launch_bounds__(kBlock) void sam_merge_kernel(const uint4 *src, uint64_t n_hits, const uint64_t *seg, uint32_t n_rec,
                                                            const uint64_t *ho, uint64_t stride, uint32_t batch, const uint64_t *vbase,
-                                                           uint4 *dst, uint32_t *err)
+                                                           uint4 *dst, uint64_t n_dst, uint32_t *err)
 {
     const uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     if (j >= n_hits) return;
@@ -60,7 +92,7 @@ __global__ __launch_bounds__(kBlock) void sam_merge_kernel(const uint4 *src, uin
         return;
     }
     const uint64_t at = vbase[(uint64_t)q * n_rec + r] + (j - seg[r] - ho[r * stride + q]);
-    if (at >= n_hits) {
+    if (at >= n_dst) {
         atomicOr(err, 2u);
         return;
     }
@@ -126,6 +158,9 @@ struct MapReads {
     // paired reads, or null: the reads are 4 x pairs, read 4p + 2m + s, a batch holds whole pairs and its
     // text is that of the join's line descriptors
     const sx_pair_opts *pairs = nullptr;
+    // 0, or (SX_MAP_UNMAPPED) the reads of a group that gets a FLAG 4 line where it has none: 1, or 2
+    // for the strands of a read
+    uint32_t unmapped = 0;
 };
 
 struct MapBufs { // what a mapping call holds on the device beside the hits' room
@@ -198,35 +233,49 @@ static int merged_room(sx_ctx *ctx, MapBufs &M, const HitRoom &room, uint64_t us
     return 0;
 }
 
-// The hits of the batch's searches in (read, record rank, hit) order: M.d_merged, query <- read x records + rank
-static int merge_batch(sx_ctx *ctx, MapBufs &M, const HitRoom &room, uint32_t batch)
+// The hits of the batch's searches in (read, record rank, hit) order: M.d_merged, query <- read x records + rank.
+// ugroup (SX_MAP_UNMAPPED): the reads of a group, and every group without a hit gets its placeholder in that order too;
+// *merged_out <- the entries of M.d_merged
+static int merge_batch(sx_ctx *ctx, MapBufs &M, const HitRoom &room, uint32_t batch, uint32_t ugroup, uint64_t *merged_out)
 {
     const uint32_t n_records = (uint32_t)M.seg.size() - 1;
-    const uint64_t used = M.seg[n_records];
-    SX_TRY(merged_room(ctx, M, room, used));
+    const uint64_t used = M.seg[n_records], groups = ugroup ? batch / ugroup : 0;
+    SX_TRY(merged_room(ctx, M, room, used + groups)); // (with placeholders: one a group at the most)
     SX_CHECK(hipMemcpyAsync(M.d_seg, M.seg.data(), M.seg.size() * 8, hipMemcpyHostToDevice, ctx->stream));
     SX_CHECK(hipStreamSynchronize(ctx->stream)); // (seg is reused by the next batch)
     const uint64_t nvq = (uint64_t)batch * n_records;
     sx_launch(ctx, SX_KC_SAM, nvq * 24, sam_vq_count_kernel, dim3(sx_div_up(nvq, kBlock)), dim3(kBlock), (const uint64_t *)M.d_ho, M.stride,
               batch, n_records, M.d_vbase);
+    if (ugroup) sx_map_unmapped_count(ctx, M.d_vbase, (uint32_t)groups, ugroup, n_records);
     SX_TRY(device_scan64_inplace(ctx, M.d_vbase, nvq, SX_KC_SAM));
-    sx_launch(ctx, SX_KC_SAM, used * 64, sam_merge_kernel, dim3(sx_div_up(used, kBlock)), dim3(kBlock), (const uint4 *)room.d_raw, used,
-              (const uint64_t *)M.d_seg, n_records, (const uint64_t *)M.d_ho, M.stride, batch, (const uint64_t *)M.d_vbase,
-              (uint4 *)M.d_merged, M.d_err);
+    uint64_t merged = used;
+    if (ugroup) {
+        uint32_t w[2] = {0, 0};
+        SX_TRY(sx_readback(ctx, (const uint32_t *)(M.d_vbase + nvq), 2, w));
+        merged = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
+        if (merged < used || merged > used + groups) return sx_fail_msg(ctx, SX_E_INTERNAL, "read mapping: the hits of a batch do not add up");
+        sx_map_unmapped_place(ctx, M.d_vbase, (uint32_t)groups, ugroup, n_records, M.d_merged, merged, M.d_err);
+    }
+    if (used)
+        sx_launch(ctx, SX_KC_SAM, used * 64, sam_merge_kernel, dim3(sx_div_up(used, kBlock)), dim3(kBlock), (const uint4 *)room.d_raw, used,
+                  (const uint64_t *)M.d_seg, n_records, (const uint64_t *)M.d_ho, M.stride, batch, (const uint64_t *)M.d_vbase,
+                  (uint4 *)M.d_merged, merged, M.d_err);
     uint32_t e = 0;
     SX_TRY(sx_readback(ctx, M.d_err, 1, &e));
     if (e) return sx_fail_msg(ctx, SX_E_INTERNAL, "read mapping: the hits of a batch do not add up");
+    *merged_out = merged;
     return 0;
 }
 
 // A batch of either kind, reads q0 .. q0 + batch: on success its hits are in M.d_merged in (read, record, hit) order and
-// *hits_out is their count; SX_E_CAPACITY: the room is too small for the *hits_out hits known of so far.
-// The plain batch: every record's search, then the merge
+// *hits_out is their count (SX_MAP_UNMAPPED: with the placeholders); SX_E_CAPACITY: the room is too small for the
+// *hits_out hits known of so far.
+// The plain batch: every record's search, then the merge (with placeholders also where there is no hit)
 static int plain_batch(sx_ctx *ctx, const sx_index *idx, const MapReads &R, MapBufs &M, const HitRoom &room, int edits, uint32_t q0,
                        uint32_t batch, uint64_t *hits_out)
 {
     SX_TRY(search_batch(ctx, idx, R, M, room, q0, batch, edits, R.search_flags, hits_out));
-    return *hits_out ? merge_batch(ctx, M, room, batch) : 0;
+    return *hits_out || R.unmapped ? merge_batch(ctx, M, room, batch, R.unmapped, hits_out) : 0;
 }
 
 // The best-stratum batch (whole groups): the rounds of sx_best.hip into the room, then its place step
@@ -241,9 +290,13 @@ static int best_batch(sx_ctx *ctx, const sx_index *idx, const MapReads &R, MapBu
     B.d_ho = M.d_ho, B.ho_stride = M.stride, B.d_stratum = S.d_stratum;
     B.d_raw = room.d_raw, B.raw_cap = room.cap, B.go_on_counting = false;
     SX_TRY(sx_best_rounds(ctx, S, B, hits_out));
-    if (*hits_out == 0) return 0;
-    SX_TRY(merged_room(ctx, M, room, *hits_out));
-    return sx_best_place(ctx, S, B, *hits_out, M.d_vbase, M.d_merged);
+    if (*hits_out == 0 && !R.unmapped) return 0;
+    if (!R.unmapped) {
+        SX_TRY(merged_room(ctx, M, room, *hits_out));
+        return sx_best_place(ctx, S, B, *hits_out, M.d_vbase, M.d_merged);
+    }
+    SX_TRY(merged_room(ctx, M, room, *hits_out + batch / R.group)); // (a placeholder a group at the most)
+    return sx_best_place(ctx, S, B, *hits_out, M.d_vbase, M.d_merged, true, hits_out);
 }
 
 // The text of A's hits: its layout, then window after window through the two device windows and the context's staging
@@ -271,17 +324,20 @@ template <class Emit> static int emit_windows_of(sx_ctx *ctx, uint64_t total, co
     return sx_sync(ctx);
 }
 
-static int emit_windows(sx_ctx *ctx, const SamTagArgs &A, const MapBufs &M, const sx_stage_events &E, sx_sink_fn sink, void *user)
+// (unmapped: the hits have placeholders, SX_MAP_UNMAPPED)
+static int emit_windows(sx_ctx *ctx, const SamTagArgs &A, const MapBufs &M, const sx_stage_events &E, sx_sink_fn sink, void *user, bool unmapped)
 {
     uint64_t total = 0;
-    SX_TRY(sam_layout(ctx, A, M.d_byte_off, &total));
-    return emit_windows_of(ctx, total, M, E, sink, user, [&](uint64_t lo, uint64_t hi, uint8_t *d_out) { return sam_emit(ctx, A, M.d_byte_off, lo, hi, d_out); });
+    SX_TRY(sam_layout(ctx, A, M.d_byte_off, &total, unmapped));
+    return emit_windows_of(ctx, total, M, E, sink, user,
+                           [&](uint64_t lo, uint64_t hi, uint8_t *d_out) { return sam_emit(ctx, A, M.d_byte_off, lo, hi, d_out, unmapped); });
 }
 
 // The text of a batch (`text`: its hits, reads and records) against an index with a sampled suffix array: its hits are taken
 // in runs of consecutive hits whose lines fit the cap (SX_FLAG_LOCATE_CHUNK_ROWS; a hit is never split: one with more lines
 // gets a buffer of its own length); a run is located, laid out and emitted through its windows before the next one starts
-static int emit_located(sx_ctx *ctx, const sx_index *idx, const SamTagArgs &text, MapBufs &M, const sx_stage_events &E, sx_sink_fn sink, void *user)
+static int emit_located(sx_ctx *ctx, const sx_index *idx, const SamTagArgs &text, MapBufs &M, const sx_stage_events &E, sx_sink_fn sink, void *user,
+                        bool unmapped)
 {
     const LocRec *d_recs = (const LocRec *)idx->d_loc_list;
     const uint64_t n_hits = text.n_hits, cap = map_located_rows(ctx->locate_chunk_rows);
@@ -306,7 +362,7 @@ static int emit_located(sx_ctx *ctx, const sx_index *idx, const SamTagArgs &text
         SamTagArgs A = text;
         A.hits = text.hits + 2 * h_lo, A.n_hits = h_hi - h_lo;
         A.positions = M.d_positions, A.pos_off = M.d_pos_off + h_lo, A.pos_base = base;
-        SX_TRY(emit_windows(ctx, A, M, E, sink, user));
+        SX_TRY(emit_windows(ctx, A, M, E, sink, user, unmapped));
         base += rows;
         h_lo = h_hi;
     }
@@ -397,7 +453,9 @@ static int map_reads_loop(sx_ctx *ctx, const sx_index *idx, const MapReads &R, i
 {
     const sx_fastq_dev &fq = *R.fq;
     const uint32_t n_reads = fq.count, n_records = (uint32_t)idx->recs.size();
-    const uint32_t g = R.pairs ? 4 : R.group ? R.group : 1; // the reads that a batch keeps together
+    // the reads that a batch keeps together: a pair's four, a best group, or (SX_MAP_UNMAPPED) the strands of a read, whose
+    // placeholder stands for both
+    const uint32_t kept = R.group ? R.group : R.unmapped, g = R.pairs ? 4 : kept ? kept : 1;
     SX_CHECK(hipSetDevice(ctx->device));
     sx_map_stats &T = ctx->map_stats; // (host counts: sx_map_last_stats)
     T = {};
@@ -405,7 +463,7 @@ static int map_reads_loop(sx_ctx *ctx, const sx_index *idx, const MapReads &R, i
     SX_TRY(M.own.take(ctx, &M.d_pat, (size_t)fq.seq_bytes));
     SX_TRY(sx_sync(ctx)); // (the callers' uploads from pageable memory are done)
 
-    const uint32_t batch_max = R.pairs ? map_pairs_batch_max(ctx->sam_batch_reads, n_reads) : map_batch_max(ctx->sam_batch_reads, R.group, n_reads);
+    const uint32_t batch_max = R.pairs ? map_pairs_batch_max(ctx->sam_batch_reads, n_reads) : map_batch_max(ctx->sam_batch_reads, kept, n_reads);
     M.window = map_window_bytes(ctx->sam_window_bytes, sx_stage_bytes);
     SX_TRY(sx_stage_ensure(ctx));
     sx_stage_events E;
@@ -465,7 +523,8 @@ static int map_reads_loop(sx_ctx *ctx, const sx_index *idx, const MapReads &R, i
                 }
                 SX_TRY(prc);
             } else {
-                SX_TRY(idx->sa_log2 ? emit_located(ctx, idx, A, M, E, sink, user) : emit_windows(ctx, A, M, E, sink, user));
+                const bool unm = R.unmapped != 0;
+                SX_TRY(idx->sa_log2 ? emit_located(ctx, idx, A, M, E, sink, user, unm) : emit_windows(ctx, A, M, E, sink, user, unm));
             }
         }
         ++T.batches;
@@ -484,6 +543,44 @@ void sx_sam_remap(sx_ctx *ctx, const uint8_t *d_seqs, const uint8_t *d_table, ui
     if (hi > lo) sx_launch(ctx, SX_KC_REMAP, 2 * (hi - lo), sam_remap_kernel, dim3(sx_div_up(hi - lo, kBlock)), dim3(kBlock), d_seqs, d_table, d_out, lo, hi);
 }
 
+void sx_map_unmapped_count(sx_ctx *ctx, uint64_t *d_cnt, uint32_t groups, uint32_t gsize, uint32_t n_rec)
+{
+    if (groups)
+        sx_launch(ctx, SX_KC_SAM, (uint64_t)groups * gsize * n_rec * 8, sam_unmapped_count_kernel, dim3(sx_div_up(groups, kBlock)), dim3(kBlock), d_cnt,
+                  groups, gsize, n_rec);
+}
+
+void sx_map_unmapped_place(sx_ctx *ctx, const uint64_t *d_vbase, uint32_t groups, uint32_t gsize, uint32_t n_rec, sx_approx_hit *d_dst, uint64_t n_dst,
+                           uint32_t *d_err)
+{
+    if (groups)
+        sx_launch(ctx, SX_KC_SAM, (uint64_t)groups * 16, sam_unmapped_place_kernel, dim3(sx_div_up(groups, kBlock)), dim3(kBlock), d_vbase, groups, gsize,
+                  n_rec, (uint4 *)d_dst, n_dst, d_err);
+}
+
+// The SAM header of SX_MAP_HEADER in one sink call: @HD, then an @SQ line a record in the list's order,
+// SN the record's name as the lines' RNAME has it, LN its symbols (N - 1)
+template <class NameOf, class LenOf> static int map_header(sx_ctx *ctx, uint32_t n_records, NameOf name_of, LenOf len_of, sx_sink_fn sink, void *user)
+{
+    std::string h = "@HD\tVN:1.6\tSO:unsorted\n";
+    for (uint32_t r = 0; r < n_records; ++r) {
+        h += "@SQ\tSN:";
+        h += name_of(r);
+        h += "\tLN:";
+        h += std::to_string(len_of(r));
+        h += "\n";
+    }
+    if (sink(user, SX_SECTION_SAM, h.data(), h.size()) != 0) return sx_fail_msg(ctx, SX_E_ARG, "the sink refused a chunk");
+    return 0;
+}
+
+static int index_header(sx_ctx *ctx, const sx_index *idx, sx_sink_fn sink, void *user)
+{
+    return map_header(
+        ctx, (uint32_t)idx->recs.size(), [&](uint32_t r) -> const std::string & { return idx->recs[r].name; },
+        [&](uint32_t r) { return (unsigned long long)(idx->recs[r].N - 1); }, sink, user);
+}
+
 int sx_map_tags_check(sx_ctx *ctx, const sx_index *idx, uint32_t flags)
 {
     if (!(flags & SX_MAP_TAGS)) return 0;
@@ -499,20 +596,29 @@ int sx_map_reads_core(sx_ctx *ctx, const sx_index *idx, const sx_fastq_dev &read
                       sx_sink_fn sink, void *user)
 {
     const uint32_t n_records = (uint32_t)idx->recs.size();
-    if (reads.count == 0 || n_records == 0) return 0;
+    const bool header = (flags & SX_MAP_HEADER) != 0;
+    if ((reads.count == 0 || n_records == 0) && !header) return 0;
     bool records_ok = true;
     for (const sx_index_rec &R : idx->recs) records_ok = records_ok && sx_map_dims_ok(R.N, R.sigma, 2);
     SX_TRY(map_check(ctx, reads.count, n_records, flags, records_ok)); // (SX_MAP_TAGS: the callers have seen to the strings)
-    const bool best = (flags & SX_MAP_BEST_STRATUM) != 0, tags = (flags & SX_MAP_TAGS) != 0;
+    if (header) SX_TRY(index_header(ctx, idx, sink, user));
+    if (reads.count == 0 || n_records == 0) return 0;
+    const bool best = (flags & SX_MAP_BEST_STRATUM) != 0, tags = (flags & SX_MAP_TAGS) != 0, unmapped = (flags & SX_MAP_UNMAPPED) != 0;
     const uint32_t sflags = sx_map_search_flags(flags);
-    if (!(flags & SX_MAP_BOTH_STRANDS)) return map_reads_loop(ctx, idx, MapReads{&reads, h_seq_off, nullptr, best ? 1u : 0u, sflags, tags}, edits, sink, user);
+    if (!(flags & SX_MAP_BOTH_STRANDS)) {
+        MapReads R = {&reads, h_seq_off, nullptr, best ? 1u : 0u, sflags, tags};
+        R.unmapped = unmapped ? 1u : 0u;
+        return map_reads_loop(ctx, idx, R, edits, sink, user);
+    }
     SX_CHECK(hipSetDevice(ctx->device));
     sx_fastq_dev both = {};
     sx_dev_scope F;
     uint16_t *d_flags;
     SX_TRY(F.take(ctx, &d_flags, 2 * (size_t)reads.count));
     SX_TRY(sx_fastq_strands_dev(ctx, &reads, &both, d_flags)); // (syncs: the callers' uploads from pageable memory are done)
-    const int rc = map_reads_loop(ctx, idx, MapReads{&both, nullptr, d_flags, best ? 2u : 0u, sflags, tags}, edits, sink, user);
+    MapReads R = {&both, nullptr, d_flags, best ? 2u : 0u, sflags, tags};
+    R.unmapped = unmapped ? 2u : 0u;
+    const int rc = map_reads_loop(ctx, idx, R, edits, sink, user);
     sx_fastq_dev_free(&both);
     return rc;
 }
@@ -524,10 +630,13 @@ int sx_map_pairs_core(sx_ctx *ctx, const sx_index *idx, const sx_fastq_dev &read
 {
     const uint32_t n_records = (uint32_t)idx->recs.size();
     if (reads1.count != reads2.count) return sx_fail_msg(ctx, SX_E_ARG, "paired reads: the two FASTQ images differ in their read counts");
-    if (reads1.count == 0 || n_records == 0) return 0;
+    const bool header = (flags & SX_MAP_HEADER) != 0;
+    if ((reads1.count == 0 || n_records == 0) && !header) return 0;
     if (sx_map_pairs_limit(reads1.count, n_records) != 0) return sx_fail_msg(ctx, SX_E_ARG, "paired reads: 4 x pairs x records must stay below 2^32");
     for (const sx_index_rec &R : idx->recs)
         if (!sx_map_dims_ok(R.N, R.sigma, 2)) return sx_fail_msg(ctx, SX_E_ARG, "read mapping: a record lacks its name, suffix array, tables or remap table");
+    if (header) SX_TRY(index_header(ctx, idx, sink, user));
+    if (reads1.count == 0 || n_records == 0) return 0;
     SX_CHECK(hipSetDevice(ctx->device));
     sx_fastq_dev mates = {}, both = {};
     int rc = sx_fastq_mates_dev(ctx, &reads1, &reads2, &mates);
@@ -587,10 +696,14 @@ int sx_map_reads_stream_ex(sx_ctx *ctx, const sx_map_record *records, uint32_t n
         sx_fastq *f;
         ~FqFree() { sx_fastq_free(f); }
     } fq_free{&fq};
-    if (fq.count == 0 || n_records == 0) return 0;
+    const bool header = (flags & SX_MAP_HEADER) != 0;
+    if ((fq.count == 0 || n_records == 0) && !header) return 0;
     bool records_ok = true;
     for (uint32_t r = 0; r < n_records; ++r) records_ok = records_ok && sx_map_record_check(records[r], 2);
     SX_TRY(map_check(ctx, fq.count, n_records, flags, records_ok));
+    if (fq.count == 0 || n_records == 0) // (the header alone; otherwise the loop's call sinks it from the index)
+        return map_header(
+            ctx, n_records, [&](uint32_t r) { return records[r].name; }, [&](uint32_t r) { return (unsigned long long)(records[r].N - 1); }, sink, user);
     SX_CHECK(hipSetDevice(ctx->device));
     // the reads of this call, then a temporary index of the host tables (every record's suffix array and tables:
     // N x (4 + 8 sigma) bytes a record with its RO table), the loop, and the index goes again

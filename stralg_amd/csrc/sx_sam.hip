@@ -18,6 +18,9 @@
 // With the texts of the records (the kernels' kTags form) every line has "\tNM:i:<nm>\tMD:Z:<md>" between
 // its quality string and its newline: one walk a hit over its edit string, the read and the text window at its first
 // position (md_render), in the size pass for the length and in the emit pass into LDS, beside the CIGAR.
+// Unmapped read groups (SX_MAP_UNMAPPED): a hit with an empty interval (R == L, which no search
+// gives) is the placeholder of a read group without a line and prints "<qname>\t4\t*\t0\t0\t*\t*\t0\t0\t<seq>\t<qual>\n"
+// -- in the kernels' kUnmapped forms alone, their fourth template parameter; the forms without it keep their code.
 // The output does not fit the device in general: the caller fills a fixed buffer window after window; lines may start
 // in one window (or slice) and end in the next, the concatenation of the windows is the file.
 #include "sx_common.hpp"
@@ -209,8 +212,10 @@ __device__ __forceinline__ uint32_t md_render(uint8_t *out, uint32_t cap, uint32
     return put_dec(out, w, cap, run);
 }
 
-// what the lines of hit h are made of; false: the hit does not fit the batch (its query, interval or offsets)
-template <bool kLocated, bool kFlags> __device__ __forceinline__ bool hit_info(const SamArgs &A, uint64_t h, HitInfo &I)
+// what the lines of hit h are made of; false: the hit does not fit the batch (its query, interval or offsets).
+// kUnmapped: a hit with R == L is the placeholder of a read group without a line, and has one line,
+// the FLAG 4 line of its read: I.pos == nullptr, I.cnt == 1 (no position, CIGAR or tags are read for it)
+template <bool kLocated, bool kFlags, bool kUnmapped = false> __device__ __forceinline__ bool hit_info(const SamArgs &A, uint64_t h, HitInfo &I)
 {
     const uint4 h0 = A.hits[2 * h];
     I.gaps = A.hits[2 * h + 1];
@@ -240,6 +245,12 @@ template <bool kLocated, bool kFlags> __device__ __forceinline__ bool hit_info(c
     I.rec = rec;
     I.n_gaps = h0.w >> 16;
     if (I.n_gaps > SX_APPROX_MAX_EDITS) I.n_gaps = SX_APPROX_MAX_EDITS;
+    if (kUnmapped && L == R) {
+        I.n_gaps = 0;
+        I.cnt = 1;
+        I.flag = 4;
+        return true;
+    }
     I.pos = kLocated ? A.positions + (A.pos_off[h] - A.pos_base) : sa + L;
     I.cnt = R - L;
     if (kFlags) I.flag = A.flags[read];
@@ -270,6 +281,10 @@ template <bool kTags = false> __device__ __forceinline__ uint32_t fixed_bytes(co
     return I.name_l + I.rn_l + I.cig_len + I.seq_l + I.qual_l + 15u + dec_digits(I.flag) + (kTags ? 13u + I.md_len : 0u);
 }
 
+// "\t4\t*\t0\t0\t*\t*\t0\t0\t" + "\t" + "\n": the whole FLAG 4 line of a placeholder beside its QNAME, SEQ and QUAL (no tags)
+constexpr uint32_t kUnmappedFixed = 19;
+__device__ __forceinline__ uint32_t unmapped_bytes(const HitInfo &I) { return I.name_l + I.seq_l + I.qual_l + kUnmappedFixed; }
+
 // ---- layout: bytes per hit ---------------------------------------------------------------------
 // what a kernel takes of a batch: the tagged forms alone carry the texts and the letters
 template <bool kTags> struct KernelArgs { typedef SamArgs type; };
@@ -277,7 +292,9 @@ template <> struct KernelArgs<true> { typedef SamTagArgs type; };
 // (the forms without tags never get there)
 __device__ __forceinline__ bool tags_render(const SamArgs &, HitInfo &, uint8_t *) { return true; }
 
-template <bool kLocated, bool kFlags, bool kTags> __global__ __launch_bounds__(kBlock) void sam_size_kernel(typename KernelArgs<kTags>::type A, uint64_t *len_out, uint32_t *err)
+// kUnmapped: the forms of SX_MAP_UNMAPPED (placeholders print a FLAG 4 line); with it false the code is the one from before
+template <bool kLocated, bool kFlags, bool kTags, bool kUnmapped>
+__global__ __launch_bounds__(kBlock) void sam_size_kernel(typename KernelArgs<kTags>::type A, uint64_t *len_out, uint32_t *err)
 {
     __shared__ uint64_t red[kWavesPerBlock];
     __shared__ uint32_t long_cnt[kBlock];
@@ -288,8 +305,10 @@ template <bool kLocated, bool kFlags, bool kTags> __global__ __launch_bounds__(k
     long_cnt[t] = 0;
     if (h < A.n_hits) {
         HitInfo I = {};
-        if (!hit_info<kLocated, kFlags>(A, h, I)) {
+        if (!hit_info<kLocated, kFlags, kUnmapped>(A, h, I)) {
             atomicOr(err, 1u);
+        } else if (kUnmapped && !I.pos) {
+            bytes = unmapped_bytes(I);
         } else {
             I.cig_len = cigar_render(nullptr, kCigarMax, I.m, I.gaps, I.n_gaps);
             if (kTags && I.cnt && !tags_render(A, I, nullptr)) {
@@ -336,8 +355,10 @@ __device__ __forceinline__ void put_bytes(uint8_t *obuf, int64_t &off, int64_t s
     off += n;
 }
 
-template <bool kLocated, bool kFlags, bool kTags> __global__ __launch_bounds__(kBlock) void sam_emit_kernel(typename KernelArgs<kTags>::type A, const uint64_t *byte_off, uint64_t lo, uint64_t hi,
-                                                          uint8_t *out)
+// kUnmapped: as in sam_size_kernel; a placeholder is kept as a hit of 1 line with HitLds::pos == nullptr and HitLds::fixed
+// the line's whole length
+template <bool kLocated, bool kFlags, bool kTags, bool kUnmapped>
+__global__ __launch_bounds__(kBlock) void sam_emit_kernel(typename KernelArgs<kTags>::type A, const uint64_t *byte_off, uint64_t lo, uint64_t hi, uint8_t *out)
 {
     __shared__ uint4 obuf4[kSlice / 16];
     __shared__ uint8_t cig[kBlock * kCigarMax];
@@ -369,7 +390,7 @@ template <bool kLocated, bool kFlags, bool kTags> __global__ __launch_bounds__(k
     uint32_t i = 0;
     {   // the walk inside the hit: whole steps of 1024 lines that end at or before the slice's first byte are skipped
         HitInfo I = {};
-        if (hit_info<kLocated, kFlags>(A, h, I)) {
+        if (hit_info<kLocated, kFlags, kUnmapped>(A, h, I)) { // (a placeholder has 1 line: no walk)
             I.cig_len = cigar_render(nullptr, kCigarMax, I.m, I.gaps, I.n_gaps);
             // (the tags' length is needed by the steps below alone: a hit of up to 1024 lines, which is nearly every hit,
             //  is not walked here, only by its lane in the loop further down)
@@ -392,13 +413,20 @@ template <bool kLocated, bool kFlags, bool kTags> __global__ __launch_bounds__(k
         // hits h .. h + 255: how many lines each has left, the first 256 lines' hits, their CIGARs
         HitInfo I = {};
         uint32_t c = 0;
-        if (h + t < A.n_hits && hit_info<kLocated, kFlags>(A, h + t, I)) c = I.cnt - (t == 0 ? (i < I.cnt ? i : I.cnt) : 0u);
+        if (h + t < A.n_hits && hit_info<kLocated, kFlags, kUnmapped>(A, h + t, I)) c = I.cnt - (t == 0 ? (i < I.cnt ? i : I.cnt) : 0u);
         const uint32_t cc = c < (uint32_t)kBlock ? c : (uint32_t)kBlock;
         uint32_t total;
         const uint32_t ex = block_exclusive_scan<OpAdd>(cc, red32, total);
         mo[t] = ex;
         if (t == 0) mo[kBlock] = total;
-        if (cc && ex < (uint32_t)kBlock) {
+        if (kUnmapped && cc && ex < (uint32_t)kBlock && !I.pos) {
+            HitLds &H = hl[t];
+            H.pos = nullptr;
+            H.cnt = 1;
+            H.fixed = unmapped_bytes(I);
+            H.name_b = I.name_b, H.name_l = I.name_l, H.seq_b = I.seq_b, H.seq_l = I.seq_l;
+            H.qual_b = I.qual_b, H.qual_l = I.qual_l;
+        } else if (cc && ex < (uint32_t)kBlock) {
             I.cig_len = cigar_render(cig + t * kCigarMax, kCigarMax, I.m, I.gaps, I.n_gaps);
             HitLds &H = hl[t];
             H.pos = I.pos;
@@ -432,13 +460,26 @@ template <bool kLocated, bool kFlags, bool kTags> __global__ __launch_bounds__(k
             }
             u = a;
             mi = t - mo[u] + (u == 0 ? i : 0u);
-            p1 = hl[u].pos[mi] + 1u;
-            len = hl[u].fixed + dec_digits(p1);
+            if (kUnmapped && !hl[u].pos) {
+                len = hl[u].fixed;
+            } else {
+                p1 = hl[u].pos[mi] + 1u;
+                len = hl[u].fixed + dec_digits(p1);
+            }
         }
         uint32_t step_bytes;
         const uint32_t lstart = block_exclusive_scan<OpAdd>(len, red32, step_bytes);
         const uint64_t line_abs = pos + lstart;
-        if (t < nlines && line_abs < s_hi && line_abs + len > s_lo) {
+        if (kUnmapped && t < nlines && line_abs < s_hi && line_abs + len > s_lo && !hl[u].pos) {
+            const HitLds &H = hl[u];
+            int64_t off = (int64_t)line_abs - (int64_t)s_lo;
+            put_bytes(obuf, off, slice_len, A.names + H.name_b, H.name_l);
+            put_bytes(obuf, off, slice_len, (const uint8_t *)"\t4\t*\t0\t0\t*\t*\t0\t0\t", 17);
+            put_bytes(obuf, off, slice_len, A.seqs + H.seq_b, H.seq_l);
+            put_bytes(obuf, off, slice_len, (const uint8_t *)"\t", 1);
+            put_bytes(obuf, off, slice_len, A.quals + H.qual_b, H.qual_l);
+            put_bytes(obuf, off, slice_len, (const uint8_t *)"\n", 1);
+        } else if (t < nlines && line_abs < s_hi && line_abs + len > s_lo) {
             const HitLds &H = hl[u];
             int64_t off = (int64_t)line_abs - (int64_t)s_lo;
             uint8_t dig[10];
@@ -686,22 +727,28 @@ static int sam_args_tags(sx_ctx *ctx, const sx_sam_batch_tags *b, SamTagArgs &A)
     return 0;
 }
 
-// the forms of the two kernels: positions located beforehand or read from a suffix array, a FLAG per read or none, and
-// each of the four with NM and MD behind QUAL
-#define SX_SAM_KERNEL_T(kernel, A, T) \
-    ((A).positions ? ((A).flags ? kernel<true, true, T> : kernel<true, false, T>) : ((A).flags ? kernel<false, true, T> : kernel<false, false, T>))
+// the forms of the two kernels: positions located beforehand or read from a suffix array, a FLAG per read or none, each of
+// the four with NM and MD behind QUAL (T), and each of the eight with placeholders (U)
+#define SX_SAM_KERNEL_T(kernel, A, T, U) \
+    ((A).positions ? ((A).flags ? kernel<true, true, T, U> : kernel<true, false, T, U>) : ((A).flags ? kernel<false, true, T, U> : kernel<false, false, T, U>))
 
-int sam_layout(sx_ctx *ctx, const SamTagArgs &A, uint64_t *d_byte_off, uint64_t *total_out)
+int sam_layout(sx_ctx *ctx, const SamTagArgs &A, uint64_t *d_byte_off, uint64_t *total_out, bool unmapped)
 {
     *total_out = 0;
     SX_TRY(sx_slab_ensure(ctx, SX_SLAB_SORT, 4096));
     uint32_t *d_err = (uint32_t *)ctx->slab[SX_SLAB_SORT].p;
     SX_CHECK(hipMemsetAsync(d_err, 0, 16, ctx->stream));
-    if (A.n_hits && A.text_list) // (a text window of about a read's length a hit beside its 32 bytes)
-        sx_launch(ctx, SX_KC_SAM, A.n_hits * 40, SX_SAM_KERNEL_T(sam_size_kernel, A, true), dim3(sx_div_up(A.n_hits, kBlock)),
+    if (A.n_hits && unmapped && A.text_list) // (SX_MAP_UNMAPPED: the same passes in kernels of their own)
+        sx_launch(ctx, SX_KC_SAM, A.n_hits * 40, SX_SAM_KERNEL_T(sam_size_kernel, A, true, true), dim3(sx_div_up(A.n_hits, kBlock)),
+                  dim3(kBlock), A, d_byte_off, d_err);
+    else if (A.n_hits && unmapped)
+        sx_launch(ctx, SX_KC_SAM, A.n_hits * 40, SX_SAM_KERNEL_T(sam_size_kernel, A, false, true), dim3(sx_div_up(A.n_hits, kBlock)),
+                  dim3(kBlock), static_cast<const SamArgs &>(A), d_byte_off, d_err);
+    else if (A.n_hits && A.text_list) // (a text window of about a read's length a hit beside its 32 bytes)
+        sx_launch(ctx, SX_KC_SAM, A.n_hits * 40, SX_SAM_KERNEL_T(sam_size_kernel, A, true, false), dim3(sx_div_up(A.n_hits, kBlock)),
                   dim3(kBlock), A, d_byte_off, d_err);
     else if (A.n_hits)
-        sx_launch(ctx, SX_KC_SAM, A.n_hits * 40, SX_SAM_KERNEL_T(sam_size_kernel, A, false), dim3(sx_div_up(A.n_hits, kBlock)),
+        sx_launch(ctx, SX_KC_SAM, A.n_hits * 40, SX_SAM_KERNEL_T(sam_size_kernel, A, false, false), dim3(sx_div_up(A.n_hits, kBlock)),
                   dim3(kBlock), static_cast<const SamArgs &>(A), d_byte_off, d_err);
     SX_TRY(device_scan64_inplace(ctx, d_byte_off, A.n_hits, SX_KC_SAM));
     uint32_t h[2] = {0, 0}, e = 0;
@@ -715,17 +762,23 @@ int sam_layout(sx_ctx *ctx, const SamTagArgs &A, uint64_t *d_byte_off, uint64_t 
 }
 
 // (asynchronous: the caller syncs)
-int sam_emit(sx_ctx *ctx, const SamTagArgs &A, const uint64_t *d_byte_off, uint64_t lo, uint64_t hi, uint8_t *d_out)
+int sam_emit(sx_ctx *ctx, const SamTagArgs &A, const uint64_t *d_byte_off, uint64_t lo, uint64_t hi, uint8_t *d_out, bool unmapped)
 {
     if (hi <= lo) return 0;
     const uint64_t slices = (hi - lo + kSlice - 1) / kSlice;
     if (slices > 0x7FFFFFFFull) return sx_fail_msg(ctx, SX_E_ARG, "SAM text: window too long");
     // per line: its bytes out, 4 bytes of position in; the read's fields once a slice
-    if (A.text_list)
-        sx_launch(ctx, SX_KC_SAM, hi - lo, SX_SAM_KERNEL_T(sam_emit_kernel, A, true), dim3((uint32_t)slices), dim3(kBlock), A,
+    if (unmapped && A.text_list)
+        sx_launch(ctx, SX_KC_SAM, hi - lo, SX_SAM_KERNEL_T(sam_emit_kernel, A, true, true), dim3((uint32_t)slices), dim3(kBlock), A,
+                  d_byte_off, lo, hi, d_out);
+    else if (unmapped)
+        sx_launch(ctx, SX_KC_SAM, hi - lo, SX_SAM_KERNEL_T(sam_emit_kernel, A, false, true), dim3((uint32_t)slices), dim3(kBlock),
+                  static_cast<const SamArgs &>(A), d_byte_off, lo, hi, d_out);
+    else if (A.text_list)
+        sx_launch(ctx, SX_KC_SAM, hi - lo, SX_SAM_KERNEL_T(sam_emit_kernel, A, true, false), dim3((uint32_t)slices), dim3(kBlock), A,
                   d_byte_off, lo, hi, d_out);
     else
-        sx_launch(ctx, SX_KC_SAM, hi - lo, SX_SAM_KERNEL_T(sam_emit_kernel, A, false), dim3((uint32_t)slices), dim3(kBlock),
+        sx_launch(ctx, SX_KC_SAM, hi - lo, SX_SAM_KERNEL_T(sam_emit_kernel, A, false, false), dim3((uint32_t)slices), dim3(kBlock),
                   static_cast<const SamArgs &>(A), d_byte_off, lo, hi, d_out);
     return 0;
 }
@@ -775,6 +828,40 @@ int sx_sam_emit_dev_tags(sx_ctx *ctx, const sx_sam_batch_tags *batch, const uint
         return sx_fail_msg(ctx, SX_E_ARG, "SAM text: a window inside [0, total) and a 16-byte aligned buffer are needed");
     SX_CHECK(hipSetDevice(ctx->device));
     SX_TRY(sam_emit(ctx, A, d_byte_offsets, byte_lo, byte_hi, d_out));
+    return sx_sync(ctx);
+}
+
+// a batch whose placeholders print FLAG 4 lines: the fields of sx_sam_batch_tags, the texts and letters optional (both or
+// neither: with them the mapped lines carry NM and MD)
+static int sam_args_unmapped(sx_ctx *ctx, const sx_sam_batch_tags *b, SamTagArgs &A)
+{
+    if (!b) return SX_E_ARG;
+    if (b->d_text_list || b->d_letters) return sam_args_tags(ctx, b, A);
+    SX_TRY(sam_args_ex(ctx, &b->ex, A));
+    if ((b->d_positions != nullptr) != (b->d_pos_off != nullptr) || ((uintptr_t)b->d_positions & 3) || ((uintptr_t)b->d_pos_off & 7))
+        return sx_fail_msg(ctx, SX_E_ARG, "SAM text: located positions come with their offsets");
+    A.positions = b->d_positions, A.pos_off = b->d_pos_off, A.pos_base = b->pos_base;
+    return 0;
+}
+
+int sx_sam_layout_dev_unmapped(sx_ctx *ctx, const sx_sam_batch_tags *batch, uint64_t *d_byte_offsets, uint64_t *total_bytes_out)
+{
+    SamTagArgs A;
+    SX_TRY(sam_args_unmapped(ctx, batch, A));
+    if (!d_byte_offsets || !total_bytes_out) return SX_E_ARG;
+    SX_CHECK(hipSetDevice(ctx->device));
+    return sam_layout(ctx, A, d_byte_offsets, total_bytes_out, true);
+}
+
+int sx_sam_emit_dev_unmapped(sx_ctx *ctx, const sx_sam_batch_tags *batch, const uint64_t *d_byte_offsets, uint64_t total_bytes, uint64_t byte_lo,
+                             uint64_t byte_hi, uint8_t *d_out)
+{
+    SamTagArgs A;
+    SX_TRY(sam_args_unmapped(ctx, batch, A));
+    if (!d_byte_offsets || byte_lo > byte_hi || byte_hi > total_bytes || (A.n_hits == 0 && byte_hi > byte_lo) || (byte_hi > byte_lo && (!d_out || ((uintptr_t)d_out & 15))))
+        return sx_fail_msg(ctx, SX_E_ARG, "SAM text: a window inside [0, total) and a 16-byte aligned buffer are needed");
+    SX_CHECK(hipSetDevice(ctx->device));
+    SX_TRY(sam_emit(ctx, A, d_byte_offsets, byte_lo, byte_hi, d_out, true));
     return sx_sync(ctx);
 }
 

@@ -22,9 +22,13 @@ mate drawn 200 - 499 symbols downstream on the other strand, with the same subst
 with indels=False, and with best=True as well, on the two files: the call's wall time, the kernel ms of its five classes
 (pair_count, pair_scan, pair_fill, pair_layout, pair_emit; a run of their own with every launch timed), the emit's rate over
 its text against the plain emit's, and the wall time of the two both_strands calls on the two files with the same flags
-(kept in profiles/pairs_bench_2p28.json).
+(kept in profiles/pairs_bench_2p28.json).  --unmapped adds FLAG 4 lines for the reads without a hit (SX_MAP_UNMAPPED, DESIGN.md
+section 22): per k the reads without a hit and the bytes their lines add, layout and emit over the same hits with a
+placeholder a read without one (sx_sam_layout_dev_unmapped / sx_sam_emit_dev_unmapped) and the cost per added byte against
+the plain passes' rate, and the streamed call with and without unmapped=True, its kernel ms of the search and of the sam
+class each in a run of its own (kept in profiles/unmapped_bench_2p28.json).
 
-    python tools/sam_bench.py [--log2n 28] [--reads 1000000] [--window-mib 1024] [--repeats 5] [--both-strands] [--best] [--no-indels] [--tags] [--pairs]
+    python tools/sam_bench.py [--log2n 28] [--reads 1000000] [--window-mib 1024] [--repeats 5] [--both-strands] [--best] [--no-indels] [--tags] [--pairs] [--unmapped]
 """
 import argparse
 import ctypes as C
@@ -54,6 +58,7 @@ def main():
     ap.add_argument("--no-indels", action="store_true", help="also the search, the text and the streamed call without indels")
     ap.add_argument("--tags", action="store_true", help="also layout, emit and the index call with NM:i and MD:Z on every line")
     ap.add_argument("--pairs", action="store_true", help="also the paired call on the reads and their mates, indels=False without and with best=True")
+    ap.add_argument("--unmapped", action="store_true", help="also layout, emit and the streamed call with a FLAG 4 line for every read without a hit")
     args = ap.parse_args()
     import torch
 
@@ -200,9 +205,47 @@ def main():
                              "emit_GBps": round(t_emit_bytes / (te * 1e-3) / 1e9, 1),
                              "layout_plus_emit_over_untagged": round((tl + te) / (layout_ms + emit_ms), 3),
                              "layout_plus_emit_over_search": round((tl + te) / search_ms, 4)}
+        if args.unmapped:
+            entry["unmapped"] = unmapped_passes(total, d_hits, layout_ms, emit_ms, nbytes)
         del d_hits, d_boff
         torch.cuda.empty_cache()
         return entry
+
+    def unmapped_passes(total, d_hits, layout_ms, emit_ms, nbytes):
+        """the same hits with a placeholder (query = the read, L = R = 0) in front of where every read without a hit would
+        have its hits, as the mapper's merge places them; layout and emit of that text"""
+        cnt = d_hoff[1:] - d_hoff[:-1]
+        lost = (cnt == 0).to(torch.int64)
+        shift = torch.cumsum(lost, 0) - lost  # (reads without a hit in front of every read)
+        n_lost = int(lost.sum().item())
+        d_all = torch.zeros((total + n_lost) * 8, dtype=torch.int32, device="cuda")
+        if total:
+            words = d_hits[:total * 32].view(torch.int32).reshape(-1, 8)
+            q = words[:, 0].to(torch.int64)
+            d_all.view(-1, 8)[torch.arange(total, device="cuda") + shift[q]] = words
+        lost_q = torch.nonzero(lost).flatten()
+        d_all.view(-1, 8)[d_hoff[:-1][lost_q] + shift[lost_q], 0] = lost_q.to(torch.int32)
+        n_all = total + n_lost
+        d_uoff = torch.zeros(n_all + 1, dtype=torch.int64, device="cuda")
+        ub = ctx.sam_batch(d_all, n_all, d_sa, N, d_names, d_name_off, d_seqs, d_off, d_quals, d_off, R, d_rname, d_rname_off, 1)
+        ctx.sam_layout_dev_unmapped(ub, d_uoff)  # warm-up
+        u_layout = [profiled("sam", lambda: ctx.sam_layout_dev_unmapped(ub, d_uoff)) for _ in range(args.repeats)]
+        u_bytes = u_layout[0][0]
+
+        def emit_unmapped():
+            for lo in range(0, u_bytes, window):
+                ctx.sam_emit_dev_unmapped(ub, d_uoff, u_bytes, lo, min(u_bytes, lo + window), d_win)
+
+        ctx.sam_emit_dev_unmapped(ub, d_uoff, u_bytes, 0, min(u_bytes, window), d_win)  # warm-up
+        u_emit = [profiled("sam", emit_unmapped) for _ in range(args.repeats)]
+        ul, ue = min(r[2] for r in u_layout), min(r[2] for r in u_emit)
+        added = u_bytes - nbytes
+        plain_ns_per_byte = (layout_ms + emit_ms) * 1e6 / max(nbytes, 1)
+        return {"reads_without_hit": n_lost, "added_lines": n_lost, "text_bytes": int(u_bytes), "added_bytes": int(added),
+                "layout_ms": round(ul, 3), "layout_ms_runs": [round(r[2], 3) for r in u_layout],
+                "emit_ms": round(ue, 3), "emit_ms_runs": [round(r[2], 3) for r in u_emit],
+                "plain_ns_per_text_byte": round(plain_ns_per_byte, 4),
+                "added_ns_per_added_byte": None if added <= 0 else round((ul + ue - layout_ms - emit_ms) * 1e6 / added, 4)}
 
     for k in [int(x) for x in args.ks.split(",")]:
         out[f"k{k}"] = text_of_search(k, True)
@@ -271,6 +314,18 @@ def main():
                 out[f"k{k}"][key] = {"call_wall_ms": round(b_wall * 1e3, 1), "call_wall_ms_runs": b_walls,
                                      "text_bytes": int(sum(b for _, b in b_seen)), "windows": len(b_seen),
                                      "plain_call_wall_ms": round(wall * 1e3, 1)}
+        if args.unmapped:  # the call with and without the bit: wall, bytes, and its search and sam kernel ms in runs of their own
+            res = {}
+            for name, kw in (("plain", {}), ("unmapped", dict(unmapped=True))):
+                call = lambda: ctx.map_reads_stream([(b"chr1", rec)], fastq, k, None, **kw)  # noqa: E731
+                u_wall, u_seen, u_walls = (wall, seen, walls) if not kw else streamed(k, **kw)  # (the plain runs: those above)
+                search = [profiled("search", call)[2] for _ in range(args.repeats)]
+                sam = [profiled("sam", call)[2] for _ in range(args.repeats)]
+                res[name] = {"call_wall_ms": round(u_wall * 1e3, 1), "call_wall_ms_runs": u_walls, "text_bytes": int(sum(b for _, b in u_seen)),
+                             "search_ms": round(min(search), 3), "search_ms_runs": [round(x, 3) for x in search],
+                             "sam_class_ms": round(min(sam), 3), "sam_class_ms_runs": [round(x, 3) for x in sam]}
+            assert res["unmapped"]["text_bytes"] == out[f"k{k}"]["unmapped"]["text_bytes"]
+            out[f"k{k}"]["unmapped"]["streamed"] = res
         if args.both_strands:
             both_wall, both_seen, both_walls = streamed(k, both_strands=True)
             out[f"k{k}"]["streamed_both_strands"] = {"call_wall_ms": round(both_wall * 1e3, 1), "call_wall_ms_runs": both_walls,

@@ -42,6 +42,13 @@
  *                                                   distance and the mismatch string of its POS, CIGAR and SEQ over the
  *                                                   record's letters, rendered on the device; goes with every other
  *                                                   switch
+ *   --unmapped                                      with -d: a read (with --both-strands: a read and its reverse complement)
+ *                                                   that prints no line gets one, where its lines would stand:
+ *                                                   "<name>\t4\t*\t0\t0\t*\t*\t0\t0\t<seq>\t<qual>", no tags; goes with
+ *                                                   every other switch but -2
+ *   --header                                        with -d: the SAM header in front of the lines, "@HD VN:1.6 SO:unsorted"
+ *                                                   and an "@SQ SN:<name> LN:<length>" a record; once, with several FASTQ
+ *                                                   files too; goes with every other switch, -2 included
  *   -2 mates.fq (--mates)                           with -d and one reads.fq: paired-end reads.  Read p of reads.fq and read p of
  *                                                   mates.fq are the mates of pair p; the output is the two lines of every
  *                                                   proper pair of their placements -- same record, one mate on either
@@ -51,7 +58,7 @@
  *                                                   strands are implied.  Goes with -i, --compact, --sa-sample, --packed,
  *                                                   --best and --no-indels (which is what it is meant to be used with: the
  *                                                   search reports some placements with indels more than once); not with
- *                                                   --tags or several read files
+ *                                                   --tags, --unmapped or several read files
  *   --min-insert N, --max-insert N                  with -2: the window of that distance (0 and 1000)
  *   (--preprocess, --edits and --in-memory are accepted for -p, -d and -i)
  *
@@ -173,7 +180,7 @@ static int map_reads(const char *fasta, char *const *reads, int n_reads, int k, 
     for (int f = 0; f < n_reads && rc == 0; ++f) {
         FILE *fq = fopen(reads[f], "rb");
         if (!fq) fail("cannot read", reads[f]);
-        rc = stralg_amd_index_map_ex(idx, fq, k, map_flags, stdout);
+        rc = stralg_amd_index_map_ex(idx, fq, k, f == 0 ? map_flags : map_flags & ~(uint32_t)SX_MAP_HEADER, stdout); /* (one header) */
         fclose(fq);
     }
     stralg_amd_index_free(idx);
@@ -198,8 +205,10 @@ static int usage(const char *self, int status)
     fprintf(stderr, "       --no-indels                        with -d K: mismatches only, every placement within K substitutions\n");
     fprintf(stderr, "                                          once (with --best: the smallest number of substitutions)\n");
     fprintf(stderr, "       --tags                             with -d: NM:i and MD:Z behind QUAL on every line\n");
+    fprintf(stderr, "       --unmapped                         with -d: a FLAG 4 line for every read that prints no line\n");
+    fprintf(stderr, "       --header                           with -d: @HD and @SQ lines in front of the text, once\n");
     fprintf(stderr, "       -2 mates.fq, --mates mates.fq      with -d and one reads.fq: paired-end reads, the lines of the proper\n");
-    fprintf(stderr, "                                          pairs (FLAG 99 / 147, 83 / 163); not with --tags\n");
+    fprintf(stderr, "                                          pairs (FLAG 99 / 147, 83 / 163); not with --tags or --unmapped\n");
     fprintf(stderr, "       --min-insert N, --max-insert N     with -2: the window of a pair's length (0, 1000)\n");
     return status;
 }
@@ -230,6 +239,10 @@ int main(int argc, char **argv)
             map_flags |= SX_MAP_NO_INDELS;
         } else if (!strcmp(s, "--tags")) {
             map_flags |= SX_MAP_TAGS;
+        } else if (!strcmp(s, "--unmapped")) {
+            map_flags |= SX_MAP_UNMAPPED;
+        } else if (!strcmp(s, "--header")) {
+            map_flags |= SX_MAP_HEADER;
         } else if (!strcmp(s, "-2") || !strcmp(s, "--mates")) {
             if (++a >= argc) return usage(argv[0], EXIT_FAILURE);
             mates = argv[a];
@@ -265,6 +278,10 @@ int main(int argc, char **argv)
     if (indexing) return to_index ? build_index(to_index) : usage(argv[0], EXIT_FAILURE);
     if (n_rest < 2 || k < 0) return usage(argv[0], EXIT_FAILURE);
     if (mates && (map_flags & SX_MAP_TAGS)) fail("-2 does not go with --tags", NULL);
+    if (mates && (map_flags & SX_MAP_UNMAPPED)) {
+        fprintf(stderr, "%s: -2 does not go with --unmapped\n", argv[0]);
+        return usage(argv[0], EXIT_FAILURE);
+    }
     if (mates && n_rest != 2) fail("-2 takes one reads file beside the mates' file", NULL);
     if (mates && window.min_insert > window.max_insert) fail("--min-insert must not exceed --max-insert", NULL);
     return map_reads(rest[0], rest + 1, n_rest - 1, k, in_memory, flags, map_flags, mates, &window);
