@@ -64,6 +64,7 @@ enum {
     SX_KC_PAIR_FILL,      /* paired reads: two line descriptors a proper combination               */
     SX_KC_PAIR_LAYOUT,    /* paired reads: bytes of every described line and their scan            */
     SX_KC_PAIR_EMIT,      /* paired reads: the text of a window of described lines                 */
+    SX_KC_MAPQ,           /* SX_MAP_MAPQ: the quality pass over a batch's merged hits */
     SX_KC_COUNT
 };
 
@@ -426,6 +427,19 @@ int sx_sam_emit_dev_tags(sx_ctx *ctx, const sx_sam_batch_tags *batch, const uint
 int sx_sam_layout_dev_unmapped(sx_ctx *ctx, const sx_sam_batch_tags *batch, uint64_t *d_byte_offsets, uint64_t *total_bytes_out);
 int sx_sam_emit_dev_unmapped(sx_ctx *ctx, const sx_sam_batch_tags *batch, const uint64_t *d_byte_offsets, uint64_t total_bytes, uint64_t byte_lo,
                              uint64_t byte_hi, uint8_t *d_out);
+/* The emitter of SX_MAP_MAPQ: the batch of sx_sam_layout_dev_unmapped (d_text_list and d_letters both
+ * or neither; a hit with R == L is a placeholder and prints its FLAG 4 line) and a 16-bit quality word a hit, d_hit_quality[h]
+ * (device memory, n_hits entries, indexed like d_hits): its low 8 bits are the MAPQ, printed in decimal where the "0" behind
+ * POS stands on every line of hit h; its bit 8 set means every line of the hit has 256 added to its FLAG (d_read_flags, or 0
+ * where that is NULL).  A placeholder's quality word is ignored: its line is the one above, with MAPQ 0.  A NULL
+ * d_hit_quality answers SX_E_ARG. */
+typedef struct sx_sam_batch_mapq {
+    sx_sam_batch_tags tags;
+    const uint16_t *d_hit_quality;
+} sx_sam_batch_mapq;
+int sx_sam_layout_dev_mapq(sx_ctx *ctx, const sx_sam_batch_mapq *batch, uint64_t *d_byte_offsets, uint64_t *total_bytes_out);
+int sx_sam_emit_dev_mapq(sx_ctx *ctx, const sx_sam_batch_mapq *batch, const uint64_t *d_byte_offsets, uint64_t total_bytes, uint64_t byte_lo,
+                         uint64_t byte_hi, uint8_t *d_out);
 
 /* Lines with a mate.  A line descriptor names a hit of the batch (its read, record, CIGAR, SEQ and QUAL
  * are the hit's) and carries what the hit does not say: line j prints
@@ -525,8 +539,28 @@ int sx_map_reads_stream(sx_ctx *ctx, const sx_map_record *records, uint32_t n_re
  * Header.  With SX_MAP_HEADER one sink call in front of the text writes "@HD\tVN:1.6\tSO:unsorted\n"
  * and, per record in the mapper's list order, "@SQ\tSN:<name>\tLN:<N - 1>\n", <name> byte for byte the RNAME of the lines.
  * Every argument check comes first (a refused call sinks nothing); an empty FASTQ gives the header alone.  It composes with
- * everything, sx_index_map_pairs included.  Neither bit changes a byte or a launch of a call without it. */
-enum { SX_MAP_BOTH_STRANDS = 1, SX_MAP_BEST_STRATUM = 8, SX_MAP_NO_INDELS = 16, SX_MAP_TAGS = 64, SX_MAP_UNMAPPED = 128, SX_MAP_HEADER = 256 };
+ * everything, sx_index_map_pairs included.  Neither bit changes a byte or a launch of a call without it.
+ * MAPQ and secondary lines.  SX_MAP_MAPQ needs SX_MAP_BEST_STRATUM (without it a hit does not say how
+ * many edits it uses, and a read's first line need not be one of its best): the bit alone answers SX_E_ARG with a message,
+ * with every other argument check, before anything is sunk.  A group is a best-stratum group: a read, or with
+ * SX_MAP_BOTH_STRANDS the read and its reverse complement.  Let n be the number of lines the same call without the bit prints
+ * for the group, over all records and strands.  The text has the same lines in the same order with the same bytes but for
+ * two fields.  FLAG: the group's first line in output order keeps its FLAG (0 or 16), every other line of the group has 256
+ * added (256 or 272).  MAPQ, the same on every line of the group: 50 for n = 1, 3 for n = 2, 1 for n = 3 or 4, 0 for n >= 5
+ * (-10 log10(1 - 1/n), rounded and floored as TopHat and STAR do; neither e* nor `edits` enters, and the lines of the next
+ * stratum, e* + 1, are not counted).  n counts lines, not distinct positions: the search with indels reports some placements
+ * twice ("1I99M" beside "100M"), so SX_MAP_NO_INDELS is what a caller combines the bit with.  FLAG 4 lines, NM and MD, the
+ * header and the limit are unchanged; the bit composes with the other flags and every index form; sx_index_map_pairs answers
+ * it with SX_E_ARG.  Bit 512 stays unknown.  A call without the bit launches what it launched and prints what it printed. */
+enum {
+    SX_MAP_BOTH_STRANDS = 1,
+    SX_MAP_BEST_STRATUM = 8,
+    SX_MAP_NO_INDELS = 16,
+    SX_MAP_TAGS = 64,
+    SX_MAP_UNMAPPED = 128,
+    SX_MAP_HEADER = 256,
+    SX_MAP_MAPQ = 1024
+};
 int sx_map_reads_stream_ex(sx_ctx *ctx, const sx_map_record *records, uint32_t n_records, const uint8_t *fastq, size_t fastq_len,
                            int edits, uint32_t flags, sx_sink_fn sink, void *user);
 /* the limit of a mapping call on its reads and records: 0, or SX_E_ARG when reads x records (twice that with

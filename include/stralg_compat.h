@@ -254,7 +254,8 @@ void stralg_amd_free_approx_result(struct stralg_amd_approx_result *result);
 int stralg_amd_map_reads(struct bwt_table *const *tables, const char *const *names, size_t n, FILE *fastq, int edits, FILE *sam);
 /* the same with the flags of sx_map_reads_stream_ex (stralg_amd.h): SX_MAP_BOTH_STRANDS maps every read and its reverse
  * complement, the latter's lines with FLAG 16; SX_MAP_BEST_STRATUM, SX_MAP_NO_INDELS, SX_MAP_UNMAPPED (a FLAG 4 line for
- * every read without one) and SX_MAP_HEADER (@HD and @SQ lines in front) as described there */
+ * every read without one), SX_MAP_HEADER (@HD and @SQ lines in front) and SX_MAP_MAPQ (with SX_MAP_BEST_STRATUM: 256 on the
+ * FLAG of every line of a read but its first, MAPQ 50 / 3 / 1 / 0 from the lines of its best stratum) as described there */
 int stralg_amd_map_reads_ex(struct bwt_table *const *tables, const char *const *names, size_t n, FILE *fastq, int edits, uint32_t flags,
                             FILE *sam);
 
@@ -276,7 +277,7 @@ void stralg_amd_index_free(struct sx_index *idx);
 struct sx_index *stralg_amd_index_from_fasta_image_ex(const uint8_t *fasta, size_t len, bool include_reverse, uint32_t flags);
 struct sx_index *stralg_amd_index_read_ex(FILE *f, uint32_t flags);
 /* stralg_amd_index_map with the flags of sx_map_reads_stream_ex (SX_MAP_BOTH_STRANDS, SX_MAP_BEST_STRATUM, SX_MAP_NO_INDELS,
- * SX_MAP_TAGS, SX_MAP_UNMAPPED, SX_MAP_HEADER) */
+ * SX_MAP_TAGS, SX_MAP_UNMAPPED, SX_MAP_HEADER, SX_MAP_MAPQ; the last needs SX_MAP_BEST_STRATUM) */
 int stralg_amd_index_map_ex(const struct sx_index *idx, FILE *fastq, int edits, uint32_t flags, FILE *sam);
 /* paired-end reads (stralg_amd.h sx_index_map_pairs): the rest of fastq1 and of fastq2 are the two mates' files, read p of
  * either the mates of pair p; the SAM lines of the proper pairs go to `sam` (flags: those of sx_index_map_pairs, SX_MAP_HEADER

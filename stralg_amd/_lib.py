@@ -13,7 +13,7 @@ PRODUCT_LIB = os.path.join(_HERE, "libstralg_amd.so")
 KC_NAMES = ["classify", "samples", "keys", "radix_hist", "radix_scatter", "scan", "names", "doubling",
             "induce_gather", "induce_scan", "induce_scatter", "induce_chain", "bwt_gather", "otable", "misc",
             "fasta", "remap", "lcp", "search", "local_sort", "sam",
-            "pair_count", "pair_scan", "pair_fill", "pair_layout", "pair_emit"]
+            "pair_count", "pair_scan", "pair_fill", "pair_layout", "pair_emit", "mapq"]
 
 
 class KernelStat(C.Structure):
@@ -80,14 +80,15 @@ SX_MAP_NO_INDELS = 16
 SX_MAP_TAGS = 64
 SX_MAP_UNMAPPED = 128
 SX_MAP_HEADER = 256
+SX_MAP_MAPQ = 1024
 SX_SEARCH_NO_INDELS = 1
 
 
-def map_flags(both_strands=False, best=False, indels=True, tags=False, unmapped=False, header=False):
+def map_flags(both_strands=False, best=False, indels=True, tags=False, unmapped=False, header=False, mapq=False):
     """the flags word of sx_map_reads_stream_ex / sx_index_map_reads_ex"""
     return ((SX_MAP_BOTH_STRANDS if both_strands else 0) | (SX_MAP_BEST_STRATUM if best else 0)
             | (0 if indels else SX_MAP_NO_INDELS) | (SX_MAP_TAGS if tags else 0) | (SX_MAP_UNMAPPED if unmapped else 0)
-            | (SX_MAP_HEADER if header else 0))
+            | (SX_MAP_HEADER if header else 0) | (SX_MAP_MAPQ if mapq else 0))
 
 
 def pair_flags(best=False, indels=True, header=False):
@@ -119,6 +120,12 @@ class SamBatchTags(C.Structure):
     and MD behind QUAL) and, optionally, positions located beforehand"""
     _fields_ = [("ex", SamBatchEx), ("d_text_list", C.c_void_p), ("d_letters", C.c_void_p), ("d_positions", C.c_void_p),
                 ("d_pos_off", C.c_void_p), ("pos_base", C.c_uint64)]
+
+
+class SamBatchMapq(C.Structure):
+    """include/stralg_amd.h sx_sam_batch_mapq: the batch of the unmapped emitter and a 16-bit quality word a hit (device
+    memory): the low 8 bits the MAPQ of the hit's lines, bit 8 set for 256 on top of their FLAG"""
+    _fields_ = [("tags", SamBatchTags), ("d_hit_quality", C.c_void_p)]
 
 
 # include/stralg_amd.h sx_pair_line (20 bytes)
@@ -267,6 +274,8 @@ def load(path=None):
         "sx_sam_emit_dev_tags": (C.c_int, [vp, C.POINTER(SamBatchTags), u64p, C.c_uint64, C.c_uint64, C.c_uint64, u8p]),
         "sx_sam_layout_dev_unmapped": (C.c_int, [vp, C.POINTER(SamBatchTags), u64p, C.POINTER(C.c_uint64)]),
         "sx_sam_emit_dev_unmapped": (C.c_int, [vp, C.POINTER(SamBatchTags), u64p, C.c_uint64, C.c_uint64, C.c_uint64, u8p]),
+        "sx_sam_layout_dev_mapq": (C.c_int, [vp, C.POINTER(SamBatchMapq), u64p, C.POINTER(C.c_uint64)]),
+        "sx_sam_emit_dev_mapq": (C.c_int, [vp, C.POINTER(SamBatchMapq), u64p, C.c_uint64, C.c_uint64, C.c_uint64, u8p]),
         "sx_sam_layout_dev_pairs": (C.c_int, [vp, C.POINTER(SamBatch), vp, C.c_uint64, u64p, C.POINTER(C.c_uint64)]),
         "sx_sam_emit_dev_pairs": (C.c_int, [vp, C.POINTER(SamBatch), vp, C.c_uint64, u64p, C.c_uint64, C.c_uint64, C.c_uint64, u8p]),
         "sx_index_map_pairs": (C.c_int, [vp, vp, u8p, C.c_size_t, u8p, C.c_size_t, C.c_int, C.POINTER(PairOpts), C.c_uint32, SINK_FN,
@@ -370,7 +379,7 @@ EXPORTS = ["sx_device_count", "sx_device_numa_node", "sx_ctx_create", "sx_ctx_de
            "sx_bwt_approx_search_dev_ex", "sx_bwt_approx_search_compact_dev_ex", "sx_bwt_approx_search_packed_dev_ex",
            "sx_bwt_best_search_dev_ex", "sx_bwt_approx_search_ex", "sx_sam_layout_dev_tags", "sx_sam_emit_dev_tags",
            "sx_sam_layout_dev_pairs", "sx_sam_emit_dev_pairs", "sx_index_map_pairs", "sx_map_pairs_limit",
-           "sx_sam_layout_dev_unmapped", "sx_sam_emit_dev_unmapped",
+           "sx_sam_layout_dev_unmapped", "sx_sam_emit_dev_unmapped", "sx_sam_layout_dev_mapq", "sx_sam_emit_dev_mapq",
            "sx_synth_dev", "sx_membw_probe", "sx_prim_sort_pairs_dev", "sx_prim_exclusive_sum_dev", "sx_prim_classify_dev"]
 
 

@@ -334,6 +334,24 @@ class Context:
         self._check(self.lib.sx_sam_emit_dev_unmapped(self.h, C.byref(b), _ptr(d_byte_offsets), total_bytes, byte_lo, byte_hi, _ptr(d_out)),
                     "sx_sam_emit_dev_unmapped")
 
+    def _mapq_batch(self, batch, d_hit_quality):
+        return _lib.SamBatchMapq(self._unmapped_batch(batch), _ptr(d_hit_quality))
+
+    def sam_layout_dev_mapq(self, batch, d_hit_quality, d_byte_offsets):
+        """sx_sam_layout_dev_mapq: sam_layout_dev_unmapped of a batch with a quality word a hit (d_hit_quality, uint16, n_hits
+        entries: the low 8 bits the MAPQ of the hit's lines, bit 8 set for 256 on top of their FLAG; None: SX_E_ARG);
+        returns the text's length"""
+        total = C.c_uint64(0)
+        b = self._mapq_batch(batch, d_hit_quality)
+        self._check(self.lib.sx_sam_layout_dev_mapq(self.h, C.byref(b), _ptr(d_byte_offsets), C.byref(total)), "sx_sam_layout_dev_mapq")
+        return int(total.value)
+
+    def sam_emit_dev_mapq(self, batch, d_hit_quality, d_byte_offsets, total_bytes, byte_lo, byte_hi, d_out):
+        """sx_sam_emit_dev_mapq: bytes [byte_lo, byte_hi) of that text into d_out (uint8, 16-byte aligned)"""
+        b = self._mapq_batch(batch, d_hit_quality)
+        self._check(self.lib.sx_sam_emit_dev_mapq(self.h, C.byref(b), _ptr(d_byte_offsets), total_bytes, byte_lo, byte_hi, _ptr(d_out)),
+                    "sx_sam_emit_dev_mapq")
+
     def sam_layout_dev_pairs(self, batch, d_lines, n_lines, d_byte_offsets):
         """sx_sam_layout_dev_pairs: d_lines (n_lines entries of _lib.PAIR_LINE_DTYPE in device memory) over the hits, reads
         and records of a plain sam_batch; d_byte_offsets (n_lines + 1 uint64) <- every line's first byte; returns the
@@ -471,7 +489,7 @@ class Context:
                                                    int(sa_sample).bit_length() - 1, row_lo, row_hi, _ptr(d_out)), "sx_sa_locate_rows_dev")
 
     def map_reads_stream(self, records, fastq, edits, sink, both_strands=False, best=False, indels=True, tags=False, unmapped=False,
-                         header=False):
+                         header=False, mapq=False):
         """sx_map_reads_stream: records = [(name bytes, BwtTable), ...] in the mapper's list order; sink(bytes) receives the
         SAM text window after window.  sink=None discards the text without touching it and returns [(time.perf_counter(),
         bytes)] per window (measurement).  both_strands (sx_map_reads_stream_ex, SX_MAP_BOTH_STRANDS): behind the lines of
@@ -483,7 +501,9 @@ class Context:
         (code SX_E_ARG = -1) before anything runs; map through an Index (Index.from_fasta) instead.  unmapped
         (SX_MAP_UNMAPPED): every read (with both_strands: read and reverse complement) that prints no line gets one FLAG 4
         line "<name>\t4\t*\t0\t0\t*\t*\t0\t0\t<seq>\t<qual>" where its lines would stand.  header (SX_MAP_HEADER): the @HD
-        line and an @SQ line per record in front of the text."""
+        line and an @SQ line per record in front of the text.  mapq (SX_MAP_MAPQ, needs best; else StralgAmdError, code SX_E_ARG = -1): per read (with both_strands: read and reverse
+        complement) the first line keeps its FLAG and every other one has 256 added; MAPQ on all of them is 50, 3, 1 or 0 for
+        1, 2, 3 to 4 or more lines of the read.  The count is of lines, so indels=False is what to combine it with."""
         recs = (_lib.MapRecord * max(1, len(records)))()
         keep = []
         for r, (name, t) in enumerate(records):
@@ -505,7 +525,7 @@ class Context:
                 return 1
 
         cb = _lib.SINK_FN(_sink)
-        flags = _lib.map_flags(both_strands, best, indels, tags, unmapped, header)
+        flags = _lib.map_flags(both_strands, best, indels, tags, unmapped, header, mapq)
         if flags:
             rc = self.lib.sx_map_reads_stream_ex(self.h, recs, len(records), _ptr(buf) if buf.size else None, buf.size, edits,
                                                  flags, cb, None)
@@ -818,12 +838,12 @@ class Index:
         return self.h
 
     def map_reads(self, fastq, edits, sink=None, ctx=None, both_strands=False, best=False, indels=True, tags=False, unmapped=False,
-                  header=False):
+                  header=False, mapq=False):
         """sx_index_map_reads: the SAM text of every match of every read of a FASTQ image within `edits` edits, byte for
         byte stralg_amd.map_reads' (the reference mapper's stdout).  sink=None returns the text; sink(bytes) receives it
         window after window and None is returned.  both_strands, best, indels, tags: as in stralg_amd.map_reads
         (sx_index_map_reads_ex); tags needs every record's string in the index (an index from_tables without strings
-        raises StralgAmdError, code SX_E_ARG = -1).  unmapped, header: as in stralg_amd.map_reads."""
+        raises StralgAmdError, code SX_E_ARG = -1).  unmapped, header, mapq: as in stralg_amd.map_reads."""
         ctx = ctx or self.ctx
         buf = np.frombuffer(bytes(fastq), dtype=np.uint8)
         chunks, failure = [], []
@@ -838,7 +858,7 @@ class Index:
                 return 1
 
         cb = _lib.SINK_FN(_sink)
-        flags = _lib.map_flags(both_strands, best, indels, tags, unmapped, header)
+        flags = _lib.map_flags(both_strands, best, indels, tags, unmapped, header, mapq)
         rc = self._map(ctx, buf, edits, flags, cb)
         if failure:
             raise failure[0]
@@ -853,7 +873,7 @@ class Index:
         return ctx.lib.sx_index_map_reads(ctx.h, self._handle(), image, buf.size, edits, cb, None)
 
     def map_reads_discard(self, fastq, edits, ctx=None, both_strands=False, best=False, indels=True, tags=False, unmapped=False,
-                          header=False):
+                          header=False, mapq=False):
         """the same with a sink that does not touch the text: [(time.perf_counter(), bytes)] per window (measurement)"""
         ctx = ctx or self.ctx
         buf = np.frombuffer(bytes(fastq), dtype=np.uint8)
@@ -864,7 +884,7 @@ class Index:
             return 0
 
         cb = _lib.SINK_FN(_sink)
-        flags = _lib.map_flags(both_strands, best, indels, tags, unmapped, header)
+        flags = _lib.map_flags(both_strands, best, indels, tags, unmapped, header, mapq)
         ctx._check(self._map(ctx, buf, edits, flags, cb), "sx_index_map_reads_ex" if flags else "sx_index_map_reads")
         return seen
 
@@ -1264,7 +1284,8 @@ def bwt_approx_search(bwt_table, patterns, edits, ctx=None, indels=True):
     return approx_matches(hits, hit_off, [p.size for p in pats], bwt_table.sa.array)
 
 
-def map_reads(fasta, fastq, edits, ctx=None, both_strands=False, best=False, indels=True, tags=False, unmapped=False, header=False):
+def map_reads(fasta, fastq, edits, ctx=None, both_strands=False, best=False, indels=True, tags=False, unmapped=False, header=False,
+              mapq=False):
     """The reference read mapper (tools/readmappers/bwt_readmapper: -p genome.fa, then -d edits genome.fa reads.fq) on the
     bytes of a FASTA and a FASTQ file: its stdout, the SAM lines of every match of every read in every record within
     `edits` edits, byte for byte.  Per read the records come in the mapper's list order, which is the FASTA file's order
@@ -1281,16 +1302,20 @@ def map_reads(fasta, fastq, edits, ctx=None, both_strands=False, best=False, ind
     records' strings, so the call then maps through a temporary Index.from_fasta on ctx (the same lines).
     unmapped: every read (with both_strands: the read and its reverse complement) that prints no line gets one,
     "<name>\t4\t*\t0\t0\t*\t*\t0\t0\t<seq>\t<qual>", where its lines would stand (no tags on it).
-    header: "@HD\tVN:1.6\tSO:unsorted" and "@SQ\tSN:<name>\tLN:<length>" per record in front of the text."""
+    header: "@HD\tVN:1.6\tSO:unsorted" and "@SQ\tSN:<name>\tLN:<length>" per record in front of the text.
+    mapq (needs best; without it StralgAmdError, code SX_E_ARG = -1): FLAG and MAPQ say which line stands for the read and how
+    alone it is in its best stratum.  Of the n lines of a read (with both_strands: of the read and its reverse complement) the
+    first keeps its FLAG, every other one has 256 added (secondary), and all carry MAPQ 50 (n = 1), 3 (n = 2), 1 (n = 3 or 4)
+    or 0 (n >= 5).  n counts lines: with indels some placements print twice, so indels=False is what to combine this with."""
     ctx = ctx or default_context()
     if tags:
         with Index.from_fasta(fasta, ctx=ctx) as idx:
             return idx.map_reads(fastq, edits, both_strands=both_strands, best=best, indels=indels, tags=True, unmapped=unmapped,
-                                 header=header)
+                                 header=header, mapq=mapq)
     records = [(name, build_complete_table(seq, True, ctx)) for name, seq in ctx.fasta_records(fasta)]
     chunks = []
     ctx.map_reads_stream(records, fastq, edits, chunks.append, both_strands=both_strands, best=best, indels=indels, unmapped=unmapped,
-                         header=header)
+                         header=header, mapq=mapq)
     return b"".join(chunks)
 
 

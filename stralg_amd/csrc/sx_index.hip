@@ -489,6 +489,7 @@ int sx_index_map_reads_ex(sx_ctx *ctx, const sx_index *idx, const uint8_t *fastq
     SX_TRY(device_check(ctx, idx));
     if (edits < 0 || edits > SX_APPROX_MAX_EDITS) return sx_fail_msg(ctx, SX_E_ARG, "read mapping: edits must be in [0, 8]");
     if (flags & ~sx_map_known_flags) return sx_fail_msg(ctx, SX_E_ARG, "read mapping: unknown flags");
+    SX_TRY(sx_map_mapq_check(ctx, flags));
     if (fastq_len > 0xFFFFFFFEull) return sx_fail_msg(ctx, SX_E_ARG, "read mapping: malformed FASTQ image (see sx_fastq_index)");
     SX_TRY(sx_map_tags_check(ctx, idx, flags)); // (before the reads go up)
     SX_CHECK(hipSetDevice(ctx->device));

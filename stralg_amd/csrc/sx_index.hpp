@@ -71,7 +71,7 @@ static inline bool sx_map_record_check(const sx_map_record &R, uint32_t min_sigm
 }
 
 // the bits of a mapping call's flags word that mean something (sx_map_reads_stream_ex, sx_index_map_reads_ex, sx_map_reads_limit)
-constexpr uint32_t sx_map_known_flags = SX_MAP_BOTH_STRANDS | SX_MAP_BEST_STRATUM | SX_MAP_NO_INDELS | SX_MAP_TAGS | SX_MAP_UNMAPPED | SX_MAP_HEADER;
+constexpr uint32_t sx_map_known_flags = SX_MAP_BOTH_STRANDS | SX_MAP_BEST_STRATUM | SX_MAP_NO_INDELS | SX_MAP_TAGS | SX_MAP_UNMAPPED | SX_MAP_HEADER | SX_MAP_MAPQ;
 // the search flags (SX_SEARCH_*) that a mapping call's flags word asks of its searches
 static inline uint32_t sx_map_search_flags(uint32_t flags) { return (flags & SX_MAP_NO_INDELS) ? (uint32_t)SX_SEARCH_NO_INDELS : 0u; }
 
@@ -88,6 +88,8 @@ int sx_map_pairs_core(sx_ctx *ctx, const sx_index *idx, const sx_fastq_dev &read
 int sx_fastq_mates_dev(sx_ctx *ctx, const sx_fastq_dev *in1, const sx_fastq_dev *in2, sx_fastq_dev *out);
 // sx_map.hip: SX_MAP_TAGS reads every record's string; SX_E_ARG with a message where the flag is set and a record has none
 int sx_map_tags_check(sx_ctx *ctx, const sx_index *idx, uint32_t flags);
+// sx_map.hip: SX_MAP_MAPQ needs SX_MAP_BEST_STRATUM; SX_E_ARG with a message where it stands alone
+int sx_map_mapq_check(sx_ctx *ctx, uint32_t flags);
 // sx_approx.hip: sx_bwt_approx_search_dev_ex over the tables of a record, full, compact or packed (search_flags: SX_SEARCH_*)
 int sx_approx_search_record(sx_ctx *ctx, const sx_index_rec &R, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t count, int max_edits,
                             uint64_t *d_hit_offsets, sx_approx_hit *d_hits, uint64_t hit_capacity, uint64_t *total_hits_out, uint32_t search_flags);

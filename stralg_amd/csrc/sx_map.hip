@@ -4,6 +4,7 @@
 // record, hit) order (on capacity: the hits' room grows or the batch is halved, and it runs again; sx_map_plan.hpp has
 // the arithmetic), then its SAM text (sx_sam.hip), window after window, to the sink.  Paired reads (sx_map_pairs_core, DESIGN.md
 // section 21) go through the same loop in batches of whole pairs; their text is that of the join's line descriptors (sx_pairs.hip).
+// With SX_MAP_MAPQ a best-stratum batch's merged hits go through the quality pass before their text.
 #include "sx_common.hpp"
 #include "sx_device.hpp"
 #include "sx_scan.hpp"
@@ -101,6 +102,83 @@ __global__ __launch_bounds__(kBlock) void sam_merge_kernel(const uint4 *src, uin
     dst[2 * at + 1] = src[2 * j + 1];
 }
 
+// ---- MAPQ and secondary lines (SX_MAP_MAPQ) -------------------------------------------------------
+// The quality pass over a best-stratum batch's merged hits (its groups' hits are consecutive there: vbase).  No lane walks
+// over a group and there are no atomics: a group's line count is a difference of the scanned row counts.
+// rows[h] <- R - L of merged hit h (a placeholder: 0), to be scanned
+__global__ __launch_bounds__(kBlock) void mapq_rows_kernel(const uint4 *hits, uint64_t n_hits, uint64_t *rows)
+{
+    const uint64_t h = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (h >= n_hits) return;
+    const uint4 h0 = hits[2 * h];
+    rows[h] = h0.z > h0.y ? h0.z - h0.y : 0u;
+}
+
+// ext[g] <- 1 where the first hit of group g (gslots consecutive entries of vbase) has more than one row: that hit is split
+// into its first row, the group's primary line, and the rest; to be scanned
+__global__ __launch_bounds__(kBlock) void mapq_split_count_kernel(const uint4 *hits, uint64_t n_hits, const uint64_t *vbase, uint32_t groups,
+                                                                  uint32_t gslots, uint64_t *ext)
+{
+    const uint64_t g = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (g >= groups) return;
+    const uint64_t first = vbase[g * gslots], end = vbase[(g + 1) * gslots];
+    uint64_t e = 0;
+    if (first < end && first < n_hits) {
+        const uint4 h0 = hits[2 * first];
+        e = h0.z > h0.y && h0.z - h0.y > 1u ? 1u : 0u;
+    }
+    ext[g] = e;
+}
+
+// the MAPQ of a group of n lines: -10 log10(1 - 1/n) as TopHat and STAR round it
+__device__ __forceinline__ uint32_t mapq_of_lines(uint64_t n) { return n <= 1 ? 50u : n == 2 ? 3u : n <= 4 ? 1u : 0u; }
+
+// One lane a merged hit h: its group from its query, the group's lines n from the scanned rows at the group's slot range, and
+// the hit goes to dst behind the split entries of the groups in front (ext, scanned) -- a group's first hit as its first
+// row (primary) and, where it has more, the rest; every other entry is secondary (bit 8 of its quality word)
+__global__ __launch_bounds__(kBlock) void mapq_split_kernel(const uint4 *hits, uint64_t n_hits, const uint64_t *rows, const uint64_t *vbase,
+                                                            const uint64_t *ext, uint32_t groups, uint32_t gslots, uint4 *dst, uint16_t *quality,
+                                                            uint64_t n_dst, uint32_t *err)
+{
+    const uint64_t h = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (h >= n_hits) return;
+    uint4 h0 = hits[2 * h];
+    const uint4 h1 = hits[2 * h + 1];
+    const uint32_t g = h0.x / gslots;
+    if (g >= groups) {
+        atomicOr(err, 2u);
+        return;
+    }
+    const uint64_t first = vbase[(uint64_t)g * gslots], end = vbase[((uint64_t)g + 1) * gslots];
+    const uint64_t x = ext[g], split = ext[g + 1] - x;
+    if (h < first || h >= end || end > n_hits || split > 1) {
+        atomicOr(err, 2u);
+        return;
+    }
+    const uint32_t q = mapq_of_lines(rows[end] - rows[first]);
+    uint64_t at = h + x + (h > first ? split : 0u);
+    if (at + (h == first ? split : 0u) >= n_dst) {
+        atomicOr(err, 2u);
+        return;
+    }
+    if (h == first && split) {
+        uint4 p = h0;
+        p.z = h0.y + 1u;
+        dst[2 * at] = p;
+        dst[2 * at + 1] = h1;
+        quality[at] = (uint16_t)q;
+        h0.y += 1u;
+        ++at;
+        dst[2 * at] = h0;
+        dst[2 * at + 1] = h1;
+        quality[at] = (uint16_t)(q | 0x100u);
+        return;
+    }
+    dst[2 * at] = h0;
+    dst[2 * at + 1] = h1;
+    quality[at] = (uint16_t)(h == first ? q : q | 0x100u);
+}
+
 // ---- the pieces of the loop ---------------------------------------------------------------------------------------------
 template <class T> static int upload(sx_ctx *ctx, sx_dev_scope &B, T **d, const T *h, size_t count)
 {
@@ -113,6 +191,7 @@ template <class T> static int upload(sx_ctx *ctx, sx_dev_scope &B, T **d, const 
 static int map_check(sx_ctx *ctx, uint64_t n_reads, uint64_t n_records, uint32_t flags, bool records_ok)
 {
     if (flags & ~sx_map_known_flags) return sx_fail_msg(ctx, SX_E_ARG, "read mapping: unknown flags");
+    SX_TRY(sx_map_mapq_check(ctx, flags));
     if (sx_map_reads_limit(n_reads, n_records, flags) != 0)
         return sx_fail_msg(ctx, SX_E_ARG, "read mapping: reads x records (twice that for both strands) must stay below 2^32");
     if (!records_ok) return sx_fail_msg(ctx, SX_E_ARG, "read mapping: a record lacks its name, suffix array, tables or remap table");
@@ -161,6 +240,7 @@ struct MapReads {
     // 0, or (SX_MAP_UNMAPPED) the reads of a group that gets a FLAG 4 line where it has none: 1, or 2
     // for the strands of a read
     uint32_t unmapped = 0;
+    bool mapq = false; // MAPQ and secondary lines from the best stratum (SX_MAP_MAPQ; group != 0)
 };
 
 struct MapBufs { // what a mapping call holds on the device beside the hits' room
@@ -175,6 +255,11 @@ struct MapBufs { // what a mapping call holds on the device beside the hits' roo
     uint64_t merged_cap = 0, stride = 0; // stride: entries of a record's hit offsets in d_ho
     size_t window = 0;
     std::vector<uint64_t> seg; // (the plain batch) where record r's hits start in the room; last, how many there are
+    // SX_MAP_MAPQ: the merged hits with every group's first hit split, a quality word each; a split count a group
+    bool mapq = false;
+    sx_approx_hit *d_split = nullptr;
+    uint16_t *d_quality = nullptr;
+    uint64_t *d_ext = nullptr;
     sx_dev_scope own;
 };
 
@@ -225,10 +310,15 @@ static int merged_room(sx_ctx *ctx, MapBufs &M, const HitRoom &room, uint64_t us
 {
     if (used > M.merged_cap) {
         if (M.d_merged) M.own.drop(M.d_merged), M.own.drop(M.d_byte_off), M.own.drop(M.d_pos_off);
-        M.d_pos_off = nullptr;
+        if (M.d_split) M.own.drop(M.d_split), M.own.drop(M.d_quality);
+        M.d_pos_off = nullptr, M.d_split = nullptr, M.d_quality = nullptr;
         M.merged_cap = used > room.cap ? used : room.cap;
         SX_TRY(M.own.take(ctx, &M.d_merged, (size_t)M.merged_cap));
         SX_TRY(M.own.take(ctx, &M.d_byte_off, (size_t)M.merged_cap + 1));
+        if (M.mapq) {
+            SX_TRY(M.own.take(ctx, &M.d_split, (size_t)M.merged_cap));
+            SX_TRY(M.own.take(ctx, &M.d_quality, (size_t)M.merged_cap));
+        }
     }
     return 0;
 }
@@ -291,12 +381,39 @@ static int best_batch(sx_ctx *ctx, const sx_index *idx, const MapReads &R, MapBu
     B.d_raw = room.d_raw, B.raw_cap = room.cap, B.go_on_counting = false;
     SX_TRY(sx_best_rounds(ctx, S, B, hits_out));
     if (*hits_out == 0 && !R.unmapped) return 0;
+    const uint64_t split = R.mapq ? batch / R.group : 0; // (SX_MAP_MAPQ: a group's first hit may become two entries)
     if (!R.unmapped) {
-        SX_TRY(merged_room(ctx, M, room, *hits_out));
+        SX_TRY(merged_room(ctx, M, room, *hits_out + split));
         return sx_best_place(ctx, S, B, *hits_out, M.d_vbase, M.d_merged);
     }
-    SX_TRY(merged_room(ctx, M, room, *hits_out + batch / R.group)); // (a placeholder a group at the most)
+    SX_TRY(merged_room(ctx, M, room, *hits_out + batch / R.group + split)); // (a placeholder a group at the most)
     return sx_best_place(ctx, S, B, *hits_out, M.d_vbase, M.d_merged, true, hits_out);
+}
+
+// The quality pass (SX_MAP_MAPQ) over the `hits` merged entries of a best-stratum batch of `batch` reads in
+// groups of `gsize`: M.d_split <- the entries with every group's first hit split where it has more than one row, M.d_quality
+// <- a quality word an entry, *split_out <- how many there are (at most one more a group; merged_room has seen to the room)
+static int quality_pass(sx_ctx *ctx, MapBufs &M, uint64_t hits, uint32_t batch, uint32_t gsize, uint32_t n_records, uint64_t *split_out)
+{
+    const uint32_t groups = batch / gsize, gslots = gsize * n_records;
+    const uint4 *src = (const uint4 *)M.d_merged;
+    uint64_t *d_rows = M.d_byte_off; // (the layout's array, which the layout fills after this pass: hits + 1 entries here)
+    sx_launch(ctx, SX_KC_MAPQ, hits * 24, mapq_rows_kernel, dim3(sx_div_up(hits, kBlock)), dim3(kBlock), src, hits, d_rows);
+    SX_TRY(device_scan64_inplace(ctx, d_rows, hits, SX_KC_MAPQ));
+    sx_launch(ctx, SX_KC_MAPQ, (uint64_t)groups * 40, mapq_split_count_kernel, dim3(sx_div_up(groups, kBlock)), dim3(kBlock), src, hits,
+              (const uint64_t *)M.d_vbase, groups, gslots, M.d_ext);
+    SX_TRY(device_scan64_inplace(ctx, M.d_ext, groups, SX_KC_MAPQ));
+    uint32_t w[2] = {0, 0};
+    SX_TRY(sx_readback(ctx, (const uint32_t *)(M.d_ext + groups), 2, w));
+    const uint64_t n_split = hits + ((uint64_t)w[0] | ((uint64_t)w[1] << 32));
+    if (n_split > hits + groups || n_split > M.merged_cap) return sx_fail_msg(ctx, SX_E_INTERNAL, "read mapping: the hits of a batch do not add up");
+    sx_launch(ctx, SX_KC_MAPQ, hits * 106, mapq_split_kernel, dim3(sx_div_up(hits, kBlock)), dim3(kBlock), src, hits, (const uint64_t *)d_rows,
+              (const uint64_t *)M.d_vbase, (const uint64_t *)M.d_ext, groups, gslots, (uint4 *)M.d_split, M.d_quality, n_split, M.d_err);
+    uint32_t e = 0;
+    SX_TRY(sx_readback(ctx, M.d_err, 1, &e));
+    if (e) return sx_fail_msg(ctx, SX_E_INTERNAL, "read mapping: the hits of a batch do not add up");
+    *split_out = n_split;
+    return 0;
 }
 
 // The text of A's hits: its layout, then window after window through the two device windows and the context's staging
@@ -324,20 +441,21 @@ template <class Emit> static int emit_windows_of(sx_ctx *ctx, uint64_t total, co
     return sx_sync(ctx);
 }
 
-// (unmapped: the hits have placeholders, SX_MAP_UNMAPPED)
-static int emit_windows(sx_ctx *ctx, const SamTagArgs &A, const MapBufs &M, const sx_stage_events &E, sx_sink_fn sink, void *user, bool unmapped)
+// (unmapped: the hits have placeholders, SX_MAP_UNMAPPED; quality: a quality word a hit, SX_MAP_MAPQ, or null)
+static int emit_windows(sx_ctx *ctx, const SamTagArgs &A, const MapBufs &M, const sx_stage_events &E, sx_sink_fn sink, void *user, bool unmapped,
+                        const uint16_t *quality)
 {
     uint64_t total = 0;
-    SX_TRY(sam_layout(ctx, A, M.d_byte_off, &total, unmapped));
+    SX_TRY(sam_layout(ctx, A, M.d_byte_off, &total, unmapped, quality));
     return emit_windows_of(ctx, total, M, E, sink, user,
-                           [&](uint64_t lo, uint64_t hi, uint8_t *d_out) { return sam_emit(ctx, A, M.d_byte_off, lo, hi, d_out, unmapped); });
+                           [&](uint64_t lo, uint64_t hi, uint8_t *d_out) { return sam_emit(ctx, A, M.d_byte_off, lo, hi, d_out, unmapped, quality); });
 }
 
 // The text of a batch (`text`: its hits, reads and records) against an index with a sampled suffix array: its hits are taken
 // in runs of consecutive hits whose lines fit the cap (SX_FLAG_LOCATE_CHUNK_ROWS; a hit is never split: one with more lines
 // gets a buffer of its own length); a run is located, laid out and emitted through its windows before the next one starts
 static int emit_located(sx_ctx *ctx, const sx_index *idx, const SamTagArgs &text, MapBufs &M, const sx_stage_events &E, sx_sink_fn sink, void *user,
-                        bool unmapped)
+                        bool unmapped, const uint16_t *quality)
 {
     const LocRec *d_recs = (const LocRec *)idx->d_loc_list;
     const uint64_t n_hits = text.n_hits, cap = map_located_rows(ctx->locate_chunk_rows);
@@ -362,7 +480,7 @@ static int emit_located(sx_ctx *ctx, const sx_index *idx, const SamTagArgs &text
         SamTagArgs A = text;
         A.hits = text.hits + 2 * h_lo, A.n_hits = h_hi - h_lo;
         A.positions = M.d_positions, A.pos_off = M.d_pos_off + h_lo, A.pos_base = base;
-        SX_TRY(emit_windows(ctx, A, M, E, sink, user, unmapped));
+        SX_TRY(emit_windows(ctx, A, M, E, sink, user, unmapped, quality ? quality + h_lo : nullptr));
         base += rows;
         h_lo = h_hi;
     }
@@ -481,6 +599,8 @@ static int map_reads_loop(sx_ctx *ctx, const sx_index *idx, const MapReads &R, i
     T.room_first = T.room_final = room.cap, T.batch_first = T.batch_final = batch_max;
     sx_best_state S;
     if (R.group) SX_TRY(S.init(ctx, batch_max, fq.seq_bytes, n_records, edits, true));
+    M.mapq = R.mapq && R.group;
+    if (M.mapq) SX_TRY(M.own.take(ctx, &M.d_ext, (size_t)batch_max / R.group + 1));
     SamTagArgs A = {}; // the batch whose text is emitted: what is the same for every batch here
     A.sa_list = idx->d_sa_list, A.sa_len_list = idx->d_sa_lens;
     A.names = fq.d_names, A.seqs = fq.d_seqs, A.quals = fq.d_quals;
@@ -524,7 +644,14 @@ static int map_reads_loop(sx_ctx *ctx, const sx_index *idx, const MapReads &R, i
                 SX_TRY(prc);
             } else {
                 const bool unm = R.unmapped != 0;
-                SX_TRY(idx->sa_log2 ? emit_located(ctx, idx, A, M, E, sink, user, unm) : emit_windows(ctx, A, M, E, sink, user, unm));
+                const uint16_t *quality = nullptr;
+                if (M.mapq) { // (the text is that of the split entries and their quality words)
+                    uint64_t n_split = 0;
+                    SX_TRY(quality_pass(ctx, M, hits, batch, R.group, n_records, &n_split));
+                    A.hits = (const uint4 *)M.d_split, A.n_hits = n_split;
+                    quality = M.d_quality;
+                }
+                SX_TRY(idx->sa_log2 ? emit_located(ctx, idx, A, M, E, sink, user, unm, quality) : emit_windows(ctx, A, M, E, sink, user, unm, quality));
             }
         }
         ++T.batches;
@@ -581,6 +708,13 @@ static int index_header(sx_ctx *ctx, const sx_index *idx, sx_sink_fn sink, void 
         [&](uint32_t r) { return (unsigned long long)(idx->recs[r].N - 1); }, sink, user);
 }
 
+int sx_map_mapq_check(sx_ctx *ctx, uint32_t flags)
+{
+    if ((flags & SX_MAP_MAPQ) && !(flags & SX_MAP_BEST_STRATUM))
+        return sx_fail_msg(ctx, SX_E_ARG, "read mapping: SX_MAP_MAPQ needs SX_MAP_BEST_STRATUM (a read's first line must be one of its best)");
+    return 0;
+}
+
 int sx_map_tags_check(sx_ctx *ctx, const sx_index *idx, uint32_t flags)
 {
     if (!(flags & SX_MAP_TAGS)) return 0;
@@ -608,6 +742,7 @@ int sx_map_reads_core(sx_ctx *ctx, const sx_index *idx, const sx_fastq_dev &read
     if (!(flags & SX_MAP_BOTH_STRANDS)) {
         MapReads R = {&reads, h_seq_off, nullptr, best ? 1u : 0u, sflags, tags};
         R.unmapped = unmapped ? 1u : 0u;
+        R.mapq = (flags & SX_MAP_MAPQ) != 0;
         return map_reads_loop(ctx, idx, R, edits, sink, user);
     }
     SX_CHECK(hipSetDevice(ctx->device));
@@ -618,6 +753,7 @@ int sx_map_reads_core(sx_ctx *ctx, const sx_index *idx, const sx_fastq_dev &read
     SX_TRY(sx_fastq_strands_dev(ctx, &reads, &both, d_flags)); // (syncs: the callers' uploads from pageable memory are done)
     MapReads R = {&both, nullptr, d_flags, best ? 2u : 0u, sflags, tags};
     R.unmapped = unmapped ? 2u : 0u;
+    R.mapq = (flags & SX_MAP_MAPQ) != 0;
     const int rc = map_reads_loop(ctx, idx, R, edits, sink, user);
     sx_fastq_dev_free(&both);
     return rc;
@@ -687,6 +823,7 @@ int sx_map_reads_stream_ex(sx_ctx *ctx, const sx_map_record *records, uint32_t n
     if (edits < 0 || edits > SX_APPROX_MAX_EDITS)
         return sx_fail_msg(ctx, SX_E_ARG, "read mapping: edits must be in [0, 8]");
     if (flags & ~sx_map_known_flags) return sx_fail_msg(ctx, SX_E_ARG, "read mapping: unknown flags");
+    SX_TRY(sx_map_mapq_check(ctx, flags));
     if (flags & SX_MAP_TAGS) // (the rule of sx_index_write for a record without its string)
         return sx_fail_msg(ctx, SX_E_ARG, "read mapping: NM and MD need every record's string, and these records are tables alone (map through an index)");
     sx_fastq fq;

@@ -21,6 +21,9 @@
 // Unmapped read groups (SX_MAP_UNMAPPED): a hit with an empty interval (R == L, which no search
 // gives) is the placeholder of a read group without a line and prints "<qname>\t4\t*\t0\t0\t*\t*\t0\t0\t<seq>\t<qual>\n"
 // -- in the kernels' kUnmapped forms alone, their fourth template parameter; the forms without it keep their code.
+// MAPQ and secondary lines (SX_MAP_MAPQ): a 16-bit quality word a hit gives the MAPQ printed where
+// the "0" behind POS stands and, by its bit 8, 256 on top of the FLAG of every line of the hit -- in the kernels' kMapq
+// forms alone, their fifth template parameter, which take the FLAG array (null: 0) and the placeholders at run time.
 // The output does not fit the device in general: the caller fills a fixed buffer window after window; lines may start
 // in one window (or slice) and end in the next, the concatenation of the windows is the file.
 #include "sx_common.hpp"
@@ -52,6 +55,7 @@ struct HitInfo {
     uint4 gaps;
     uint32_t n_gaps;
     uint32_t rec, nm, md_len; // (kTags) the record's rank; NM and the bytes of MD once tags_render has run
+    uint32_t mapq;            // (kMapq) the MAPQ of the hit's lines
 };
 
 __device__ __forceinline__ uint32_t dec_digits(uint32_t v)
@@ -215,7 +219,10 @@ __device__ __forceinline__ uint32_t md_render(uint8_t *out, uint32_t cap, uint32
 // what the lines of hit h are made of; false: the hit does not fit the batch (its query, interval or offsets).
 // kUnmapped: a hit with R == L is the placeholder of a read group without a line, and has one line,
 // the FLAG 4 line of its read: I.pos == nullptr, I.cnt == 1 (no position, CIGAR or tags are read for it)
-template <bool kLocated, bool kFlags, bool kUnmapped = false> __device__ __forceinline__ bool hit_info(const SamArgs &A, uint64_t h, HitInfo &I)
+// kMapq: quality[h] gives the hit's MAPQ and, by bit 8, 256 on top of its FLAG; the FLAG array may
+// be null (FLAG 0) and a placeholder's quality word is not looked at
+template <bool kLocated, bool kFlags, bool kUnmapped = false, bool kMapq = false>
+__device__ __forceinline__ bool hit_info(const SamArgs &A, uint64_t h, HitInfo &I, const uint16_t *quality = nullptr)
 {
     const uint4 h0 = A.hits[2 * h];
     I.gaps = A.hits[2 * h + 1];
@@ -253,7 +260,13 @@ template <bool kLocated, bool kFlags, bool kUnmapped = false> __device__ __force
     }
     I.pos = kLocated ? A.positions + (A.pos_off[h] - A.pos_base) : sa + L;
     I.cnt = R - L;
-    if (kFlags) I.flag = A.flags[read];
+    if (kMapq) {
+        const uint32_t w = quality[h];
+        I.flag = (A.flags ? A.flags[read] : 0u) | (w & 0x100u);
+        I.mapq = w & 0xFFu;
+    } else if (kFlags) {
+        I.flag = A.flags[read];
+    }
     return true;
 }
 
@@ -275,9 +288,11 @@ __device__ __forceinline__ bool tags_render(const SamTagArgs &A, HitInfo &I, uin
 
 // "\t0\t" + "\t" + "\t0\t" + "\t*\t0\t0\t" + "\t" + "\n": the 16 bytes of a line beside its fields and digits; a FLAG
 // takes its digits in place of the first "0" (without kFlags I.flag is the constant 0: one digit, 16 bytes)
-template <bool kTags = false> __device__ __forceinline__ uint32_t fixed_bytes(const HitInfo &I)
+template <bool kTags = false, bool kMapq = false> __device__ __forceinline__ uint32_t fixed_bytes(const HitInfo &I)
 {
     // (kTags) "\tNM:i:" + "\tMD:Z:" and the one digit of NM <= 8: 13 bytes beside the bytes of MD
+    // (kMapq) the MAPQ takes its digits in place of the "0" behind POS
+    if (kMapq) return I.name_l + I.rn_l + I.cig_len + I.seq_l + I.qual_l + 14u + dec_digits(I.flag) + dec_digits(I.mapq) + (kTags ? 13u + I.md_len : 0u);
     return I.name_l + I.rn_l + I.cig_len + I.seq_l + I.qual_l + 15u + dec_digits(I.flag) + (kTags ? 13u + I.md_len : 0u);
 }
 
@@ -287,14 +302,19 @@ __device__ __forceinline__ uint32_t unmapped_bytes(const HitInfo &I) { return I.
 
 // ---- layout: bytes per hit ---------------------------------------------------------------------
 // what a kernel takes of a batch: the tagged forms alone carry the texts and the letters
-template <bool kTags> struct KernelArgs { typedef SamArgs type; };
-template <> struct KernelArgs<true> { typedef SamTagArgs type; };
+// and the kMapq forms, with tags or without, the quality words as well
+template <bool kTags, bool kMapq = false> struct KernelArgs { typedef SamArgs type; };
+template <> struct KernelArgs<true, false> { typedef SamTagArgs type; };
+template <bool kTags> struct KernelArgs<kTags, true> { typedef SamMapqArgs type; };
+__device__ __forceinline__ const uint16_t *quality_of(const SamArgs &) { return nullptr; }
+__device__ __forceinline__ const uint16_t *quality_of(const SamMapqArgs &A) { return A.quality; }
 // (the forms without tags never get there)
 __device__ __forceinline__ bool tags_render(const SamArgs &, HitInfo &, uint8_t *) { return true; }
 
 // kUnmapped: the forms of SX_MAP_UNMAPPED (placeholders print a FLAG 4 line); with it false the code is the one from before
-template <bool kLocated, bool kFlags, bool kTags, bool kUnmapped>
-__global__ __launch_bounds__(kBlock) void sam_size_kernel(typename KernelArgs<kTags>::type A, uint64_t *len_out, uint32_t *err)
+// kMapq: the forms of SX_MAP_MAPQ (kFlags and kUnmapped set: both are looked at at run time); the same holds of it
+template <bool kLocated, bool kFlags, bool kTags, bool kUnmapped, bool kMapq = false>
+__global__ __launch_bounds__(kBlock) void sam_size_kernel(typename KernelArgs<kTags, kMapq>::type A, uint64_t *len_out, uint32_t *err)
 {
     __shared__ uint64_t red[kWavesPerBlock];
     __shared__ uint32_t long_cnt[kBlock];
@@ -305,7 +325,7 @@ __global__ __launch_bounds__(kBlock) void sam_size_kernel(typename KernelArgs<kT
     long_cnt[t] = 0;
     if (h < A.n_hits) {
         HitInfo I = {};
-        if (!hit_info<kLocated, kFlags, kUnmapped>(A, h, I)) {
+        if (!hit_info<kLocated, kFlags, kUnmapped, kMapq>(A, h, I, quality_of(A))) {
             atomicOr(err, 1u);
         } else if (kUnmapped && !I.pos) {
             bytes = unmapped_bytes(I);
@@ -315,7 +335,7 @@ __global__ __launch_bounds__(kBlock) void sam_size_kernel(typename KernelArgs<kT
                 atomicOr(err, 1u);
                 I.cnt = 0;
             }
-            bytes = (uint64_t)I.cnt * fixed_bytes<kTags>(I);
+            bytes = (uint64_t)I.cnt * fixed_bytes<kTags, kMapq>(I);
             if (I.cnt <= kInlineMatches) {
                 for (uint32_t i = 0; i < I.cnt; ++i) bytes += dec_digits(I.pos[i] + 1u);
             } else {
@@ -357,8 +377,9 @@ __device__ __forceinline__ void put_bytes(uint8_t *obuf, int64_t &off, int64_t s
 
 // kUnmapped: as in sam_size_kernel; a placeholder is kept as a hit of 1 line with HitLds::pos == nullptr and HitLds::fixed
 // the line's whole length
-template <bool kLocated, bool kFlags, bool kTags, bool kUnmapped>
-__global__ __launch_bounds__(kBlock) void sam_emit_kernel(typename KernelArgs<kTags>::type A, const uint64_t *byte_off, uint64_t lo, uint64_t hi, uint8_t *out)
+// kMapq: as in sam_size_kernel; the MAPQ of the step's hits lies beside their FLAGs
+template <bool kLocated, bool kFlags, bool kTags, bool kUnmapped, bool kMapq = false>
+__global__ __launch_bounds__(kBlock) void sam_emit_kernel(typename KernelArgs<kTags, kMapq>::type A, const uint64_t *byte_off, uint64_t lo, uint64_t hi, uint8_t *out)
 {
     __shared__ uint4 obuf4[kSlice / 16];
     __shared__ uint8_t cig[kBlock * kCigarMax];
@@ -369,6 +390,7 @@ __global__ __launch_bounds__(kBlock) void sam_emit_kernel(typename KernelArgs<kT
     __shared__ uint64_t nxt[2];
     __shared__ uint16_t hflag[kFlags ? kBlock : 1]; // (kFlags) the FLAG of the step's hits
     __shared__ uint8_t md[kTags ? kBlock * kMdMax : 1]; // (kTags) MD:Z of the step's hits, rendered once a hit like the CIGAR
+    __shared__ uint8_t hmapq[kMapq ? kBlock : 1];       // (kMapq) the MAPQ of the step's hits
     uint8_t *obuf = (uint8_t *)obuf4;
     const uint32_t t = threadIdx.x;
     const uint64_t s_lo = lo + (uint64_t)blockIdx.x * kSlice;
@@ -390,12 +412,12 @@ __global__ __launch_bounds__(kBlock) void sam_emit_kernel(typename KernelArgs<kT
     uint32_t i = 0;
     {   // the walk inside the hit: whole steps of 1024 lines that end at or before the slice's first byte are skipped
         HitInfo I = {};
-        if (hit_info<kLocated, kFlags, kUnmapped>(A, h, I)) { // (a placeholder has 1 line: no walk)
+        if (hit_info<kLocated, kFlags, kUnmapped, kMapq>(A, h, I, quality_of(A))) { // (a placeholder has 1 line: no walk)
             I.cig_len = cigar_render(nullptr, kCigarMax, I.m, I.gaps, I.n_gaps);
             // (the tags' length is needed by the steps below alone: a hit of up to 1024 lines, which is nearly every hit,
             //  is not walked here, only by its lane in the loop further down)
             if (kTags && I.cnt > kWalk * kBlock && !tags_render(A, I, nullptr)) I.cnt = 0;
-            const uint32_t fixed = fixed_bytes<kTags>(I);
+            const uint32_t fixed = fixed_bytes<kTags, kMapq>(I);
             while (I.cnt - i > kWalk * kBlock) {
                 uint64_t b = 0;
 #pragma unroll
@@ -413,7 +435,7 @@ __global__ __launch_bounds__(kBlock) void sam_emit_kernel(typename KernelArgs<kT
         // hits h .. h + 255: how many lines each has left, the first 256 lines' hits, their CIGARs
         HitInfo I = {};
         uint32_t c = 0;
-        if (h + t < A.n_hits && hit_info<kLocated, kFlags, kUnmapped>(A, h + t, I)) c = I.cnt - (t == 0 ? (i < I.cnt ? i : I.cnt) : 0u);
+        if (h + t < A.n_hits && hit_info<kLocated, kFlags, kUnmapped, kMapq>(A, h + t, I, quality_of(A))) c = I.cnt - (t == 0 ? (i < I.cnt ? i : I.cnt) : 0u);
         const uint32_t cc = c < (uint32_t)kBlock ? c : (uint32_t)kBlock;
         uint32_t total;
         const uint32_t ex = block_exclusive_scan<OpAdd>(cc, red32, total);
@@ -436,10 +458,11 @@ __global__ __launch_bounds__(kBlock) void sam_emit_kernel(typename KernelArgs<kT
                 (void)tags_render(A, I, md + t * kMdMax); // (a hit that the layout refused never gets here)
                 H.tags = I.md_len | (I.nm << 8);
             }
-            H.fixed = fixed_bytes<kTags>(I);
+            H.fixed = fixed_bytes<kTags, kMapq>(I);
             H.name_b = I.name_b, H.name_l = I.name_l, H.seq_b = I.seq_b, H.seq_l = I.seq_l;
             H.qual_b = I.qual_b, H.qual_l = I.qual_l, H.rn_b = I.rn_b, H.rn_l = I.rn_l;
             if (kFlags) hflag[t] = (uint16_t)I.flag;
+            if (kMapq) hmapq[t] = (uint8_t)I.mapq;
         }
         __syncthreads();
         const uint32_t nlines = total < (uint32_t)kBlock ? total : (uint32_t)kBlock;
@@ -497,7 +520,15 @@ __global__ __launch_bounds__(kBlock) void sam_emit_kernel(typename KernelArgs<kT
             put_bytes(obuf, off, slice_len, A.rnames + H.rn_b, H.rn_l);
             put_bytes(obuf, off, slice_len, (const uint8_t *)"\t", 1);
             put_bytes(obuf, off, slice_len, dig, nd);
-            put_bytes(obuf, off, slice_len, (const uint8_t *)"\t0\t", 3);
+            if (kMapq) {
+                uint8_t qdig[3];
+                const uint32_t nq = put_dec(qdig, 0, 3, hmapq[u]);
+                put_bytes(obuf, off, slice_len, (const uint8_t *)"\t", 1);
+                put_bytes(obuf, off, slice_len, qdig, nq);
+                put_bytes(obuf, off, slice_len, (const uint8_t *)"\t", 1);
+            } else {
+                put_bytes(obuf, off, slice_len, (const uint8_t *)"\t0\t", 3);
+            }
             put_bytes(obuf, off, slice_len, cig + u * kCigarMax, H.cig_len);
             put_bytes(obuf, off, slice_len, (const uint8_t *)"\t*\t0\t0\t", 7);
             put_bytes(obuf, off, slice_len, A.seqs + H.seq_b, H.seq_l);
@@ -732,13 +763,29 @@ static int sam_args_tags(sx_ctx *ctx, const sx_sam_batch_tags *b, SamTagArgs &A)
 #define SX_SAM_KERNEL_T(kernel, A, T, U) \
     ((A).positions ? ((A).flags ? kernel<true, true, T, U> : kernel<true, false, T, U>) : ((A).flags ? kernel<false, true, T, U> : kernel<false, false, T, U>))
 
-int sam_layout(sx_ctx *ctx, const SamTagArgs &A, uint64_t *d_byte_off, uint64_t *total_out, bool unmapped)
+// the kMapq forms: positions located beforehand or not, tags or not; the FLAG array and the placeholders are run-time matters
+#define SX_SAM_KERNEL_Q(kernel, Q) \
+    ((Q).positions ? ((Q).text_list ? kernel<true, true, true, true, true> : kernel<true, true, false, true, true>) \
+                   : ((Q).text_list ? kernel<false, true, true, true, true> : kernel<false, true, false, true, true>))
+
+static SamMapqArgs mapq_args_of(const SamTagArgs &A, const uint16_t *quality)
+{
+    SamMapqArgs Q;
+    static_cast<SamTagArgs &>(Q) = A;
+    Q.quality = quality;
+    return Q;
+}
+
+int sam_layout(sx_ctx *ctx, const SamTagArgs &A, uint64_t *d_byte_off, uint64_t *total_out, bool unmapped, const uint16_t *quality)
 {
     *total_out = 0;
     SX_TRY(sx_slab_ensure(ctx, SX_SLAB_SORT, 4096));
     uint32_t *d_err = (uint32_t *)ctx->slab[SX_SLAB_SORT].p;
     SX_CHECK(hipMemsetAsync(d_err, 0, 16, ctx->stream));
-    if (A.n_hits && unmapped && A.text_list) // (SX_MAP_UNMAPPED: the same passes in kernels of their own)
+    if (A.n_hits && quality) // (SX_MAP_MAPQ: kernels of their own again; 2 bytes more a hit)
+        sx_launch(ctx, SX_KC_SAM, A.n_hits * 42, SX_SAM_KERNEL_Q(sam_size_kernel, A), dim3(sx_div_up(A.n_hits, kBlock)), dim3(kBlock),
+                  mapq_args_of(A, quality), d_byte_off, d_err);
+    else if (A.n_hits && unmapped && A.text_list) // (SX_MAP_UNMAPPED: the same passes in kernels of their own)
         sx_launch(ctx, SX_KC_SAM, A.n_hits * 40, SX_SAM_KERNEL_T(sam_size_kernel, A, true, true), dim3(sx_div_up(A.n_hits, kBlock)),
                   dim3(kBlock), A, d_byte_off, d_err);
     else if (A.n_hits && unmapped)
@@ -762,13 +809,16 @@ int sam_layout(sx_ctx *ctx, const SamTagArgs &A, uint64_t *d_byte_off, uint64_t 
 }
 
 // (asynchronous: the caller syncs)
-int sam_emit(sx_ctx *ctx, const SamTagArgs &A, const uint64_t *d_byte_off, uint64_t lo, uint64_t hi, uint8_t *d_out, bool unmapped)
+int sam_emit(sx_ctx *ctx, const SamTagArgs &A, const uint64_t *d_byte_off, uint64_t lo, uint64_t hi, uint8_t *d_out, bool unmapped, const uint16_t *quality)
 {
     if (hi <= lo) return 0;
     const uint64_t slices = (hi - lo + kSlice - 1) / kSlice;
     if (slices > 0x7FFFFFFFull) return sx_fail_msg(ctx, SX_E_ARG, "SAM text: window too long");
     // per line: its bytes out, 4 bytes of position in; the read's fields once a slice
-    if (unmapped && A.text_list)
+    if (quality)
+        sx_launch(ctx, SX_KC_SAM, hi - lo, SX_SAM_KERNEL_Q(sam_emit_kernel, A), dim3((uint32_t)slices), dim3(kBlock), mapq_args_of(A, quality),
+                  d_byte_off, lo, hi, d_out);
+    else if (unmapped && A.text_list)
         sx_launch(ctx, SX_KC_SAM, hi - lo, SX_SAM_KERNEL_T(sam_emit_kernel, A, true, true), dim3((uint32_t)slices), dim3(kBlock), A,
                   d_byte_off, lo, hi, d_out);
     else if (unmapped)
@@ -862,6 +912,36 @@ int sx_sam_emit_dev_unmapped(sx_ctx *ctx, const sx_sam_batch_tags *batch, const 
         return sx_fail_msg(ctx, SX_E_ARG, "SAM text: a window inside [0, total) and a 16-byte aligned buffer are needed");
     SX_CHECK(hipSetDevice(ctx->device));
     SX_TRY(sam_emit(ctx, A, d_byte_offsets, byte_lo, byte_hi, d_out, true));
+    return sx_sync(ctx);
+}
+
+// The emitter of SX_MAP_MAPQ over hits that the caller made up: the batch of sx_sam_layout_dev_unmapped and a quality word a hit
+static int sam_args_mapq(sx_ctx *ctx, const sx_sam_batch_mapq *b, SamTagArgs &A)
+{
+    if (!b) return SX_E_ARG;
+    SX_TRY(sam_args_unmapped(ctx, &b->tags, A));
+    if (!b->d_hit_quality || ((uintptr_t)b->d_hit_quality & 1)) return sx_fail_msg(ctx, SX_E_ARG, "SAM text: MAPQ needs a 16-bit quality word a hit");
+    return 0;
+}
+
+int sx_sam_layout_dev_mapq(sx_ctx *ctx, const sx_sam_batch_mapq *batch, uint64_t *d_byte_offsets, uint64_t *total_bytes_out)
+{
+    SamTagArgs A;
+    SX_TRY(sam_args_mapq(ctx, batch, A));
+    if (!d_byte_offsets || !total_bytes_out) return SX_E_ARG;
+    SX_CHECK(hipSetDevice(ctx->device));
+    return sam_layout(ctx, A, d_byte_offsets, total_bytes_out, true, batch->d_hit_quality);
+}
+
+int sx_sam_emit_dev_mapq(sx_ctx *ctx, const sx_sam_batch_mapq *batch, const uint64_t *d_byte_offsets, uint64_t total_bytes, uint64_t byte_lo,
+                         uint64_t byte_hi, uint8_t *d_out)
+{
+    SamTagArgs A;
+    SX_TRY(sam_args_mapq(ctx, batch, A));
+    if (!d_byte_offsets || byte_lo > byte_hi || byte_hi > total_bytes || (A.n_hits == 0 && byte_hi > byte_lo) || (byte_hi > byte_lo && (!d_out || ((uintptr_t)d_out & 15))))
+        return sx_fail_msg(ctx, SX_E_ARG, "SAM text: a window inside [0, total) and a 16-byte aligned buffer are needed");
+    SX_CHECK(hipSetDevice(ctx->device));
+    SX_TRY(sam_emit(ctx, A, d_byte_offsets, byte_lo, byte_hi, d_out, true, batch->d_hit_quality));
     return sx_sync(ctx);
 }
 

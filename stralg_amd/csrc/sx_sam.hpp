@@ -35,12 +35,21 @@ struct SamTagArgs : SamArgs {
     const uint8_t *letters = nullptr;
 };
 
+// The same with a 16-bit quality word a hit (the kernels' kMapq form): its low 8 bits are the MAPQ of
+// every line of the hit, its bit 8 puts 256 on top of their FLAG.  The other kernels take the parts above alone.
+struct SamMapqArgs : SamTagArgs {
+    const uint16_t *quality = nullptr;
+};
+
 // d_byte_off[h] (n_hits + 1 entries) <- the first output byte of hit h's lines, the last entry and *total_out <- the
 // text's length.  unmapped (SX_MAP_UNMAPPED): a hit with R == L is a read group's placeholder and
 // prints the FLAG 4 line of its read (kernels of their own; without it a hit with R == L prints nothing)
-int sam_layout(sx_ctx *ctx, const SamTagArgs &A, uint64_t *d_byte_off, uint64_t *total_out, bool unmapped = false);
+// quality (SX_MAP_MAPQ): a quality word a hit, or null; with it the kernels are the kMapq forms, which
+// print placeholders whatever `unmapped` says
+int sam_layout(sx_ctx *ctx, const SamTagArgs &A, uint64_t *d_byte_off, uint64_t *total_out, bool unmapped = false, const uint16_t *quality = nullptr);
 // bytes [lo, hi) of the text to d_out (asynchronous: the caller syncs)
-int sam_emit(sx_ctx *ctx, const SamTagArgs &A, const uint64_t *d_byte_off, uint64_t lo, uint64_t hi, uint8_t *d_out, bool unmapped = false);
+int sam_emit(sx_ctx *ctx, const SamTagArgs &A, const uint64_t *d_byte_off, uint64_t lo, uint64_t hi, uint8_t *d_out, bool unmapped = false,
+             const uint16_t *quality = nullptr);
 
 // Lines with a mate: the text of n_lines line descriptors over A's hits, reads and records (A's suffix
 // arrays, positions and flags are not read: a descriptor has its POS and its FLAG).  d_byte_off[j] (n_lines + 1 entries) <-

@@ -26,9 +26,14 @@ its text against the plain emit's, and the wall time of the two both_strands cal
 section 22): per k the reads without a hit and the bytes their lines add, layout and emit over the same hits with a
 placeholder a read without one (sx_sam_layout_dev_unmapped / sx_sam_emit_dev_unmapped) and the cost per added byte against
 the plain passes' rate, and the streamed call with and without unmapped=True, its kernel ms of the search and of the sam
-class each in a run of its own (kept in profiles/unmapped_bench_2p28.json).
+class each in a run of its own (kept in profiles/unmapped_bench_2p28.json).  --mapq adds MAPQ and secondary flags from the best
+stratum (SX_MAP_MAPQ): per k (and per no-indels entry) the best-stratum hits of the batch with every read's
+first hit split and a quality word a hit, made here as the mapper's quality pass makes them, layout and emit of their text
+through sx_sam_layout_dev_mapq / sx_sam_emit_dev_mapq beside the plain passes over the same hits, and the streamed call with
+best=True with and without mapq=True: wall, bytes, and the kernel ms of its mapq class (the quality pass: two scans and three
+kernels a batch) and of its sam class, each in a run of its own (kept in profiles/mapq_bench_2p28.json).
 
-    python tools/sam_bench.py [--log2n 28] [--reads 1000000] [--window-mib 1024] [--repeats 5] [--both-strands] [--best] [--no-indels] [--tags] [--pairs] [--unmapped]
+    python tools/sam_bench.py [--log2n 28] [--reads 1000000] [--window-mib 1024] [--repeats 5] [--both-strands] [--best] [--no-indels] [--tags] [--pairs] [--unmapped] [--mapq]
 """
 import argparse
 import ctypes as C
@@ -59,6 +64,7 @@ def main():
     ap.add_argument("--tags", action="store_true", help="also layout, emit and the index call with NM:i and MD:Z on every line")
     ap.add_argument("--pairs", action="store_true", help="also the paired call on the reads and their mates, indels=False without and with best=True")
     ap.add_argument("--unmapped", action="store_true", help="also layout, emit and the streamed call with a FLAG 4 line for every read without a hit")
+    ap.add_argument("--mapq", action="store_true", help="also layout, emit and the streamed best call with MAPQ and secondary flags")
     args = ap.parse_args()
     import torch
 
@@ -209,7 +215,72 @@ def main():
             entry["unmapped"] = unmapped_passes(total, d_hits, layout_ms, emit_ms, nbytes)
         del d_hits, d_boff
         torch.cuda.empty_cache()
+        if args.mapq:
+            entry["mapq"] = mapq_passes(k, indels)
         return entry
+
+    def mapq_passes(k, indels):
+        """the best-stratum hits of the batch (one record: they stand in (read, hit) order) as the mapper's quality pass leaves
+        them -- every read's first hit split where it has more than one row, a quality word an entry --, then layout and emit
+        of that text with the quality words and, over the same entries, without"""
+        d_stratum = torch.zeros(R, dtype=torch.uint8, device="cuda")
+        d_bho = torch.zeros(R + 1, dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        total = ctx.bwt_best_search_dev(d_c, d_o, d_ro, N, sigma, d_pat, d_off, R, k, d_stratum, d_bho, indels=indels)
+        d_hits = torch.zeros(max(total, 1) * 32, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        ctx.bwt_best_search_dev(d_c, d_o, d_ro, N, sigma, d_pat, d_off, R, k, d_stratum, d_bho, d_hits, total, indels=indels)
+        words = d_hits[:total * 32].view(torch.int32).reshape(-1, 8)
+        q = words[:, 0].to(torch.int64)
+        rows = (words[:, 2].to(torch.int64) & 0xFFFFFFFF) - (words[:, 1].to(torch.int64) & 0xFFFFFFFF)
+        cum = torch.cat([torch.zeros(1, dtype=torch.int64, device="cuda"), torch.cumsum(rows, 0)])
+        first, end = d_bho[:-1], d_bho[1:]
+        n_lines = cum[end] - cum[first]  # (a read's lines)
+        split = ((end > first) & (rows[first.clamp(max=max(total - 1, 0))] > 1)).to(torch.int64)
+        ext = torch.cumsum(split, 0) - split
+        n_all = total + int(split.sum().item())
+        h = torch.arange(total, device="cuda")
+        is_first = h == first[q]
+        at = h + ext[q] + (~is_first).to(torch.int64) * split[q]
+        d_all = torch.zeros(max(n_all, 1) * 8, dtype=torch.int32, device="cuda")
+        d_all.view(-1, 8)[at] = words
+        two = torch.nonzero(is_first & (split[q] == 1)).flatten()
+        d_all.view(-1, 8)[at[two] + 1] = words[two]
+        d_all.view(-1, 8)[at[two], 2] = words[two, 1] + 1  # (the primary: row L alone)
+        d_all.view(-1, 8)[at[two] + 1, 1] = words[two, 1] + 1
+        n = n_lines[q]
+        cls = torch.where(n <= 1, 50, torch.where(n == 2, 3, torch.where(n <= 4, 1, 0)))
+        quality = torch.zeros(max(n_all, 1), dtype=torch.int16, device="cuda")
+        quality[at] = (cls | (~is_first).to(torch.int64) * 256).to(torch.int16)
+        quality[at[two] + 1] = (cls[two] | 256).to(torch.int16)
+        groups = torch.bincount(torch.where(n_lines == 0, 4, torch.where(n_lines == 1, 0, torch.where(n_lines == 2, 1, torch.where(n_lines <= 4, 2, 3)))),
+                                minlength=5).cpu().tolist()
+        del words, q, rows, cum, at, two, n, cls, h, is_first
+        d_qoff = torch.zeros(n_all + 1, dtype=torch.int64, device="cuda")
+        batch = ctx.sam_batch(d_all, n_all, d_sa, N, d_names, d_name_off, d_seqs, d_off, d_quals, d_off, R, d_rname, d_rname_off, 1)
+        res = {"hits": int(total), "entries": int(n_all), "split": int(n_all - total), "lines": int(n_lines.sum().item()),
+               "reads_by_mapq_50_3_1_0": groups[:4], "reads_without_a_line": groups[4]}
+        for name, layout, emit in (("plain", lambda: ctx.sam_layout_dev(batch, d_qoff),
+                                    lambda nb, lo, hi: ctx.sam_emit_dev(batch, d_qoff, nb, lo, hi, d_win)),
+                                   ("mapq", lambda: ctx.sam_layout_dev_mapq(batch, quality, d_qoff),
+                                    lambda nb, lo, hi: ctx.sam_emit_dev_mapq(batch, quality, d_qoff, nb, lo, hi, d_win))):
+            layout()  # warm-up
+            l_runs = [profiled("sam", layout) for _ in range(args.repeats)]
+            nb = l_runs[0][0]
+
+            def emit_all():
+                for lo in range(0, nb, window):
+                    emit(nb, lo, min(nb, lo + window))
+
+            emit(nb, 0, min(nb, window))  # warm-up
+            e_runs = [profiled("sam", emit_all) for _ in range(args.repeats)]
+            res[name] = {"text_bytes": int(nb), "layout_ms": round(min(r[2] for r in l_runs), 3), "layout_ms_runs": [round(r[2], 3) for r in l_runs],
+                         "emit_ms": round(min(r[2] for r in e_runs), 3), "emit_ms_runs": [round(r[2], 3) for r in e_runs]}
+        res["layout_plus_emit_over_plain"] = round((res["mapq"]["layout_ms"] + res["mapq"]["emit_ms"]) /
+                                                   max(res["plain"]["layout_ms"] + res["plain"]["emit_ms"], 1e-9), 3)
+        del d_hits, d_all, d_qoff, quality
+        torch.cuda.empty_cache()
+        return res
 
     def unmapped_passes(total, d_hits, layout_ms, emit_ms, nbytes):
         """the same hits with a placeholder (query = the read, L = R = 0) in front of where every read without a hit would
@@ -326,6 +397,21 @@ def main():
                              "sam_class_ms": round(min(sam), 3), "sam_class_ms_runs": [round(x, 3) for x in sam]}
             assert res["unmapped"]["text_bytes"] == out[f"k{k}"]["unmapped"]["text_bytes"]
             out[f"k{k}"]["unmapped"]["streamed"] = res
+        if args.mapq:  # the best call with and without the bit: wall, bytes, the kernel ms of the quality pass and of the sam class
+            for where, more in [(out[f"k{k}"]["mapq"], {})] + ([(out[f"k{k}"]["no_indels"]["mapq"], dict(indels=False))] if args.no_indels else []):
+                res = {}
+                for name, kw in (("best", dict(best=True, **more)), ("best_mapq", dict(best=True, mapq=True, **more))):
+                    call = lambda: ctx.map_reads_stream([(b"chr1", rec)], fastq, k, None, **kw)  # noqa: E731
+                    q_wall, q_seen, q_walls = streamed(k, **kw)
+                    sam = [profiled("sam", call)[2] for _ in range(args.repeats)]
+                    res[name] = {"call_wall_ms": round(q_wall * 1e3, 1), "call_wall_ms_runs": q_walls, "text_bytes": int(sum(b for _, b in q_seen)),
+                                 "sam_class_ms": round(min(sam), 3), "sam_class_ms_runs": [round(x, 3) for x in sam]}
+                    if "mapq" in kw:
+                        qp = [profiled("mapq", call)[2] for _ in range(args.repeats)]
+                        res[name]["quality_pass_ms"] = round(min(qp), 3)
+                        res[name]["quality_pass_ms_runs"] = [round(x, 3) for x in qp]
+                assert res["best_mapq"]["text_bytes"] == where["mapq"]["text_bytes"] and res["best"]["text_bytes"] == where["plain"]["text_bytes"]
+                where["streamed"] = res
         if args.both_strands:
             both_wall, both_seen, both_walls = streamed(k, both_strands=True)
             out[f"k{k}"]["streamed_both_strands"] = {"call_wall_ms": round(both_wall * 1e3, 1), "call_wall_ms_runs": both_walls,

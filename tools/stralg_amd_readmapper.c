@@ -49,6 +49,14 @@
  *   --header                                        with -d: the SAM header in front of the lines, "@HD VN:1.6 SO:unsorted"
  *                                                   and an "@SQ SN:<name> LN:<length>" a record; once, with several FASTQ
  *                                                   files too; goes with every other switch, -2 included
+ *   --mapq                                          with -d and --best: FLAG and MAPQ from the read's best stratum.  Of the n
+ *                                                   lines of a read (with --both-strands: of the read and its reverse
+ *                                                   complement) the first keeps its FLAG, every other one has 256 added
+ *                                                   (secondary: 256 or 272), and all carry MAPQ 50 (n = 1), 3 (n = 2),
+ *                                                   1 (n = 3 or 4) or 0 (n >= 5).  n counts lines, and the search with indels
+ *                                                   reports some placements twice: --no-indels is what it is meant to be
+ *                                                   used with.  Goes with every other switch but -2; without --best it is
+ *                                                   refused before any output
  *   -2 mates.fq (--mates)                           with -d and one reads.fq: paired-end reads.  Read p of reads.fq and read p of
  *                                                   mates.fq are the mates of pair p; the output is the two lines of every
  *                                                   proper pair of their placements -- same record, one mate on either
@@ -58,7 +66,7 @@
  *                                                   strands are implied.  Goes with -i, --compact, --sa-sample, --packed,
  *                                                   --best and --no-indels (which is what it is meant to be used with: the
  *                                                   search reports some placements with indels more than once); not with
- *                                                   --tags, --unmapped or several read files
+ *                                                   --tags, --unmapped, --mapq or several read files
  *   --min-insert N, --max-insert N                  with -2: the window of that distance (0 and 1000)
  *   (--preprocess, --edits and --in-memory are accepted for -p, -d and -i)
  *
@@ -207,8 +215,11 @@ static int usage(const char *self, int status)
     fprintf(stderr, "       --tags                             with -d: NM:i and MD:Z behind QUAL on every line\n");
     fprintf(stderr, "       --unmapped                         with -d: a FLAG 4 line for every read that prints no line\n");
     fprintf(stderr, "       --header                           with -d: @HD and @SQ lines in front of the text, once\n");
+    fprintf(stderr, "       --mapq                             with -d and --best: per read the first line keeps its FLAG, the others\n");
+    fprintf(stderr, "                                          get 256 added; MAPQ 50, 3, 1, 0 for 1, 2, 3-4, 5 or more lines of the\n");
+    fprintf(stderr, "                                          read (meant for --no-indels); not without --best, not with -2\n");
     fprintf(stderr, "       -2 mates.fq, --mates mates.fq      with -d and one reads.fq: paired-end reads, the lines of the proper\n");
-    fprintf(stderr, "                                          pairs (FLAG 99 / 147, 83 / 163); not with --tags or --unmapped\n");
+    fprintf(stderr, "                                          pairs (FLAG 99 / 147, 83 / 163); not with --tags, --unmapped or --mapq\n");
     fprintf(stderr, "       --min-insert N, --max-insert N     with -2: the window of a pair's length (0, 1000)\n");
     return status;
 }
@@ -243,6 +254,8 @@ int main(int argc, char **argv)
             map_flags |= SX_MAP_UNMAPPED;
         } else if (!strcmp(s, "--header")) {
             map_flags |= SX_MAP_HEADER;
+        } else if (!strcmp(s, "--mapq")) {
+            map_flags |= SX_MAP_MAPQ;
         } else if (!strcmp(s, "-2") || !strcmp(s, "--mates")) {
             if (++a >= argc) return usage(argv[0], EXIT_FAILURE);
             mates = argv[a];
@@ -280,6 +293,10 @@ int main(int argc, char **argv)
     if (mates && (map_flags & SX_MAP_TAGS)) fail("-2 does not go with --tags", NULL);
     if (mates && (map_flags & SX_MAP_UNMAPPED)) {
         fprintf(stderr, "%s: -2 does not go with --unmapped\n", argv[0]);
+        return usage(argv[0], EXIT_FAILURE);
+    }
+    if ((map_flags & SX_MAP_MAPQ) && (mates || !(map_flags & SX_MAP_BEST_STRATUM))) {
+        fprintf(stderr, "%s: --mapq %s\n", argv[0], mates ? "does not go with -2" : "needs --best");
         return usage(argv[0], EXIT_FAILURE);
     }
     if (mates && n_rest != 2) fail("-2 takes one reads file beside the mates' file", NULL);
